@@ -17,7 +17,15 @@ everything from the k-d tree build to the finished, host-resident canvases is in
 timed step against the unmodified reference's digests (tests/golden/full_size.npz); "decoder": the decoder side of the same
 GOF (reconstruct + post-reconstruction tail + D1/D2 metric per frame), timed and verified separately.
 
-Printed JSON (one line, rank 0): metric/value/unit as BASELINE.json, plus
+A plain run sets up, warms up, times the K steps and prints one JSON line (rank 0): metric/value/unit as BASELINE.json,
+ms_per_step (one timed step), dtype, stage_ms_per_frame of the timed steps, plus
+  first_gof_ms / untimed_pass_ms / pool / orientation -- the first pass of this process over the GOF as it is (no priming
+                  passes; the contexts reserve their worst case up front: pool.hipmalloc_calls), S3's ladder steps and
+                  fallbacks per GOF
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs below).  Everything else runs only with
+--full, after the timed steps, and adds to the line:
+  verified     -- the last timed step against the reference's digests (above)
+  decoder / tail / ingest / per_rank_proxy / metric_* -- the side legs, each timed on its own
   roofline     -- the dominant GPU step of the timed region, chosen over ALL timed stages by GPU time with the GPU to
                   itself (SURVEY.md 8d's S1 + S2 + S6 row -- the source tree build, the 16-NN lists and the normals, 94 N
                   bytes -- is one of the candidates, "tree_knn_normals"): algorithmic bytes per launch (SURVEY.md 8d
@@ -25,9 +33,6 @@ Printed JSON (one line, rank 0): metric/value/unit as BASELINE.json, plus
                   stream, inside the timed region) against 8 TB/s HBM;
                   "path" = the contract figure of the whole path, B_alg per frame x frames/s / peak; "stages" = achieved
                   GB/s of every stage whose algorithmic bytes are defined
-  first_gof_ms / untimed_pass_ms / pool / orientation -- the first pass of this process over the GOF as it is (no priming
-                  passes; the contexts reserve their worst case up front: pool.hipmalloc_calls), S3's ladder steps and
-                  fallbacks per GOF
   cpu_baseline -- the unmodified reference (oracle/_ref, kind "reference") or our restatement (kind "port") on the host
                   cores of this box: "value" = one frame, one thread (what MPEG's anchors use); "all_cores_value" = a GOF
                   through the reference's own TBB path (ENABLE_TBB build with its vendored TBB: frames in parallel, points
@@ -48,6 +53,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the verification against the reference's "
+                    "digests, the roofline, the side legs (metric, per-rank proxy, tail, decoder, ingest) and the CPU baseline (the options "
+                    "--cpu-baseline, --tail, --decoder and --ingest choose among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64; a fixed, seeded sample of the canvases)")
     ap.add_argument("--prime", type=int, default=0, help="untimed passes of set-up before the W warmup steps (rounds 3-4 needed three: "
                     "the contexts' pools sized their buffers by first use, and a first-use hipMalloc synchronises the device; round "
                     "5 reserves the sequence's worst case at context creation, tmc2_ctx_reserve, and reports the first passes as "
@@ -179,10 +189,11 @@ def start_frames(workload, indices, gen_procs=0):
 
 
 def relaunch_under_launcher(a):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment): become
+    """`python bench.py --gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment): run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same flags>`
-    -- one rank per GPU, the frame loop of PCCEncoder.cpp:4729-4750 sharded f -> rank f mod N.  Refuses, before anything is set up,
-    when the node has fewer GPUs than ranks (unless --dist-backend gloo, where ranks share the visible GPUs)."""
+    as a child and exit with its status -- one rank per GPU, the frame loop of PCCEncoder.cpp:4729-4750 sharded f -> rank f mod N.
+    Refuses, before anything is set up, when the node has fewer GPUs than ranks (unless --dist-backend gloo, where ranks share
+    the visible GPUs)."""
     import socket
     if a.dist_backend == "nccl" and not a.preflight_only:
         import torch
@@ -196,7 +207,8 @@ def relaunch_under_launcher(a):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stderr.write("bench.py: --gpus %d without a launcher: %s\n" % (a.gpus, " ".join(cmd[1:9])))
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)             # (a fresh child: this process may have initialised the runtime)
 
 
 def preflight(a, torch, dist, sharder, rank, world):
@@ -451,6 +463,39 @@ def verify_frames(a, frames, indices, W, H, host_bufs):
     return (not bad), ("%d frames x 10 digests equal the reference's" % len(frames) if not bad else "; ".join(bad[:8]))
 
 
+CANVASES = ("occupancy", "occ_video", "block_to_patch", "geo0", "geo1", "attribute")
+DUMP_BYTES = 48 << 20      # what dump_outputs writes of canvases in all (every rank, at 4 bytes a value)
+
+
+def dump_outputs(d, frames, indices, W, H, host_bufs, gof_frames):
+    """--dump-outputs DIR: what the last timed step handed its caller, the same bytes verify_frames digests, as .npy files a
+    second build of the project can be compared with.  Per GOF frame f of this rank: f<f>_patches.npy (the packed patch
+    records in patch order, one row per patch, the int32 fields as float64) and f<f>_<canvas>.npy for the six canvases --
+    whole where a canvas is small, else a fixed sample of positions (numpy's default_rng(0), the same positions for every
+    frame) as float32 (block_to_patch: float64); canvas.npy = [W, H].  The inputs are synthetic and seeded: the same arguments
+    give the same files."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    per_canvas = DUMP_BYTES // (4 * len(CANVASES) * max(1, gof_frames))      # values per canvas and frame
+    picks = {}
+    np.save(os.path.join(d, "canvas.npy"), np.array([W, H], np.float64))
+    for slot, (fr, i) in enumerate(zip(frames, indices)):
+        patches = fr.get_patches()[0][fr.get_patch_order()]
+        names = [n for n in patches.dtype.names if n not in ("depthOffset", "occOffset")]     # (offsets into the library's pools)
+        np.save(os.path.join(d, "f%d_patches.npy" % i), np.stack([patches[n] for n in names], 1).astype(np.float64))
+        if host_bufs is not None:
+            img, att = host_bufs[slot]
+        else:
+            img, att = fr.get_geometry_images(), fr.get_attribute_images()
+        for k in CANVASES:
+            flat = (att if k == "attribute" else img[k]).reshape(-1)
+            if flat.size > per_canvas:
+                if k not in picks:
+                    picks[k] = np.sort(np.random.default_rng(0).choice(flat.size, per_canvas, replace=False))
+                flat = flat[picks[k]]
+            np.save(os.path.join(d, "f%d_%s.npy" % (i, k)), flat.astype(np.float64 if flat.dtype.itemsize > 2 else np.float32))
+
+
 def case_fixture(name):
     """tests/golden/full_size.npz (make_golden.py full_size): digests of the unmodified reference for one case, {} if absent."""
     import numpy as np
@@ -631,7 +676,7 @@ def main():
     if a.cpu_child:
         return cpu_child(a.cpu_child, a.workload, a.iterations, a.case)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        relaunch_under_launcher(a)                              # (does not return)
+        relaunch_under_launcher(a)                              # (exits)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -859,16 +904,20 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms, calls = enc.stage_ms(), enc.stage_calls()
-    # parity of what was just timed (outside the timing): every frame of every rank against the reference's MD5s
-    try:
-        verdict, detail = verify_frames(a, frames, my_indices, W, H, host_out(W, H) if to_host_here else None)
-    except Exception as e:
-        verdict, detail = False, "verification failed to run: %r" % (e,)
-    if world > 1:
-        t = torch.tensor([-1 if verdict is None else int(bool(verdict))], dtype=torch.int32, device=sharder.device)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        if verdict is not None or int(t.item()) >= 0:
-            verdict = bool(int(t.item()) > 0) and verdict is not False
+    if a.dump_outputs:                                      # (before the --full legs run the frames again)
+        dump_outputs(a.dump_outputs, frames, my_indices, W, H, host_out(W, H) if to_host_here else None, a.frames)
+    if a.full:
+        # parity of what was just timed (outside the timing): every frame of every rank against the reference's MD5s
+        try:
+            verdict, detail = verify_frames(a, frames, my_indices, W, H, host_out(W, H) if to_host_here else None)
+        except Exception as e:
+            verdict, detail = False, "verification failed to run: %r" % (e,)
+        if world > 1:
+            t = torch.tensor([-1 if verdict is None else int(bool(verdict))], dtype=torch.int32, device=sharder.device)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            if verdict is not None or int(t.item()) >= 0:
+                verdict = bool(int(t.item()) > 0) and verdict is not False
+
     def drop_shared():
         for v in shared.values():
             if hasattr(v, "close"):
@@ -881,6 +930,65 @@ def main():
         if comm is not None:
             comm.close()
         return
+    out = {
+        "metric": "encoder patch+image-gen frames/sec, %s %d-frame GOF" % (a.workload, a.frames),
+        "value": round(a.frames * a.steps / dt, 4), "unit": "frames/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "priming_passes": max(0, a.prime), "ms_per_step": round(1000.0 * dt / a.steps, 2), "step_ms": step_ms, "higher_is_better": True,
+        "first_gof_ms": pass_ms[0] if pass_ms else None, "untimed_pass_ms": pass_ms, "passes_resumed_with_larger_buffers": resumed_passes[0], "pool": dict(enc.pool_stats(), reserved=bool(a.reserve) and reserve_note is None, note=reserve_note),
+        "first_gof_excess_ms_per_frame": dict(sorted(((k, round((first_stage_ms.get(k, 0.0) - v / a.steps) / max(1, len(frames)), 3))
+                                                      for k, v in ms.items() if first_stage_ms.get(k, 0.0) - v / a.steps > 0.2 * len(frames)
+                                                      and not k.startswith(("refine_row_entries", "refine_voxels", "refine_sweeps_executed"))),   # (counters, not times)
+                                                     key=lambda kv: -kv[1])[:8]),
+        "scaling": "strong", "vs_baseline": None, "dtype": "int32/f64", "data": "synthetic",
+        "config": {"workload": "%s-like synthetic, %d frames, %d points/frame avg, ctc-common + %s "
+                               "(refine iterations %d on voxels of %d, %d-bit geometry, occupancyPrecision %d), canvas %dx%d" %
+                               (a.workload, a.frames, n_points // max(1, len(frames)), a.packing, a.iterations, c["vox_dim"],
+                                c["bits3d"] - 1, P, W, H),
+                   "case": a.case_name if a.is_case else None,
+                   "stages": "S0-S22: k-d tree, kNN, normals, orientation, segmentation, refinement, patches, packing, "
+                             "occupancy + geometry images, dilation, reconstruction, colour transfer, attribute images, "
+                             "push-pull padding (identity video codec between the phases); the D1/D2 metric (S23) is "
+                             "reported separately (metric_ms_per_frame, --full)",
+                   "canvases": ("each rank -> page-locked shared host memory (%s); patch records -> rank 0 over %s" %
+                                ("; ".join(sorted(set("a /dev/shm segment per rank" if hasattr(v, "close") else str(v) for v in shared.values()))) or "private buffers",
+                                 "RCCL" if a.dist_backend == "nccl" else "gloo")) if (world > 1 and a.gather == "host")
+                               else ("gathered to rank 0 over RCCL, copied out from there" if world > 1 else "page-locked host memory"),
+                   "host": (("native: one tmc2_gof_encode_sharded call per GOF and rank (libtmc2gof.so: C++ threads over the C-ABI; weights, "
+                             "canvas height and patch records cross the node as RCCL collectives issued from C++)" if comm is not None else
+                             "native: one tmc2_gof_encode call per GOF (libtmc2gof.so, C++ threads over the C-ABI)") if native
+                            else "python: GofEncoder's worker threads over the C-ABI" + ("" if native_fallback[0] is None else " (the C++ / RCCL host was asked for and not available: %s)" % native_fallback[0])),
+                   "frames_per_gpu": len(frames), "host_workers_per_gpu": workers, "host_step_slots_per_gpu": slots, "parallelism": "frames f%%%d" % world},
+        "stage_ms_per_frame": {k: round(v / (a.steps * len(frames)), 3) for k, v in sorted(ms.items())},
+        # S3's cliff: a frame whose contracted graph is inconsistent at 0.98 walks the threshold ladder (a contraction + a cluster
+        # walk per step: milliseconds) and, past its last step, falls back to the growth point by point (hundreds of milliseconds,
+        # and the GOF's rendezvous waits for it).  Per GOF of the timed region:
+        "orientation": {"frames_per_gof": a.frames,
+                        "contracted_walks_per_gof": round(calls.get("orient_contract", 0) / a.steps, 2),
+                        "ladder_steps_per_gof": round(calls.get("orient_tau_retry", 0) / a.steps, 2),
+                        "point_level_fallbacks_per_gof": round(calls.get("orient_normals_regrowth", 0) / a.steps, 2),
+                        "pair_table_overflows_per_gof": round(calls.get("orient_pair_table_overflow", 0) / a.steps, 2),
+                        "exact_size_repeats_per_gof": round(calls.get("orient_exact_size_repeat", 0) / a.steps, 2),
+                        "what": "this rank's frames; SURVEY 8a S3 (PCCNormalsGenerator.cpp:198-242): the exact directed growth runs on the "
+                                "contracted graph; ladder = thresholds 0.99 / 0.995 / 0.998 tried after 0.98"},
+    }
+
+    def finish():
+        print(json.dumps(out))
+        sys.stdout.flush()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        drop_shared()
+        # Orderly teardown (round 3 left through os._exit after an unexplained heap corruption in a bench process; DESIGN.md section 9
+        # has what round 4 found): frames before their contexts, each worker thread ended and joined, contexts closed, then the
+        # interpreter's own exit.
+        if comm is not None:
+            comm.close()
+        for fr in frames:
+            fr.close()
+        enc.close(join=True)
+    if not a.full:
+        return finish()
     # The timed region runs 32 frames at once: their launches share the chip and queue behind each other, so a kernel's
     # event-bracketed time in the region says how long it was in flight, not how much of the GPU it needs.  The kernel the
     # roofline is reported for is therefore chosen by its time with the GPU to itself (one frame, outside the timing);
@@ -967,61 +1075,20 @@ def main():
             traffic_note = "%s has no entry for %s" % (os.path.basename(latest), dom)
     except (OSError, ValueError, KeyError, IndexError):
         pass
-    out = {
-        "metric": "encoder patch+image-gen frames/sec, %s %d-frame GOF" % (a.workload, a.frames),
-        "value": round(a.frames * a.steps / dt, 4), "unit": "frames/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "priming_passes": max(0, a.prime), "ms_per_step": round(1000.0 * dt / a.steps, 2), "step_ms": step_ms, "higher_is_better": True,
-        "first_gof_ms": pass_ms[0] if pass_ms else None, "untimed_pass_ms": pass_ms, "passes_resumed_with_larger_buffers": resumed_passes[0], "pool": dict(enc.pool_stats(), reserved=bool(a.reserve) and reserve_note is None, note=reserve_note),
-        "first_gof_excess_ms_per_frame": dict(sorted(((k, round((first_stage_ms.get(k, 0.0) - v / a.steps) / max(1, len(frames)), 3))
-                                                      for k, v in ms.items() if first_stage_ms.get(k, 0.0) - v / a.steps > 0.2 * len(frames)
-                                                      and not k.startswith(("refine_row_entries", "refine_voxels", "refine_sweeps_executed"))),   # (counters, not times)
-                                                     key=lambda kv: -kv[1])[:8]),
-        "scaling": "strong", "vs_baseline": None, "dtype": "int32/f64", "data": "synthetic",
-        "verified": verdict, "verified_detail": detail,
-        "config": {"workload": "%s-like synthetic, %d frames, %d points/frame avg, ctc-common + %s "
-                               "(refine iterations %d on voxels of %d, %d-bit geometry, occupancyPrecision %d), canvas %dx%d" %
-                               (a.workload, a.frames, n_points // max(1, len(frames)), a.packing, a.iterations, c["vox_dim"],
-                                c["bits3d"] - 1, P, W, H),
-                   "case": a.case_name if a.is_case else None,
-                   "stages": "S0-S22: k-d tree, kNN, normals, orientation, segmentation, refinement, patches, packing, "
-                             "occupancy + geometry images, dilation, reconstruction, colour transfer, attribute images, "
-                             "push-pull padding (identity video codec between the phases); the D1/D2 metric (S23) is "
-                             "reported separately (metric_ms_per_frame)",
-                   "canvases": ("each rank -> page-locked shared host memory (%s); patch records -> rank 0 over %s" %
-                                ("; ".join(sorted(set("a /dev/shm segment per rank" if hasattr(v, "close") else str(v) for v in shared.values()))) or "private buffers",
-                                 "RCCL" if a.dist_backend == "nccl" else "gloo")) if (world > 1 and a.gather == "host")
-                               else ("gathered to rank 0 over RCCL, copied out from there" if world > 1 else "page-locked host memory"),
-                   "host": (("native: one tmc2_gof_encode_sharded call per GOF and rank (libtmc2gof.so: C++ threads over the C-ABI; weights, "
-                             "canvas height and patch records cross the node as RCCL collectives issued from C++)" if comm is not None else
-                             "native: one tmc2_gof_encode call per GOF (libtmc2gof.so, C++ threads over the C-ABI)") if native
-                            else "python: GofEncoder's worker threads over the C-ABI" + ("" if native_fallback[0] is None else " (the C++ / RCCL host was asked for and not available: %s)" % native_fallback[0])),
-                   "frames_per_gpu": len(frames), "host_workers_per_gpu": workers, "host_step_slots_per_gpu": slots, "parallelism": "frames f%%%d" % world},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
-                     "frac": round(achieved / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_note, "avg_launch_ms": round(avg_ms, 4),
-                     "launches": launches, "alone_avg_launch_ms": round(s_avg, 4), "alone_achieved": round(s_ach, 2),
-                     "alone_frac": round(s_ach / 8000.0, 5),
-                     "algorithmic_MB_per_launch": round(dom_bytes / 1e6, 2),
-                     "what": "the dominant GPU step by time with the GPU to itself (one frame in flight: the library's "
-                             "few-frames-in-flight regime, option REFINE_OVERLAP), over every timed stage with a contract byte "
-                             "count (SURVEY.md 8d; tree_knn_normals = its S1 + S2 + S6 row, the source tree build included: 94 N); "
-                             "refine_sweep = one of the %d sweeps of S5 = 4VL + 24V + 26N bytes" % I,
-                     "N": int(N), "M": int(M), "V": int(V), "L": round(L, 1),
-                     "path": {"B_alg_GB_per_frame": round(b_alg / 1e9, 3), "achieved": round(b_alg * fps / 1e9, 1),
-                              "frac": round(b_alg * fps / 1e9 / 8000.0, 5)},
-                     "stages": per_stage},
-        "stage_ms_per_frame": {k: round(v / (a.steps * len(frames)), 3) for k, v in sorted(ms.items())},
-        # S3's cliff: a frame whose contracted graph is inconsistent at 0.98 walks the threshold ladder (a contraction + a cluster
-        # walk per step: milliseconds) and, past its last step, falls back to the growth point by point (hundreds of milliseconds,
-        # and the GOF's rendezvous waits for it).  Per GOF of the timed region:
-        "orientation": {"frames_per_gof": a.frames,
-                        "contracted_walks_per_gof": round(calls.get("orient_contract", 0) / a.steps, 2),
-                        "ladder_steps_per_gof": round(calls.get("orient_tau_retry", 0) / a.steps, 2),
-                        "point_level_fallbacks_per_gof": round(calls.get("orient_normals_regrowth", 0) / a.steps, 2),
-                        "pair_table_overflows_per_gof": round(calls.get("orient_pair_table_overflow", 0) / a.steps, 2),
-                        "exact_size_repeats_per_gof": round(calls.get("orient_exact_size_repeat", 0) / a.steps, 2),
-                        "what": "this rank's frames; SURVEY 8a S3 (PCCNormalsGenerator.cpp:198-242): the exact directed growth runs on the "
-                                "contracted graph; ladder = thresholds 0.99 / 0.995 / 0.998 tried after 0.98"},
-    }
+    out["verified"], out["verified_detail"] = verdict, detail
+    out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
+                       "frac": round(achieved / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_note, "avg_launch_ms": round(avg_ms, 4),
+                       "launches": launches, "alone_avg_launch_ms": round(s_avg, 4), "alone_achieved": round(s_ach, 2),
+                       "alone_frac": round(s_ach / 8000.0, 5),
+                       "algorithmic_MB_per_launch": round(dom_bytes / 1e6, 2),
+                       "what": "the dominant GPU step by time with the GPU to itself (one frame in flight: the library's "
+                               "few-frames-in-flight regime, option REFINE_OVERLAP), over every timed stage with a contract byte "
+                               "count (SURVEY.md 8d; tree_knn_normals = its S1 + S2 + S6 row, the source tree build included: 94 N); "
+                               "refine_sweep = one of the %d sweeps of S5 = 4VL + 24V + 26N bytes" % I,
+                       "N": int(N), "M": int(M), "V": int(V), "L": round(L, 1),
+                       "path": {"B_alg_GB_per_frame": round(b_alg / 1e9, 3), "achieved": round(b_alg * fps / 1e9, 1),
+                                "frac": round(b_alg * fps / 1e9 / 8000.0, 5)},
+                       "stages": per_stage}
     # the measured ceiling next to the nominal 8 TB/s: a device-to-device copy of 1 GiB, bytes read +
     # bytes written per second, with the GPU to itself (outside the timed region)
     try:
@@ -1154,20 +1221,7 @@ def main():
         for key in ("all_cores_value", "frame_processes_value"):
             if out["cpu_baseline"].get(key):
                 out["cpu_baseline"]["gpu_over_" + key[:-6]] = round(out["value"] / out["cpu_baseline"][key], 2)
-    print(json.dumps(out))
-    sys.stdout.flush()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    drop_shared()
-    # Orderly teardown (round 3 left through os._exit after an unexplained heap corruption in a bench process; DESIGN.md section 9
-    # has what round 4 found): frames before their contexts, each worker thread ended and joined, contexts closed, then the
-    # interpreter's own exit.
-    if comm is not None:
-        comm.close()
-    for fr in frames:
-        fr.close()
-    enc.close(join=True)
+    finish()
 
 
 if __name__ == "__main__":

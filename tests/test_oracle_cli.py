@@ -6,6 +6,7 @@ decoded == generated, so these logs pin S11-S22 and the post-reconstruction tail
 (oracle/ref_harness.cpp) drives the same members stage by stage and transcribes a few inline lines of encode(); the oracle
 restates them.  Both must give the CLI's bytes."""
 import hashlib
+import json
 import os
 import re
 import subprocess
@@ -18,10 +19,10 @@ from tmc2_amd.synth import synth_cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 APP = os.path.join(ROOT, "oracle", "_ref", "PccAppEncoder")
-REF = "/root/reference"
+# the CTC cfg files (ctc-common + ctc-all-intra + longdress_vox10 + ctc-r3) flattened into options (tests/golden/make_cli_args.py)
+CTC_ARGS = os.path.join(ROOT, "tests", "golden", "cli_ctc_args.json")
 
-pytestmark = pytest.mark.skipif(not (os.path.exists(APP) and os.path.isdir(os.path.join(REF, "cfg"))),
-                                reason="needs the reference tree and oracle/_ref/PccAppEncoder (make -C oracle ref)")
+pytestmark = pytest.mark.skipif(not os.path.exists(APP), reason="needs oracle/_ref/PccAppEncoder (make -C oracle ref)")
 
 STUB = """#!/bin/sh
 # identity "video codec" behind the reference's HMAPP wrapper (PCCHMAppVideoEncoder.cpp:59-90): reconstruction = input
@@ -41,16 +42,20 @@ def run_cli(tmp, frames, iterations):
     os.chmod(stub, 0o755)
     for i, (xyz, rgb) in enumerate(frames):
         T.ply_write(os.path.join(tmp, "in_%04d.ply" % i), xyz, rgb, ascii=False)
-    cfg = os.path.join(REF, "cfg")
-    cmd = [APP, "--configurationFolder=" + cfg + "/", "--config=" + cfg + "/common/ctc-common.cfg",
-           "--config=" + cfg + "/condition/ctc-all-intra.cfg", "--config=" + cfg + "/sequence/longdress_vox10.cfg",
-           "--config=" + cfg + "/rate/ctc-r3.cfg", "--uncompressedDataPath=" + os.path.join(tmp, "in_%04d.ply"),
-           "--startFrameNumber=0", "--frameCount=%d" % len(frames), "--groupOfFramesSize=%d" % len(frames),
-           "--iterationCountRefineSegmentation=%d" % iterations,
-           "--videoEncoderOccupancyCodecId=HMAPP", "--videoEncoderGeometryCodecId=HMAPP", "--videoEncoderAttributeCodecId=HMAPP",
-           "--videoEncoderOccupancyPath=" + stub, "--videoEncoderGeometryPath=" + stub, "--videoEncoderAttributePath=" + stub,
-           "--keepIntermediateFiles=1", "--nbThread=1", "--computeMetrics=0", "--computeChecksum=0",
-           "--reconstructedDataPath=" + os.path.join(tmp, "rec_%04d.ply"), "--compressedStreamPath=" + os.path.join(tmp, "S.bin")]
+    with open(CTC_ARGS) as f:
+        ctc = json.load(f)["args"]
+    # the ctc-common colour conversion (HDRTools) configurations: the CLI only checks that they exist, and that selects the
+    # same conversion as the cfg files do
+    for k in ("colorSpaceConversionConfig", "inverseColorSpaceConversionConfig"):
+        open(os.path.join(tmp, k + ".cfg"), "w").close()
+        ctc.append("--%s=%s" % (k, os.path.join(tmp, k + ".cfg")))
+    cmd = [APP] + ctc + ["--uncompressedDataPath=" + os.path.join(tmp, "in_%04d.ply"),
+                         "--startFrameNumber=0", "--frameCount=%d" % len(frames), "--groupOfFramesSize=%d" % len(frames),
+                         "--iterationCountRefineSegmentation=%d" % iterations,
+                         "--videoEncoderOccupancyCodecId=HMAPP", "--videoEncoderGeometryCodecId=HMAPP", "--videoEncoderAttributeCodecId=HMAPP",
+                         "--videoEncoderOccupancyPath=" + stub, "--videoEncoderGeometryPath=" + stub, "--videoEncoderAttributePath=" + stub,
+                         "--keepIntermediateFiles=1", "--nbThread=1", "--computeMetrics=0", "--computeChecksum=0",
+                         "--reconstructedDataPath=" + os.path.join(tmp, "rec_%04d.ply"), "--compressedStreamPath=" + os.path.join(tmp, "S.bin")]
     subprocess.run(cmd, cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     pictures, section = {}, None
     with open(os.path.join(tmp, "S_enc_picture_log.txt")) as f:

@@ -20,12 +20,12 @@ for c in loot basketball; do
 done
 cd $REPO
 bash tools/gpu/gaps.sh $TAG > /dev/null 2>&1
-timeout -k 10 1200 python bench.py --steps 20 --warmup 5 > $O/bench_${TAG}_final.json 2> $O/bench_${TAG}_final.err; echo "longdress rc=$?"
+timeout -k 10 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_${TAG}_final.json 2> $O/bench_${TAG}_final.err; echo "longdress rc=$?"
 for c in loot redandblack soldier basketball; do
-  timeout -k 5 600 python bench.py --config $c --cpu-baseline 3 --ingest 0 --tail 0 > $O/bench_${TAG}_$c.json 2> $O/bench_${TAG}_$c.err; echo "$c rc=$?"
+  timeout -k 5 600 python bench.py --full --config $c --cpu-baseline 3 --ingest 0 --tail 0 > $O/bench_${TAG}_$c.json 2> $O/bench_${TAG}_$c.err; echo "$c rc=$?"
 done
-timeout -k 5 600 python bench.py --workload longdress_vox10_noisy --steps 3 --warmup 1 --cpu-baseline 3 --tail 0 --ingest 0 --decoder 0 > $O/bench_${TAG}_rough_shell.json 2> $O/bench_${TAG}_rough_shell.err; echo "rough shell rc=$?"
-timeout -k 5 420 python bench.py --gpus 2 --dist-backend gloo --steps 5 --warmup 2 --cpu-baseline 0 > $O/bench_${TAG}_two_ranks_one_gpu.json 2> $O/bench_${TAG}_two_ranks_one_gpu.err; echo "two ranks (bench.py starts its own launcher) rc=$?"
+timeout -k 5 600 python bench.py --full --workload longdress_vox10_noisy --steps 3 --warmup 1 --cpu-baseline 3 --tail 0 --ingest 0 --decoder 0 > $O/bench_${TAG}_rough_shell.json 2> $O/bench_${TAG}_rough_shell.err; echo "rough shell rc=$?"
+timeout -k 5 420 python bench.py --full --gpus 2 --dist-backend gloo --steps 5 --warmup 2 --cpu-baseline 0 > $O/bench_${TAG}_two_ranks_one_gpu.json 2> $O/bench_${TAG}_two_ranks_one_gpu.err; echo "two ranks (bench.py starts its own launcher) rc=$?"
 python - <<PY
 import json
 for c in ("final", "loot", "redandblack", "soldier", "basketball", "rough_shell", "two_ranks_one_gpu"):
