@@ -111,12 +111,13 @@ void        tmc2_set_host_parallelism( int maxConcurrentHostSteps );
 /* Per-context options: everything that tunes or cross-checks the path is a property of ONE context -- no process-global state, and
  * the library does not look at the environment while it runs.  key = the knob's name (DESIGN.md section 5 lists them):
  * "REFINE_OVERLAP" (0 / 1, below), "KDTREE_HOST" (0 / 1 / 2, below), "UF_PRECHECK" / "UF_SCOPE" / "UF_CHECK" (the union passes'
- * conservative forms and debug invariants), "KD_HUGEMAX" / "KD_PIECE_PER" / "KD_DECIDE" (forms of the device tree build),
+ * conservative forms and debug invariants), "KD_HUGEMAX" / "KD_DECIDE" (forms of the device tree build),
  * "REFINE_*" (forms and grids of the refinement), "METRICS_K", "ORIENT_*"; a "TMC2_" prefix is accepted and dropped.  When a
  * context is created its options start as the TMC2_* variables of the process environment (read once, there); value NULL
  * unsets an option.  None of them ever changes a result.  Options may be set from any thread while frames of the context are
- * in flight (a mutex guards the table; a stage reads an option when it starts).  tmc2_ctx_get_option returns a COPY that belongs
- * to the calling thread and stays valid until that thread's eighth later look-up -- never a pointer into the table.      */
+ * in flight (a mutex guards the table; a stage reads an option when it starts).  tmc2_ctx_get_option returns a pointer to a COPY
+ * held in one string reserved for it per calling thread, valid until that thread's next tmc2_ctx_get_option call -- never a
+ * pointer into the table; NULL if the option is unset.                                                                  */
 int         tmc2_ctx_set_option( tmc2_ctx* ctx, const char* key, const char* value );
 const char* tmc2_ctx_get_option( tmc2_ctx* ctx, const char* key );
 /* Reserve, at context creation time, the device memory the frames of a sequence will need (upper bounds of the sequence: points

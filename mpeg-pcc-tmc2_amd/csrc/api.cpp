@@ -277,7 +277,7 @@ int tmc2_ctx_create( int device, tmc2_ctx** out ) {
 }
 
 /* Per-context options: no process-global state, no environment look-ups at run time.  key: the knob's name without the
-   TMC2_ prefix ("REFINE_OVERLAP", "KDTREE_HOST", "UF_CHECK", "KD_FORM", ...: the names DESIGN.md lists); value NULL unsets it. */
+   TMC2_ prefix ("REFINE_OVERLAP", "KDTREE_HOST", "UF_CHECK", "KD_DECIDE", ...: the names DESIGN.md lists); value NULL unsets it. */
 int tmc2_ctx_set_option( tmc2_ctx* ctx, const char* key, const char* value ) {
   if ( !ctx || !key || !*key ) {
     tmc2::setError( "tmc2_ctx_set_option: invalid argument" );
@@ -293,7 +293,11 @@ int tmc2_ctx_set_option( tmc2_ctx* ctx, const char* key, const char* value ) {
 }
 const char* tmc2_ctx_get_option( tmc2_ctx* ctx, const char* key ) {
   if ( !ctx || !key ) return nullptr;
-  return tmc2::ctxOption( ctx, strncmp( key, "TMC2_", 5 ) == 0 ? key + 5 : key );
+  const auto v = tmc2::ctxOption( ctx, strncmp( key, "TMC2_", 5 ) == 0 ? key + 5 : key );
+  if ( !v ) return nullptr;
+  static thread_local std::string held;  // (valid until this thread's next call: include/tmc2hip.h)
+  held = *v;
+  return held.c_str();
 }
 
 /* Device memory for the frames this context will see, allocated NOW: every buffer a stage asks the context's pool for is carved
@@ -384,7 +388,6 @@ void tmc2::destroyContextNow( tmc2_ctx* ctx ) {
   for ( auto e : ctx->freeEvents ) (void)hipEventDestroy( e );
   {
     ApiScope scope( ctx );
-    ctx->gridTable.release();
     ctx->gridBits.release();
     ctx->scanState.release();
     ctx->voxelBitmap.release();
@@ -550,47 +553,42 @@ namespace tmc2 {
 // (tmc2_set_refine_overlap; unset: the environment variable TMC2_REFINE_OVERLAP decides, off without it)
 // Options are per context (tmc2_ctx_set_option; defaults = the TMC2_* environment at tmc2_ctx_create).  The two process-wide
 // setters of rounds 2-4 (tmc2_set_refine_overlap, tmc2_set_kdtree_placement) only preset what a context WITHOUT the option does.
-const char* ctxOption( const tmc2_ctx* ctx, const char* key ) {
+std::optional<std::string> ctxOption( const tmc2_ctx* ctx, const char* key ) {
   if ( !ctx ) {
     const std::string name = std::string( "TMC2_" ) + key;
-    return getenv( name.c_str() );
+    const char*       e    = getenv( name.c_str() );
+    return e ? std::optional<std::string>( e ) : std::nullopt;
   }
-  // a COPY of the value, in a slot of the calling thread (eight slots, used in turn): the map may change under a reader's feet --
-  // options are set from the caller's thread while stage code of the context's worker thread looks them up -- and what
-  // tmc2_ctx_get_option hands out must outlive the next set / unset of the key
-  static thread_local std::string slots[8];
-  static thread_local unsigned    turn = 0;
-  std::lock_guard<std::mutex>     g( ctx->optionsLock );
-  const auto                      it = ctx->options.find( key );
-  if ( it == ctx->options.end() ) return nullptr;
-  std::string& slot = slots[turn++ & 7u];
-  slot              = it->second;
-  return slot.c_str();
+  // a COPY of the value: options are set from the caller's thread while stage code of the context's worker thread looks them up
+  std::lock_guard<std::mutex> g( ctx->optionsLock );
+  const auto                  it = ctx->options.find( key );
+  if ( it == ctx->options.end() ) return std::nullopt;
+  return it->second;
 }
 static std::atomic<int> g_refineOverlap{-1};
 bool refineOverlap( const tmc2_ctx* ctx ) {
-  if ( const char* e = ctxOption( ctx, "REFINE_OVERLAP" ) ) return e[0] == '1';
+  if ( const auto e = ctxOption( ctx, "REFINE_OVERLAP" ) ) return ( *e )[0] == '1';
   return g_refineOverlap.load( std::memory_order_relaxed ) > 0;
 }
 // where the k-d trees are built (tmc2_set_kdtree_placement; TMC2_KDTREE_HOST=1 presets "host")
 static std::atomic<int> g_kdtreeOnHost{-1};
 int kdtreePlacement( const tmc2_ctx* ctx ) {
-  if ( const char* e = ctxOption( ctx, "KDTREE_HOST" ) )
-    if ( e[0] >= '0' && e[0] <= '2' ) return e[0] - '0';
+  if ( const auto e = ctxOption( ctx, "KDTREE_HOST" ) )
+    if ( ( *e )[0] >= '0' && ( *e )[0] <= '2' ) return ( *e )[0] - '0';
   const int v = g_kdtreeOnHost.load( std::memory_order_relaxed );
   return v < 0 ? 0 : v;
 }
 int unionPrecheck( const tmc2_ctx* ctx ) {
-  const char* e = ctxOption( ctx, "UF_PRECHECK" );
-  return e ? ( e[0] != '0' ) : 1;
+  const auto e = ctxOption( ctx, "UF_PRECHECK" );
+  return e ? ( ( *e )[0] != '0' ) : 1;
 }
 bool unionAgentScope( const tmc2_ctx* ctx ) {
-  const char* e = ctxOption( ctx, "UF_SCOPE" );
-  return e && e[0] == 'a';
+  const auto e = ctxOption( ctx, "UF_SCOPE" );
+  return e && ( *e )[0] == 'a';
 }
 bool unionCheck( const tmc2_ctx* ctx ) {
-  const char* e = ctxOption( ctx, "UF_CHECK" );
-  return e && e[0] == '1';
+  const auto e = ctxOption( ctx, "UF_CHECK" );
+  return e && ( *e )[0] == '1';
 }
 void setRefineOverlapDefault( int on ) { g_refineOverlap.store( on ? 1 : 0, std::memory_order_relaxed ); }
 void setKdtreePlacement( int mode ) { g_kdtreeOnHost.store( mode < 0 || mode > 2 ? 0 : mode, std::memory_order_relaxed ); }

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <functional>
 #include <vector>
@@ -165,9 +166,7 @@ __device__ __forceinline__ uint32_t chunkedIndex() {
   return b * blockDim.x + threadIdx.x;
 }
 #endif
-inline uint32_t chunkedGrid( uint32_t blocks, bool chunked = true ) {
-  return chunked ? ( blocks + 7u ) & ~7u : ( ( blocks & 7u ) ? blocks : blocks + 1u );
-}
+inline uint32_t chunkedGrid( uint32_t blocks ) { return ( blocks + 7u ) & ~7u; }
 
 // pointToPixel of a reconstructed point in one word: canvas x, y (15 bits each: canvases up to kMaxCanvasDim pixels a side,
 // enforced where a canvas size enters -- generateGeometryImages, the decoder frame), map layer, "a D1 point follows"
@@ -258,8 +257,7 @@ struct tmc2_ctx {
   // round's boxes and counters).  Reused from round to round: every user synchronises the stream before the next one refills them.
   tmc2::PinnedBuf               hostTables, hostRecords;
   std::vector<int32_t>          orientScratch;                      // per-vertex state of the orientation walk
-  tmc2::DevBuf<uint32_t>        gridTable;       // persistent dense voxel-key table (kept all-ones between uses)
-  tmc2::DevBuf<uint2>           gridBits;        // its occupancy, .x: one bit per key (kept all-zero between uses: S5 probes ball rows in it), .y: occupied keys below the word
+  tmc2::DevBuf<uint2>           gridBits;        // S5's voxel-key occupancy, .x: one bit per key (kept all-zero between uses: S5 probes ball rows in it), .y: occupied keys below the word
   int                           refineCapTier = 0;  // the smallest neighbourhood-kernel instantiation that held this context's last frames
   uint32_t                      refineHitsPerVoxel = 640;  // room per voxel for the balls' hits kept between S5's two passes over the balls (grows when a frame runs out)
   tmc2::DevBuf<unsigned long long> scanState;    // look-back state of exclusiveScanU32: [0] tile tickets, [1 + t] tile t (epoch-tagged)
@@ -435,18 +433,6 @@ struct OrientCrossEdge {
   uint32_t u, v;  // start / end vertex (original indices)
   double   d;     // n_u . n_v on the original normals
 };
-struct OrientContraction {
-  const uint32_t*        root;    // [n]   cluster (= root vertex id) of every vertex
-  const uint8_t*         parity;  // [n]   1: the vertex' sign is the opposite of its cluster's
-  const uint32_t*        off;     // [n+1] cross edges of cluster c: edges[off[c] .. off[c+1])
-  const OrientCrossEdge* edges;
-};
-bool orientContractedSigns( size_t n, const OrientContraction& g, double tau, int8_t* clusterSign, uint32_t* component,
-                            std::vector<uint32_t>& seeds, void* scratch );
-void resolveSeedSigns( size_t n, const OrientContraction& g, int kNN, const std::vector<uint32_t>& seeds,
-                       const uint32_t* component, const std::function<const uint32_t*( size_t )>& rowOf,
-                       const std::function<const double*( size_t, int )>& normalOf, const int16_t* xyz0,
-                       int8_t* clusterSign );
 // the contracted graph in compact form (device contraction, orient_contract.hip): clusters numbered by first member, per
 // ordered pair of clusters the one light cross edge that can be accepted + the strong one-way edges
 struct OrientCompactEdge {
@@ -504,9 +490,9 @@ int refinePrepareGeometry( tmc2_frame* f, int maxNNCount, double lambda, int ite
 inline uint32_t cappedBlocks( const tmc2_ctx* ctx, size_t wanted ) {
   return uint32_t( std::max<size_t>( 1, std::min<size_t>( wanted, size_t( 8 ) * size_t( ctx->cuCount ) ) ) );
 }
-// The value of a context's option (key without the TMC2_ prefix), nullptr if unset.  ctx == nullptr (the host-only entry points
-// have no context): the process environment.
-const char* ctxOption( const tmc2_ctx* ctx, const char* key );
+// A copy of a context's option (key without the TMC2_ prefix), taken under the context's options lock; nullopt if unset.
+// ctx == nullptr (the host-only entry points have no context): the process environment.
+std::optional<std::string> ctxOption( const tmc2_ctx* ctx, const char* key );
 int  kdtreePlacement( const tmc2_ctx* ctx );  // 0 device, 1 host, 2 adaptive (host while a host slot is free, else device)
 // union passes (S3 contraction, S7 components): answer "same set already?" from the CU's possibly stale view before any
 // find / compare-and-swap (TMC2_UF_PRECHECK=0 switches it off); TMC2_UF_CHECK=1: debug invariants after every union pass

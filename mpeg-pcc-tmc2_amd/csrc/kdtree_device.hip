@@ -971,16 +971,16 @@ __global__ __launch_bounds__( kLandBlock ) void lvSwapTwoKernel( BuildArgs a, ui
 
 constexpr size_t kPieceLdsBytes = size_t( kPieceMax ) * ( sizeof( Pt ) + 4 + 2 + 2 + 2 ) + 16 + 2 * size_t( kPieceRecs ) * sizeof( PieceRec );
 
-template <int K, bool PROFILE = false>  // positions per thread: kPieceMax / K threads
-__global__ __launch_bounds__( kPieceMax / K ) void pieceKernel( BuildArgs a ) {
+constexpr int kPiecePer = 4;  // positions per thread: kPieceMax / 4 = 1 024 threads (eight per thread, 512 threads, measured and dropped)
+template <bool PROFILE = false>
+__global__ __launch_bounds__( kPieceMax / kPiecePer ) void pieceKernel( BuildArgs a ) {
   unsigned long long profLast = 0, prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define PIECE_MARK( k )                                        \
   if ( PROFILE && threadIdx.x == 0 ) {                         \
     const unsigned long long now_ = wall_clock64();            \
     prof[k] += now_ - profLast, profLast = now_;               \
   }
-  constexpr int THREADS = kPieceMax / K, WAVES = THREADS / 64;
-  static_assert( K == 4 || K == 8, "pieceKernel: four or eight positions per thread" );
+  constexpr int K = kPiecePer, THREADS = kPieceMax / K, WAVES = THREADS / 64;
   extern __shared__ __align__( 16 ) unsigned char pieceLds[];
   Pt*       P     = reinterpret_cast<Pt*>( pieceLds );                       // [kPieceMax] the piece's points
   uint32_t* perm  = reinterpret_cast<uint32_t*>( P + kPieceMax );            // [kPieceMax]
@@ -1091,10 +1091,7 @@ __global__ __launch_bounds__( kPieceMax / K ) void pieceKernel( BuildArgs a ) {
       bool     waveLive = true;
       {
         uint16_t raw[K];
-        if ( K == 4 )
-          *reinterpret_cast<uint2*>( raw ) = *reinterpret_cast<const uint2*>( segOf + p0 );
-        else
-          *reinterpret_cast<uint4*>( raw ) = *reinterpret_cast<const uint4*>( segOf + p0 );
+        *reinterpret_cast<uint2*>( raw ) = *reinterpret_cast<const uint2*>( segOf + p0 );
         bool same = true, live = false;
 #pragma unroll
         for ( int k = 0; k < K; ++k ) rec[k] = raw[k], same = same && raw[k] == raw[0], live = live || raw[k] != kNoRec;
@@ -1133,10 +1130,7 @@ __global__ __launch_bounds__( kPieceMax / K ) void pieceKernel( BuildArgs a ) {
 #pragma unroll
         for ( int k = 0; k < K; ++k ) preA[k] = at, out[k] = uint16_t( at ), at += ( f1 >> k ) & 1u;
         preA[K] = at;
-        if ( K == 4 )
-          *reinterpret_cast<uint2*>( pre + p0 ) = *reinterpret_cast<const uint2*>( out );
-        else
-          *reinterpret_cast<uint4*>( pre + p0 ) = *reinterpret_cast<const uint4*>( out );
+        *reinterpret_cast<uint2*>( pre + p0 ) = *reinterpret_cast<const uint2*>( out );
         if ( tid == THREADS - 1 ) pre[kPieceMax] = uint16_t( at );
       }
       pieceBarrier();
@@ -1191,10 +1185,7 @@ __global__ __launch_bounds__( kPieceMax / K ) void pieceKernel( BuildArgs a ) {
 #pragma unroll
         for ( int k = 0; k < K; ++k ) preA[k] = at, out[k] = uint16_t( at ), at += ( f2 >> k ) & 1u;
         preA[K] = at;
-        if ( K == 4 )
-          *reinterpret_cast<uint2*>( pre + p0 ) = *reinterpret_cast<const uint2*>( out );
-        else
-          *reinterpret_cast<uint4*>( pre + p0 ) = *reinterpret_cast<const uint4*>( out );
+        *reinterpret_cast<uint2*>( pre + p0 ) = *reinterpret_cast<const uint2*>( out );
         if ( tid == THREADS - 1 ) pre[kPieceMax] = uint16_t( at );
       }
       pieceBarrier();
@@ -1331,10 +1322,7 @@ __global__ __launch_bounds__( kPieceMax / K ) void pieceKernel( BuildArgs a ) {
             ldsMax( &ch->mx[0], mxx ), ldsMax( &ch->mx[1], mxy ), ldsMax( &ch->mx[2], mxz );
           }
         }
-        if ( K == 4 )
-          *reinterpret_cast<uint2*>( segOf + p0 ) = *reinterpret_cast<const uint2*>( out );
-        else
-          *reinterpret_cast<uint4*>( segOf + p0 ) = *reinterpret_cast<const uint4*>( out );
+        *reinterpret_cast<uint2*>( segOf + p0 ) = *reinterpret_cast<const uint2*>( out );
       }
       cur ^= 1;
     }
@@ -1388,8 +1376,8 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
   // few level passes, which move a few dozen segments of 4 097 .. hugeMax points with five chip-wide launches each; option
   // KD_HUGEMAX).  Round 4's three tiers and its level passes (options KD_FORM=tiers, KD_LEVELS=r4 of round 5, kept there as a
   // third cross-check next to the host builder and the oracle) left the library in round 6.
-  const char*    hugeEnv = ctxOption( ctx, "KD_HUGEMAX" );
-  const uint32_t hugeMax = std::min<uint32_t>( kHugeLimit, std::max<uint32_t>( kPieceMax, hugeEnv ? uint32_t( atoi( hugeEnv ) ) : 16384u ) );
+  const auto     hugeEnv = ctxOption( ctx, "KD_HUGEMAX" );
+  const uint32_t hugeMax = std::min<uint32_t>( kHugeLimit, std::max<uint32_t>( kPieceMax, hugeEnv ? uint32_t( atoi( hugeEnv->c_str() ) ) : 16384u ) );
   TMC2_TRY( d_work.alloc( 3 * size_t( n ) + 2 * ( size_t( tiles ) + 1 ) ) );  // seg, loc1, loc2, tile totals x 2
   TMC2_TRY( d_segs.alloc( 2 * maxSegs ) );
   TMC2_TRY( d_small.alloc( kMaxLevels + 16 ) );  // [0..64] segments per level, then node count, levels, barrier, root box
@@ -1432,8 +1420,8 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
   TMC2_TRY( d_list.alloc( size_t( tiles ) * kScanTile ) );
   TMC2_TRY( d_partial.alloc( size_t( n ) / ( kLandBlock * kLandRounds ) + 2 ) );
   a.lvA = d_lv.p, a.lvB = d_lv.p + maxLv, a.list = d_list.p, a.partial = d_partial.p;
-  const char* decideOpt = ctxOption( ctx, "KD_DECIDE" );  // (test hook: "global" = the fold of a level of more than kDecideRng segments)
-  a.decideRng = decideOpt && decideOpt[0] == 'g' ? 0u : uint32_t( kDecideRng );
+  const auto decideOpt = ctxOption( ctx, "KD_DECIDE" );  // (test hook: "global" = the fold of a level of more than kDecideRng segments)
+  a.decideRng = decideOpt && ( *decideOpt )[0] == 'g' ? 0u : uint32_t( kDecideRng );
   hipLaunchKernelGGL( lvRootKernel, dim3( 1 ), dim3( 128 ), 0, s, a );
   hipLaunchKernelGGL( lvInitKernel, dim3( std::min<uint32_t>( grdE.x, 1024u ) ), blk, 0, s, a );  // (each workgroup reports the root's range once)
   hipLaunchKernelGGL( lvDecideKernel, dim3( 1 ), dim3( kDecideThreads ), 0, s, a, 0u );
@@ -1484,14 +1472,14 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
     hipLaunchKernelGGL( hugeSegmentsKernel, dim3( std::min<uint32_t>( hugeSegs, 4u * uint32_t( ctx->cuCount ) ) ), dim3( 64 * kHugeWaves ), 0, s, a );
   const uint32_t retired = out[kMaxLevels + 3] + hugeSegs * ( 2u * hugeMax / uint32_t( kPieceMax ) );
   if ( retired ) {
-    const char* perEnv = ctxOption( ctx, "KD_PIECE_PER" );  // positions per thread: 4 (1 024 threads) or 8 (512)
+    const dim3 grid( std::min<uint32_t>( retired, 8u * uint32_t( ctx->cuCount ) ) ), block( kPieceMax / kPiecePer );
     if ( ctxOption( ctx, "KD_PIECE_PROFILE" ) ) {  // diagnostic: where a depth's time goes (thread 0 of every workgroup, between barriers)
       DevBuf<unsigned long long> d_prof;
       TMC2_TRY( d_prof.alloc( 16 ) );
       TMC2_HIP( hipMemsetAsync( d_prof.p, 0, 16 * 8, s ) );
       a.pieceProfile = d_prof.p;
-      TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( pieceKernel<4, true> ), kPieceLdsBytes, ctx->device, 256 ) );
-      hipLaunchKernelGGL( ( pieceKernel<4, true> ), dim3( std::min<uint32_t>( retired, 8u * uint32_t( ctx->cuCount ) ) ), dim3( kPieceMax / 4 ), kPieceLdsBytes, s, a );
+      TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( pieceKernel<true> ), kPieceLdsBytes, ctx->device, 256 ) );
+      hipLaunchKernelGGL( pieceKernel<true>, grid, block, kPieceLdsBytes, s, a );
       unsigned long long h[16];
       TMC2_HIP( hipMemcpyAsync( h, d_prof.p, sizeof( h ), hipMemcpyDeviceToHost, s ) );
       TMC2_HIP( hipStreamSynchronize( s ) );
@@ -1500,16 +1488,9 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
       fprintf( stderr, "pieceKernel: %llu pieces, us per piece between the barriers of its depths (thread 0 of each workgroup):", h[8] );
       for ( int k = 0; k < 8; ++k ) fprintf( stderr, " %s %.1f |", what[k], 0.01 * double( h[k] ) / double( std::max<unsigned long long>( h[8], 1 ) ) );
       fprintf( stderr, "\n" );
-    }
-    const dim3  grid( std::min<uint32_t>( retired, 8u * uint32_t( ctx->cuCount ) ) );
-    if ( ctxOption( ctx, "KD_PIECE_PROFILE" ) ) {
-      // (done above)
-    } else if ( perEnv && atoi( perEnv ) == 8 ) {
-      TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( pieceKernel<8> ), kPieceLdsBytes, ctx->device, 256 ) );
-      hipLaunchKernelGGL( pieceKernel<8>, grid, dim3( kPieceMax / 8 ), kPieceLdsBytes, s, a );
     } else {
-      TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( pieceKernel<4> ), kPieceLdsBytes, ctx->device, 256 ) );
-      hipLaunchKernelGGL( pieceKernel<4>, grid, dim3( kPieceMax / 4 ), kPieceLdsBytes, s, a );
+      TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( pieceKernel<> ), kPieceLdsBytes, ctx->device, 256 ) );
+      hipLaunchKernelGGL( pieceKernel<>, grid, block, kPieceLdsBytes, s, a );
     }
     TMC2_HIP( hipGetLastError() );
     TMC2_HIP( hipStreamSynchronize( s ) );

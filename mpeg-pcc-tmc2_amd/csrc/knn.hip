@@ -77,7 +77,7 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
                                                      const KdNode* __restrict__ nodes, RootBox root,
                                                      const Pt* __restrict__ queries, uint32_t nq,
                                                      uint32_t* __restrict__ outIdx, uint32_t* __restrict__ outDist,
-                                                     int xcdAware, uint32_t nTree, int nodeBits,
+                                                     uint32_t nTree, int nodeBits,
                                                      const uint32_t* __restrict__ nqLive, const uint32_t* __restrict__ rowMap ) {
   if ( nqLive ) nq = min( nq, *nqLive );
   // packed far-child entry (LDS form): node id in the low nodeBits, three offsets of ( 64 - nodeBits ) / 3 bits above it --
@@ -91,14 +91,11 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
   // part of the tree -- land on eight different L2s, and every L2 ends up streaming the whole tree (9.4 MB at longdress size
   // against 4 MB of L2: 9.5 x the algorithmic bytes reached HBM).  With the mapping below XCD x works through the x-th eighth
   // of the queries: its L2 holds an eighth of the tree.  (The grid is a multiple of 8 blocks; blocks past the end leave.)
-  uint32_t block = blockIdx.x;
-  if ( xcdAware ) {
-    // (a compacted list: the eighths are eighths of the LIVE blocks, the grid was sized for the worst case)
-    const uint32_t perXcd = nqLive ? ( ( nq + 255u ) / 256u + 7u ) >> 3 : gridDim.x >> 3;
-    if ( ( blockIdx.x >> 3 ) >= perXcd ) return;
-    block = ( blockIdx.x & 7u ) * perXcd + ( blockIdx.x >> 3 );
-  }
-  const uint32_t j = block * blockDim.x + threadIdx.x;
+  // (a compacted list: the eighths are eighths of the LIVE blocks, the grid was sized for the worst case)
+  const uint32_t perXcd = nqLive ? ( ( nq + 255u ) / 256u + 7u ) >> 3 : gridDim.x >> 3;
+  if ( ( blockIdx.x >> 3 ) >= perXcd ) return;
+  const uint32_t block = ( blockIdx.x & 7u ) * perXcd + ( blockIdx.x >> 3 );
+  const uint32_t j     = block * blockDim.x + threadIdx.x;
   if ( j >= nq ) return;
   const Pt  qp = SELF ? ptsTree[j] : queries[j];
   const int qx = qp.x, qy = qp.y, qz = qp.z;
@@ -264,7 +261,7 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
 
 // nqLive / rowMap: see knnKernel
 template <bool SELF>
-int dispatch( const tmc2_ctx* ctx, hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, uint32_t* idx, uint32_t* dist,
+int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, uint32_t* idx, uint32_t* dist,
               const uint32_t* nqLive = nullptr, const uint32_t* rowMap = nullptr ) {
   if ( t.depth > kMaxStack ) {
     setError( "k-d tree depth %d exceeds the traversal stack (%d)", t.depth, kMaxStack );
@@ -280,10 +277,7 @@ int dispatch( const tmc2_ctx* ctx, hipStream_t s, const TreeDev& t, const Pt* q,
     rb.hi[d] = t.hi[d];
   }
   const dim3 block( 256 );
-  // (test hook TMC2_KNN_XCD=0: blocks in launch order)
-  const char* xcdEnv   = ctxOption( ctx, "KNN_XCD" );
-  const int   xcdAware = xcdEnv && xcdEnv[0] == '0' ? 0 : 1;
-  const dim3  grid( xcdAware ? uint32_t( ( ( nq + 255 ) / 256 + 7 ) & ~uint64_t( 7 ) ) : uint32_t( ( nq + 255 ) / 256 ) );
+  const dim3 grid( uint32_t( ( ( nq + 255 ) / 256 + 7 ) & ~uint64_t( 7 ) ) );  // (a multiple of 8 blocks: knnKernel's XCD mapping)
   // the packed LDS stack needs: every offset < 2^14 (tree box and queries inside a 16383-wide window -- the caller
   // vouches for the queries with t.queriesBounded), node ids < 2^22, and at most kLdsLevels pending far children
   bool lds = t.depth <= kLdsLevels && ( ( t.queriesBounded && t.n <= ( uint64_t( 1 ) << 21 ) ) || ( ( SELF || t.queriesTight ) && t.n <= ( uint64_t( 1 ) << 23 ) ) );
@@ -292,10 +286,10 @@ int dispatch( const tmc2_ctx* ctx, hipStream_t s, const TreeDev& t, const Pt* q,
 #define TMC2_LAUNCH_K( KK )                                                                                          \
   if ( lds ) {                                                                                                       \
     hipLaunchKernelGGL( ( knnKernel<KK, SELF, true> ), grid, block, 0, s, t.ptsTree, t.perm, t.nodes, rb, q,          \
-                        uint32_t( nq ), idx, dist, xcdAware, uint32_t( t.n ), nodeBits, nqLive, rowMap );                             \
+                        uint32_t( nq ), idx, dist, uint32_t( t.n ), nodeBits, nqLive, rowMap );                             \
   } else {                                                                                                           \
     hipLaunchKernelGGL( ( knnKernel<KK, SELF, false> ), grid, block, 0, s, t.ptsTree, t.perm, t.nodes, rb, q,         \
-                        uint32_t( nq ), idx, dist, xcdAware, uint32_t( t.n ), nodeBits, nqLive, rowMap );                             \
+                        uint32_t( nq ), idx, dist, uint32_t( t.n ), nodeBits, nqLive, rowMap );                             \
   }
   switch ( k ) {
     case 1: TMC2_LAUNCH_K( 1 ); break;
@@ -332,7 +326,7 @@ TreeDev frameTree( const tmc2_frame* f ) {
 int launchKnnSelf( tmc2_frame* f, int k ) {
   TMC2_TRY( f->d_knn.alloc( f->n * size_t( k ) ) );
   const int sid = f->ctx->stageBegin( "knn_self" );
-  const int r   = dispatch<true>( f->ctx, f->ctx->stream, frameTree( f ), nullptr, f->n, k, f->d_knn.p, nullptr );
+  const int r   = dispatch<true>( f->ctx->stream, frameTree( f ), nullptr, f->n, k, f->d_knn.p, nullptr );
   f->ctx->stageEnd( sid );
   if ( r == TMC2_OK ) {
     f->k       = k;
@@ -353,7 +347,7 @@ int launchKnnQueries( tmc2_frame* f, const Pt* d_queries, uint64_t nq, int k, ui
 int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx,
                    uint32_t* d_dist, const char* stage ) {
   const int sid = ctx->stageBegin( stage );
-  const int r   = dispatch<false>( ctx, ctx->stream, tree, d_queries, nq, k, d_idx, d_dist );
+  const int r   = dispatch<false>( ctx->stream, tree, d_queries, nq, k, d_idx, d_dist );
   ctx->stageEnd( sid );
   return r;
 }
@@ -449,7 +443,7 @@ int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uin
     if ( r == TMC2_OK ) {
       hipLaunchKernelGGL( gatherHardKernel, grd, blk, 0, s, d_easy, d_rank.p, d_queries, uint32_t( nq ), d_hard.p, d_rowMap.p );
       // pass 2: the grid is sized for the worst case, the live count is on the device (no round trip)
-      r = dispatch<false>( ctx, s, tree, d_hard.p, nq, k, d_idx, d_dist, d_count.p, d_rowMap.p );
+      r = dispatch<false>( s, tree, d_hard.p, nq, k, d_idx, d_dist, d_count.p, d_rowMap.p );
     }
   }
   ctx->stageEnd( sid );

@@ -625,8 +625,8 @@ int orderedSums( tmc2_ctx* ctx, const double* termsA, uint32_t nA, const double*
   TMC2_TRY( d_step.alloc( 16 * size_t( o.nbMax ) ) );
   TMC2_TRY( d_expo.alloc( 8 * size_t( o.nbMax ) ) );
   o.approx = d_approx.p, o.d1 = d_d1.p, o.expo = reinterpret_cast<int*>( d_expo.p ), o.step = reinterpret_cast<osum::Step*>( d_step.p );
-  const char* form         = ctxOption( ctx, "METRICS_SUMS" );
-  const int   trustNothing = form && form[0] == 's';
+  const auto form         = ctxOption( ctx, "METRICS_SUMS" );
+  const int  trustNothing = form && ( *form )[0] == 's';
   if ( o.nbA + o.nbB ) hipLaunchKernelGGL( osumBlockKernel<false>, dim3( o.nbA + o.nbB ), dim3( 256 ), 0, s, termsA, nA, termsB, nB, o );
   hipLaunchKernelGGL( osumGuessKernel, dim3( 8 ), dim3( 64 ), 0, s, o, trustNothing );
   if ( ( o.nbA + o.nbB ) && !trustNothing ) hipLaunchKernelGGL( osumBlockKernel<true>, dim3( o.nbA + o.nbB ), dim3( 256 ), 0, s, termsA, nA, termsB, nB, o );
@@ -648,10 +648,8 @@ double psnr( double dist, double p, double factor ) { return 10 * std::log10( ( 
 
 // The metric's searches against a DE-DUPLICATED cloud (round 6: in two launches, knn.hip launchKnnSplit): most points of one cloud
 // are points of the other, and in a tree without duplicate positions the group "all points at the minimum distance" of such a
-// query is that one point.  Option KNN_SPLIT=0: one launch, as before.
+// query is that one point.
 int metricsKnn( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int K, uint32_t* d_idx, uint32_t* d_dist ) {
-  const char* splitEnv = ctxOption( ctx, "KNN_SPLIT" );
-  if ( splitEnv && splitEnv[0] == '0' ) return launchKnnTree( ctx, tree, d_queries, nq, K, d_idx, d_dist, "metrics_knn" );
   DevBuf<uint32_t> d_easy;
   TMC2_TRY( d_easy.alloc( std::max<uint64_t>( nq, 1 ) ) );
   return launchKnnSplit( ctx, tree, d_queries, nq, K, d_easy.p, d_idx, d_dist, "metrics_knn", true );
@@ -805,8 +803,8 @@ int metricsBothWidths( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec
                        double* out, int64_t* counts ) {
   bool overflow = false;
   // (test hook TMC2_METRICS_K=32: the wide search straight away)
-  const char* kEnv = ctxOption( ctx, "METRICS_K" );
-  if ( !( kEnv && atoi( kEnv ) == 32 ) ) {
+  const auto kEnv = ctxOption( ctx, "METRICS_K" );
+  if ( !( kEnv && atoi( kEnv->c_str() ) == 32 ) ) {
     TMC2_TRY( metricsDevice( ctx, src, rec, d_srcNormals, resolution, 16, out, counts, &overflow ) );
     if ( !overflow ) return TMC2_OK;
   }

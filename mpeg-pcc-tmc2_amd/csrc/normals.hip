@@ -194,8 +194,7 @@ int launchNormals( tmc2_frame* f ) {
   }
   TMC2_TRY( f->d_normals.alloc( f->n * 3 ) );
   const int  sid = f->ctx->stageBegin( "normals" );
-  const char* pcOpt = ctxOption( f->ctx, "POINT_CHUNK" );  // (0: the blocks as they come, rounds 1-5)
-  const dim3  block( 256 ), grid( chunkedGrid( uint32_t( ( f->n + 255 ) / 256 ), !( pcOpt && pcOpt[0] == '0' ) ) );
+  const dim3 block( 256 ), grid( chunkedGrid( uint32_t( ( f->n + 255 ) / 256 ) ) );
   if ( f->k == 16 ) {
     hipLaunchKernelGGL( normalsKernel<16>, grid, block, 0, f->ctx->stream, f->d_pts.p, f->d_knn.p, uint32_t( f->n ),
                         f->d_normals.p );

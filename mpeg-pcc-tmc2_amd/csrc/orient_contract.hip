@@ -551,8 +551,8 @@ int contractOrientationDevice( tmc2_frame* f, double tau, DevBuf<uint32_t>& d_ci
   TMC2_TRY( d_crossMask.alloc( n ) );
   TMC2_TRY( d_keepMask.alloc( n ) );
   // (test hook TMC2_ORIENT_PAIRS: log2 of the pair table's capacity; small values force the overflow path)
-  const char*    pairsEnv = ctxOption( f->ctx, "ORIENT_PAIRS" );
-  const uint32_t pairCap  = 1u << ( pairsEnv ? std::min( 24, std::max( 4, atoi( pairsEnv ) ) ) : 20 );
+  const auto     pairsEnv = ctxOption( f->ctx, "ORIENT_PAIRS" );
+  const uint32_t pairCap  = 1u << ( pairsEnv ? std::min( 24, std::max( 4, atoi( pairsEnv->c_str() ) ) ) : 20 );
   TMC2_TRY( d_pairs.alloc( 2 * size_t( pairCap ) ) );
   TMC2_TRY( d_strongFirst.alloc( 2 * size_t( pairCap ) ) );
   if ( n >= ( 1u << 28 ) ) return TMC2_OK;  // (edge ids are u * 16 + j in 32 bits; the caller walks the points)
@@ -570,10 +570,10 @@ int contractOrientationDevice( tmc2_frame* f, double tau, DevBuf<uint32_t>& d_ci
   // parityUnionKernel 349 -> 272 us), the pair-table passes as the blocks come (in eighths the inserts of a pair of clusters
   // meet in time: pairInsertKernel 95 -> 106 us); tree order costs every pass its coalesced own-row reads and wins nothing on
   // clouds that arrive in scan order.
-  const char*     orderOpt = ctxOption( ctx, "ORIENT_ORDER" );
-  const bool      chunked  = !( orderOpt && orderOpt[0] == 'i' );
-  const bool      chunkedPairs = orderOpt && orderOpt[0] != 'i';
-  const uint32_t* perm     = orderOpt && orderOpt[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
+  const auto      orderOpt = ctxOption( ctx, "ORIENT_ORDER" );
+  const bool      chunked  = !( orderOpt && ( *orderOpt )[0] == 'i' );
+  const bool      chunkedPairs = orderOpt && ( *orderOpt )[0] != 'i';
+  const uint32_t* perm     = orderOpt && ( *orderOpt )[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
   const double*   normals  = f->d_normals.p;
   TMC2_TRY( d_count.alloc( size_t( n ) + 1 ) );  // (initWordsKernel zeroes it; later: kept edges per cluster, C + 1 used)
   hipLaunchKernelGGL( initWordsKernel<16>, grdN16, blk, 0, s, f->d_knn.p, normals, f->d_mutual.p, perm, chunked, tau, n, d_mask.p, d_strongAll.p,
@@ -602,9 +602,9 @@ int contractOrientationDevice( tmc2_frame* f, double tau, DevBuf<uint32_t>& d_ci
   // back together.  A frame that needs more room (or whose pair table overflowed) is repeated with exact sizes, two round trips.
   // (test hook TMC2_ORIENT_SPEC = "<edges>,<clusters>": shrinks the speculative room so that small clouds take the repeat)
   uint32_t kSpecEdges = 384 * 1024, kSpecClusters = 64 * 1024;
-  if ( const char* spec = ctxOption( f->ctx, "ORIENT_SPEC" ) ) {
+  if ( const auto spec = ctxOption( f->ctx, "ORIENT_SPEC" ) ) {
     unsigned e = 0, c = 0;
-    if ( sscanf( spec, "%u,%u", &e, &c ) == 2 ) kSpecEdges = std::max( 1u, std::min( kSpecEdges, e ) ), kSpecClusters = std::max( 2u, std::min( kSpecClusters, c ) );
+    if ( sscanf( spec->c_str(), "%u,%u", &e, &c ) == 2 ) kSpecEdges = std::max( 1u, std::min( kSpecEdges, e ) ), kSpecClusters = std::max( 2u, std::min( kSpecClusters, c ) );
   }
   DevBuf<OrientCompactEdge> d_edges;
   DevBuf<OrientClusterRec>  d_rec;

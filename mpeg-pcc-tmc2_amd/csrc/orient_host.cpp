@@ -19,7 +19,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <functional>
 
 #include "internal.h"
 
@@ -53,13 +52,11 @@ __attribute__( ( always_inline ) ) inline unsigned __int128 edgeKey( const HeapE
 struct VertexHeap {
   std::vector<HeapEntry> heap;
   VState*                st;
-  const uint32_t*        owner;  // nullptr: one pending entry per vertex; else per owner[vertex] (cluster walk)
 
-  VertexHeap( size_t n, VState* state, const uint32_t* ownerOf = nullptr ) : st( state ), owner( ownerOf ) {
+  VertexHeap( size_t n, VState* state ) : st( state ) {
     for ( size_t i = 0; i < n; ++i ) st[i] = kAbsent;
     heap.reserve( n / 4 + 16 );
   }
-  size_t slotOf( uint32_t v ) const { return owner ? owner[v] : v; }
   // strict "a has a smaller key than b" in the reference's edge order (weight, start, end)
   static bool less( const HeapEntry& a, const HeapEntry& b ) { return edgeKey( a ) < edgeKey( b ); }
   void siftUp( size_t i ) {
@@ -68,11 +65,11 @@ struct VertexHeap {
       const size_t p = ( i - 1 ) >> 2;
       if ( !less( heap[p], e ) ) break;
       heap[i]           = heap[p];
-      st[slotOf( heap[i].v )] = int32_t( i );
+      st[heap[i].v] = int32_t( i );
       i                 = p;
     }
     heap[i]     = e;
-    st[slotOf( e.v )] = int32_t( i );
+    st[e.v] = int32_t( i );
   }
   void siftDown( size_t i ) {
     const size_t    n = heap.size();
@@ -91,11 +88,11 @@ struct VertexHeap {
       }
       if ( !less( e, heap[c] ) ) break;
       heap[i]           = heap[c];
-      st[slotOf( heap[i].v )] = int32_t( i );
+      st[heap[i].v] = int32_t( i );
       i                 = c;
     }
     heap[i]     = e;
-    st[slotOf( e.v )] = int32_t( i );
+    st[e.v] = int32_t( i );
   }
   // offer in-edge (signed dot d as it stands now, start) to unvisited vertex v whose state is `pos`; the key of a
   // pending vertex lives in its heap entry (the heap is small and cache resident)
@@ -105,7 +102,7 @@ struct VertexHeap {
       siftUp( heap.size() - 1 );
     } else {
       HeapEntry&      h = heap[size_t( pos )];
-      const HeapEntry c{d, v, start};  // same end vertex in the per-vertex walk; any vertex of the cluster otherwise
+      const HeapEntry c{d, v, start};
       if ( less( h, c ) ) {
         h = c;
         siftUp( size_t( pos ) );
@@ -119,7 +116,7 @@ struct VertexHeap {
     if ( i == heap.size() ) return;
     const bool up = less( heap[i], last );
     heap[i]       = last;
-    st[slotOf( last.v )] = int32_t( i );
+    st[last.v] = int32_t( i );
     if ( up )
       siftUp( i );
     else
@@ -133,7 +130,7 @@ struct VertexHeap {
       heap[0] = last;
       siftDown( 0 );
     }
-    st[slotOf( top.v )] = kVisited;
+    st[top.v] = kVisited;
     return top;
   }
 };
@@ -272,135 +269,15 @@ static bool growSigns( const int16_t* xyz, size_t n, const uint32_t* knn, int k,
 // Seeds.  The reference orients the first point of every connected component by a rule that reads the normals of its
 // already oriented neighbours (orientSeedSign below).  Everything else in the component is oriented RELATIVE to its
 // seed, so the walk gives every seed +1 provisionally, numbers the components in the order it opens them
-// (component[c], per cluster) and lists the seeds; resolveSeedSigns() then applies the rule seed by seed -- "already
+// (component[c], per cluster) and lists the seeds; resolveSeedSignsCompact() then applies the rule seed by seed -- "already
 // oriented" at the time seed k was picked means exactly "in a component < k" -- and a cluster's final sign is its
 // provisional one times its component's.  The rule's inputs (one k-NN row and <= k + 2 normals per seed) can thus be
 // fetched in one piece after the walk.  Returns false if a strong cross edge disagrees.
-bool orientContractedSigns( size_t n, const OrientContraction& g, double tau, int8_t* clusterSign, uint32_t* component,
-                            std::vector<uint32_t>& seeds, void* scratch ) {
-  VState*    st    = reinterpret_cast<VState*>( scratch );       // by cluster (root vertex id)
-  uint32_t*  phase = reinterpret_cast<uint32_t*>( scratch ) + n;
-  VertexHeap heap( n, st, g.root );
-  for ( size_t i = 0; i < n; ++i ) clusterSign[i] = 1, phase[i] = 0;
-  std::vector<uint32_t> queue;
-  queue.reserve( 1 << 12 );
-  uint32_t epoch = 0;
-  auto absorb = [&]( uint32_t c0 ) -> bool {
-    ++epoch;
-    phase[c0] = epoch;
-    queue.clear();
-    queue.push_back( c0 );
-    for ( size_t head = 0; head < queue.size(); ++head ) {
-      const uint32_t c  = queue[head];
-      const double   sc = double( clusterSign[c] );
-      for ( uint32_t e = g.off[c]; e < g.off[c + 1]; ++e ) {
-        const OrientCrossEdge& x  = g.edges[e];
-        const uint32_t         c2 = g.root[x.v];
-        const double           d  = ( ( g.parity[x.u] ^ g.parity[x.v] ) & 1 ) ? -( sc * x.d ) : sc * x.d;  // = sign[u] n_u.n_v (-1)^parity[v]
-        const bool             strong = std::fabs( x.d ) >= tau;
-        const int32_t          pv     = st[c2];
-        if ( pv == kVisited ) {
-          if ( strong && phase[c2] == epoch && ( d < 0.0 ) != ( clusterSign[c2] < 0 ) ) return false;
-        } else if ( strong ) {
-          if ( pv >= 0 ) heap.remove( size_t( pv ) );
-          st[c2]          = kVisited;
-          clusterSign[c2] = d < 0.0 ? -1 : 1;
-          phase[c2]       = epoch;
-          queue.push_back( c2 );
-        } else {
-          heap.offer( x.v, pv, d, x.u );
-        }
-      }
-    }
-    return true;
-  };
-  seeds.clear();
-  for ( size_t seed = 0; seed < n; ++seed ) {
-    const uint32_t c = g.root[seed];
-    if ( st[c] == kVisited ) continue;
-    seeds.push_back( uint32_t( seed ) );
-    st[c]          = kVisited;
-    clusterSign[c] = int8_t( ( g.parity[seed] & 1 ) ? -1 : 1 );  // the seed itself: +1 for now
-    if ( !absorb( c ) ) return false;
-    while ( !heap.heap.empty() ) {
-      const HeapEntry e  = heap.popMax();
-      const uint32_t  c2 = g.root[e.v];
-      clusterSign[c2]    = e.d < 0.0 ? -1 : 1;
-      if ( !absorb( c2 ) ) return false;
-    }
-    // everything visited since the last seed belongs to this component: stamp it (phase[] holds absorption epochs,
-    // the epochs of one component are consecutive)
-  }
-  // component of a cluster = number of seeds opened before (or at) its absorption: epochs are handed out in order, so
-  // a second pass over the seeds' epochs is enough
-  {
-    std::vector<uint32_t> firstEpoch( seeds.size() );
-    for ( size_t k = 0; k < seeds.size(); ++k ) firstEpoch[k] = phase[g.root[seeds[k]]];
-    for ( size_t i = 0; i < n; ++i ) {
-      if ( g.root[i] != i ) continue;
-      const uint32_t ep = phase[i];
-      component[i]      = uint32_t( std::upper_bound( firstEpoch.begin(), firstEpoch.end(), ep ) - firstEpoch.begin() ) - 1u;
-    }
-  }
-  return true;
-}
-
-// Seed rule, after the walk: compSign[k] for every component, and the clusters' final signs.
-// rowOf( k ) / normalOf( k, j ): the k-NN row of seed k and the normals of (j = 0) the seed, (j = 1) the point before it
-// in index order, (j = 2 + t) its t-th neighbour.
-void resolveSeedSigns( size_t n, const OrientContraction& g, int kNN, const std::vector<uint32_t>& seeds,
-                       const uint32_t* component, const std::function<const uint32_t*( size_t )>& rowOf,
-                       const std::function<const double*( size_t, int )>& normalOf, const int16_t* xyz0,
-                       int8_t* clusterSign ) {
-  std::vector<int8_t> compSign( seeds.size(), 1 );
-  for ( size_t k = 0; k < seeds.size(); ++k ) {
-    const uint32_t  i   = seeds[k];
-    const uint32_t* row = rowOf( k );
-    // sign of v as it stood when seed k was picked: 0 if v had not been oriented yet
-    const auto signThen = [&]( uint32_t v ) -> int {
-      const uint32_t c = g.root[v];
-      if ( component[c] >= k ) return 0;
-      const int sc = int( clusterSign[c] ) * int( compSign[component[c]] );
-      return ( g.parity[v] & 1 ) ? -sc : sc;
-    };
-    double acc[3]   = {0.0, 0.0, 0.0};
-    size_t accCount = 0;
-    for ( int j = 0; j < kNN; ++j ) {
-      const uint32_t v  = row[j];
-      const int      sv = v != i ? signThen( v ) : 0;
-      if ( sv != 0 ) {
-        const double* nv = normalOf( k, 2 + j );
-        acc[0] += double( sv ) * nv[0];
-        acc[1] += double( sv ) * nv[1];
-        acc[2] += double( sv ) * nv[2];
-        ++accCount;
-      }
-    }
-    if ( accCount == 0 ) {
-      if ( i != 0 ) {
-        const int     sp = signThen( i - 1 );  // i is the smallest index not oriented yet: i - 1 has been
-        const double* np = normalOf( k, 1 );
-        acc[0] = double( sp == 0 ? 1 : sp ) * np[0];
-        acc[1] = double( sp == 0 ? 1 : sp ) * np[1];
-        acc[2] = double( sp == 0 ? 1 : sp ) * np[2];
-      } else {
-        acc[0] = 0.0 - xyz0[0];
-        acc[1] = 0.0 - xyz0[1];
-        acc[2] = 0.0 - xyz0[2];
-      }
-    }
-    compSign[k] = dot( normalOf( k, 0 ), acc ) < 0.0 ? -1 : 1;
-  }
-  for ( size_t i = 0; i < n; ++i )
-    if ( g.root[i] == i && compSign[component[i]] < 0 ) clusterSign[i] = int8_t( -clusterSign[i] );
-}
-
-// ---- the walk on the COMPACT contracted graph (device contraction) -----------------------------------------------------------
-// orientContractedSigns() with clusters as the only vertices: every array is per cluster (18 K entries instead of 0.84 M: the
-// whole working set sits in the host's L1 / L2), a cluster's edge list holds one light edge per target cluster (the only one of
-// its offers into that cluster that can be accepted) and the strong one-way edges, with the target cluster and the ends'
-// parities already folded in.  Clusters are numbered by first member, so "the smallest point not oriented yet" -- the next seed
-// -- is the first member of the first cluster not visited yet.
+// The walk runs on the COMPACT form of the contracted graph (the device contraction's, or compactOnHost below): every array
+// is per cluster (18 K entries instead of 0.84 M: the whole working set sits in the host's L1 / L2), a cluster's edge list
+// holds one light edge per target cluster (the only one of its offers into that cluster that can be accepted) and the strong
+// one-way edges, with the target cluster and the ends' parities already folded in.  Clusters are numbered by first member,
+// so "the smallest point not oriented yet" -- the next seed -- is the first member of the first cluster not visited yet.
 namespace {
 struct ClusterHeap {  // indexed 4-ary max-heap, one pending entry per cluster; key = the reference's (|d|, start, end)
   struct Entry {
@@ -481,7 +358,7 @@ struct ClusterHeap {  // indexed 4-ary max-heap, one pending entry per cluster; 
 };
 }  // namespace
 
-// clusterSign[c]: the sign of cluster c's root-relative frame (as orientContractedSigns); component[c]: the component it
+// clusterSign[c]: the sign of cluster c's root-relative frame; component[c]: the component it
 // belongs to; seeds / seedClusters: the first point and the cluster of every component, in the order they were opened
 bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign, uint32_t* component, std::vector<uint32_t>& seeds,
                          std::vector<uint32_t>& seedClusters ) {
@@ -743,8 +620,8 @@ std::vector<double> orientTauLadder( const tmc2_ctx* ctx ) {
 }
 
 double orientFirstTau( const tmc2_ctx* ctx ) {
-  const char* e = ctxOption( ctx, "ORIENT_TAU" );  // test hook; >= 2 goes straight to the plain growth
-  return e ? atof( e ) : 0.98;
+  const auto e = ctxOption( ctx, "ORIENT_TAU" );  // test hook; >= 2 goes straight to the plain growth
+  return e ? atof( e->c_str() ) : 0.98;
 }
 
 // returns the number of growths it took (1: the first attempt held; each disagreement costs one more).
@@ -778,60 +655,37 @@ int orientSpanningTreeSigns( const int16_t* xyz, size_t n, const uint32_t* knn, 
                std::chrono::duration<double, std::milli>( tc1 - tc0 ).count(), int( okc ), clusters, edges.size(), n * size_t( k ) );
     }
     if ( okc ) {
-      // (TMC2_ORIENT_HOST_WALK=points: the per-point-array walk over the full cross-edge list, kept as the cross-check)
-      const char* walkEnv = ctxOption( ctx, "ORIENT_HOST_WALK" );
-      const auto  tw0     = std::chrono::steady_clock::now();
-      bool        okw;
-      size_t      seedCount = 0;
-      if ( walkEnv && walkEnv[0] == 'p' ) {
-        const OrientContraction g{root.data(), parity.data(), off.data(), edges.data()};
-        std::vector<int8_t>     clusterSign( n );
-        std::vector<uint32_t>   component( n ), seeds;
-        okw       = orientContractedSigns( n, g, first, clusterSign.data(), component.data(), seeds, scratch );
-        seedCount = seeds.size();
-        if ( okw ) {
-          const auto rowOf    = [&]( size_t s ) { return knn + size_t( seeds[s] ) * k; };
-          const auto normalOf = [&]( size_t s, int j ) {
-            const uint32_t i = seeds[s];
+      const auto  tw0 = std::chrono::steady_clock::now();
+      HostCompact hc;
+      compactOnHost( n, root, parity, off, edges, first, hc );
+      const OrientCompact   g = hc.view();
+      std::vector<int8_t>   clusterSign( g.clusters + 1 );
+      std::vector<uint32_t> component( g.clusters + 1 ), seeds, seedClusters;
+      const auto tg0 = std::chrono::steady_clock::now();
+      const bool okw = orientCompactSigns( g, first, clusterSign.data(), component.data(), seeds, seedClusters );
+      if ( ctxOption( ctx, "ORIENT_TIMING" ) )
+        fprintf( stderr, "  the growth over the compact graph alone: %.2f ms (%u clusters, %u edges)\n",
+                 std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - tg0 ).count(), g.clusters, g.rec[g.clusters].off );
+      if ( okw ) {
+        // the seed rule's tables: (point, cluster, parity) of the point before the seed and of its neighbours; their normals
+        std::vector<uint32_t> who( seeds.size() * size_t( k + 1 ) * 3 );
+        std::vector<double>   nrm( seeds.size() * size_t( k + 2 ) * 3 );
+        for ( size_t sd = 0; sd < seeds.size(); ++sd ) {
+          const uint32_t i = seeds[sd];
+          for ( int j = 0; j < k + 2; ++j ) {
             const uint32_t v = j == 0 ? i : ( j == 1 ? ( i ? i - 1 : 0 ) : knn[size_t( i ) * k + ( j - 2 )] );
-            return normals + 3 * size_t( v );
-          };
-          resolveSeedSigns( n, g, k, seeds, component.data(), rowOf, normalOf, xyz, clusterSign.data() );
-          for ( size_t i = 0; i < n; ++i ) sign[i] = int8_t( ( parity[i] & 1 ) ? -clusterSign[root[i]] : clusterSign[root[i]] );
-        }
-      } else {
-        HostCompact hc;
-        compactOnHost( n, root, parity, off, edges, first, hc );
-        const OrientCompact   g = hc.view();
-        std::vector<int8_t>   clusterSign( g.clusters + 1 );
-        std::vector<uint32_t> component( g.clusters + 1 ), seeds, seedClusters;
-        const auto tg0 = std::chrono::steady_clock::now();
-        okw       = orientCompactSigns( g, first, clusterSign.data(), component.data(), seeds, seedClusters );
-        if ( ctxOption( ctx, "ORIENT_TIMING" ) )
-          fprintf( stderr, "  the growth over the compact graph alone: %.2f ms (%u clusters, %u edges)\n",
-                   std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - tg0 ).count(), g.clusters, g.rec[g.clusters].off );
-        seedCount = seeds.size();
-        if ( okw ) {
-          // the seed rule's tables: (point, cluster, parity) of the point before the seed and of its neighbours; their normals
-          std::vector<uint32_t> who( seeds.size() * size_t( k + 1 ) * 3 );
-          std::vector<double>   nrm( seeds.size() * size_t( k + 2 ) * 3 );
-          for ( size_t sd = 0; sd < seeds.size(); ++sd ) {
-            const uint32_t i = seeds[sd];
-            for ( int j = 0; j < k + 2; ++j ) {
-              const uint32_t v = j == 0 ? i : ( j == 1 ? ( i ? i - 1 : 0 ) : knn[size_t( i ) * k + ( j - 2 )] );
-              if ( j >= 1 ) {
-                uint32_t* w = who.data() + ( sd * size_t( k + 1 ) + size_t( j - 1 ) ) * 3;
-                w[0] = v, w[1] = hc.cid[v], w[2] = parity[v];
-              }
-              for ( int c = 0; c < 3; ++c ) nrm[( sd * size_t( k + 2 ) + size_t( j ) ) * 3 + c] = normals[3 * size_t( v ) + c];
+            if ( j >= 1 ) {
+              uint32_t* w = who.data() + ( sd * size_t( k + 1 ) + size_t( j - 1 ) ) * 3;
+              w[0] = v, w[1] = hc.cid[v], w[2] = parity[v];
             }
+            for ( int c = 0; c < 3; ++c ) nrm[( sd * size_t( k + 2 ) + size_t( j ) ) * 3 + c] = normals[3 * size_t( v ) + c];
           }
-          resolveSeedSignsCompact( g, k, seeds, seedClusters, component.data(), who.data(), nrm.data(), xyz, clusterSign.data() );
-          for ( size_t i = 0; i < n; ++i ) sign[i] = int8_t( ( parity[i] & 1 ) ? -clusterSign[hc.cid[i]] : clusterSign[hc.cid[i]] );
         }
+        resolveSeedSignsCompact( g, k, seeds, seedClusters, component.data(), who.data(), nrm.data(), xyz, clusterSign.data() );
+        for ( size_t i = 0; i < n; ++i ) sign[i] = int8_t( ( parity[i] & 1 ) ? -clusterSign[hc.cid[i]] : clusterSign[hc.cid[i]] );
       }
       if ( ctxOption( ctx, "ORIENT_TIMING" ) )
-        fprintf( stderr, "contracted walk %.1f ms ok=%d seeds %zu\n", std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - tw0 ).count(), int( okw ), seedCount );
+        fprintf( stderr, "contracted walk %.1f ms ok=%d seeds %zu\n", std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - tw0 ).count(), int( okw ), seeds.size() );
       if ( okw ) return growths;
     }
   }

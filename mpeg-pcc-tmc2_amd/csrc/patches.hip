@@ -744,9 +744,9 @@ int ensureMutualMask( tmc2_frame* f ) {
   const int kt = f->ctx->stageBegin( "k:ccMutualMask" );
   // option MUTUAL_ORDER (this pass and S7's union / relaxation passes): "input" = index order, blocks as they come (rounds 1-5);
   // "chunk" = index order, XCD x on the x-th eighth of the blocks; "tree" = tree order, same eighths
-  const char*     order   = ctxOption( f->ctx, "MUTUAL_ORDER" );
-  const bool      chunked = !( order && order[0] == 'i' );
-  const uint32_t* perm    = order && order[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
+  const auto      order   = ctxOption( f->ctx, "MUTUAL_ORDER" );
+  const bool      chunked = !( order && ( *order )[0] == 'i' );
+  const uint32_t* perm    = order && ( *order )[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
   const uint32_t  blocks  = ( n + 255 ) / 256;
   hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( chunked ? ( ( blocks + 7 ) & ~7u ) : blocks ), dim3( 256 ), 0, f->ctx->stream, f->d_knn.p,
                       perm, chunked, n, f->d_mutual.p );
@@ -831,19 +831,17 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   f->patches.clear();
   f->depthCount = 0;
   f->occCount   = 0;
-  // (option POINT_CHUNK=0: the one-point-per-lane passes of S7-S9 with the blocks as they come, rounds 1-5; default: XCD x takes the
-  //  x-th eighth of the blocks -- chunkedIndex)
-  const char* pcOpt = ctxOption( ctx, "POINT_CHUNK" );
-  const dim3  blk( 256 ), grdN( chunkedGrid( ( n + 255 ) / 256, !( pcOpt && pcOpt[0] == '0' ) ) );
+  // (the one-point-per-lane passes of S7-S9: XCD x takes the x-th eighth of the blocks -- chunkedIndex)
+  const dim3  blk( 256 ), grdN( chunkedGrid( ( n + 255 ) / 256 ) );
   uint32_t    rawCount = n, relaxToken = 0;
   int        rounds   = 0;
   TMC2_TRY( ensureMutualMask( f ) );  // usually there already: the orientation (S3) needs the same bits
   DevBuf<uint16_t>& d_mutual   = f->d_mutual;
   const bool        agentScope = unionAgentScope( f->ctx );
   // the union / relaxation passes: option MUTUAL_ORDER as in ensureMutualMask (here the default is "chunk")
-  const char*     ccOrder = ctxOption( ctx, "MUTUAL_ORDER" );
-  const bool      chunked = !( ccOrder && ccOrder[0] == 'i' );
-  const uint32_t* perm    = ccOrder && ccOrder[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
+  const auto      ccOrder = ctxOption( ctx, "MUTUAL_ORDER" );
+  const bool      chunked = !( ccOrder && ( *ccOrder )[0] == 'i' );
+  const uint32_t* perm    = ccOrder && ( *ccOrder )[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
   const dim3      grdT( chunked ? ( ( grdN.x + 7u ) & ~7u ) : grdN.x );
   while ( rawCount > 0 ) {
     // ---- S7 -----------------------------------------------------------------------------------------

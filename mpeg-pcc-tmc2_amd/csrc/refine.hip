@@ -6,13 +6,14 @@
 //
 // Reference shape: hash maps of voxels, a k-d tree over voxel centres, and `iterationCount` sequential
 // sweeps over the voxel list.  MI355X shape:
-//   * voxelisation without hashing or sorting: a dense key table in HBM (2^(3s+1) words; 128 MiB at
-//     vox10 -- trivial next to 288 GB, kept all-ones between frames and cleaned by scatter) receives
-//     atomicMin(first point index); a flag+prefix-sum over the POINTS then numbers the voxels in
+//   * voxelisation without hashing or sorting: a dense occupancy bitmap over the voxel keys (one bit per key,
+//     2^(3s+1) keys; kept all-zero between frames and cleaned by scatter) with the number of occupied keys
+//     below every word -- the RANK of an occupied key -- receives the points; atomicMin(point index) per rank
+//     finds every voxel's first point, and a flag+prefix-sum over the POINTS then numbers the voxels in
 //     first-appearance order, which is exactly the reference's voxel order (:1422-1434).
-//   * neighbourhoods by direct lookup of the <=1357 integer offsets of the radius ball in that table,
-//     one wavefront per voxel, bitonic sort of (dist^2, voxel id) in LDS -- the radius search result is
-//     canonical (sorted by (dist,index), nanoflann.hpp:945-952), so no tree is needed -- followed by a
+//   * neighbourhoods by probing the ROWS of the radius ball in that bitmap (rank -> voxel record for every
+//     occupied cell), one wavefront per voxel, bitonic sort of (dist^2, voxel id) in LDS -- the radius search result
+//     is canonical (sorted by (dist,index), nanoflann.hpp:945-952), so no tree is needed -- followed by a
 //     wave prefix sum of member counts for the 1024-point truncation (:1484-1501).
 //   * each sweep is Jacobi in the histograms (they are refreshed only at the end of a sweep); the only
 //     sequential coupling is the INDIRECT_EDGE marking, visible to later voxels of the same sweep
@@ -32,7 +33,7 @@ enum : uint8_t { NO_EDGE = 0x00, INDIRECT_EDGE = 0x01, M_DIRECT_EDGE = 0x10, S_D
 
 struct Grid {
   int      voxShift, gridShift, half;
-  uint32_t tableSize;
+  uint32_t keyCount;  // 2^(3 gridShift + 1) voxel keys
 };
 
 __device__ __forceinline__ uint32_t cellKey( int x0, int y0, int z0, int s ) {
@@ -40,10 +41,9 @@ __device__ __forceinline__ uint32_t cellKey( int x0, int y0, int z0, int s ) {
 }
 
 // ---- voxelisation ---------------------------------------------------------------------------------
-// (bits: one bit per key -- the occupancy of the key table, which the neighbourhood passes probe 64 cells of a ball row at a
+// (bits: one bit per key -- the occupancy of the keys, which the neighbourhood passes probe 64 cells of a ball row at a
 //  time; look before the atomic: a voxel's points set the same bit)
-__global__ __launch_bounds__( 256 ) void voxelKeyKernel( const Pt* __restrict__ pts, uint32_t n, Grid g,
-                                                          uint32_t* __restrict__ key, uint32_t* __restrict__ table,
+__global__ __launch_bounds__( 256 ) void voxelKeyKernel( const Pt* __restrict__ pts, uint32_t n, Grid g, uint32_t* __restrict__ key,
                                                           uint2* __restrict__ bits /* .x: 32 keys' occupancy, .y: see below */ ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= n ) return;
@@ -51,7 +51,6 @@ __global__ __launch_bounds__( 256 ) void voxelKeyKernel( const Pt* __restrict__ 
   const uint32_t k = cellKey( ( int( p.x ) + g.half ) >> g.voxShift, ( int( p.y ) + g.half ) >> g.voxShift,
                               ( int( p.z ) + g.half ) >> g.voxShift, g.gridShift );
   key[i]           = k;
-  if ( table ) atomicMin( &table[k], i );  // (the cell-by-cell form only: the row-wise form numbers the voxels through the ranks)
   const uint32_t bit = 1u << ( k & 31 );
   if ( !( loadStaleOk( &bits[k >> 5].x ) & bit ) ) atomicOr( &bits[k >> 5].x, bit );
 }
@@ -127,8 +126,8 @@ __global__ __launch_bounds__( 256 ) void rankToVoxelKernel( const uint32_t* __re
   }
 }
 
-// The first point of every voxel WITHOUT the dense key table (row-wise form: rounds 1-3 kept 2^(3s+1) words per context for this,
-// 1 GiB with voxels of 2 or 11-bit geometry): firstPoint[rank of the point's key] takes the minimum over the voxel's points.
+// The first point of every voxel WITHOUT a dense key table (rounds 1-3 kept 2^(3s+1) words per context for this, 1 GiB with
+// voxels of 2 or 11-bit geometry): firstPoint[rank of the point's key] takes the minimum over the voxel's points.
 __global__ __launch_bounds__( 256 ) void firstPointKernel( const uint32_t* __restrict__ key, uint32_t n, const uint2* __restrict__ bits,
                                                             uint32_t* __restrict__ firstPoint ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,30 +135,23 @@ __global__ __launch_bounds__( 256 ) void firstPointKernel( const uint32_t* __res
   uint32_t* slot = &firstPoint[rankOfKey( bits, key[i] )];
   if ( i < loadStaleOk( slot ) ) atomicMin( slot, i );
 }
-// the first point of the voxel point i belongs to: through the key table, or through the ranks
-__device__ __forceinline__ uint32_t firstPointOf( uint32_t k, const uint32_t* __restrict__ table, const uint2* __restrict__ bits,
-                                                  const uint32_t* __restrict__ firstPoint ) {
-  return table ? table[k] : firstPoint[rankOfKey( bits, k )];
-}
 
-__global__ __launch_bounds__( 256 ) void firstFlagKernel( const uint32_t* __restrict__ key,
-                                                           const uint32_t* __restrict__ table, const uint2* __restrict__ bits,
+__global__ __launch_bounds__( 256 ) void firstFlagKernel( const uint32_t* __restrict__ key, const uint2* __restrict__ bits,
                                                            const uint32_t* __restrict__ firstPoint, uint32_t n,
                                                            uint32_t* __restrict__ flag ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( i < n ) flag[i] = ( firstPointOf( key[i], table, bits, firstPoint ) == i ) ? 1u : 0u;
+  if ( i < n ) flag[i] = ( firstPoint[rankOfKey( bits, key[i] )] == i ) ? 1u : 0u;
 }
 
 // vid[i] = rank of the voxel's first point; member counts; centre of each voxel
 __global__ __launch_bounds__( 256 ) void assignVoxelKernel( const Pt* __restrict__ pts, const uint32_t* __restrict__ key,
-                                                             const uint32_t* __restrict__ table, const uint2* __restrict__ bits,
-                                                             const uint32_t* __restrict__ firstPoint,
+                                                             const uint2* __restrict__ bits, const uint32_t* __restrict__ firstPoint,
                                                              const uint32_t* __restrict__ rank, uint32_t n, Grid g,
                                                              uint32_t* __restrict__ vid, uint32_t* __restrict__ count,
                                                              Pt* __restrict__ centre ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= n ) return;
-  const uint32_t first = firstPointOf( key[i], table, bits, firstPoint );
+  const uint32_t first = firstPoint[rankOfKey( bits, key[i] )];
   const uint32_t v     = rank[first];
   vid[i]               = v;
   atomicAdd( &count[v], 1u );
@@ -170,20 +162,9 @@ __global__ __launch_bounds__( 256 ) void assignVoxelKernel( const Pt* __restrict
   }
 }
 
-// table: first point index -> voxel id (only the voxel's first point writes)
-__global__ __launch_bounds__( 256 ) void tableToVoxelKernel( const uint32_t* __restrict__ key,
-                                                              const uint32_t* __restrict__ flag,
-                                                              const uint32_t* __restrict__ vid, uint32_t n,
-                                                              uint32_t* __restrict__ table ) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( i < n && flag[i] ) table[key[i]] = vid[i];
-}
-
-__global__ __launch_bounds__( 256 ) void tableCleanKernel( const uint32_t* __restrict__ key, uint32_t n,
-                                                            uint32_t* __restrict__ table, uint2* __restrict__ bits ) {
+__global__ __launch_bounds__( 256 ) void bitsCleanKernel( const uint32_t* __restrict__ key, uint32_t n, uint2* __restrict__ bits ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= n ) return;
-  if ( table ) table[key[i]] = 0xFFFFFFFFu;
   bits[key[i] >> 5].x = 0u;  // (whole words: every key of the word belongs to this frame; the prefix sums are rebuilt per frame)
 }
 
@@ -259,8 +240,8 @@ struct BallHits {
 // The ball as ROWS: for every (dy, dz) with dy^2 + dz^2 < r2 the cells dx = -xr .. xr (xr the largest with dx^2 + dy^2 + dz^2
 // < r2).  Keys are linear in x, so the <= 2 xr + 1 <= 25 cells of a row are consecutive BITS of the occupancy bitmap: one lane
 // probes a whole row with two 4-byte loads instead of one load per cell (voxels of 2: 301 rows against 3 911 cells, of which
-// 8 % are occupied).  Only the occupied cells go on to the key table (the voxel id) and to the voxel's centre (aliased keys:
-// accept only the voxel whose centre really sits there).  Leaves the hits in keys[] as ( d2 << idBits ) | id, unsorted.
+// 8 % are occupied).  Only the occupied cells go on to their rank's voxel record (id, centre; aliased keys: accept only the
+// voxel whose centre really sits there).  Leaves the hits in keys[] as ( d2 << idBits ) | id, unsorted.
 //   rows[i] = ( dy + 128 ) | ( dz + 128 ) << 8 | xr << 16
 // phase 1: the occupied cells of the ball as packed offsets ( dx + 16 ) | ( dy + 16 ) << 5 | ( dz + 16 ) << 10 | d2 << 15
 // phase 2: id + centre of each, in place (a chunk of candidates is read whole before anything lands at or below it)
@@ -368,7 +349,7 @@ __device__ __forceinline__ int collectBall( const Pt c, const Pt* __restrict__ c
 }
 
 // ---- neighbourhoods ---------------------------------------------------------------------------------
-// One wavefront per voxel.  offsets[] = all integer (dx,dy,dz) with d2 < radius2, packed, any order.
+// One wavefront per voxel.  rows[] = the ball's rows (collectBall).
 // Collect hits (d2 << idBits | voxel id) in LDS, bitonic-sort, cut after the cumulative member count reaches maxNN; write
 // row length, weight, the row itself (rows back to back: the wave reserves its slots from a cursor -- what a frame needs
 // is ~ maxNN / (points per voxel) entries per voxel, a fraction of the ball) and the DEV row: the members of the row
@@ -384,11 +365,11 @@ constexpr int ldsWavesPerSimd( int cap, int waves ) {
 
 template <int CAP, int WAVES>
 __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void neighbourhoodKernel(
-    const Pt* __restrict__ centre, const uint32_t* __restrict__ count, const uint32_t* __restrict__ table, Grid g, uint32_t V,
-    const int* __restrict__ offsets, int nOffsets, int maxNN, double lambda, int idBits, int devRange, uint32_t devStride,
+    const Pt* __restrict__ centre, const uint32_t* __restrict__ count, Grid g, uint32_t V,
+    const int* __restrict__ rows, int nRows, int maxNN, double lambda, int idBits, int devRange, uint32_t devStride,
     uint32_t rowCapacity, uint32_t* __restrict__ rowLen, uint32_t* __restrict__ devLen, double* __restrict__ weight,
     uint32_t* __restrict__ adjOff, uint32_t* __restrict__ adj, uint32_t* __restrict__ dev, uint32_t* __restrict__ rowCursor,
-    uint32_t* __restrict__ overflow, const uint2* __restrict__ bits /* non-null: offsets = the ball's ROWS (collectBall) */,
+    uint32_t* __restrict__ overflow, const uint2* __restrict__ bits /* occupancy bitmap + ranks of the keys */,
     const uint2* __restrict__ voxelOfRank /* record of the voxel that owns the rank-th occupied key (rankRecord) */,
     uint32_t* __restrict__ lastKey /* the last key each row keeps: what the gathered reverse rows test against */,
     BallHits saved /* .buf non-null: the ball's hits are kept for the reverse rows (round 6) */ ) {
@@ -397,20 +378,14 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
   const uint32_t      v    = blockIdx.x * WAVES + wave;
   uint32_t*           keys = keysAll[wave];
   if ( v >= V ) return;  // (a wave of the last workgroup without a voxel; the kernel has no workgroup barrier)
-  const uint32_t idMask  = ( 1u << idBits ) - 1u;
-  const Pt       c       = centre[v];
-  const int      gridMax = 1 << g.gridShift;  // cell coordinates run 0..gridMax inclusive
-  int            hits    = 0;
-  // The ball's cells in batches of kBatch x 64: all table look-ups of a batch are issued before the first one is needed, then
-  // all centre look-ups of its hits (two dependent round trips per batch instead of two per 64 cells: the kernel is bound by
-  // exactly this latency).  The order of the hits does not matter: they are sorted below.
-  constexpr int kBatch = 8;
-  uint32_t*     bins   = keys + CAP - 160;  // (the host checks that the ball leaves this room)
+  const uint32_t idMask = ( 1u << idBits ) - 1u;
+  const Pt       c      = centre[v];
+  uint32_t*      bins   = keys + CAP - 160;  // (the host checks that the ball leaves this room)
   for ( int b = lane; b < 128; b += 64 ) bins[b] = 0;
   __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-  // (row-wise form: the bins -- members and hits per squared distance -- fill while the ball is collected: a voxel's member
-  //  count rides in its centre record, which the collection reads anyway)
-  if ( bits ) hits = collectBall<CAP>( c, centre, voxelOfRank, bits, g, offsets, nOffsets, idBits, keys, lane, overflow, bins );
+  // (the bins -- members and hits per squared distance -- fill while the ball is collected: a voxel's member count rides in its
+  //  centre record, which the collection reads anyway; the order of the hits does not matter: they are sorted below)
+  int hits = collectBall<CAP>( c, centre, voxelOfRank, bits, g, rows, nRows, idBits, keys, lane, overflow, bins );
   if ( saved.buf ) {  // the hits as they are now (every voxel of the ball, unsorted): the reverse rows pass reads them instead of collecting the ball again
     const uint32_t region = blockIdx.x % kHitRegions;
     uint32_t       at     = 0;
@@ -425,59 +400,20 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
       if ( !room ) atomicMax( overflow + 3, 1u );  // (the reverse rows pass collects the balls itself, the next frames get more room)
     }
   }
-  for ( int base = 0; !bits && base < nOffsets; base += 64 * kBatch ) {
-    uint32_t u[kBatch], d2[kBatch], cell[kBatch];
-#pragma unroll
-    for ( int k = 0; k < kBatch; ++k ) {
-      const int o = base + 64 * k + lane;
-      u[k]        = 0xFFFFFFFFu;
-      d2[k] = cell[k] = 0;
-      if ( o < nOffsets ) {
-        const int packed = offsets[o];
-        const int dx = ( packed & 0xFF ) - 128, dy = ( ( packed >> 8 ) & 0xFF ) - 128, dz = ( ( packed >> 16 ) & 0xFF ) - 128;
-        const int x = c.x + dx, y = c.y + dy, z = c.z + dz;
-        if ( x >= 0 && y >= 0 && z >= 0 && x <= gridMax && y <= gridMax && z <= gridMax ) {
-          u[k]    = table[cellKey( x, y, z, g.gridShift )];
-          d2[k]   = uint32_t( dx * dx + dy * dy + dz * dz );
-          cell[k] = uint32_t( x ) | ( uint32_t( y ) << 10 ) | ( uint32_t( z ) << 20 );  // (cell coordinates are at most 512)
-        }
-      }
-    }
-    uint32_t key[kBatch];
-#pragma unroll
-    for ( int k = 0; k < kBatch; ++k ) {
-      key[k] = 0xFFFFFFFFu;
-      if ( u[k] != 0xFFFFFFFFu ) {
-        const Pt cu = centre[u[k]];  // aliased keys: accept only the voxel whose centre really sits here
-        if ( ( uint32_t( cu.x ) | ( uint32_t( cu.y ) << 10 ) | ( uint32_t( cu.z ) << 20 ) ) == cell[k] ) key[k] = ( d2[k] << idBits ) | u[k];
-      }
-    }
-#pragma unroll
-    for ( int k = 0; k < kBatch; ++k ) {
-      const unsigned long long m = __ballot( key[k] != 0xFFFFFFFFu );
-      if ( key[k] != 0xFFFFFFFFu ) keys[hits + __popcll( m & ( ( 1ull << lane ) - 1ull ) )] = key[k];
-      hits += __popcll( m );
-    }
-  }
   // Only the head of the sorted list is ever used: the row ends where the running member count reaches maxNN.  The squared
   // distance takes few values, so the cut is found BEFORE sorting -- member totals per distance (LDS atomics into the unused
   // tail of the key array), a wave scan over them -- and the hits beyond the distance the cut falls in are dropped: the
   // sort below handles ~ 100-150 keys instead of the 300-400 voxels of the whole ball.
   uint32_t membersBefore = 0, hitsBefore = 0, hitsCut = 0;  // of the distance the cut falls in
   bool     cutFound      = false;
-  // Row-wise form: a row is a SET to everything that reads it (integer sums over it, marks through it, the reverse rows test
-  // membership by the last key), so only the hits of the distance the cut falls in have to be put in order -- by voxel id, to
-  // find where the row ends -- and not the whole row: ~ 100 keys to sort instead of 400-500 (the sort was two thirds of this
-  // kernel).  They go to the free room above the hits; the cell-by-cell form (and a ball too full for that room) sorts everything.
+  // A row is a SET to everything that reads it (integer sums over it, marks through it, the reverse rows test membership by
+  // the last key), so only the hits of the distance the cut falls in have to be put in order -- by voxel id, to find where the
+  // row ends -- and not the whole row: ~ 100 keys to sort instead of 400-500 (the sort was two thirds of this kernel).  They
+  // go to the free room above the hits; a ball too full for that room sorts everything.
   bool     partial       = false;
   int      Pc            = 64;
   uint32_t lastKeyValue  = 0;
   {
-    if ( !bits )
-      for ( int i = lane; i < hits; i += 64 ) {
-        const uint32_t key = keys[i];
-        atomicAdd( &bins[min( key >> idBits, 127u )], ( count[key & idMask] & 0xFFu ) | ( 1u << 20 ) );
-      }
     __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
     const uint32_t w0 = bins[2 * lane], w1 = bins[2 * lane + 1];
     const uint32_t b0 = w0 & 0xFFFFFu, b1 = w1 & 0xFFFFFu, e0 = w0 >> 20, e1 = w1 >> 20;
@@ -499,7 +435,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
       hitsCut          = __shfl( even ? e0 : e1, first, 64 );
       cutFound         = true;
       while ( Pc < int( hitsCut ) ) Pc <<= 1;
-      partial = bits != nullptr && hits + Pc <= CAP - 160;
+      partial = hits + Pc <= CAP - 160;
     }
     if ( partial ) {
       uint32_t* cut   = keys + ( CAP - 160 - Pc );  // (above every hit: nothing this loop still has to read)
@@ -641,7 +577,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
   rowBase += region * rowCapacity;
   if ( lane == 0 ) {
     rowLen[v] = uint32_t( used );
-    if ( lastKey ) lastKey[v] = partial ? lastKeyValue : ( used > 0 ? keys[used - 1] : 0u );
+    lastKey[v] = partial ? lastKeyValue : ( used > 0 ? keys[used - 1] : 0u );
     adjOff[v] = fit ? rowBase : 0u;
     weight[v] = __ddiv_rn( lambda, double( nn ) );
     if ( !fit ) atomicMax( overflow, 1u );  // the host repeats the pass with room for whole balls
@@ -847,33 +783,6 @@ __global__ __launch_bounds__( 256 ) void smoothInitKernel( const uint4* __restri
     s2 += __shfl_xor( s2, off, 64 );
   }
   if ( lane == 0 ) rec[v] = make_uint4( s0, s1, s2, 1u );
-}
-
-// reverse neighbourhood rows: radj[roff[u] ..] = the voxels v whose (truncated) row lists u
-__global__ __launch_bounds__( 256 ) void reverseCountKernel( const uint32_t* __restrict__ adjOff, const uint32_t* __restrict__ rowLen,
-                                                              const uint32_t* __restrict__ adj, uint32_t V,
-                                                              uint32_t* __restrict__ rcount ) {
-  const int      lane = threadIdx.x & 15;
-  const uint32_t v    = blockIdx.x * 16 + ( threadIdx.x >> 4 );
-  if ( v >= V ) return;
-  const uint32_t* row = adj + adjOff[v];
-  const uint32_t  len = rowLen[v];
-  for ( uint32_t i = lane; i < len; i += 16 ) atomicAdd( &rcount[row[i]], 1u );
-}
-
-__global__ __launch_bounds__( 256 ) void reverseFillKernel( const uint32_t* __restrict__ adjOff, const uint32_t* __restrict__ rowLen,
-                                                             const uint32_t* __restrict__ adj, uint32_t V,
-                                                             const uint32_t* __restrict__ roff, uint32_t* __restrict__ cursor,
-                                                             uint32_t* __restrict__ radj ) {
-  const int      lane = threadIdx.x & 15;
-  const uint32_t v    = blockIdx.x * 16 + ( threadIdx.x >> 4 );
-  if ( v >= V ) return;
-  const uint32_t* row = adj + adjOff[v];
-  const uint32_t  len = rowLen[v];
-  for ( uint32_t i = lane; i < len; i += 16 ) {
-    const uint32_t u                          = row[i];
-    radj[roff[u] + atomicAdd( &cursor[u], 1u )] = v;
-  }
 }
 
 __device__ __forceinline__ int argOfPacked( uint32_t s0, uint32_t s1, uint32_t s2 ) {
@@ -1138,7 +1047,7 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
                                                        const uint32_t* __restrict__ pointStart,
                                                        const uint32_t* __restrict__ pointList,
                                                        const double* __restrict__ normals, const uint32_t* __restrict__ roff,
-                                                       const uint32_t* __restrict__ rlen /* null: roff is a CSR of V + 1 offsets */,
+                                                       const uint32_t* __restrict__ rlen,
                                                        const uint32_t* __restrict__ radj, uint8_t* __restrict__ edge,
                                                        uint8_t* __restrict__ ppi, uint4* __restrict__ hist,
                                                        uint8_t* __restrict__ partition, uint32_t* __restrict__ flags, int iter, int pairedPush ) {
@@ -1226,7 +1135,7 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
         // borrows between the halves cancel in the final sums whatever the order of the adds
         const uint32_t d0 = h0 - h.x, d1 = h1 - h.y, d2 = h2 - h.z;
         if ( d0 | d1 | d2 ) {
-          const uint32_t rb = roff[v], re = rlen ? rb + rlen[v] : roff[v + 1];
+          const uint32_t rb = roff[v], re = rb + rlen[v];
           // (round 6: the first two words in ONE 64-bit add.  A word's difference is the true integer T = dHi * 65536 + dLo modulo
           //  2^32, and with fields below 2^15 -- pairedPush: maxNN + 255 < 32 768 -- |T| < 2^31, so T is d as an int32; adding
           //  T0 + T1 * 2^32 as a SIGNED 64-bit number to x + y * 2^32 is exact integer arithmetic on the pair: every true word stays
@@ -1267,8 +1176,8 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
 // refineSegmentationGridBased in two halves.  geometry(): everything that depends on the points alone -- voxels, points grouped
 // by voxel, neighbourhood rows -- queued without waiting for the last result; a frame's host thread runs it BEFORE the
 // sequential orientation walk (S3), so the device builds the rows while the host walks.  finish(): the rest (histograms of
-// the initial partition, sweeps).  The dense voxel table stays filled in between (no other stage of the frame's context
-// uses it); a job dropped half-way empties it again.
+// the initial partition, sweeps).  The context's occupancy bitmap stays filled in between (no other stage of the frame's
+// context uses it); a job dropped half-way empties it again.
 struct RefineJob {
   // parameters
   int    maxNNCount = 0, iterationCount = 0, voxDim = 0, searchRadius = 0;
@@ -1280,23 +1189,22 @@ struct RefineJob {
   uint32_t         n = 0, V = 0, W = 0, devStride = 32, totalLen = 0;
   int              devRange = 1, idBits = 26;
   Grid             g{};
-  std::vector<int> offsets;  // the ball: its ROWS (byRows) or its cells
-  uint32_t*        table = nullptr;
-  uint2*           bits  = nullptr;  // occupancy bitmap of the key table (.x; kept all-zero between frames) + ranks (.y)
-  bool             tableFilled = false, byRows = true;
+  std::vector<int> rows;  // the ball's rows (collectBall)
+  uint2*           bits       = nullptr;  // occupancy bitmap of the keys (.x; kept all-zero between frames) + ranks (.y)
+  bool             bitsFilled = false;
   int              capTier = 2;  // which instantiation of the neighbourhood kernels (launchNeighbourhood)
   size_t           Vp = 0, W2 = 0, ball = 0, perVoxel = 0;
   uint64_t         capacity = 0;
   uint32_t         res[5] = {0, 0, 0, 0, 0};  // the neighbourhood pass' answer: row entries written, overflow flag, reverse row entries, room asked for, kept hits out of room
   uint32_t         hitRegionCap = 0;
   DevBuf<uint32_t> d_key, d_flag, d_vid, d_small, d_count, d_rowLen, d_devLen, d_adjOff, d_hist, d_activeBuf, d_pointStart,
-      d_pointList, d_cursor, d_rcount, d_rcursor, d_lastRescore, d_flags, d_gbits, d_adj, d_dev, d_lastKey, d_roffG, d_rlenG, d_radjG,
+      d_pointList, d_cursor, d_lastRescore, d_flags, d_gbits, d_adj, d_dev, d_lastKey, d_roffG, d_rlenG, d_radjG,
       d_voxelOfRank, d_hitBuf, d_hitCtl, d_hitOff, d_hitLen, d_rowCtl;
   std::vector<uint32_t> rowCtlHost;  // the forward rows' region cursors, fetched with the pass' answer (their sum: the row entries)
   DevBuf<Pt>      d_centre;
   DevBuf<double>  d_weight;
   DevBuf<uint8_t> d_state;  // edge | ppi, V bytes each (padded to whole 32-voxel words)
-  const int*      d_offsets = nullptr;  // the ball's rows / cells: the context's table for ( radius, form )
+  const int*      d_rows = nullptr;  // the ball's rows: the context's table for the radius
   bool matches( int nn, double l, int it, int vd, int sr ) const {
     return nn == maxNNCount && l == lambda && it == iterationCount && vd == voxDim && sr == searchRadius;
   }
@@ -1313,9 +1221,9 @@ struct RefineJob {
 };
 
 RefineJob::~RefineJob() {
-  if ( tableFilled && bits && d_key.p ) {  // dropped between the halves: hand the context's bitmap (and table) back empty
+  if ( bitsFilled && d_key.p ) {  // dropped between the halves: hand the context's bitmap back empty
     ApiScope scope( ctx );
-    hipLaunchKernelGGL( tableCleanKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, s, d_key.p, n, table, bits );
+    hipLaunchKernelGGL( bitsCleanKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, s, d_key.p, n, bits );
     (void)hipStreamSynchronize( s );  // (the buffers go back to the pool when the members are destroyed)
   }
 }
@@ -1332,27 +1240,24 @@ inline int capTierFor( size_t cells ) {  // the smallest tier whose room holds `
   return t;
 }
 
-// forward rows and -- on the row-wise path -- the reverse rows behind them (d_small: [1] row cursor, [2] overflow, [3] reverse
-// row cursor, [4] with overflow code 3: the room the fullest ball asks for)
+// forward rows and the reverse rows behind them (d_small: [1] row cursor, [2] overflow, [3] reverse row cursor, [4] with
+// overflow code 3: the room the fullest ball asks for)
 void RefineJob::launchNeighbourhood() {
-  const int nBall = int( offsets.size() );  // rows or cells
+  const int nRows = int( rows.size() );
   const uint32_t rowRegionCap = uint32_t( capacity / kRowRegions );  // (the tables hold kRowRegions regions of this many entries)
   BallHits  savedHits{};
-  if ( byRows && d_hitBuf.p ) {
+  if ( d_hitBuf.p ) {
     savedHits.buf = d_hitBuf.p, savedHits.regionCap = hitRegionCap, savedHits.cursor = d_hitCtl.p, savedHits.off = d_hitOff.p, savedHits.len = d_hitLen.p;
   }
 #define TMC2_NEIGHBOURHOOD( CAP, WAVES )                                                                                       \
   hipLaunchKernelGGL( ( neighbourhoodKernel<CAP, WAVES> ), dim3( ( V + WAVES - 1 ) / WAVES ), dim3( 64 * WAVES ), 0, s, d_centre.p,      \
-                      d_count.p, table, g, V, d_offsets, nBall, maxNNCount, lambda, idBits, devRange, devStride,             \
+                      d_count.p, g, V, d_rows, nRows, maxNNCount, lambda, idBits, devRange, devStride,                      \
                       rowRegionCap, d_rowLen.p, d_devLen.p, d_weight.p, d_adjOff.p, d_adj.p, d_dev.p, d_rowCtl.p,            \
-                      d_small.p + 2, byRows ? bits : (const uint2*)nullptr, reinterpret_cast<const uint2*>( d_voxelOfRank.p ),   \
-                      byRows ? d_lastKey.p : (uint32_t*)nullptr, savedHits );                                                  \
-  if ( byRows )                                                                                                                \
+                      d_small.p + 2, bits, reinterpret_cast<const uint2*>( d_voxelOfRank.p ), d_lastKey.p, savedHits );      \
   hipLaunchKernelGGL( ( reverseRowsKernel<CAP, WAVES> ), dim3( ( V + WAVES - 1 ) / WAVES ), dim3( 64 * WAVES ), 0, s, d_centre.p, reinterpret_cast<const uint2*>( d_voxelOfRank.p ), \
-                      bits, g, V, d_offsets, nBall, idBits, d_lastKey.p, rowRegionCap, d_roffG.p, d_rlenG.p, d_radjG.p,          \
+                      bits, g, V, d_rows, nRows, idBits, d_lastKey.p, rowRegionCap, d_roffG.p, d_rlenG.p, d_radjG.p,          \
                       d_rowCtl.p + kRowRegions * 32, d_small.p + 2, savedHits )
-  // LDS per wavefront = room for the ball's OCCUPIED cells (row-wise form; a surface fills 5-10 % of a ball) or for all its
-  // cells; the smaller the room, the more wavefronts a CU holds (kCapTiers) -- a frame whose balls need more raises the overflow
+  // LDS per wavefront = room for the ball's OCCUPIED cells (a surface fills 5-10 % of a ball); the smaller the room, the more wavefronts a CU holds (kCapTiers) -- a frame whose balls need more raises the overflow
   // word to 3, says how much, and is repeated in the tier that holds it (remembered per context)
   switch ( capTier ) {
     case 0: TMC2_NEIGHBOURHOOD( 1024, 8 ); break;
@@ -1383,16 +1288,12 @@ int RefineJob::geometry( tmc2_frame* f ) {
   g.gridShift          = 0;
   for ( size_t i = gridDim; i > 1; ++g.gridShift, i >>= 1 ) {}
   g.half      = voxDim >> 1;
-  g.tableSize = 1u << ( 3 * g.gridShift + 1 );
+  g.keyCount  = 1u << ( 3 * g.gridShift + 1 );
   if ( g.gridShift > 9 ) {
     setError( "refineSegmentationGridBased: grid of 2^%d cells per axis unsupported", g.gridShift );
     return TMC2_E_UNSUPPORTED;
   }
   const int r2 = searchRadius >> g.voxShift;
-  // (test hook TMC2_REFINE_NEIGHBOURHOOD=cells: the rounds 1-3 form -- one table look-up per cell of the ball, reverse rows by
-  //  scattering the forward rows -- kept as the cross-check of the row-wise form)
-  const char* nbEnv = ctxOption( ctx, "REFINE_NEIGHBOURHOOD" );
-  byRows            = !( nbEnv && nbEnv[0] == 'c' );
   {
     int R = 0;
     while ( R * R < r2 ) ++R;
@@ -1404,9 +1305,8 @@ int RefineJob::geometry( tmc2_frame* f ) {
           if ( dx * dx + dy * dy + dz * dz < r2 ) {
             ++ball;
             xr = std::max( xr, dx );
-            if ( !byRows ) offsets.push_back( ( dx + 128 ) | ( ( dy + 128 ) << 8 ) | ( ( dz + 128 ) << 16 ) );
           }
-        if ( byRows && xr >= 0 ) offsets.push_back( ( dy + 128 ) | ( ( dz + 128 ) << 8 ) | ( xr << 16 ) );
+        if ( xr >= 0 ) rows.push_back( ( dy + 128 ) | ( ( dz + 128 ) << 8 ) | ( xr << 16 ) );
       }
   }
   if ( ball > 4096 - 160 || r2 > 128 ) {  // (the neighbourhood kernel keeps 160 words of its 2048 / 4096 for its own use)  // (search radius 192: r2 = 48 with voxels of 4, 96 with voxels of 2 -> 3 911 cells)
@@ -1417,16 +1317,8 @@ int RefineJob::geometry( tmc2_frame* f ) {
   devStride = devRange == 1 ? 32u : 128u;
   idBits    = r2 <= 64 ? 26 : 25;   // neighbourhood sort key: d2 above, voxel id below
   const int sidSetup = ctx->stageBegin( "refine_setup" );
-  table = nullptr;
-  if ( !byRows ) {  // the dense key table (2^(3s+1) words: 1 GiB with voxels of 2 or 11-bit geometry) only for the cell-by-cell form
-    if ( ctx->gridTable.count < g.tableSize ) {
-      TMC2_TRY( ctx->gridTable.alloc( g.tableSize ) );
-      TMC2_HIP( hipMemsetAsync( ctx->gridTable.p, 0xFF, size_t( g.tableSize ) * 4, s ) );
-    }
-    table = ctx->gridTable.p;
-  }
   {
-    const size_t bitWords = size_t( g.tableSize ) / 32 + 2;  // (+ spare words: a row's second word may lie behind the last key)
+    const size_t bitWords = size_t( g.keyCount ) / 32 + 2;  // (+ spare words: a row's second word may lie behind the last key)
     if ( ctx->gridBits.count < bitWords ) {
       TMC2_TRY( ctx->gridBits.alloc( bitWords ) );
       TMC2_HIP( hipMemsetAsync( ctx->gridBits.p, 0, bitWords * sizeof( uint2 ), s ) );
@@ -1438,13 +1330,13 @@ int RefineJob::geometry( tmc2_frame* f ) {
   TMC2_TRY( d_vid.alloc( n ) );
   TMC2_TRY( d_small.alloc( 16 ) );  // [0] voxel count, [1] adjacency size, [2] closure flag
   const dim3 blk( 256 ), grdN( ( n + 255 ) / 256 );
-  tableFilled = true;
-  hipLaunchKernelGGL( voxelKeyKernel, grdN, blk, 0, s, f->d_pts.p, n, g, d_key.p, table, bits );
+  bitsFilled = true;
+  hipLaunchKernelGGL( voxelKeyKernel, grdN, blk, 0, s, f->d_pts.p, n, g, d_key.p, bits );
   DevBuf<uint32_t> d_firstPoint;
-  if ( byRows ) {
+  {
     // ranks of the occupied keys (the words' prefix sums), then the first point of every rank: the voxels are numbered through
-    // them -- and the row-wise neighbourhood passes look voxels up by them
-    const uint32_t   words  = g.tableSize / 32 + 2;
+    // them -- and the neighbourhood passes look voxels up by them
+    const uint32_t   words  = g.keyCount / 32 + 2;
     const uint32_t   blocks = ( words + kBitsBlock - 1 ) / kBitsBlock;
     DevBuf<uint32_t> d_blockTotal, d_blockBase;
     TMC2_TRY( d_blockTotal.alloc( blocks ) );
@@ -1456,7 +1348,7 @@ int RefineJob::geometry( tmc2_frame* f ) {
     hipLaunchKernelGGL( bitsPrefixKernel, dim3( blocks ), blk, 0, s, bits, words, d_blockBase.p );
     hipLaunchKernelGGL( firstPointKernel, grdN, blk, 0, s, d_key.p, n, bits, d_firstPoint.p );
   }
-  hipLaunchKernelGGL( firstFlagKernel, grdN, blk, 0, s, d_key.p, table, bits, d_firstPoint.p, n, d_flag.p );
+  hipLaunchKernelGGL( firstFlagKernel, grdN, blk, 0, s, d_key.p, bits, d_firstPoint.p, n, d_flag.p );
   DevBuf<uint32_t> d_rank;
   TMC2_TRY( d_rank.alloc( n ) );
   volatile uint32_t* answer = ctx->answerLine( tmc2_ctx::kAnswerRefineVoxels );  // (the voxel count straight to a page-locked word: no copy)
@@ -1483,8 +1375,6 @@ int RefineJob::geometry( tmc2_frame* f ) {
   TMC2_TRY( d_pointList.alloc( n ) );
   TMC2_TRY( d_cursor.alloc( V ) );
   TMC2_TRY( d_flags.alloc( 2 * size_t( iterationCount ) + 2 ) );
-  TMC2_TRY( d_rcount.alloc( size_t( V ) + 1 ) );
-  TMC2_TRY( d_rcursor.alloc( size_t( V ) + 1 ) );
   TMC2_TRY( d_lastRescore.alloc( V ) );
   TMC2_TRY( d_gbits.alloc( closureZeroWords + V ) );
   TMC2_TRY( fillRegions( ctx, {{d_count.p, ( size_t( V ) + 1 ) * 4, 0},
@@ -1493,22 +1383,16 @@ int RefineJob::geometry( tmc2_frame* f ) {
                                {d_cursor.p, size_t( V ) * 4, 0},
                                {d_small.p + 1, 20, 0},  // [1] row cursor, [2] overflow, [3] reverse row cursor, [4] room asked for, [5] kept hits out of room
                                {d_flags.p, ( 2 * size_t( iterationCount ) + 2 ) * 4, 0},
-                               {d_rcount.p, ( size_t( V ) + 1 ) * 4, 0},
-                               {d_rcursor.p, ( size_t( V ) + 1 ) * 4, 0},
                                {d_lastRescore.p, size_t( V ) * 4, 0},
                                {d_gbits.p, closureZeroWords * 4, 0},
                                {d_gbits.p + closureZeroWords, size_t( V ) * 4, 0xFF}} ) );  // kNoVoxel
-  d_offsets = ctx->constTable( ( uint64_t( 0x5335 ) << 32 ) | ( uint64_t( r2 ) << 1 ) | ( byRows ? 1u : 0u ), offsets );
-  if ( !d_offsets ) return TMC2_E_HIP;
-  hipLaunchKernelGGL( assignVoxelKernel, grdN, blk, 0, s, f->d_pts.p, d_key.p, table, bits, d_firstPoint.p, d_rank.p, n, g, d_vid.p,
+  d_rows = ctx->constTable( ( uint64_t( 0x5335 ) << 32 ) | uint64_t( r2 ), rows );
+  if ( !d_rows ) return TMC2_E_HIP;
+  hipLaunchKernelGGL( assignVoxelKernel, grdN, blk, 0, s, f->d_pts.p, d_key.p, bits, d_firstPoint.p, d_rank.p, n, g, d_vid.p,
                       d_count.p, d_centre.p );
-  if ( byRows ) {
-    TMC2_TRY( d_voxelOfRank.alloc( 2 * size_t( V ) ) );  // (uint2 records)
-    hipLaunchKernelGGL( rankToVoxelKernel, grdN, blk, 0, s, d_key.p, d_flag.p, d_vid.p, n, bits, reinterpret_cast<uint2*>( d_voxelOfRank.p ), d_count.p,
-                        d_centre.p );
-  } else {
-    hipLaunchKernelGGL( tableToVoxelKernel, grdN, blk, 0, s, d_key.p, d_flag.p, d_vid.p, n, table );
-  }
+  TMC2_TRY( d_voxelOfRank.alloc( 2 * size_t( V ) ) );  // (uint2 records)
+  hipLaunchKernelGGL( rankToVoxelKernel, grdN, blk, 0, s, d_key.p, d_flag.p, d_vid.p, n, bits, reinterpret_cast<uint2*>( d_voxelOfRank.p ), d_count.p,
+                      d_centre.p );
   // points grouped by voxel, for the re-scoring pass
   TMC2_TRY( exclusiveScanU32( ctx, d_count.p, d_pointStart.p, size_t( V ) + 1, nullptr ) );
   hipLaunchKernelGGL( voxelPointListKernel, grdN, blk, 0, s, d_vid.p, d_pointStart.p, n, d_cursor.p, d_pointList.p );
@@ -1519,29 +1403,29 @@ int RefineJob::geometry( tmc2_frame* f ) {
     return TMC2_E_UNSUPPORTED;
   }
   TMC2_TRY( d_dev.alloc( size_t( V ) * devStride ) );
-  const char* capEnv  = ctxOption( ctx, "REFINE_ROWCAP" );
+  const auto capEnv   = ctxOption( ctx, "REFINE_ROWCAP" );
   perVoxel            = std::min<size_t>( ball, 2 * size_t( maxNNCount > 0 ? maxNNCount : 1 ) * V / std::max<uint32_t>( n, 1u ) + 32 );
-  if ( capEnv && capEnv[0] == 't' ) perVoxel = 1;
+  if ( capEnv && ( *capEnv )[0] == 't' ) perVoxel = 1;
   capacity = rowTableEntries( perVoxel );
   if ( capacity > 0xFFFFFFFFull ) {
     setError( "refineSegmentationGridBased: %u voxels x %zu row entries exceed the neighbourhood table", V, perVoxel );
     return TMC2_E_UNSUPPORTED;
   }
-  capTier = std::max( capTierFor( ball ), 3 );  // (the cell-by-cell form keeps every cell of the ball: the tiers of rounds 4-5)
-  if ( byRows ) capTier = std::min( capTier, std::max( 0, ctx->refineCapTier ) );  // (test hook TMC2_REFINE_CAPTIER: start there)
-  if ( const char* tierEnv = ctxOption( ctx, "REFINE_CAPTIER" ) ) capTier = std::min( kLastCapTier, std::max( byRows ? 0 : capTier, atoi( tierEnv ) ) );
+  // the tier this context's frames have needed so far, at most one that holds the whole ball (test hook TMC2_REFINE_CAPTIER: start there)
+  capTier = std::min( std::max( capTierFor( ball ), 3 ), std::max( 0, ctx->refineCapTier ) );
+  if ( const auto tierEnv = ctxOption( ctx, "REFINE_CAPTIER" ) ) capTier = std::min( kLastCapTier, std::max( 0, atoi( tierEnv->c_str() ) ) );
   TMC2_TRY( d_adj.alloc( size_t( capacity ) ) );
-  if ( byRows ) {  // the reverse rows hold the same entries as the forward rows: same room
-    TMC2_TRY( d_lastKey.alloc( V ) );
-    TMC2_TRY( d_roffG.alloc( V ) );
-    TMC2_TRY( d_rlenG.alloc( V ) );
-    TMC2_TRY( d_radjG.alloc( size_t( capacity ) ) );
-    // the balls' hits, kept for the reverse rows pass (option REFINE_HITS=0: it collects the balls again, as rounds 4-5 did;
-    // =tiny: a region runs out of room and says so -- the same).  Room: what this context's frames have needed, a surface's ~ 500
-    // of the 3 911 cells of a ball of voxels of 2 to begin with.
-    const char*  hitsEnv = ctxOption( ctx, "REFINE_HITS" );
-    const size_t perHit  = hitsEnv && hitsEnv[0] == 't' ? 1 : std::min<size_t>( ball, size_t( ctx->refineHitsPerVoxel ) );
-    if ( !( hitsEnv && hitsEnv[0] == '0' ) && uint64_t( V ) * perHit < 0xFFFFFFFFull ) {
+  TMC2_TRY( d_lastKey.alloc( V ) );
+  TMC2_TRY( d_roffG.alloc( V ) );  // the reverse rows hold the same entries as the forward rows: same room
+  TMC2_TRY( d_rlenG.alloc( V ) );
+  TMC2_TRY( d_radjG.alloc( size_t( capacity ) ) );
+  {
+    // the balls' hits, kept for the reverse rows pass (option REFINE_HITS=tiny: a region runs out of room and says so -- the
+    // reverse rows pass then collects the balls again).  Room: what this context's frames have needed, a surface's ~ 500 of the
+    // 3 911 cells of a ball of voxels of 2 to begin with.
+    const auto   hitsEnv = ctxOption( ctx, "REFINE_HITS" );
+    const size_t perHit  = hitsEnv && ( *hitsEnv )[0] == 't' ? 1 : std::min<size_t>( ball, size_t( ctx->refineHitsPerVoxel ) );
+    if ( uint64_t( V ) * perHit < 0xFFFFFFFFull ) {
       hitRegionCap = uint32_t( ( uint64_t( V ) * perHit + kHitRegions - 1 ) / kHitRegions );
       TMC2_TRY( d_hitBuf.alloc( size_t( hitRegionCap ) * kHitRegions ) );
       TMC2_TRY( d_hitCtl.alloc( kHitRegions * 32 ) );
@@ -1600,7 +1484,7 @@ int RefineJob::finish() {
       return TMC2_E_UNSUPPORTED;
     }
     TMC2_TRY( d_adj.alloc( size_t( capacity ) ) );
-    if ( byRows ) TMC2_TRY( d_radjG.alloc( size_t( capacity ) ) );
+    TMC2_TRY( d_radjG.alloc( size_t( capacity ) ) );
     TMC2_HIP( hipMemsetAsync( d_small.p + 1, 0, 20, s ) );  // [1] row cursor, [2] overflow, [3] reverse row cursor, [4] room asked for, [5] kept hits out of room
     if ( d_hitCtl.p ) TMC2_HIP( hipMemsetAsync( d_hitCtl.p, 0, kHitRegions * 32 * 4, s ) );
     TMC2_HIP( hipMemsetAsync( d_rowCtl.p, 0, 2 * kRowRegions * 32 * 4, s ) );
@@ -1609,27 +1493,17 @@ int RefineJob::finish() {
     TMC2_HIP( hipMemcpyAsync( rowCtlHost.data(), d_rowCtl.p, kRowRegions * 32 * 4, hipMemcpyDeviceToHost, s ) );
   }
   d_hitBuf.release(), d_hitCtl.release(), d_hitOff.release(), d_hitLen.release();  // (both passes over the balls are done: the stream was synchronised above)
-  hipLaunchKernelGGL( tableCleanKernel, grdN, blk, 0, s, d_key.p, n, table, bits );
-  tableFilled = false;
+  hipLaunchKernelGGL( bitsCleanKernel, grdN, blk, 0, s, d_key.p, n, bits );
+  bitsFilled = false;
   hipLaunchKernelGGL( histAccumulateKernel, grdN, blk, 0, s, d_vid.p, f->d_partition.p, (const uint8_t*)nullptr, n,
                       d_hist.p );
   hipLaunchKernelGGL( initVoxelStateKernel, grdV, blk, 0, s, reinterpret_cast<const uint4*>( d_hist.p ), d_count.p, V,
                       d_edge, d_ppi, d_active );
-  // reverse rows (CSR), S records (double-buffered), epochs, closure scratch
-  DevBuf<uint32_t> d_roff, d_radj, d_lists;
+  // S records (double-buffered), epochs, closure scratch (the reverse rows were gathered behind the forward rows)
+  DevBuf<uint32_t> d_lists;
   DevBuf<uint4>    d_rec;
   TMC2_TRY( d_lists.alloc( size_t( kSubLists ) * V ) );  // (a voxel is listed once per sweep: any sub-list can hold them all)
   TMC2_TRY( d_rec.alloc( 2 * size_t( V ) ) );
-  const uint32_t *revOff = d_roffG.p, *revLen = d_rlenG.p, *revAdj = d_radjG.p;  // gathered behind the forward rows
-  if ( !byRows ) {  // the rounds 1-3 form: count, prefix sum, scatter
-    TMC2_TRY( d_roff.alloc( size_t( V ) + 1 ) );
-    TMC2_TRY( d_radj.alloc( std::max<size_t>( totalLen, 1 ) ) );
-    hipLaunchKernelGGL( reverseCountKernel, grdV16, blk, 0, s, d_adjOff.p, d_rowLen.p, d_adj.p, V, d_rcount.p );
-    TMC2_TRY( exclusiveScanU32( ctx, d_rcount.p, d_roff.p, size_t( V ) + 1, nullptr ) );
-    hipLaunchKernelGGL( reverseFillKernel, grdV16, blk, 0, s, d_adjOff.p, d_rowLen.p, d_adj.p, V, d_roff.p, d_rcursor.p,
-                        d_radj.p );
-    revOff = d_roff.p, revLen = nullptr, revAdj = d_radj.p;
-  }
   hipLaunchKernelGGL( smoothInitKernel, grdV16, blk, 0, s, reinterpret_cast<const uint4*>( d_hist.p ), d_adjOff.p,
                       d_rowLen.p, d_adj.p, V, d_rec.p );
   ctx->stageEnd( sidSetup );
@@ -1638,27 +1512,27 @@ int RefineJob::finish() {
   // closureKernel: a run of voxels per workgroup; LDS = the run's active voxels + the ring
   // (test hooks: TMC2_REFINE_CLOSURE_BLOCKS = its grid, TMC2_REFINE_CLOSURE_THREADS = its workgroup; TMC2_REFINE_RING = room
   // of the LDS ring beyond the run -- 1 sends nearly every fan-out through the spill ring)
-  const char*    gridEnv    = ctxOption( ctx, "REFINE_CLOSURE_BLOCKS" );
-  const char*    threadsEnv = ctxOption( ctx, "REFINE_CLOSURE_THREADS" );
-  const char*    ringEnv    = ctxOption( ctx, "REFINE_RING" );
+  const auto     gridEnv    = ctxOption( ctx, "REFINE_CLOSURE_BLOCKS" );
+  const auto     threadsEnv = ctxOption( ctx, "REFINE_CLOSURE_THREADS" );
+  const auto     ringEnv    = ctxOption( ctx, "REFINE_RING" );
   // (round 6, sixteen in flight, this round's kernels around it -- profiles/r06_knobs_in_flight.txt: two workgroups per CU of 512 /
   //  256 / 128 threads -> 186.2-188.4 / 191.3-192.4 / 187.5 frames/s; one per CU of 256: 190.4; four of 256: 190.0 -- half the
   //  idle waves of rounds 3-5 for the many-in-flight regime, the walk's deepest chain is what a launch takes either way)
-  const int      closureThreads = threadsEnv ? std::min( 1024, std::max( 64, atoi( threadsEnv ) & ~63 ) ) : ( refineOverlap( ctx ) ? 512 : 256 );
+  const int      closureThreads = threadsEnv ? std::min( 1024, std::max( 64, atoi( threadsEnv->c_str() ) & ~63 ) ) : ( refineOverlap( ctx ) ? 512 : 256 );
   const uint32_t perGroup   = 4;  // voxels of the run per 32-lane group
-  const uint32_t wantGrid   = gridEnv ? uint32_t( std::max( 1, atoi( gridEnv ) ) )
+  const uint32_t wantGrid   = gridEnv ? uint32_t( std::max( 1, atoi( gridEnv->c_str() ) ) )
                                       : std::min<uint32_t>( ( refineOverlap( ctx ) ? 4u : 2u ) * uint32_t( ctx->cuCount ),
                                                             ( V + perGroup * ( closureThreads / 32 ) - 1 ) / ( perGroup * ( closureThreads / 32 ) ) );
   // (two workgroups per CU: 8 % slower alone than four and 3 % more frames per second with sixteen frames in flight -- a
   // workgroup's groups idle through most of the walk, and idle waves are in the way of the other frames' kernels)
   const uint32_t run        = std::min<uint32_t>( 8192u, std::max<uint32_t>( 1u, ( V + wantGrid - 1 ) / wantGrid ) );
   const dim3     grdClosure( ( V + run - 1 ) / run );
-  const uint32_t ringCap    = run + ( ringEnv ? uint32_t( std::min( 8192, std::max( 1, atoi( ringEnv ) ) ) ) : 1024u );
+  const uint32_t ringCap    = run + ( ringEnv ? uint32_t( std::min( 8192, std::max( 1, atoi( ringEnv->c_str() ) ) ) ) : 1024u );
   const size_t   closureLds = 4 * ( size_t( run ) + ringCap );
   if ( closureLds > 48 * 1024 ) TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( closureKernel ), closureLds, ctx->device ) );
   // (test hook TMC2_REFINE_SWEEP_BLOCKS: the sweep kernel's grid)
-  const char* sweepGridEnv = ctxOption( ctx, "REFINE_SWEEP_BLOCKS" );
-  const dim3  grdSweep( uint32_t( std::min<size_t>( ( size_t( V ) + 15 ) / 16, sweepGridEnv ? size_t( std::max( 1, atoi( sweepGridEnv ) ) ) : size_t( refineOverlap( ctx ) ? 8 : 2 ) * ctx->cuCount ) ) );
+  const auto  sweepGridEnv = ctxOption( ctx, "REFINE_SWEEP_BLOCKS" );
+  const dim3  grdSweep( uint32_t( std::min<size_t>( ( size_t( V ) + 15 ) / 16, sweepGridEnv ? size_t( std::max( 1, atoi( sweepGridEnv->c_str() ) ) ) : size_t( refineOverlap( ctx ) ? 8 : 2 ) * ctx->cuCount ) ) );
   // (tmc2_set_refine_overlap( 1 ) = "few frames in flight": the chip has room, so both kernels of a sweep take the grids that
   //  are fastest with the GPU to themselves -- four closure workgroups and eight sweep workgroups per CU)
   // (round 4 sweep over the grids, 16 frames in flight / one sweep alone: sweep kernel 2 / 4 / 8 / 16 workgroups per CU ->
@@ -1669,11 +1543,11 @@ int RefineJob::finish() {
   //  longdress 189.2 / 191.7 / 191.8 frames/s -- two per CU)
   // (the sweep's pushes: two words of a target in one 64-bit add where the histogram fields stay below 2^15 -- a row holds at most
   //  maxNN + 255 members; option REFINE_PUSH=words: three 32-bit adds, as rounds 2-5)
-  const char* pushEnv    = ctxOption( ctx, "REFINE_PUSH" );
-  const int   pairedPush = maxNNCount + 255 < 32768 && !( pushEnv && pushEnv[0] == 'w' ) ? 1 : 0;
-  const bool wantTrace = ctxOption( ctx, "REFINE_TRACE" ) != nullptr;
+  const auto pushEnv    = ctxOption( ctx, "REFINE_PUSH" );
+  const int  pairedPush = maxNNCount + 255 < 32768 && !( pushEnv && ( *pushEnv )[0] == 'w' ) ? 1 : 0;
+  const bool wantTrace = ctxOption( ctx, "REFINE_TRACE" ).has_value();
   DevBuf<unsigned long long> d_timing;  // test hook TMC2_REFINE_TIMING: where the closure spends its time, per sweep
-  const bool                 wantTiming = ctxOption( ctx, "REFINE_TIMING" ) != nullptr;
+  const bool                 wantTiming = ctxOption( ctx, "REFINE_TIMING" ).has_value();
   if ( wantTiming ) {
     TMC2_TRY( d_timing.alloc( 8 * size_t( iterationCount ) ) );
     TMC2_HIP( hipMemsetAsync( d_timing.p, 0, 64 * size_t( iterationCount ), s ) );
@@ -1687,7 +1561,7 @@ int RefineJob::finish() {
   // (Measured and dropped, twice: the 2 I launches of the loop as ONE hipGraph per frame -- round 5, option REFINE_GRAPH, removed in
   //  round 6 -- and as ONE kernel whose phases take their work by ticket -- round 6, profiles/r06_one_launch_sweeps.txt.  The loop has no
   //  host decision in it, but what sixteen frames in flight share is wave-slot time, not launches: DESIGN.md section 5.)
-  const bool      debugSweeps = ctxOption( ctx, "REFINE_DEBUG" ) != nullptr;
+  const bool      debugSweeps = ctxOption( ctx, "REFINE_DEBUG" ).has_value();
   for ( int iter = 0; iter < iterationCount; ++iter ) {
     const int cur    = iter & 1, nxt = cur ^ 1;
     uint4 *   recCur = d_rec.p + size_t( cur ) * V, *recNxt = d_rec.p + size_t( nxt ) * V;
@@ -1699,7 +1573,7 @@ int RefineJob::finish() {
       fprintf( stderr, "refine: sweep %d closure done (%d), %u workgroups of %d, run %u, ring %u\n", iter, int( e ), grdClosure.x, closureThreads, run, ringCap );
     }
     hipLaunchKernelGGL( sweepKernel, grdSweep, blk, 0, s, d_lists.p, V, counts[cur], state[cur], recCur, recNxt,
-                        d_lastRescore.p, d_weight.p, d_pointStart.p, d_pointList.p, f->d_normals.p, revOff, revLen, revAdj, d_edge,
+                        d_lastRescore.p, d_weight.p, d_pointStart.p, d_pointList.p, f->d_normals.p, d_roffG.p, d_rlenG.p, d_radjG.p, d_edge,
                         d_ppi, reinterpret_cast<uint4*>( d_hist.p ), f->d_partition.p, wantTrace ? d_flags.p : nullptr, iter, pairedPush );
     if ( debugSweeps ) {
       const hipError_t e = hipStreamSynchronize( s );

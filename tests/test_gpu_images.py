@@ -152,15 +152,12 @@ def test_gpu_transfer_colors_long_candidate_lists(gpu_ctx, oracle):
         assert np.array_equal(gpu_ctx.transfer_colors(xyz, rgb, tgt), oracle.transfer_colors(xyz, rgb, tgt))
 
 
-@pytest.mark.parametrize("split", [None, "0"])
-def test_gpu_transfer_colors_identical_points_and_duplicates(gpu_ctx, oracle, ctx_options, split):
+def test_gpu_transfer_colors_identical_points_and_duplicates(gpu_ctx, oracle):
     """Round 6: both searches of the colour transfer run in two launches -- the queries that have an identical point in the tree
-    first (bound 0), then the compacted rest (TMC2_KNN_SPLIT=0: one launch, as before).  The cases that decide whether the first
+    first (bound 0), then the compacted rest.  The cases that decide whether the first
     pass is exact: targets that ARE source points, targets that are not, DUPLICATE positions with different colours in the source
     and in the target (which of several identical points the reference returns is the traversal's order), targets on split planes
     (coordinates equal to many others along an axis), a target cloud that is all duplicates of one point."""
-    if split:
-        ctx_options.setenv("TMC2_KNN_SPLIT", split)
     rng = np.random.default_rng(17)
     for case in range(4):
         xyz, rgb = synth_cloud("small", case)
@@ -184,7 +181,7 @@ def test_gpu_transfer_colors_identical_points_and_duplicates(gpu_ctx, oracle, ct
             rgb = np.concatenate([rgb, rng.integers(0, 256, (len(slab) + len(slab[::3]), 3)).astype(np.uint8)])
             tgt = np.concatenate([tgt, slab[::2], slab[::5]])
         tgt = tgt[rng.permutation(len(tgt))]
-        assert np.array_equal(gpu_ctx.transfer_colors(xyz, rgb, tgt), oracle.transfer_colors(xyz, rgb, tgt)), (case, split)
+        assert np.array_equal(gpu_ctx.transfer_colors(xyz, rgb, tgt), oracle.transfer_colors(xyz, rgb, tgt)), case
     one = np.repeat(xyz[:1], 500, 0)
     assert np.array_equal(gpu_ctx.transfer_colors(xyz, rgb, one), oracle.transfer_colors(xyz, rgb, one)), "all targets one point"
 

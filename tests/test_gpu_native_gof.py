@@ -237,16 +237,16 @@ def test_gpu_native_gof_sharded_over_the_gpus_of_this_box(tmp_path):
 @pytest.mark.gpu
 def test_gpu_two_contexts_two_sets_of_options():
     """Options are per context (tmc2_ctx_set_option): two contexts of one process build the same tree through different forms of
-    the piece kernel, and the environment is read once, when a context is created."""
+    the decide pass, and the environment is read once, when a context is created."""
     import os
     xyz, _ = synth_cloud("medium")
     a = T.Context(0)
-    os.environ["TMC2_KD_PIECE_PER"] = "8"
+    os.environ["TMC2_KD_DECIDE"] = "global"
     try:
         b = T.Context(0)
     finally:
-        del os.environ["TMC2_KD_PIECE_PER"]
-    assert a.get_option("KD_PIECE_PER") is None and b.get_option("KD_PIECE_PER") == "8"
+        del os.environ["TMC2_KD_DECIDE"]
+    assert a.get_option("KD_DECIDE") is None and b.get_option("KD_DECIDE") == "global"
     a.set_option("TMC2_KD_HUGEMAX", 4096)                      # (the prefix is accepted)
     assert a.get_option("KD_HUGEMAX") == "4096"
     fa, fb = a.frame(xyz), b.frame(xyz)

@@ -122,13 +122,13 @@ def test_gpu_kdtree_order_matches_reference_build(gpu_ctx, oracle, ctx_options, 
 
 
 @pytest.mark.parametrize("option,value,case", [("KD_DECIDE", "global", "n40000"), ("KD_DECIDE", "global", "dense120000"),
-                                               ("KD_PIECE_PER", "8", "root30000"), ("KD_HUGEMAX", "4096", "dense120000"),
+                                               ("KD_HUGEMAX", "4096", "dense120000"),
                                                ("KD_HUGEMAX", "65536", "dense120000"), ("KD_HUGEMAX", "4096", "n40000")])
 def test_gpu_kdtree_cross_check_forms(gpu_ctx, ctx_options, option, value, case):
     """The forms of the device builder that are not the default -- the decide pass folding through global memory (what a level of
-    more than 2 000 segments takes), eight positions per thread in the piece kernel, no workgroup-per-segment tier / a larger one
-    -- leave the host builder's permutation too.  (Round 4's tiers and level passes, options KD_FORM / KD_LEVELS of round 5, left
-    the library in round 6: the host builder and the oracle are the cross-checks.)"""
+    more than 2 000 segments takes), no workgroup-per-segment tier / a larger one -- leave the host builder's permutation too.
+    (Round 4's tiers and level passes, options KD_FORM / KD_LEVELS of round 5, and the piece kernel with eight positions per
+    thread have left the library: the host builder and the oracle are the cross-checks.)"""
     rng = np.random.default_rng(11)
     n = int("".join(ch for ch in case if ch.isdigit()))
     xyz = rng.integers(0, 24 if case.startswith("dense") else 1024, (n, 3)).astype(np.int16)
@@ -243,16 +243,12 @@ def test_gpu_refine_key_aliasing(gpu_ctx, oracle):
 
 
 @pytest.mark.parametrize("vox_dim", [4, 2])
-@pytest.mark.parametrize("form", ["cells", "rows-tier1", "rows-tier2", "rows-tier3", "rows-tier4"])
+@pytest.mark.parametrize("form", ["rows-tier1", "rows-tier2", "rows-tier3", "rows-tier4"])
 def test_gpu_refine_neighbourhood_forms(gpu_ctx, oracle, ctx_options, vox_dim, form):
-    """S5's neighbourhood rows two ways -- row-wise through the occupancy bitmap with gathered reverse rows (round 4, default)
-    and cell by cell with scattered reverse rows (rounds 1-3, TMC2_REFINE_NEIGHBOURHOOD=cells) -- and in every LDS tier of the
-    row-wise kernels: same bits as the reference's refinement.  A cloud with coordinates at the top of the range, so that
-    voxel keys alias in both."""
-    if form == "cells":
-        ctx_options.setenv("TMC2_REFINE_NEIGHBOURHOOD", "cells")
-    else:
-        ctx_options.setenv("TMC2_REFINE_CAPTIER", form[-1])
+    """S5's neighbourhood rows -- row-wise through the occupancy bitmap with gathered reverse rows (round 4) -- in every LDS tier
+    of the kernels: same bits as the reference's refinement.  A cloud with coordinates at the top of the range, so that voxel
+    keys alias.  (The cell-by-cell form of rounds 1-3 with scattered reverse rows was removed; the oracle is the cross-check.)"""
+    ctx_options.setenv("TMC2_REFINE_CAPTIER", form[-1])
     for shift_to_top in (False, True):
         xyz, _ = synth_cloud("small")
         if shift_to_top:
@@ -282,11 +278,11 @@ def test_gpu_refine_push_as_three_words(oracle, ctx_options, gpu_ctx, vox_dim):
 
 
 @pytest.mark.parametrize("vox_dim", [4, 2])
-@pytest.mark.parametrize("hits", ["0", "tiny"])
+@pytest.mark.parametrize("hits", ["tiny"])
 def test_gpu_refine_reverse_rows_without_the_kept_hits(oracle, ctx_options, gpu_ctx, vox_dim, hits):
     """Round 6: the forward pass over the balls keeps every ball's hits and the reverse rows pass reads them instead of collecting
-    the balls again.  TMC2_REFINE_HITS=0 switches that off (rounds 4-5), =tiny leaves the kept hits no room: a region says so, the
-    reverse rows pass collects the balls itself, and the context gives its next frames more room -- same bits either way."""
+    the balls again.  TMC2_REFINE_HITS=tiny leaves the kept hits no room: a region says so, the reverse rows pass collects the
+    balls itself, and the context gives its next frames more room -- same bits."""
     ctx_options.setenv("TMC2_REFINE_HITS", hits)
     xyz, _ = synth_cloud("small")
     nrm = oracle.normals(xyz)

@@ -107,17 +107,16 @@ def test_host_orientation_disconnected_components(oracle):
     assert np.array_equal(bits(T.host_orient_normals(two, knn, raw)), bits(oracle.orient_normals(two, knn, raw)))
 
 
-def test_host_orientation_compact_and_per_point_walks_agree(oracle, monkeypatch):
+def test_host_orientation_compact_and_per_point_walks_agree(oracle):
     """The walk over the compact contracted graph (clusters numbered by first member, per pair of clusters the light edges of
-    largest |n_u . n_v| + one strong edge per sign: what the device hands to the host) and the walk over the full cross-edge
-    list with per-point arrays give the reference's normals on a 180 K-point cloud with several components."""
+    largest |n_u . n_v| + one strong edge per sign: what the device hands to the host) gives the reference's normals on a
+    180 K-point cloud with several components.  (The walk over the full cross-edge list with per-point arrays it was once
+    compared with has been removed.)"""
     xyz, _ = synth_cloud("medium")
     two = np.unique(np.concatenate([xyz, (xyz[::3] // 2 + np.array([700, 20, 40])).astype(np.int16)]), axis=0)
     knn = oracle.knn_self(two, 16)
     raw = oracle.compute_normals(two, knn)
     exp = oracle.orient_normals(two, knn, raw)
-    assert np.array_equal(bits(T.host_orient_normals(two, knn, raw)), bits(exp))
-    monkeypatch.setenv("TMC2_ORIENT_HOST_WALK", "points")
     assert np.array_equal(bits(T.host_orient_normals(two, knn, raw)), bits(exp))
 
 
