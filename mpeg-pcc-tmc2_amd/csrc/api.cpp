@@ -592,6 +592,50 @@ bool unionCheck( const tmc2_ctx* ctx ) {
 }
 void setRefineOverlapDefault( int on ) { g_refineOverlap.store( on ? 1 : 0, std::memory_order_relaxed ); }
 void setKdtreePlacement( int mode ) { g_kdtreeOnHost.store( mode < 0 || mode > 2 ? 0 : mode, std::memory_order_relaxed ); }
+int buildKdTreePlaced( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, const int16_t* hostXyz, const char* stage, DeviceTree& tree ) {
+  const int placement = kdtreePlacement( ctx );
+  // adaptive: take a host slot if one is free right now, otherwise the device builds it (same tree either way)
+  HostGate gate( ctx, placement == 1 );
+  if ( placement == 0 || !gate.held ) {
+    const int sid = ctx->stageBegin( stage );
+    TMC2_TRY( buildKdTreeDevice( ctx, d_pts, n, tree ) );
+    ctx->stageEnd( sid );
+    return TMC2_OK;
+  }
+  // built in page-locked staging (the orientation's row / sign staging is idle at this point) and uploaded as is
+  Pt*       hp = ctx->hostD.get<Pt>( n );
+  uint32_t* hi = ctx->hostA.get<uint32_t>( n );
+  if ( !hp || !hi ) {
+    setError( "kdtree: hipHostMalloc failed" );
+    return TMC2_E_HIP;
+  }
+  hipStream_t s = ctx->stream;
+  if ( !hostXyz ) {  // (the read-back is not part of the host stage)
+    TMC2_HIP( hipMemcpyAsync( hp, d_pts, n * sizeof( Pt ), hipMemcpyDeviceToHost, s ) );
+    TMC2_HIP( hipStreamSynchronize( s ) );
+  }
+  KdTreeHost host;
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    if ( hostXyz )
+      for ( uint64_t i = 0; i < n; ++i ) hp[i] = Pt{hostXyz[3 * size_t( i )], hostXyz[3 * size_t( i ) + 1], hostXyz[3 * size_t( i ) + 2], 0};
+    host.buildInPlace( hp, hi, n );
+    const auto t1 = std::chrono::steady_clock::now();
+    ctx->stageAddHostMs( ( std::string( stage ) + "_host" ).c_str(), std::chrono::duration<double, std::milli>( t1 - t0 ).count() );
+  }
+  gate.release();
+  TMC2_TRY( tree.ptsTree.alloc( n ) );
+  TMC2_TRY( tree.perm.alloc( n ) );
+  TMC2_TRY( tree.nodes.alloc( host.nodes.size() ) );
+  TMC2_HIP( hipMemcpyAsync( tree.ptsTree.p, hp, n * sizeof( Pt ), hipMemcpyHostToDevice, s ) );
+  TMC2_HIP( hipMemcpyAsync( tree.perm.p, hi, n * sizeof( uint32_t ), hipMemcpyHostToDevice, s ) );
+  TMC2_HIP( hipMemcpyAsync( tree.nodes.p, host.nodes.data(), host.nodes.size() * sizeof( KdNode ), hipMemcpyHostToDevice, s ) );
+  TMC2_HIP( hipStreamSynchronize( s ) );
+  for ( int d = 0; d < 3; ++d ) tree.lo[d] = host.lo[d], tree.hi[d] = host.hi[d];
+  tree.depth = host.depth;
+  tree.n     = n;
+  return TMC2_OK;
+}
 }  // namespace tmc2
 
 const int* tmc2_ctx::constTable( uint64_t key, const std::vector<int>& host ) {
@@ -616,39 +660,7 @@ const int* tmc2_ctx::constTable( uint64_t key, const std::vector<int>& host ) {
 
 int tmc2_frame::ensureTree() {
   if ( haveTree ) return TMC2_OK;
-  const int placement = tmc2::kdtreePlacement( ctx );
-  // adaptive: take a host slot if one is free right now, otherwise the device builds it (same tree either way)
-  tmc2::HostGate gate( ctx, placement == 1 );
-  if ( placement == 0 || !gate.held ) {
-    const int sid = ctx->stageBegin( "kdtree_build" );
-    TMC2_TRY( tmc2::buildKdTreeDevice( ctx, d_pts.p, n, d_ptsTree, d_perm, d_nodes, tree.lo, tree.hi, tree.depth ) );
-    ctx->stageEnd( sid );
-    haveTree = true;
-    return TMC2_OK;
-  }
-  // built in page-locked staging (the orientation's row / sign staging is idle at this point) and uploaded as is
-  Pt*       hp = ctx->hostD.get<Pt>( n );
-  uint32_t* hi = ctx->hostA.get<uint32_t>( n );
-  if ( !hp || !hi ) {
-    setError( "kdtree: hipHostMalloc failed" );
-    return TMC2_E_HIP;
-  }
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    for ( uint64_t i = 0; i < n; ++i ) hp[i] = Pt{h_xyz[3 * size_t( i )], h_xyz[3 * size_t( i ) + 1], h_xyz[3 * size_t( i ) + 2], 0};
-    tree.buildInPlace( hp, hi, n );
-    const auto t1 = std::chrono::steady_clock::now();
-    ctx->stageAddHostMs( "kdtree_build_host", std::chrono::duration<double, std::milli>( t1 - t0 ).count() );
-  }
-  gate.release();
-  TMC2_TRY( d_ptsTree.alloc( n ) );
-  TMC2_TRY( d_perm.alloc( n ) );
-  TMC2_TRY( d_nodes.alloc( tree.nodes.size() ) );
-  hipStream_t s = ctx->stream;
-  TMC2_HIP( hipMemcpyAsync( d_ptsTree.p, hp, n * sizeof( Pt ), hipMemcpyHostToDevice, s ) );
-  TMC2_HIP( hipMemcpyAsync( d_perm.p, hi, n * sizeof( uint32_t ), hipMemcpyHostToDevice, s ) );
-  TMC2_HIP( hipMemcpyAsync( d_nodes.p, tree.nodes.data(), tree.nodes.size() * sizeof( KdNode ), hipMemcpyHostToDevice, s ) );
-  TMC2_HIP( hipStreamSynchronize( s ) );
+  TMC2_TRY( tmc2::buildKdTreePlaced( ctx, d_pts.p, n, h_xyz.data(), "kdtree_build", tree ) );
   haveTree = true;
   return TMC2_OK;
 }
@@ -666,7 +678,7 @@ int tmc2_frame_get_kdtree_order( tmc2_frame* f, uint32_t* perm, int32_t* depth )
   if ( !f || !perm ) return TMC2_E_INVALID;
   tmc2::ApiScope scope( f->ctx );
   TMC2_TRY( f->ensureTree() );
-  TMC2_HIP( hipMemcpyAsync( perm, f->d_perm.p, f->n * sizeof( uint32_t ), hipMemcpyDeviceToHost, f->ctx->stream ) );
+  TMC2_HIP( hipMemcpyAsync( perm, f->tree.perm.p, f->n * sizeof( uint32_t ), hipMemcpyDeviceToHost, f->ctx->stream ) );
   TMC2_HIP( hipStreamSynchronize( f->ctx->stream ) );
   if ( depth ) *depth = f->tree.depth;
   return TMC2_OK;

@@ -20,7 +20,6 @@
 // leaves for its <=16-element lists -- and reduced in fp64 in that order.
 // S21: every pyramid level is an image-parallel kernel over all six planes (2 maps x RGB) at once.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 
 #include "internal.h"
@@ -514,38 +513,7 @@ int reconstructPointCloud( tmc2_frame* f ) {
   ctx->stageEnd( sid );
   f->reconCount = M;
   // ---- tree over the reconstruction (like S1) --------------------------------------------------------------
-  const int placement = kdtreePlacement( ctx );
-  HostGate  treeGate( ctx, placement == 1 );
-  if ( placement == 0 || !treeGate.held ) {
-    const int kt = ctx->stageBegin( "kdtree_build_recon" );
-    TMC2_TRY( buildKdTreeDevice( ctx, f->d_recon.p, M, f->d_reconTreePts, f->d_reconPerm, f->d_reconNodes, f->reconTree.lo,
-                                 f->reconTree.hi, f->reconTree.depth ) );
-    ctx->stageEnd( kt );
-  } else {
-    Pt*       hp = ctx->hostD.get<Pt>( M );
-    uint32_t* hi = ctx->hostA.get<uint32_t>( M );
-    if ( !hp || !hi ) {
-      setError( "generatePointCloud: hipHostMalloc failed" );
-      return TMC2_E_HIP;
-    }
-    TMC2_HIP( hipMemcpyAsync( hp, f->d_recon.p, size_t( M ) * sizeof( Pt ), hipMemcpyDeviceToHost, s ) );
-    TMC2_HIP( hipStreamSynchronize( s ) );
-    {
-      const auto t0 = std::chrono::steady_clock::now();
-      f->reconTree.buildInPlace( hp, hi, M );
-      const auto t1 = std::chrono::steady_clock::now();
-      ctx->stageAddHostMs( "kdtree_build_recon_host", std::chrono::duration<double, std::milli>( t1 - t0 ).count() );
-    }
-    treeGate.release();
-    TMC2_TRY( f->d_reconTreePts.alloc( M ) );
-    TMC2_TRY( f->d_reconPerm.alloc( M ) );
-    TMC2_TRY( f->d_reconNodes.alloc( f->reconTree.nodes.size() ) );
-    TMC2_HIP( hipMemcpyAsync( f->d_reconTreePts.p, hp, size_t( M ) * sizeof( Pt ), hipMemcpyHostToDevice, s ) );
-    TMC2_HIP( hipMemcpyAsync( f->d_reconPerm.p, hi, size_t( M ) * 4, hipMemcpyHostToDevice, s ) );
-    TMC2_HIP( hipMemcpyAsync( f->d_reconNodes.p, f->reconTree.nodes.data(), f->reconTree.nodes.size() * sizeof( KdNode ),
-                              hipMemcpyHostToDevice, s ) );
-    TMC2_HIP( hipStreamSynchronize( s ) );
-  }
+  TMC2_TRY( buildKdTreePlaced( ctx, f->d_recon.p, M, nullptr, "kdtree_build_recon", f->reconTree ) );
   f->haveReconstruction = true;
   return TMC2_OK;
 }
@@ -570,22 +538,14 @@ int generateAttributeImages( tmc2_frame* f ) {
   int          sid = 0;
   DevBuf<uint32_t> d_small;
   TMC2_TRY( d_small.alloc( 8 ) );
-  TreeDev rt;
-  rt.ptsTree = f->d_reconTreePts.p;
-  rt.perm    = f->d_reconPerm.p;
-  rt.nodes   = f->d_reconNodes.p;
-  for ( int d = 0; d < 3; ++d ) rt.lo[d] = f->reconTree.lo[d], rt.hi[d] = f->reconTree.hi[d];
-  rt.depth = f->reconTree.depth;
-  rt.n     = M;
-  rt.queriesBounded = true;  // queried with the frame's own points; dispatch() checks both boxes
-  rt.queriesTight   = true;  // (non-negative and below 2^13, like the reconstruction the tree is built over)
   // ---- S18 ----------------------------------------------------------------------------------------------
   TMC2_TRY( f->d_reconRgb.alloc( size_t( M ) * 4 ) );
   const dim3 grdM( ( M + 255 ) / 256 );
   // (the sort-depth flag is a page-locked word of the context, read after the stage's last synchronisation: no copy)
   volatile uint32_t* h_err = ctx->answerLine( tmc2_ctx::kAnswerAttrError );
-  TMC2_TRY( transferColorsDevice( ctx, frameTree( f ), f->d_pts.p, f->d_rgb.p, n, rt, f->d_recon.p, M, f->d_reconRgb.p,
-                                  const_cast<uint32_t*>( h_err ) ) );
+  // (each tree is queried with the other cloud's points: non-negative and below 2^13, like its own)
+  TMC2_TRY( transferColorsDevice( ctx, f->tree.view( QueryBox::Tight ), f->d_pts.p, f->d_rgb.p, n, f->reconTree.view( QueryBox::Tight ),
+                                  f->d_recon.p, M, f->d_reconRgb.p, const_cast<uint32_t*>( h_err ) ) );
   // ---- S20 ----------------------------------------------------------------------------------------------
   sid = ctx->stageBegin( "attribute_images" );
   DevBuf<uint8_t> d_occ;
@@ -706,11 +666,8 @@ int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* s
   ApiScope    scope( ctx );
   hipStream_t s = ctx->stream;
   struct Side {
-    KdTreeHost       tree;
-    DevBuf<Pt>       pts, ptsTree;
-    DevBuf<uint32_t> perm;
-    DevBuf<KdNode>   nodes;
-    TreeDev          dev;
+    DevBuf<Pt> pts;
+    DeviceTree tree;
   } S, T;
   auto upload = [&]( Side& sd, const int16_t* xyz, uint64_t cnt ) -> int {
     std::vector<Pt> pts( cnt );
@@ -718,11 +675,7 @@ int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* s
     TMC2_TRY( sd.pts.alloc( cnt ) );
     TMC2_HIP( hipMemcpyAsync( sd.pts.p, pts.data(), cnt * sizeof( Pt ), hipMemcpyHostToDevice, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
-    TMC2_TRY( buildKdTreeDevice( ctx, sd.pts.p, cnt, sd.ptsTree, sd.perm, sd.nodes, sd.tree.lo, sd.tree.hi, sd.tree.depth ) );
-    sd.dev.ptsTree = sd.ptsTree.p, sd.dev.perm = sd.perm.p, sd.dev.nodes = sd.nodes.p;
-    for ( int d = 0; d < 3; ++d ) sd.dev.lo[d] = sd.tree.lo[d], sd.dev.hi[d] = sd.tree.hi[d];
-    sd.dev.depth = sd.tree.depth, sd.dev.n = cnt;
-    return TMC2_OK;
+    return buildKdTreeDevice( ctx, sd.pts.p, cnt, sd.tree );
   };
   TMC2_TRY( upload( S, srcXyz, n ) );
   TMC2_TRY( upload( T, tgtXyz, m ) );
@@ -734,7 +687,8 @@ int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* s
   TMC2_TRY( d_out.alloc( 4 * m ) );
   TMC2_TRY( d_err.alloc( 1 ) );
   TMC2_HIP( hipMemcpyAsync( d_rgb.p, c4.data(), 4 * n, hipMemcpyHostToDevice, s ) );
-  TMC2_TRY( transferColorsDevice( ctx, S.dev, S.pts.p, d_rgb.p, uint32_t( n ), T.dev, T.pts.p, uint32_t( m ), d_out.p, d_err.p ) );
+  TMC2_TRY( transferColorsDevice( ctx, S.tree.view( QueryBox::Any ), S.pts.p, d_rgb.p, uint32_t( n ), T.tree.view( QueryBox::Any ), T.pts.p,
+                                  uint32_t( m ), d_out.p, d_err.p ) );
   std::vector<uint8_t> o4( 4 * m );
   uint32_t             err = 0;
   TMC2_HIP( hipMemcpyAsync( o4.data(), d_out.p, 4 * m, hipMemcpyDeviceToHost, s ) );

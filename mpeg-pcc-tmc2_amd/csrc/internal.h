@@ -190,7 +190,7 @@ struct PlaceDev {
   int64_t depthOff;
 };
 
-// a k-d tree resident on the device (tree-order points, permutation, nodes) -- what the k-NN kernels traverse
+// a view of a DeviceTree -- what the k-NN kernels traverse
 struct TreeDev {
   const Pt*       ptsTree = nullptr;
   const uint32_t* perm    = nullptr;
@@ -200,6 +200,29 @@ struct TreeDev {
   uint64_t        n     = 0;
   bool            queriesBounded = false;  // the caller vouches: every query coordinate lies in [-4096, 12287]
   bool            queriesTight   = false;  // ... and even in [0, 8191] (a frame's own points / reconstruction): larger trees keep the LDS stack
+};
+// what the caller of a search vouches for its query coordinates: nothing, TreeDev::queriesBounded, or that and queriesTight
+enum class QueryBox { Any, Bounded, Tight };
+
+// a k-d tree resident on the device: tree-order points, permutation, nodes (buildKdTreeDevice, or buildKdTreePlaced's upload of a
+// KdTreeHost), root box, depth (levels)
+struct DeviceTree {
+  DevBuf<Pt>       ptsTree;
+  DevBuf<uint32_t> perm;  // tree order -> original index
+  DevBuf<KdNode>   nodes;
+  int32_t          lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  int              depth = 0;
+  uint64_t         n     = 0;
+  TreeDev          view( QueryBox queries ) const {
+    TreeDev t;
+    t.ptsTree = ptsTree.p, t.perm = perm.p, t.nodes = nodes.p;
+    for ( int d = 0; d < 3; ++d ) t.lo[d] = lo[d], t.hi[d] = hi[d];
+    t.depth          = depth;
+    t.n              = n;
+    t.queriesBounded = queries != QueryBox::Any;
+    t.queriesTight   = queries == QueryBox::Tight;
+    return t;
+  }
 };
 
 // GPU time per named stage / kernel: hipEvent pairs recorded on the context's stream, folded lazily when the
@@ -323,7 +346,6 @@ struct tmc2_frame {
   // host side
   std::vector<int16_t> h_xyz;
   std::vector<uint8_t> h_rgb;
-  tmc2::KdTreeHost     tree;
   bool                 haveTree = false;
   int                  ensureTree();  // builds + uploads the k-d tree on first use (S1 belongs to the timed path)
   // device work that needs the points only and may run while the host walks the orientation graph (S3): called by the
@@ -332,9 +354,7 @@ struct tmc2_frame {
   std::shared_ptr<void> refineJob;  // the refine step's geometry, prepared ahead (refine.hip)
   // device side
   tmc2::DevBuf<tmc2::Pt>     d_pts;       // original order
-  tmc2::DevBuf<tmc2::Pt>     d_ptsTree;   // tree order
-  tmc2::DevBuf<uint32_t>     d_perm;      // tree order -> original index
-  tmc2::DevBuf<tmc2::KdNode> d_nodes;
+  tmc2::DeviceTree           tree;        // over d_pts (ensureTree); queried with the frame's own points or its reconstruction: QueryBox::Tight
   tmc2::DevBuf<uint8_t>      d_rgb;       // [n][4] (rgb + pad)
   tmc2::DevBuf<uint32_t>     d_knn;       // [n][k]
   tmc2::DevBuf<double>       d_normals;   // [n][3]
@@ -379,10 +399,7 @@ struct tmc2_frame {
   tmc2::DevBuf<uint16_t>  d_attr16;             // decoded attribute frames, 16-bit 4:4:4: [2 maps][3 channels][H][W]
   bool                    haveAttr16 = false;
   bool                    haveBoundaryTypes = false, haveColors16 = false, haveSmoothed = false, haveRgbPost = false;
-  tmc2::KdTreeHost        reconTree;
-  tmc2::DevBuf<tmc2::Pt>  d_reconTreePts;
-  tmc2::DevBuf<uint32_t>  d_reconPerm;
-  tmc2::DevBuf<tmc2::KdNode> d_reconNodes;
+  tmc2::DeviceTree        reconTree;            // over d_recon (reconstructPointCloud)
 };
 
 namespace tmc2 {
@@ -414,7 +431,6 @@ int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint
 // 0xFFFFFFFF), then the compacted rest through the ordinary kernel, rows in place (knn.hip: what a caller may do with d_easy)
 int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_easy, uint32_t* d_idx,
                     uint32_t* d_dist, const char* stage, bool uniqueTreeRows = false );
-TreeDev frameTree( const tmc2_frame* f );
 int generateAttributeImages( tmc2_frame* f );
 int reconstructPointCloud( tmc2_frame* f );
 inline void invalidateReconstruction( tmc2_frame* f ) {  // new or replaced canvases: everything derived from them is stale
@@ -499,8 +515,11 @@ int  kdtreePlacement( const tmc2_ctx* ctx );  // 0 device, 1 host, 2 adaptive (h
 int  unionPrecheck( const tmc2_ctx* ctx );
 bool unionCheck( const tmc2_ctx* ctx );
 bool unionAgentScope( const tmc2_ctx* ctx );  // TMC2_UF_SCOPE=agent: every load of the union passes at agent scope (the formally clean form)
-int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, DevBuf<Pt>& d_ptsTree, DevBuf<uint32_t>& d_perm,
-                       DevBuf<KdNode>& d_nodes, int32_t lo[3], int32_t hi[3], int& depth );
+int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, DeviceTree& tree );
+// the frame's tree and the reconstruction's, built where kdtreePlacement says.  hostXyz: the same points as int16 triples on the
+// host, or null (they are read back from d_pts).  Stage `stage` times a device build, `stage` + "_host" a host build
+// (kdtree_build / kdtree_build_host, kdtree_build_recon / kdtree_build_recon_host).
+int buildKdTreePlaced( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, const int16_t* hostXyz, const char* stage, DeviceTree& tree );
 // opt-in to more than 48 KB of dynamic LDS for a kernel (once per device and kernel, serialised)
 int allowLargeLds( const void* kernel, size_t bytes, int device, size_t staticBytes = 64 );
 // answer (optional): the total ALSO goes to host[0] of a page-locked answer line of the context (tmc2_ctx::answerLine), stored by the

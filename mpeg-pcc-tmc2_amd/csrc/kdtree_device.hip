@@ -1349,21 +1349,21 @@ __global__ __launch_bounds__( kPieceMax / kPiecePer ) void pieceKernel( BuildArg
 
 }  // namespace
 
-// Builds the tree of d_pts[0..n) on the context's stream.  Outputs: points and permutation in tree order, node records
+// Builds the tree of d_pts[0..n) on the context's stream into `tree`: points and permutation in tree order, node records
 // (root = node 0), root box, depth (levels).  All buffers come from the context's pool.
-int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>& d_ptsTree, DevBuf<uint32_t>& d_perm,
-                       DevBuf<KdNode>& d_nodes, int32_t lo[3], int32_t hi[3], int& depth ) {
+int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DeviceTree& tree ) {
   const uint32_t n = uint32_t( n64 );
-  depth            = 0;
-  for ( int d = 0; d < 3; ++d ) lo[d] = hi[d] = 0;
+  tree.n           = n64;
+  tree.depth       = 0;
+  for ( int d = 0; d < 3; ++d ) tree.lo[d] = tree.hi[d] = 0;
   if ( n == 0 ) return TMC2_OK;
   hipStream_t    s       = ctx->stream;
   const uint32_t tiles   = ( n + kScanTile - 1 ) / kScanTile;
   const size_t   maxSegs = 2 * ( size_t( n ) / ( kLeafMax + 1 ) + 1 ) + 2;
   const size_t   maxNode = 2 * size_t( n ) + 2;  // (every split takes exactly two ids: hugeSegmentsKernel, pieceKernel, lvDecideKernel)
-  TMC2_TRY( d_ptsTree.alloc( n ) );
-  TMC2_TRY( d_perm.alloc( n ) );
-  TMC2_TRY( d_nodes.alloc( maxNode ) );
+  TMC2_TRY( tree.ptsTree.alloc( n ) );
+  TMC2_TRY( tree.perm.alloc( n ) );
+  TMC2_TRY( tree.nodes.alloc( maxNode ) );
   DevBuf<uint32_t>   d_work, d_small;
   DevBuf<BuildSeg>   d_segs;
   DevBuf<RetiredSeg> d_retired;
@@ -1383,10 +1383,10 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
   TMC2_TRY( d_small.alloc( kMaxLevels + 16 ) );  // [0..64] segments per level, then node count, levels, barrier, root box
   static_assert( kMaxLevels + 16 <= 128, "lvRootKernel clears the counters with one workgroup of 128" );
   BuildArgs a;
-  a.pts = d_pts, a.n = n, a.tiles = tiles, a.P = d_ptsTree.p, a.perm = d_perm.p;
+  a.pts = d_pts, a.n = n, a.tiles = tiles, a.P = tree.ptsTree.p, a.perm = tree.perm.p;
   a.seg = d_work.p, a.loc1 = d_work.p + n, a.loc2 = d_work.p + 2 * size_t( n );
   a.tile1 = d_work.p + 3 * size_t( n ), a.tile2 = a.tile1 + tiles + 1;
-  a.segA = d_segs.p, a.segB = d_segs.p + maxSegs, a.nodes = d_nodes.p;
+  a.segA = d_segs.p, a.segB = d_segs.p + maxSegs, a.nodes = tree.nodes.p;
   a.counts    = d_small.p;
   a.nodeCount = d_small.p + kMaxLevels + 1;
   a.levels    = d_small.p + kMaxLevels + 2;
@@ -1462,10 +1462,10 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
     setError( "kdtree: more than %d levels", kMaxLevels - 1 );
     return TMC2_E_UNSUPPORTED;
   }
-  depth = found;
-  hint  = std::max( found, 1 );
+  tree.depth = found;
+  hint       = std::max( found, 1 );
   const int32_t* box = reinterpret_cast<const int32_t*>( out + kMaxLevels + 8 );
-  for ( int d = 0; d < 3; ++d ) lo[d] = box[d], hi[d] = box[3 + d];
+  for ( int d = 0; d < 3; ++d ) tree.lo[d] = box[d], tree.hi[d] = box[3 + d];
   // everything below the level passes: one workgroup per piece
   const uint32_t hugeSegs = out[kMaxLevels + 7];
   if ( hugeSegs )  // (segments of up to hugeMax points: one workgroup each cuts its segment into pieces, which join the list)
@@ -1499,7 +1499,7 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DevBuf<Pt>&
       setError( "kdtree: more than %d levels", kMaxLevels - 1 );
       return TMC2_E_UNSUPPORTED;
     }
-    depth = std::max( depth, int( fin ) );
+    tree.depth = std::max( tree.depth, int( fin ) );
   }
   return TMC2_OK;
 }

@@ -306,27 +306,10 @@ int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, 
 
 }  // namespace
 
-TreeDev frameTree( const tmc2_frame* f ) {
-  TreeDev t;
-  t.ptsTree = f->d_ptsTree.p;
-  t.perm    = f->d_perm.p;
-  t.nodes   = f->d_nodes.p;
-  for ( int d = 0; d < 3; ++d ) {
-    t.lo[d] = f->tree.lo[d];
-    t.hi[d] = f->tree.hi[d];
-  }
-  t.depth = f->tree.depth;
-  t.n     = f->n;
-  // queries against a frame's tree are the frame's own points or its reconstruction (non-negative, < 2^13)
-  t.queriesBounded = true;
-  t.queriesTight   = true;  // (... and below 2^13: inside [0, 8191])
-  return t;
-}
-
 int launchKnnSelf( tmc2_frame* f, int k ) {
   TMC2_TRY( f->d_knn.alloc( f->n * size_t( k ) ) );
   const int sid = f->ctx->stageBegin( "knn_self" );
-  const int r   = dispatch<true>( f->ctx->stream, frameTree( f ), nullptr, f->n, k, f->d_knn.p, nullptr );
+  const int r   = dispatch<true>( f->ctx->stream, f->tree.view( QueryBox::Tight ), nullptr, f->n, k, f->d_knn.p, nullptr );
   f->ctx->stageEnd( sid );
   if ( r == TMC2_OK ) {
     f->k       = k;
@@ -338,10 +321,9 @@ int launchKnnSelf( tmc2_frame* f, int k ) {
 
 int launchKnnQueries( tmc2_frame* f, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx, uint32_t* d_dist,
                       bool queriesBounded ) {
-  TreeDev t        = frameTree( f );
-  t.queriesBounded = queriesBounded;
-  t.queriesTight   = false;  // (a caller's own queries: anywhere in the bounded window)
-  return launchKnnTree( f->ctx, t, d_queries, nq, k, d_idx, d_dist, "knn_query" );
+  // (a caller's own queries: at best anywhere in the bounded window)
+  return launchKnnTree( f->ctx, f->tree.view( queriesBounded ? QueryBox::Bounded : QueryBox::Any ), d_queries, nq, k, d_idx, d_dist,
+                        "knn_query" );
 }
 
 int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx,

@@ -40,28 +40,18 @@ struct CloudView {
 
 // a cloud + its tree on the device
 struct DevCloud {
-  size_t           n = 0;
-  KdTreeHost       tree;
-  DevBuf<Pt>       pts, ptsTree;
-  DevBuf<uint32_t> perm;
-  DevBuf<KdNode>   nodes;
-  DevBuf<uint8_t>  rgb4;
-  DevBuf<double>   nrm;
-  TreeDev          dev() const {
-    TreeDev t;
-    t.ptsTree = ptsTree.p, t.perm = perm.p, t.nodes = nodes.p;
-    for ( int d = 0; d < 3; ++d ) t.lo[d] = tree.lo[d], t.hi[d] = tree.hi[d];
-    t.depth = tree.depth, t.n = n;
-    return t;
-  }
-  int buildTree( tmc2_ctx* ctx ) { return buildKdTreeDevice( ctx, pts.p, n, ptsTree, perm, nodes, tree.lo, tree.hi, tree.depth ); }
+  size_t          n = 0;
+  DevBuf<Pt>      pts;
+  DeviceTree      tree;
+  DevBuf<uint8_t> rgb4;
+  DevBuf<double>  nrm;
+  int             buildTree( tmc2_ctx* ctx ) { return buildKdTreeDevice( ctx, pts.p, n, tree ); }
   // this cloud's tree as queried with the points of `q` (whose own tree gives their bounding box: the packed LDS-stack
   // traversal of the k-NN kernel needs every query coordinate within [-4096, 12287])
   TreeDev devFor( const DevCloud& q ) const {
-    TreeDev t        = dev();
-    t.queriesBounded = true;
-    for ( int d = 0; d < 3; ++d ) t.queriesBounded = t.queriesBounded && q.tree.lo[d] >= -4096 && q.tree.hi[d] <= 12287;
-    return t;
+    bool bounded = true;
+    for ( int d = 0; d < 3; ++d ) bounded = bounded && q.tree.lo[d] >= -4096 && q.tree.hi[d] <= 12287;
+    return tree.view( bounded ? QueryBox::Bounded : QueryBox::Any );
   }
 };
 

@@ -573,7 +573,7 @@ int contractOrientationDevice( tmc2_frame* f, double tau, DevBuf<uint32_t>& d_ci
   const auto      orderOpt = ctxOption( ctx, "ORIENT_ORDER" );
   const bool      chunked  = !( orderOpt && ( *orderOpt )[0] == 'i' );
   const bool      chunkedPairs = orderOpt && ( *orderOpt )[0] != 'i';
-  const uint32_t* perm     = orderOpt && ( *orderOpt )[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
+  const uint32_t* perm     = orderOpt && ( *orderOpt )[0] == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= n ? f->tree.perm.p : nullptr;
   const double*   normals  = f->d_normals.p;
   TMC2_TRY( d_count.alloc( size_t( n ) + 1 ) );  // (initWordsKernel zeroes it; later: kept edges per cluster, C + 1 used)
   hipLaunchKernelGGL( initWordsKernel<16>, grdN16, blk, 0, s, f->d_knn.p, normals, f->d_mutual.p, perm, chunked, tau, n, d_mask.p, d_strongAll.p,

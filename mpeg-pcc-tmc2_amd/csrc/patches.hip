@@ -746,7 +746,7 @@ int ensureMutualMask( tmc2_frame* f ) {
   // "chunk" = index order, XCD x on the x-th eighth of the blocks; "tree" = tree order, same eighths
   const auto      order   = ctxOption( f->ctx, "MUTUAL_ORDER" );
   const bool      chunked = !( order && ( *order )[0] == 'i' );
-  const uint32_t* perm    = order && ( *order )[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
+  const uint32_t* perm    = order && ( *order )[0] == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= n ? f->tree.perm.p : nullptr;
   const uint32_t  blocks  = ( n + 255 ) / 256;
   hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( chunked ? ( ( blocks + 7 ) & ~7u ) : blocks ), dim3( 256 ), 0, f->ctx->stream, f->d_knn.p,
                       perm, chunked, n, f->d_mutual.p );
@@ -841,7 +841,7 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   // the union / relaxation passes: option MUTUAL_ORDER as in ensureMutualMask (here the default is "chunk")
   const auto      ccOrder = ctxOption( ctx, "MUTUAL_ORDER" );
   const bool      chunked = !( ccOrder && ( *ccOrder )[0] == 'i' );
-  const uint32_t* perm    = ccOrder && ( *ccOrder )[0] == 't' && f->haveTree && f->d_perm.p && f->d_perm.count >= n ? f->d_perm.p : nullptr;
+  const uint32_t* perm    = ccOrder && ( *ccOrder )[0] == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= n ? f->tree.perm.p : nullptr;
   const dim3      grdT( chunked ? ( ( grdN.x + 7u ) & ~7u ) : grdN.x );
   while ( rawCount > 0 ) {
     // ---- S7 -----------------------------------------------------------------------------------------

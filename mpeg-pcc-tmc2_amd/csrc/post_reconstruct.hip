@@ -334,17 +334,6 @@ __global__ __launch_bounds__( 256 ) void yuv16ToRgb8Kernel( const ushort4* __res
                         uint8_t( fmax( 0.0, fmin( round( b * 255 ), 255.0 ) ) ), 0 );
 }
 
-TreeDev reconTreeDev( const tmc2_frame* f ) {
-  TreeDev rt;
-  rt.ptsTree = f->d_reconTreePts.p;
-  rt.perm    = f->d_reconPerm.p;
-  rt.nodes   = f->d_reconNodes.p;
-  for ( int d = 0; d < 3; ++d ) rt.lo[d] = f->reconTree.lo[d], rt.hi[d] = f->reconTree.hi[d];
-  rt.depth          = f->reconTree.depth;
-  rt.n              = f->reconCount;
-  rt.queriesBounded = true;  // queries are points of the reconstruction before / after smoothing
-  return rt;
-}
 int needReconstruction( tmc2_frame* f, const char* who ) {
   if ( !f->haveReconstruction || f->reconCount == 0 ) {
     setError( "%s: the frame has no reconstruction (tmc2_codec_generate_point_cloud or tmc2_encoder_generate_attribute_images first)", who );
@@ -482,16 +471,12 @@ int transferColors16bitBP( tmc2_frame* f ) {
     return TMC2_E_UNSUPPORTED;
   }
   // the tree over the smoothed cloud (the one over the cloud before smoothing is S18's)
-  DevBuf<Pt>       d_treePts;
-  DevBuf<uint32_t> d_perm;
-  DevBuf<KdNode>   d_nodes;
-  TreeDev          tt;
+  DeviceTree smoothed;
   {
     const int kt = ctx->stageBegin( "kdtree_build_smoothed" );
-    TMC2_TRY( buildKdTreeDevice( ctx, f->d_reconSmoothed.p, M, d_treePts, d_perm, d_nodes, tt.lo, tt.hi, tt.depth ) );
+    TMC2_TRY( buildKdTreeDevice( ctx, f->d_reconSmoothed.p, M, smoothed ) );
     ctx->stageEnd( kt );
   }
-  tt.ptsTree = d_treePts.p, tt.perm = d_perm.p, tt.nodes = d_nodes.p, tt.n = M, tt.queriesBounded = true;
   const uint32_t entries = K * 8;
   DevBuf<uint32_t> d_moved, d_idx8, d_dist8, d_nn1, d_nn1Dist, d_count, d_offset, d_cursor;
   DevBuf<Pt>       d_queries, d_partPts;
@@ -513,12 +498,14 @@ int transferColors16bitBP( tmc2_frame* f ) {
   const ushort4* colors = reinterpret_cast<const ushort4*>( f->d_colors16.p );
   hipLaunchKernelGGL( movedGatherKernel, grdM, blk, 0, s, f->d_boundaryType.p, d_rank.p, f->d_reconSmoothed.p, M, d_moved.p,
                       d_queries.p );
-  TMC2_TRY( launchKnnTree( ctx, reconTreeDev( f ), d_queries.p, K, 8, d_idx8.p, d_dist8.p, "knn8_moved_in_recon" ) );
+  // (the queries of both trees are points of the reconstruction before / after smoothing)
+  TMC2_TRY( launchKnnTree( ctx, f->reconTree.view( QueryBox::Bounded ), d_queries.p, K, 8, d_idx8.p, d_dist8.p, "knn8_moved_in_recon" ) );
   sid = ctx->stageBegin( "transfer_colors16" );
   hipLaunchKernelGGL( forwardColor16Kernel, grdK, blk, 0, s, d_idx8.p, d_dist8.p, colors, f->d_recon.p, K,
                       reinterpret_cast<ushort4*>( d_refined.p ), d_partPts.p );
   ctx->stageEnd( sid );
-  TMC2_TRY( launchKnnTree( ctx, tt, d_partPts.p, entries, 1, d_nn1.p, d_nn1Dist.p, "knn1_neighbours_in_smoothed" ) );
+  TMC2_TRY( launchKnnTree( ctx, smoothed.view( QueryBox::Bounded ), d_partPts.p, entries, 1, d_nn1.p, d_nn1Dist.p,
+                           "knn1_neighbours_in_smoothed" ) );
   sid = ctx->stageBegin( "transfer_colors16" );
   TMC2_HIP( hipMemsetAsync( d_count.p, 0, size_t( K ) * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_cursor.p, 0, size_t( K ) * 4, s ) );
