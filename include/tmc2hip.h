@@ -327,7 +327,9 @@ int tmc2_codec_generate_point_cloud( tmc2_frame* f );
 /* ---- post-reconstruction tail (PCCEncoder::encode :571-719, PCCDecoder::decode :330-470) -------------------- */
 /* All of these work on the reconstruction left by tmc2_encoder_generate_attribute_images (PCCCodec::generatePointCloud on
  * the resident, or decoded, occupancy / geometry canvases).  CTC settings: two maps in one stream, lossy attributes,
- * flagGeometrySmoothing 1, gridSmoothing 1, attrTransferFilterType 1, flagColorSmoothing 0.
+ * flagGeometrySmoothing 1, gridSmoothing 1, attrTransferFilterType 1; flagColorSmoothing 0 (the CTC) leaves the sequence as it
+ * is, a stream whose attribute-smoothing SEI sets it adds tmc2_codec_color_smoothing between the colour transfer and the
+ * conversion to 8-bit RGB.
  * replaces: PCCCodec::identifyBoundaryPoints (PccLibCommon/source/PCCCodec.cpp:268-327), as generatePointCloud runs it
  * over all points when flagGeometrySmoothing is set (:955-976): PCCPointSet3::boundaryPointTypes_ becomes 0 / 1.     */
 int tmc2_codec_identify_boundary_points( tmc2_frame* f );
@@ -345,6 +347,24 @@ int tmc2_codec_smooth_point_cloud_postprocess( tmc2_frame* f, int gridSize, doub
  * arguments of PCCEncoder.cpp:657-672 / PCCDecoder.cpp:416-431: source = the cloud before smoothing with its 16-bit
  * colours, target = the smoothed cloud; only the moved points (boundary type 3) are recoloured.                     */
 int tmc2_codec_transfer_colors_16bit_bp( tmc2_frame* f );
+/* replaces: PCCCodec::colorSmoothing (PCCCodec.cpp:151-238: addGridColorCentroid :1170, gridFilteringColor :1193,
+ * smoothPointCloudColorLC :1279) on the frame's finished cloud -- the branch "applyAttrSmoothingType_ != 0 &&
+ * flagColorSmoothing_" of PCCEncoder.cpp:701-705 / PCCDecoder.cpp:463; call after tmc2_codec_transfer_colors_16bit_bp and before
+ * tmc2_codec_convert_yuv16_to_rgb8.  gridSize = occupancyPrecision_ (what colorSmoothing reads; NOT the SEI's cgridSize_): 2, 4,
+ * 8 or 16.  Boundary points (type 1) take the trilinear blend of the mean colours of the 2x2x2 grid cells around them when
+ * its luma differs enough from their own; positions and boundary types do not change.  The patch of a point is taken as the
+ * geometry smoothing takes it (blockToPatch through pointToPixel), the cube of the grid is 2^geometryBitDepth3D: the value
+ * tmc2_segmenter_compute was given, or tmc2_frame_set_geometry_bit_depth_3d (a decoder-side frame has no other source).
+ * TMC2_E_STATE without 16-bit colours or bit depth; TMC2_E_UNSUPPORTED for a cell of more than 65535 points (the reference's
+ * uint16 count wraps) and for other grid sizes.                                                                        */
+int tmc2_codec_color_smoothing( tmc2_frame* f, int gridSize, double thresholdColorSmoothing, double thresholdColorDifference,
+                                double thresholdColorVariation );
+int tmc2_frame_set_geometry_bit_depth_3d( tmc2_frame* f, int geometryBitDepth3D );
+/* the same on host arrays (as tmc2_transfer_colors is to the frame entry): xyz int16[M][3], colors16 uint16[M][3] in / out,
+ * boundaryType uint16[M], patchIndex uint32[M] (only equality of two points' values matters)                           */
+int tmc2_color_smoothing( tmc2_ctx* ctx, const int16_t* xyz, uint16_t* colors16, const uint16_t* boundaryType, const uint32_t* patchIndex,
+                          uint64_t M, int gridSize, int geometryBitDepth3D, double thresholdColorSmoothing,
+                          double thresholdColorDifference, double thresholdColorVariation );
 /* replaces: PCCPointSet3::convertYUV16ToRGB8 (PccLibCommon/include/PCCPointSet.h:133-166) */
 int tmc2_codec_convert_yuv16_to_rgb8( tmc2_frame* f );
 /* the finished cloud (any pointer may be NULL): positions int16[M][3] (smoothed once the smoothing ran), 16-bit colours
@@ -448,6 +468,10 @@ int tmc2_host_place_segments( int frames, const int32_t* counts, tmc2_patch* pat
                               int64_t* occupancyOutBase, int32_t* widths, int32_t* heights );
 /* the exact spanning-tree orientation behind tmc2_normals_orient (normals in/out, knn = [n][k]) */
 int tmc2_host_orient_normals( const int16_t* xyz, uint64_t n, const uint32_t* knn, int k, double* normals );
+/* the exact restatement of PCCCodec::colorSmoothing behind tmc2_color_smoothing / tmc2_codec_color_smoothing (same arrays) */
+int tmc2_host_color_smoothing( const int16_t* xyz, uint16_t* colors16, const uint16_t* boundaryType, const uint32_t* patchIndex,
+                               uint64_t M, int gridSize, int geometryBitDepth3D, double thresholdColorSmoothing,
+                               double thresholdColorDifference, double thresholdColorVariation );
 
 #ifdef __cplusplus
 }

@@ -143,8 +143,20 @@ class MetricsDropIn {
 // The per-frame finish of PCCDecoder::decode (PCCDecoder.cpp:325-470; the encoder's own reconstruction loop :571-719 is the
 // same code) for the CTC lossy conditions, one tile per frame: occupancy map and blockToPatch from the decoded occupancy
 // video, generatePointCloud, colorPointCloud from the decoded (colour-converted, 16-bit 4:4:4) attribute frames, grid
-// geometry smoothing, transferColors16bitBP onto the moved points, convertYUV16ToRGB8 -- on the device, from the reference's
-// own containers, into `reconstruct` (positions, 16-bit and 8-bit colours, boundary point types).
+// geometry smoothing, transferColors16bitBP onto the moved points, colorSmoothing where the attribute-smoothing SEI turns it on,
+// convertYUV16ToRGB8 -- on the device, from the reference's own containers, into `reconstruct` (positions, 16-bit and 8-bit
+// colours, boundary point types).
+// What PCCDecoder::decode reads for `colorSmoothing( reconstruct, colorTransform, ppSEIParams )` (PCCDecoder.cpp:463): the flag
+// (applyAttrSmoothingType_ != 0 && ppSEIParams.flagColorSmoothing_), the cube (ppSEIParams.geometryBitDepth3D_), the grid size
+// -- ppSEIParams.occupancyPrecision_, NOT the SEI's cgridSize_, which colorSmoothing never reads -- and the three thresholds.
+struct ColorSmoothingArgs {
+  bool   flagColorSmoothing       = false;
+  size_t occupancyPrecision       = 4;
+  size_t geometryBitDepth3D       = 11;
+  double thresholdColorSmoothing  = 10.0;
+  double thresholdColorDifference = 10.0;
+  double thresholdColorVariation  = 6.0;
+};
 class DecoderDropIn {
  public:
   explicit DecoderDropIn( int device );
@@ -152,7 +164,9 @@ class DecoderDropIn {
   DecoderDropIn( const DecoderDropIn& ) = delete;
   DecoderDropIn& operator=( const DecoderDropIn& ) = delete;
   int reconstructFrame( pcc::PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize, double thresholdSmoothing,
-                        pcc::PCCPointSet3& reconstruct );
+                        pcc::PCCPointSet3& reconstruct );  // flagColorSmoothing off
+  int reconstructFrame( pcc::PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize, double thresholdSmoothing,
+                        const ColorSmoothingArgs& colorSmoothing, pcc::PCCPointSet3& reconstruct );
   const char* lastError() const { return tmc2_last_error(); }
 
  private:

@@ -80,6 +80,10 @@ DecoderDropIn::~DecoderDropIn() {
 }
 int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize,
                                      double thresholdSmoothing, PCCPointSet3& reconstruct ) {
+  return reconstructFrame( context, frameIdx, occupancyPrecision, gridSize, thresholdSmoothing, ColorSmoothingArgs(), reconstruct );
+}
+int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize,
+                                     double thresholdSmoothing, const ColorSmoothingArgs& colorSmoothing, PCCPointSet3& reconstruct ) {
   if ( !ctx_ ) return TMC2_E_NO_DEVICE;
   auto&                   tile = context[frameIdx].getTile( 0 );
   std::vector<tmc2_patch> records;
@@ -117,6 +121,12 @@ int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_
   if ( ( rc = tmc2_codec_color_point_cloud( f, att.data() ) ) != TMC2_OK ) return rc;
   if ( ( rc = tmc2_codec_smooth_point_cloud_postprocess( f, int( gridSize ), thresholdSmoothing ) ) != TMC2_OK ) return rc;
   if ( ( rc = tmc2_codec_transfer_colors_16bit_bp( f ) ) != TMC2_OK ) return rc;
+  if ( colorSmoothing.flagColorSmoothing ) {  // PCCDecoder.cpp:463 (a decoder-side frame learns the cube from the SEI parameters)
+    if ( ( rc = tmc2_frame_set_geometry_bit_depth_3d( f, int( colorSmoothing.geometryBitDepth3D ) ) ) != TMC2_OK ) return rc;
+    if ( ( rc = tmc2_codec_color_smoothing( f, int( colorSmoothing.occupancyPrecision ), colorSmoothing.thresholdColorSmoothing,
+                                            colorSmoothing.thresholdColorDifference, colorSmoothing.thresholdColorVariation ) ) != TMC2_OK )
+      return rc;
+  }
   if ( ( rc = tmc2_codec_convert_yuv16_to_rgb8( f ) ) != TMC2_OK ) return rc;
   const int64_t M = tmc2_frame_recon_count( f );
   if ( M < 0 ) return TMC2_E_STATE;

@@ -400,6 +400,7 @@ struct tmc2_frame {
   bool                    haveAttr16 = false;
   bool                    haveBoundaryTypes = false, haveColors16 = false, haveSmoothed = false, haveRgbPost = false;
   tmc2::DeviceTree        reconTree;            // over d_recon (reconstructPointCloud)
+  int                     geometryBitDepth3D = 0;  // the cube the colour smoothing's grid spans (segmentPatches, or tmc2_frame_set_geometry_bit_depth_3d); 0: unknown
 };
 
 namespace tmc2 {

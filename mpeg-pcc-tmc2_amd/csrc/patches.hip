@@ -1029,6 +1029,7 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   TMC2_HIP( hipGetLastError() );
   f->rounds      = rounds;
   f->havePatches = true;
+  f->geometryBitDepth3D = sp->geometryBitDepth3D;  // (the cube of T6's grid)
   return TMC2_OK;
 }
 

@@ -284,6 +284,15 @@ class Context:
         _check(self.L.tmc2_transfer_colors(self.h, _ptr(a), _ptr(b), C.c_uint64(len(a)), _ptr(c), C.c_uint64(len(c)), _ptr(out)))
         return out
 
+    # PCCCodec::colorSmoothing
+    def color_smoothing(self, xyz, colors16, boundary, patch_index, grid_size, bits3d, thr_smoothing=10.0, thr_difference=10.0,
+                        thr_variation=6.0):
+        """tmc2_color_smoothing on host arrays: the smoothed 16-bit colours (a copy)."""
+        a = _color_smoothing_arrays(xyz, colors16, boundary, patch_index)
+        _check(self.L.tmc2_color_smoothing(self.h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.c_uint64(len(a[0])), int(grid_size),
+                                          int(bits3d), C.c_double(thr_smoothing), C.c_double(thr_difference), C.c_double(thr_variation)))
+        return a[1]
+
     # PCCMetrics::compute (one frame)
     def decoder_frame(self, patches, width, height, occ_precision, occ_video, geometry):
         """A frame without a source cloud: decoded patch records (list order), occupancy video, geometry maps [2][H][W]."""
@@ -613,13 +622,26 @@ class Frame:
     def codec_convert_yuv16_to_rgb8(self):
         _check(self.L.tmc2_codec_convert_yuv16_to_rgb8(self.h))
 
-    def codec_post_reconstruct(self, attribute16=None, grid_size=8, threshold=64.0):
+    def set_geometry_bit_depth_3d(self, bits3d):
+        """The cube of the colour smoothing's grid, for a frame that did not run segmenter_compute (a decoder-side frame)."""
+        _check(self.L.tmc2_frame_set_geometry_bit_depth_3d(self.h, int(bits3d)))
+
+    def codec_color_smoothing(self, grid_size, thr_smoothing=10.0, thr_difference=10.0, thr_variation=6.0):
+        """PCCCodec::colorSmoothing on the finished cloud (after codec_transfer_colors_16bit_bp, before codec_convert_yuv16_to_rgb8);
+        grid_size = occupancyPrecision; the thresholds default as PCCEncoderParameters does."""
+        _check(self.L.tmc2_codec_color_smoothing(self.h, int(grid_size), C.c_double(thr_smoothing), C.c_double(thr_difference),
+                                                C.c_double(thr_variation)))
+
+    def codec_post_reconstruct(self, attribute16=None, grid_size=8, threshold=64.0, color_smoothing=None):
         """The whole tail in the reference's order: boundary points, 16-bit colours from the decoded attribute frames, grid
-        geometry smoothing, colour transfer onto the moved points, YUV -> RGB."""
+        geometry smoothing, colour transfer onto the moved points, [colour smoothing,] YUV -> RGB.  color_smoothing: None (the
+        CTC: flagColorSmoothing off) or the arguments of codec_color_smoothing as a tuple, (grid_size[, thresholds ...])."""
         self.codec_identify_boundary_points()
         self.codec_color_point_cloud(attribute16)
         self.codec_smooth_point_cloud_postprocess(grid_size, threshold)
         self.codec_transfer_colors_16bit_bp()
+        if color_smoothing is not None:
+            self.codec_color_smoothing(*color_smoothing)
         self.codec_convert_yuv16_to_rgb8()
 
     def get_post_reconstruction(self, xyz=True, colors16=True, rgb=True, boundary=True):
@@ -902,3 +924,23 @@ def host_orient_normals(xyz, knn, normals):
     out = np.array(normals, dtype=np.float64, order="C", copy=True)
     _check(L.tmc2_host_orient_normals(_ptr(xyz), C.c_uint64(len(xyz)), _ptr(knn), int(knn.shape[1]), _ptr(out)))
     return out
+
+
+def _color_smoothing_arrays(xyz, colors16, boundary, patch_index):
+    xyz = np.ascontiguousarray(xyz, dtype=np.int16)
+    out = np.array(colors16, dtype=np.uint16, order="C", copy=True)
+    bt = np.ascontiguousarray(boundary, dtype=np.uint16)
+    patch = np.ascontiguousarray(patch_index, dtype=np.uint32)
+    if xyz.shape != (len(xyz), 3) or out.shape != xyz.shape or bt.shape != (len(xyz),) or patch.shape != (len(xyz),):
+        raise Tmc2Error("color_smoothing: xyz [M][3], colors16 [M][3], boundary [M] and patch_index [M] of one M expected")
+    return xyz, out, bt, patch
+
+
+def host_color_smoothing(xyz, colors16, boundary, patch_index, grid_size, bits3d, thr_smoothing=10.0, thr_difference=10.0,
+                         thr_variation=6.0):
+    """tmc2_host_color_smoothing: PCCCodec::colorSmoothing restated on the host (no device); returns the smoothed colours."""
+    L = load_library()
+    a = _color_smoothing_arrays(xyz, colors16, boundary, patch_index)
+    _check(L.tmc2_host_color_smoothing(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.c_uint64(len(a[0])), int(grid_size), int(bits3d),
+                                       C.c_double(thr_smoothing), C.c_double(thr_difference), C.c_double(thr_variation)))
+    return a[1]
