@@ -597,10 +597,8 @@ int buildKdTreePlaced( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, const int16_t
   // adaptive: take a host slot if one is free right now, otherwise the device builds it (same tree either way)
   HostGate gate( ctx, placement == 1 );
   if ( placement == 0 || !gate.held ) {
-    const int sid = ctx->stageBegin( stage );
-    TMC2_TRY( buildKdTreeDevice( ctx, d_pts, n, tree ) );
-    ctx->stageEnd( sid );
-    return TMC2_OK;
+    StageScope span( ctx, stage );
+    return buildKdTreeDevice( ctx, d_pts, n, tree );
   }
   // built in page-locked staging (the orientation's row / sign staging is idle at this point) and uploaded as is
   Pt*       hp = ctx->hostD.get<Pt>( n );
@@ -658,6 +656,29 @@ const int* tmc2_ctx::constTable( uint64_t key, const std::vector<int>& host ) {
   return p;
 }
 
+void tmc2_frame::resetDerived() {
+  haveTree = haveKnn = haveNormals = havePartition = haveMutual = false;
+  havePatches = haveAttr16 = false;
+  patchesChanged();
+  patches.clear();
+  packOrder.clear();
+  packMatch.clear();
+  depthCount = occCount = 0;
+  rounds = packedHeight = packedWidth = 0;
+  refineJob.reset();
+}
+
+int tmc2::normalsCompute( tmc2_frame* f, int k, int orientation, const std::function<int()>* beforeHostWalk ) {
+  TMC2_TRY( tmc2_normals_compute_normals( f, k ) );
+  if ( orientation == 0 ) return TMC2_OK;
+  if ( orientation != 1 ) {
+    setError( "normalOrientation=%d unsupported (0 none, 1 spanning tree)", orientation );
+    return TMC2_E_UNSUPPORTED;
+  }
+  tmc2::ApiScope scope( f->ctx );
+  return orientNormalsHost( f, beforeHostWalk );
+}
+
 int tmc2_frame::ensureTree() {
   if ( haveTree ) return TMC2_OK;
   TMC2_TRY( tmc2::buildKdTreePlaced( ctx, d_pts.p, n, h_xyz.data(), "kdtree_build", tree ) );
@@ -698,18 +719,8 @@ uint64_t tmc2_frame_point_count( const tmc2_frame* f ) { return f ? f->n : 0; }
 
 int tmc2_frame_reset( tmc2_frame* f ) {
   if ( !f ) return TMC2_E_INVALID;
-  f->haveTree = f->haveKnn = f->haveNormals = f->havePartition = f->haveMutual = false;
-  f->havePatches = f->havePacking = f->haveGeometryImages = f->haveAttributeImages = f->haveReconstruction = false;
-  f->haveBoundaryTypes = f->haveColors16 = f->haveSmoothed = f->haveRgbPost = f->haveAttr16 = false;
-  f->patches.clear();
-  f->packOrder.clear();
-  f->packMatch.clear();
-  f->depthCount = f->occCount = 0;
-  f->rounds = f->packedHeight = f->packedWidth = 0;
-  {
-    tmc2::ApiScope scope( f->ctx );
-    f->refineJob.reset();
-  }
+  tmc2::ApiScope scope( f->ctx );  // (a refine job hands its buffers back to the context's pool)
+  f->resetDerived();
   return TMC2_OK;
 }
 
@@ -758,13 +769,7 @@ int tmc2_normals_orient( tmc2_frame* f ) {
   return orientNormalsHost( f );
 }
 
-int tmc2_normals_compute( tmc2_frame* f, int k, int orientation ) {
-  TMC2_TRY( tmc2_normals_compute_normals( f, k ) );
-  if ( orientation == 1 ) return tmc2_normals_orient( f );
-  if ( orientation == 0 ) return TMC2_OK;
-  setError( "normalOrientation=%d unsupported (0 none, 1 spanning tree)", orientation );
-  return TMC2_E_UNSUPPORTED;
-}
+int tmc2_normals_compute( tmc2_frame* f, int k, int orientation ) { return tmc2::normalsCompute( f, k, orientation, nullptr ); }
 
 int tmc2_frame_get_normals( tmc2_frame* f, double* normals ) {
   if ( !f || !normals || !f->haveNormals ) {

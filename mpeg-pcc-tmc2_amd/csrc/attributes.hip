@@ -456,7 +456,7 @@ int transferColorsDevice( tmc2_ctx* ctx, const TreeDev& srcTree, const Pt* d_src
   TMC2_TRY( d_easy8.alloc( M ) );
   TMC2_TRY( launchKnnSplit( ctx, srcTree, d_tgtPts, M, 8, d_easy8.p, d_idx8.p, d_dist8.p, "knn8_recon_in_source" ) );
   TMC2_TRY( launchKnnSplit( ctx, tgtTree, d_srcPts, n, 1, d_idx1.p, d_idx1.p, d_dist1.p, "knn1_source_in_recon" ) );
-  const int sid = ctx->stageBegin( "transfer_colors" );
+  StageScope stage( ctx, "transfer_colors" );
   TMC2_TRY( fillRegions( ctx, {{d_count.p, size_t( M ) * 4, 0}, {d_cursor.p, size_t( M ) * 4, 0}, {d_error, 4, 0}} ) );
   const dim3 grdM( ( M + 255 ) / 256 ), grdN( ( n + 255 ) / 256 );
   hipLaunchKernelGGL( forwardColorKernel, grdM, blk, 0, s, d_idx8.p, d_dist8.p, d_easy8.p, d_srcRgb4, M, d_fwd.p );
@@ -465,7 +465,6 @@ int transferColorsDevice( tmc2_ctx* ctx, const TreeDev& srcTree, const Pt* d_src
   hipLaunchKernelGGL( backwardFillKernel, grdN, blk, 0, s, d_idx1.p, d_dist1.p, d_offset.p, n, d_cursor.p, d_entries.p );
   hipLaunchKernelGGL( combineColorKernel, grdM, blk, 0, s, d_count.p, d_offset.p, d_entries.p, d_srcRgb4, d_fwd.p, M,
                       d_outRgb4, d_error );
-  ctx->stageEnd( sid );
   TMC2_HIP( hipGetLastError() );
   return TMC2_OK;
 }
@@ -477,15 +476,14 @@ int reconstructPointCloud( tmc2_frame* f ) {
     setError( "generatePointCloud: geometry images missing" );
     return TMC2_E_STATE;
   }
-  f->haveReconstruction = f->haveAttributeImages = false;
-  f->haveBoundaryTypes = f->haveColors16 = f->haveSmoothed = f->haveRgbPost = false;
+  f->canvasesChanged();  // (the reconstruction is about to be replaced: what is derived from the canvases starts over)
   tmc2_ctx*    ctx = f->ctx;
   hipStream_t  s   = ctx->stream;
   const int    W = f->canvasW, H = f->canvasH, prec = f->occPrecision;
   const dim3   blk( 256 );
   const uint32_t tiles = f->tileCount;
   // ---- S17 ----------------------------------------------------------------------------------------------
-  int sid = ctx->stageBegin( "reconstruct" );
+  StageScope       stage( ctx, "reconstruct" );
   DevBuf<uint32_t> d_tileCount, d_tileOffset, d_small;
   TMC2_TRY( d_tileCount.alloc( std::max( tiles, 1u ) ) );
   TMC2_TRY( d_tileOffset.alloc( std::max( tiles, 1u ) ) );
@@ -501,7 +499,6 @@ int reconstructPointCloud( tmc2_frame* f ) {
     M = answer[0];
   }
   if ( M == 0 ) {
-    ctx->stageEnd( sid );
     setError( "generatePointCloud: empty reconstruction" );
     return TMC2_E_STATE;
   }
@@ -510,7 +507,7 @@ int reconstructPointCloud( tmc2_frame* f ) {
   hipLaunchKernelGGL( reconTileKernel<true>, dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
                       f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, d_tileOffset.p, f->d_recon.p,
                       f->d_pointToPixel.p );
-  ctx->stageEnd( sid );
+  stage.end();
   f->reconCount = M;
   // ---- tree over the reconstruction (like S1) --------------------------------------------------------------
   TMC2_TRY( buildKdTreePlaced( ctx, f->d_recon.p, M, nullptr, "kdtree_build_recon", f->reconTree ) );
@@ -535,7 +532,6 @@ int generateAttributeImages( tmc2_frame* f ) {
   const size_t area = size_t( W ) * H;
   const dim3   blk( 256 );
   const uint32_t n = uint32_t( f->n ), M = uint32_t( f->reconCount );
-  int          sid = 0;
   DevBuf<uint32_t> d_small;
   TMC2_TRY( d_small.alloc( 8 ) );
   // ---- S18 ----------------------------------------------------------------------------------------------
@@ -547,7 +543,7 @@ int generateAttributeImages( tmc2_frame* f ) {
   TMC2_TRY( transferColorsDevice( ctx, f->tree.view( QueryBox::Tight ), f->d_pts.p, f->d_rgb.p, n, f->reconTree.view( QueryBox::Tight ),
                                   f->d_recon.p, M, f->d_reconRgb.p, const_cast<uint32_t*>( h_err ) ) );
   // ---- S20 ----------------------------------------------------------------------------------------------
-  sid = ctx->stageBegin( "attribute_images" );
+  StageScope      stage( ctx, "attribute_images" );
   DevBuf<uint8_t> d_occ;
   TMC2_TRY( d_occ.alloc( area ) );
   TMC2_TRY( f->d_attr.alloc( 6 * area ) );
@@ -638,7 +634,7 @@ int generateAttributeImages( tmc2_frame* f ) {
   }
   // ---- S22 ----------------------------------------------------------------------------------------------
   hipLaunchKernelGGL( attributeGroupDilateKernel, dim3( uint32_t( ( area + 255 ) / 256 ) ), blk, 0, s, d_occ.p, W, H, f->d_attr.p );
-  ctx->stageEnd( sid );
+  stage.end();  // (before the host waits: an event recorded after the wait is stamped later)
   TMC2_HIP( hipStreamSynchronize( s ) );
   TMC2_HIP( hipGetLastError() );
   const uint32_t err = *h_err;

@@ -205,10 +205,10 @@ int tmc2_color_convert_rgb444_to_yuv420( tmc2_ctx* ctx, const uint8_t* rgb, int 
   TMC2_TRY( d_rgb.alloc( 3 * area ) );
   TMC2_TRY( d_yuv.alloc( area * 3 / 2 ) );
   TMC2_HIP( hipMemcpyAsync( d_rgb.p, rgb, 3 * area, hipMemcpyHostToDevice, ctx->stream ) );
-  const int sid = ctx->stageBegin( "rgb444_to_yuv420" );
-  const int r   = tmc2::rgb444ToYuv420Device( ctx, d_rgb.p, width, height, downsamplingFilter, d_yuv.p );
-  ctx->stageEnd( sid );
-  TMC2_TRY( r );
+  {
+    tmc2::StageScope stage( ctx, "rgb444_to_yuv420" );
+    TMC2_TRY( tmc2::rgb444ToYuv420Device( ctx, d_rgb.p, width, height, downsamplingFilter, d_yuv.p ) );
+  }
   TMC2_HIP( hipMemcpyAsync( yuv420, d_yuv.p, area * 3 / 2, hipMemcpyDeviceToHost, ctx->stream ) );
   TMC2_HIP( hipStreamSynchronize( ctx->stream ) );
   return TMC2_OK;
@@ -224,10 +224,10 @@ int tmc2_color_convert_yuv420_to_yuv444( tmc2_ctx* ctx, const uint8_t* yuv420, i
   TMC2_TRY( d_yuv.alloc( area * 3 / 2 ) );
   TMC2_TRY( d_out.alloc( 3 * area ) );
   TMC2_HIP( hipMemcpyAsync( d_yuv.p, yuv420, area * 3 / 2, hipMemcpyHostToDevice, ctx->stream ) );
-  const int sid = ctx->stageBegin( "yuv420_to_yuv444" );
-  const int r   = tmc2::yuv420ToYuv444Device( ctx, d_yuv.p, width, height, upsamplingFilter, d_out.p );
-  ctx->stageEnd( sid );
-  TMC2_TRY( r );
+  {
+    tmc2::StageScope stage( ctx, "yuv420_to_yuv444" );
+    TMC2_TRY( tmc2::yuv420ToYuv444Device( ctx, d_yuv.p, width, height, upsamplingFilter, d_out.p ) );
+  }
   TMC2_HIP( hipMemcpyAsync( yuv444, d_out.p, 3 * area * sizeof( uint16_t ), hipMemcpyDeviceToHost, ctx->stream ) );
   TMC2_HIP( hipStreamSynchronize( ctx->stream ) );
   return TMC2_OK;
@@ -247,12 +247,11 @@ int tmc2_encoder_attribute_to_yuv420( tmc2_frame* f, int downsamplingFilter, uin
   const size_t area = size_t( W ) * H, frame = area * 3 / 2;
   tmc2::DevBuf<uint8_t> d_yuv;
   TMC2_TRY( d_yuv.alloc( 2 * frame ) );
-  const int sid = ctx->stageBegin( "rgb444_to_yuv420" );
-  int       r   = TMC2_OK;
-  for ( int m = 0; m < 2 && r == TMC2_OK; ++m )
-    r = tmc2::rgb444ToYuv420Device( ctx, f->d_attr.p + size_t( m ) * 3 * area, W, H, downsamplingFilter, d_yuv.p + size_t( m ) * frame );
-  ctx->stageEnd( sid );
-  TMC2_TRY( r );
+  {
+    tmc2::StageScope stage( ctx, "rgb444_to_yuv420" );
+    for ( int m = 0; m < 2; ++m )
+      TMC2_TRY( tmc2::rgb444ToYuv420Device( ctx, f->d_attr.p + size_t( m ) * 3 * area, W, H, downsamplingFilter, d_yuv.p + size_t( m ) * frame ) );
+  }
   TMC2_HIP( hipMemcpyAsync( yuv420, d_yuv.p, 2 * frame, hipMemcpyDeviceToHost, ctx->stream ) );
   TMC2_HIP( hipStreamSynchronize( ctx->stream ) );
   return TMC2_OK;
@@ -274,12 +273,11 @@ int tmc2_codec_set_decoded_attribute_yuv420( tmc2_frame* f, const uint8_t* yuv42
   TMC2_TRY( d_yuv.alloc( 2 * frame ) );
   TMC2_TRY( f->d_attr16.alloc( 6 * area ) );
   TMC2_HIP( hipMemcpyAsync( d_yuv.p, yuv420, 2 * frame, hipMemcpyHostToDevice, ctx->stream ) );
-  const int sid = ctx->stageBegin( "yuv420_to_yuv444" );
-  int       r   = TMC2_OK;
-  for ( int m = 0; m < 2 && r == TMC2_OK; ++m )
-    r = tmc2::yuv420ToYuv444Device( ctx, d_yuv.p + size_t( m ) * frame, W, H, upsamplingFilter, f->d_attr16.p + size_t( m ) * 3 * area );
-  ctx->stageEnd( sid );
-  TMC2_TRY( r );
+  {
+    tmc2::StageScope stage( ctx, "yuv420_to_yuv444" );
+    for ( int m = 0; m < 2; ++m )
+      TMC2_TRY( tmc2::yuv420ToYuv444Device( ctx, d_yuv.p + size_t( m ) * frame, W, H, upsamplingFilter, f->d_attr16.p + size_t( m ) * 3 * area ) );
+  }
   TMC2_HIP( hipStreamSynchronize( ctx->stream ) );
   f->haveAttr16 = true;
   return TMC2_OK;

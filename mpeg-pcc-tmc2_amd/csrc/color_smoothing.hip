@@ -280,7 +280,7 @@ int colorSmoothingDevice( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype
   TMC2_TRY( d_small.alloc( 4 ) );
   TMC2_TRY( d_pointSlot.alloc( M ) );
   TMC2_TRY( d_entries.alloc( M ) );
-  const int sid = ctx->stageBegin( "color_smoothing" );
+  StageScope stage( ctx, "color_smoothing" );
   TMC2_HIP( hipMemsetAsync( d_bits.p, 0, size_t( words ) * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_small.p, 0, 16, s ) );
   hipLaunchKernelGGL( markColorCellsKernel, grdM, blk, 0, s, d_pts, d_btype, M, g, d_bits.p );
@@ -289,10 +289,7 @@ int colorSmoothingDevice( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype
   uint32_t cells = 0;
   TMC2_HIP( hipMemcpyAsync( &cells, d_small.p, 4, hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
-  if ( cells == 0 ) {  // no boundary point inside the faces: nothing is filtered
-    ctx->stageEnd( sid );
-    return TMC2_OK;
-  }
+  if ( cells == 0 ) return TMC2_OK;  // no boundary point inside the faces: nothing is filtered
   DevBuf<uint32_t>  d_count, d_offset, d_cursor;
   DevBuf<ColorCell> d_table;
   TMC2_TRY( d_count.alloc( cells ) );
@@ -310,7 +307,7 @@ int colorSmoothingDevice( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype
                       d_offset.p, cells, d_entries.p, colors, patches, thrVariation, d_table.p, d_small.p + 1 );
   const CellLookup lookup{g, d_bits.p, d_rank.p, d_table.p};
   hipLaunchKernelGGL( filterColorsKernel, grdM, blk, 0, s, d_pts, d_btype, M, lookup, thrSmoothing, thrDifference, colors );
-  ctx->stageEnd( sid );
+  stage.end();
   uint32_t err[2] = {0, 0};
   TMC2_HIP( hipMemcpyAsync( err, d_small.p + 1, 8, hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );

@@ -562,6 +562,7 @@ int globalPatchAllocationCore( std::vector<GpaFrameIO>& frames, int minW, int mi
 // a packed patch list (list order, pool in list order) becomes the frame's state: records on the host, pool re-uploaded
 int installPacking( tmc2_frame* f, const GpaFrameIO& g ) {
   ApiScope scope( f->ctx );
+  f->packingChanged();
   f->patches   = g.list;  // list order from here on: the reference rewrites the patch indices to list positions
   f->packMatch = g.match;
   f->packOrder.resize( g.list.size() );
@@ -574,7 +575,6 @@ int installPacking( tmc2_frame* f, const GpaFrameIO& g ) {
   }
   f->packedHeight       = g.height;
   f->packedWidth        = g.width;
-  f->haveGeometryImages = f->haveAttributeImages = f->haveReconstruction = false;
   return TMC2_OK;
 }
 

@@ -292,18 +292,20 @@ int createDecoderFrame( tmc2_ctx* ctx, const tmc2_patch* patches, int count, int
   hipStream_t  s    = ctx->stream;
   const size_t area = size_t( W ) * H;
   const int    Wv = W / occPrecision, Hv = H / occPrecision, Wb = W / 16, Hb = H / 16;
-  TMC2_TRY( uploadPlacement( f.get() ) );
   TMC2_TRY( f->d_occVideo.alloc( size_t( Wv ) * Hv ) );
   TMC2_TRY( f->d_blockToPatch.alloc( size_t( Wb ) * Hb ) );
   TMC2_TRY( f->d_geo.alloc( 2 * area ) );
   TMC2_TRY( f->d_occMap.alloc( area ) );
+  // (last of what can fail before the stream is waited for: its copies read the context's staging until then)
+  TMC2_TRY( uploadPlacement( f.get() ) );
   TMC2_HIP( hipMemcpyAsync( f->d_occVideo.p, occVideo, size_t( Wv ) * Hv, hipMemcpyHostToDevice, s ) );
   TMC2_HIP( hipMemcpyAsync( f->d_geo.p, geometry, 2 * area * sizeof( uint16_t ), hipMemcpyHostToDevice, s ) );
   TMC2_HIP( hipMemsetAsync( f->d_occMap.p, 0, area, s ) );  // (the precise encoder-side map does not exist on this side)
-  const int sid = ctx->stageBegin( "block_to_patch" );
-  hipLaunchKernelGGL( blockToPatchKernel, dim3( ( Wb * Hb + 255 ) / 256 ), dim3( 256 ), 0, s, f->d_place.p, count, f->d_occVideo.p, Wb,
-                      Hb, Wv, occPrecision, f->d_blockToPatch.p );
-  ctx->stageEnd( sid );
+  {
+    StageScope stage( ctx, "block_to_patch" );
+    hipLaunchKernelGGL( blockToPatchKernel, dim3( ( Wb * Hb + 255 ) / 256 ), dim3( 256 ), 0, s, f->d_place.p, count, f->d_occVideo.p, Wb,
+                        Hb, Wv, occPrecision, f->d_blockToPatch.p );
+  }
   TMC2_HIP( hipStreamSynchronize( s ) );
   TMC2_HIP( hipGetLastError() );
   f->canvasW = W, f->canvasH = H, f->occPrecision = occPrecision;
@@ -323,17 +325,12 @@ int generateGeometryImages( tmc2_frame* f, int W, int H, int occRes, int occPrec
               kMaxCanvasDim, occRes, occPrecision );
     return TMC2_E_UNSUPPORTED;
   }
-  // new canvases: whatever was derived from the old ones is stale
-  f->haveGeometryImages = false;
-  invalidateReconstruction( f );
+  f->packingChanged();  // new canvases: the old ones and whatever was derived from them are stale
   tmc2_ctx*   ctx = f->ctx;
   hipStream_t s   = ctx->stream;
   const int   P   = int( f->patches.size() );
   const size_t area = size_t( W ) * H;
   const int    Wv = W / occPrecision, Hv = H / occPrecision, Wb = W / 16, Hb = H / 16;
-  TMC2_TRY( uploadPlacement( f ) );
-  DevBuf<PlaceDev>& d_place     = f->d_place;
-  DevBuf<uint32_t>& d_tilePatch = f->d_tilePatch;
   // (the "patch outside the canvas" flag is a page-locked word of the context: a kernel that finds one stores there, the host reads it
   //  after the synchronisation below -- no copy)
   volatile uint32_t* h_err = ctx->answerLine( tmc2_ctx::kAnswerGeoError );
@@ -344,7 +341,11 @@ int generateGeometryImages( tmc2_frame* f, int W, int H, int occRes, int occPrec
   TMC2_TRY( f->d_occVideo.alloc( size_t( Wv ) * Hv ) );
   TMC2_TRY( f->d_blockToPatch.alloc( size_t( Wb ) * Hb ) );
   TMC2_TRY( f->d_geo.alloc( 2 * area ) );
-  const int sid = ctx->stageBegin( "geometry_images" );
+  // (last of what can fail before the stream is waited for: its copies read the context's staging until then)
+  TMC2_TRY( uploadPlacement( f ) );
+  DevBuf<PlaceDev>& d_place     = f->d_place;
+  DevBuf<uint32_t>& d_tilePatch = f->d_tilePatch;
+  StageScope        stage( ctx, "geometry_images" );
   TMC2_TRY( fillRegions( ctx, {{f->d_occMap.p, area, 0}, {f->d_geo.p, 2 * area * sizeof( uint16_t ), 0}} ) );
   const dim3 blk( 256 );
   if ( f->tileCount )
@@ -359,7 +360,7 @@ int generateGeometryImages( tmc2_frame* f, int W, int H, int occRes, int occPrec
   hipLaunchKernelGGL( carryRowsKernel, dim3( ( H + 63 ) / 64, 2 ), dim3( 64 ), 0, s, d_empty.p, W, H, f->d_geo.p );
   hipLaunchKernelGGL( groupDilateKernel, dim3( uint32_t( ( area + 255 ) / 256 ) ), blk, 0, s, f->d_occVideo.p, W, H, Wv,
                       occPrecision, f->d_geo.p );
-  ctx->stageEnd( sid );
+  stage.end();  // (before the host waits)
   TMC2_HIP( hipStreamSynchronize( s ) );
   TMC2_HIP( hipGetLastError() );
   const uint32_t err = *h_err;
@@ -410,7 +411,7 @@ int tmc2_frame_set_decoded_geometry( tmc2_frame* f, const uint8_t* occVideo, con
                         int( f->patches.size() ), f->d_occVideo.p, Wb, Hb, f->canvasW / f->occPrecision, f->occPrecision,
                         f->d_blockToPatch.p );
   }
-  tmc2::invalidateReconstruction( f );  // whatever was reconstructed from the previous canvases is stale
+  f->canvasesChanged();  // whatever was reconstructed from the previous canvases is stale
   TMC2_HIP( hipStreamSynchronize( s ) );
   TMC2_HIP( hipGetLastError() );
   return TMC2_OK;

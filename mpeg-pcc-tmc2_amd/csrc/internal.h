@@ -265,6 +265,8 @@ struct PinnedBuf {
     return reinterpret_cast<T*>( p );
   }
 };
+struct StageScope;
+struct RefineJob;  // refine.hip
 }  // namespace tmc2
 
 struct tmc2_ctx {
@@ -316,12 +318,28 @@ struct tmc2_ctx {
   bool                          timing = true;
   int                           cuCount = 256;
   void foldStage( tmc2::StageTimer& t );
+  void stageAddHostMs( const char* name, double ms );
+
+ private:
+  friend struct tmc2::StageScope;  // the only way to time a stage
   int  stageBegin( const char* name );
   void stageEnd( int id );
-  void stageAddHostMs( const char* name, double ms );
 };
 
 namespace tmc2 {
+// The timed span of a stage on the context's stream: opened here, closed by end() (where the end event has to be recorded before
+// something that follows in the same scope, a hipStreamSynchronize above all) or on every other way out of the scope.
+struct StageScope {
+  StageScope( tmc2_ctx* c, const char* name ) : ctx( c ), id( c->stageBegin( name ) ) {}
+  StageScope( const StageScope& ) = delete;
+  StageScope& operator=( const StageScope& ) = delete;
+  ~StageScope() { end(); }
+  void end() { ctx->stageEnd( id ), id = -1; }  // (a second call finds no span)
+
+ private:
+  tmc2_ctx* ctx;
+  int       id;
+};
 void destroyContextNow( tmc2_ctx* ctx );
 // first member of a frame, so destroyed last: counts the frame in its context and, when it was the last one of a context whose
 // destruction has been asked for, destroys the context
@@ -348,10 +366,16 @@ struct tmc2_frame {
   std::vector<uint8_t> h_rgb;
   bool                 haveTree = false;
   int                  ensureTree();  // builds + uploads the k-d tree on first use (S1 belongs to the timed path)
-  // device work that needs the points only and may run while the host walks the orientation graph (S3): called by the
-  // orientation step right before its sequential host part, when set (tmc2_segmenter_compute: the refine step's geometry)
-  std::function<int()>  beforeHostWalk;
-  std::shared_ptr<void> refineJob;  // the refine step's geometry, prepared ahead (refine.hip)
+  std::shared_ptr<tmc2::RefineJob> refineJob;  // the refine step's geometry, prepared ahead (refine.hip)
+  // What a new product makes stale.  Each level clears its own flag and calls the next; the levels above the patches (tree, k-NN,
+  // normals, partition) are replaced one at a time by their own stages and setters and are not part of the chain.
+  void resetDerived();  // every product of the frame: only the points stay
+  void patchesChanged() { havePacking = false, packingChanged(); }
+  void packingChanged() { haveGeometryImages = false, canvasesChanged(); }
+  void canvasesChanged() {
+    haveAttributeImages = haveReconstruction = false;
+    haveBoundaryTypes = haveColors16 = haveSmoothed = haveRgbPost = false;
+  }
   // device side
   tmc2::DevBuf<tmc2::Pt>     d_pts;       // original order
   tmc2::DeviceTree           tree;        // over d_pts (ensureTree); queried with the frame's own points or its reconstruction: QueryBox::Tight
@@ -434,13 +458,13 @@ int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uin
                     uint32_t* d_dist, const char* stage, bool uniqueTreeRows = false );
 int generateAttributeImages( tmc2_frame* f );
 int reconstructPointCloud( tmc2_frame* f );
-inline void invalidateReconstruction( tmc2_frame* f ) {  // new or replaced canvases: everything derived from them is stale
-  f->haveAttributeImages = f->haveReconstruction = false;
-  f->haveBoundaryTypes = f->haveColors16 = f->haveSmoothed = f->haveRgbPost = false;
-}
 int uploadPlacement( tmc2_frame* f );
 int launchNormals( tmc2_frame* f );
-int orientNormalsHost( tmc2_frame* f );
+// beforeHostWalk: device work that needs the points only and may run while the host walks the orientation graph (S3); called once,
+// right after the first successful contraction and before the sequential host part (tmc2_segmenter_compute: the refine step's geometry)
+int orientNormalsHost( tmc2_frame* f, const std::function<int()>* beforeHostWalk = nullptr );
+// tmc2_normals_compute with the orientation's hook (api.cpp)
+int normalsCompute( tmc2_frame* f, int k, int orientation, const std::function<int()>* beforeHostWalk );
 int ensureMutualMask( tmc2_frame* f );  // k = 16 only
 int launchEdgeDots( tmc2_frame* f, double* d_edgeDot );
 constexpr size_t kOrientNegCountWords = 64 * 32;  // d_negCount: 64 counters, one per 128 bytes

@@ -308,9 +308,8 @@ int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, 
 
 int launchKnnSelf( tmc2_frame* f, int k ) {
   TMC2_TRY( f->d_knn.alloc( f->n * size_t( k ) ) );
-  const int sid = f->ctx->stageBegin( "knn_self" );
-  const int r   = dispatch<true>( f->ctx->stream, f->tree.view( QueryBox::Tight ), nullptr, f->n, k, f->d_knn.p, nullptr );
-  f->ctx->stageEnd( sid );
+  StageScope stage( f->ctx, "knn_self" );
+  const int  r = dispatch<true>( f->ctx->stream, f->tree.view( QueryBox::Tight ), nullptr, f->n, k, f->d_knn.p, nullptr );
   if ( r == TMC2_OK ) {
     f->k       = k;
     f->haveKnn    = true;
@@ -328,10 +327,8 @@ int launchKnnQueries( tmc2_frame* f, const Pt* d_queries, uint64_t nq, int k, ui
 
 int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx,
                    uint32_t* d_dist, const char* stage ) {
-  const int sid = ctx->stageBegin( stage );
-  const int r   = dispatch<false>( ctx->stream, tree, d_queries, nq, k, d_idx, d_dist );
-  ctx->stageEnd( sid );
-  return r;
+  StageScope span( ctx, stage );
+  return dispatch<false>( ctx->stream, tree, d_queries, nq, k, d_idx, d_dist );
 }
 
 namespace {
@@ -401,7 +398,7 @@ int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uin
                     uint32_t* d_dist, const char* stage, bool uniqueTreeRows ) {
   hipStream_t s = ctx->stream;
   if ( nq == 0 ) return TMC2_OK;
-  const int sid = ctx->stageBegin( stage );
+  StageScope       span( ctx, stage );
   DevBuf<uint32_t> d_flag, d_rank, d_rowMap, d_count;
   DevBuf<Pt>       d_hard;
   TMC2_TRY( d_flag.alloc( nq ) );
@@ -428,7 +425,6 @@ int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uin
       r = dispatch<false>( s, tree, d_hard.p, nq, k, d_idx, d_dist, d_count.p, d_rowMap.p );
     }
   }
-  ctx->stageEnd( sid );
   return r;
 }
 

@@ -655,10 +655,9 @@ int qualityTerms( tmc2_ctx* ctx, const DevCloud& A, const DevCloud& B, bool with
   TMC2_TRY( d_dist.alloc( size_t( nA ) * K ) );
   TMC2_TRY( d_terms.alloc( size_t( nA ) * 5 ) );
   TMC2_TRY( metricsKnn( ctx, B.devFor( A ), A.pts.p, nA, K, d_idx.p, d_dist.p ) );
-  const int sid = ctx->stageBegin( "metrics_terms" );
+  StageScope stage( ctx, "metrics_terms" );
   hipLaunchKernelGGL( distortionTermsKernel, dim3( ( nA + 255 ) / 256 ), dim3( 256 ), 0, s, A.pts.p, A.rgb4.p, B.pts.p, B.rgb4.p,
                       withNormals ? B.nrm.p : (const double*)nullptr, d_idx.p, d_dist.p, K, nA, d_terms.p, d_error );
-  ctx->stageEnd( sid );
   return TMC2_OK;
 }
 
@@ -671,12 +670,6 @@ void qualityFromSums( const double* sse, double num, bool withNormals, double re
   out[7] = psnr( out[4], 1.0, 1.0 );
 }
 
-struct StageScope {  // closes a stage on every way out
-  tmc2_ctx* ctx;
-  int       id;
-  ~StageScope() { ctx->stageEnd( id ); }
-};
-
 // PCCMetrics::compute for one frame from clouds resident on the device.  d_srcNormals: fp64[src.n][3] or null.
 // *overflow = true: some query's K results were all equidistant (K = 16 only): the caller repeats with K = 32.
 int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, const double* d_srcNormals, double resolution, int K,
@@ -688,7 +681,7 @@ int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, co
   const bool       withNormals = d_srcNormals != nullptr;
   const dim3       blk( 256 );
   {
-    StageScope prep{ctx, ctx->stageBegin( "metrics_prepare" )};
+    StageScope prep( ctx, "metrics_prepare" );
     TMC2_TRY( removeDuplicatesDevice( ctx, src, dS, d_firstS ) );
     TMC2_TRY( removeDuplicatesDevice( ctx, rec, dR, d_firstR ) );
     if ( counts ) counts[0] = int64_t( dS.n ), counts[1] = int64_t( dR.n );
@@ -765,9 +758,10 @@ int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, co
     TMC2_TRY( d_sums.alloc( 16 ) );
     TMC2_TRY( qualityTerms( ctx, dS, dR, withNormals, K, d_termsS, d_error.p ) );
     TMC2_TRY( qualityTerms( ctx, dR, dS, withNormals, K, d_termsR, d_error.p ) );
-    const int    sid = ctx->stageBegin( "metrics_sums" );
-    TMC2_TRY( orderedSums( ctx, d_termsS.p, uint32_t( dS.n ), d_termsR.p, uint32_t( dR.n ), d_sums.p ) );
-    ctx->stageEnd( sid );
+    {
+      StageScope stage( ctx, "metrics_sums" );
+      TMC2_TRY( orderedSums( ctx, d_termsS.p, uint32_t( dS.n ), d_termsR.p, uint32_t( dR.n ), d_sums.p ) );
+    }
     double   sse[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t err     = 0;
     TMC2_HIP( hipMemcpyAsync( sse, d_sums.p, sizeof( sse ), hipMemcpyDeviceToHost, s ) );
@@ -814,7 +808,7 @@ struct UploadedSource {
   DevBuf<double>  nrm;
   int put( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const double* srcNormals, CloudView& view ) {
     hipStream_t s = ctx->stream;
-    StageScope  up{ctx, ctx->stageBegin( "metrics_upload" )};
+    StageScope  up( ctx, "metrics_upload" );
     TMC2_TRY( xyz.alloc( 3 * size_t( n ) ) );
     TMC2_TRY( rgb.alloc( 3 * size_t( n ) ) );
     TMC2_HIP( hipMemcpyAsync( xyz.p, srcXyz, 6 * size_t( n ), hipMemcpyHostToDevice, s ) );
@@ -885,9 +879,10 @@ extern "C" int tmc2_metrics_ordered_sums( tmc2_ctx* ctx, const double* termsA, u
   TMC2_TRY( d_out.alloc( 16 ) );
   if ( nA ) TMC2_HIP( hipMemcpyAsync( d_a.p, termsA, 5 * size_t( nA ) * sizeof( double ), hipMemcpyHostToDevice, s ) );
   if ( nB ) TMC2_HIP( hipMemcpyAsync( d_b.p, termsB, 5 * size_t( nB ) * sizeof( double ), hipMemcpyHostToDevice, s ) );
-  const int sid = ctx->stageBegin( "metrics_sums" );
-  TMC2_TRY( orderedSums( ctx, d_a.p, uint32_t( nA ), d_b.p, uint32_t( nB ), d_out.p ) );
-  ctx->stageEnd( sid );
+  {
+    StageScope stage( ctx, "metrics_sums" );
+    TMC2_TRY( orderedSums( ctx, d_a.p, uint32_t( nA ), d_b.p, uint32_t( nB ), d_out.p ) );
+  }
   TMC2_HIP( hipMemcpyAsync( out, d_out.p, 10 * sizeof( double ), hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
   TMC2_HIP( hipGetLastError() );

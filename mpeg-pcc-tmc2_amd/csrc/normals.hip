@@ -193,7 +193,7 @@ int launchNormals( tmc2_frame* f ) {
     return TMC2_E_STATE;
   }
   TMC2_TRY( f->d_normals.alloc( f->n * 3 ) );
-  const int  sid = f->ctx->stageBegin( "normals" );
+  StageScope stage( f->ctx, "normals" );
   const dim3 block( 256 ), grid( chunkedGrid( uint32_t( ( f->n + 255 ) / 256 ) ) );
   if ( f->k == 16 ) {
     hipLaunchKernelGGL( normalsKernel<16>, grid, block, 0, f->ctx->stream, f->d_pts.p, f->d_knn.p, uint32_t( f->n ),
@@ -202,11 +202,9 @@ int launchNormals( tmc2_frame* f ) {
     hipLaunchKernelGGL( normalsKernel<8>, grid, block, 0, f->ctx->stream, f->d_pts.p, f->d_knn.p, uint32_t( f->n ),
                         f->d_normals.p );
   } else {
-    f->ctx->stageEnd( sid );
     setError( "normals: k=%d not instantiated (8, 16)", f->k );
     return TMC2_E_UNSUPPORTED;
   }
-  f->ctx->stageEnd( sid );
   TMC2_HIP( hipGetLastError() );
   f->haveNormals = true;
   return TMC2_OK;
@@ -293,11 +291,10 @@ int launchInitialSegmentation( tmc2_frame* f, const double weight[3] ) {
   TMC2_TRY( f->d_partition.alloc( f->n ) );
   Weights6 wv;
   for ( int j = 0; j < 6; ++j ) wv.w[j] = weight[j % 3];
-  const int  sid = f->ctx->stageBegin( "initial_segmentation" );
+  StageScope stage( f->ctx, "initial_segmentation" );
   const dim3 block( 256 ), grid( uint32_t( ( f->n + 255 ) / 256 ) );
   hipLaunchKernelGGL( initialSegmentationKernel, grid, block, 0, f->ctx->stream, f->d_normals.p, uint32_t( f->n ), wv,
                       f->d_partition.p );
-  f->ctx->stageEnd( sid );
   TMC2_HIP( hipGetLastError() );
   f->havePartition = true;
   return TMC2_OK;

@@ -726,7 +726,7 @@ void orientNormalsSpanningTree( const int16_t* xyz, size_t n, const uint32_t* kn
     for ( size_t i = 0; i < 3 * n; ++i ) normals[i] = -normals[i];
 }
 
-int orientNormalsHost( tmc2_frame* f ) {
+int orientNormalsHost( tmc2_frame* f, const std::function<int()>* beforeHostWalk ) {
   if ( !f->haveKnn || !f->haveNormals ) {
     setError( "orientNormals: adjacency / normals not computed" );
     return TMC2_E_STATE;
@@ -748,13 +748,14 @@ int orientNormalsHost( tmc2_frame* f ) {
   for ( const double tau : orientTauLadder( ctx ) ) {
     if ( tau != orientFirstTau( ctx ) ) ctx->stageAddHostMs( "orient_tau_retry", 0.0 );  // (counts the repeats with a tighter threshold)
     OrientCompact g{};
-    const int     sid = ctx->stageBegin( "orient_contract" );
-    TMC2_TRY( contractOrientationDevice( f, tau, d_root, d_parity, g, contracted ) );  // (d_root: cluster ids here)
-    ctx->stageEnd( sid );
+    {
+      StageScope stage( ctx, "orient_contract" );
+      TMC2_TRY( contractOrientationDevice( f, tau, d_root, d_parity, g, contracted ) );  // (d_root: cluster ids here)
+    }
     if ( contracted ) {
-      if ( f->beforeHostWalk ) {  // device work that overlaps the walk (once, whatever the number of thresholds tried)
-        TMC2_TRY( f->beforeHostWalk() );
-        f->beforeHostWalk = nullptr;
+      if ( beforeHostWalk ) {  // device work that overlaps the walk (once, whatever the number of thresholds tried)
+        TMC2_TRY( ( *beforeHostWalk )() );
+        beforeHostWalk = nullptr;
       }
       const uint32_t        C           = g.clusters;
       int8_t*               clusterSign = reinterpret_cast<int8_t*>( ctx->hostC.get<uint32_t>( 4 + ( n + 4 ) / 4 + 4 ) + 4 );  // (behind the counters)

@@ -115,6 +115,7 @@ int packFlexibleHost( tmc2_frame* f, int presetWidth, int occRes, int numTilesHo
     return TMC2_E_STATE;
   }
   const int P = int( f->patches.size() );
+  f->packingChanged();
   f->packOrder.resize( P );
   f->packMatch.assign( P, -1 );
   for ( int i = 0; i < P; ++i ) f->packOrder[i] = i;
@@ -262,6 +263,7 @@ int packSpatialConsistencyHost( tmc2_frame* f, tmc2_frame* prevFrame, int preset
     return TMC2_E_STATE;
   }
   const int P = int( f->patches.size() );
+  f->packingChanged();
   f->packOrder.assign( P, 0 );
   f->packMatch.assign( P, -1 );
   f->packedHeight = 0;

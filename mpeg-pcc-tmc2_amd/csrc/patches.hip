@@ -741,7 +741,7 @@ int ensureMutualMask( tmc2_frame* f ) {
   if ( f->haveMutual ) return TMC2_OK;
   const uint32_t n = uint32_t( f->n );
   TMC2_TRY( f->d_mutual.alloc( n ) );
-  const int kt = f->ctx->stageBegin( "k:ccMutualMask" );
+  StageScope stage( f->ctx, "k:ccMutualMask" );
   // option MUTUAL_ORDER (this pass and S7's union / relaxation passes): "input" = index order, blocks as they come (rounds 1-5);
   // "chunk" = index order, XCD x on the x-th eighth of the blocks; "tree" = tree order, same eighths
   const auto      order   = ctxOption( f->ctx, "MUTUAL_ORDER" );
@@ -750,7 +750,6 @@ int ensureMutualMask( tmc2_frame* f ) {
   const uint32_t  blocks  = ( n + 255 ) / 256;
   hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( chunked ? ( ( blocks + 7 ) & ~7u ) : blocks ), dim3( 256 ), 0, f->ctx->stream, f->d_knn.p,
                       perm, chunked, n, f->d_mutual.p );
-  f->ctx->stageEnd( kt );
   TMC2_HIP( hipGetLastError() );
   f->haveMutual = true;
   return TMC2_OK;
@@ -829,6 +828,7 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
                                {d_small.p, 64, 0}} ) );
 
   f->patches.clear();
+  f->patchesChanged();  // (a packing of the old list, and everything made from it, must not be read with the new one)
   f->depthCount = 0;
   f->occCount   = 0;
   // (the one-point-per-lane passes of S7-S9: XCD x takes the x-th eighth of the blocks -- chunkedIndex)
@@ -845,14 +845,14 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   const dim3      grdT( chunked ? ( ( grdN.x + 7u ) & ~7u ) : grdN.x );
   while ( rawCount > 0 ) {
     // ---- S7 -----------------------------------------------------------------------------------------
-    int sid = ctx->stageBegin( "patches_cc" );
+    StageScope cc( ctx, "patches_cc" );
     hipLaunchKernelGGL( ccInitKernel<16>, grdT, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n, d_parent.p,
                         d_lab.p, d_ccCount.p );
     {
-      const int kt = ctx->stageBegin( "k:ccUnion" );
+      StageScope kt( ctx, "k:ccUnion" );
       hipLaunchKernelGGL( ccUnionKernel<16>, grdT, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n,
                           d_parent.p, unionPrecheck( f->ctx ), agentScope );
-      ctx->stageEnd( kt );
+      kt.end();
       if ( unionCheck( f->ctx ) ) {  // debug invariants (soak tests): costs a round trip
         uint32_t bad[2] = {0, 0};
         TMC2_HIP( hipMemsetAsync( d_small.p + 8, 0, 8, s ) );
@@ -872,11 +872,11 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     // last sweep of the batch still change a label" (then sweep on and label again) and the number of patches
     uint32_t P = 0;
     for ( int guard = 0; guard < 1 << 20; ++guard ) {
-      const int kt = ctx->stageBegin( "k:ccRelax" );
+      StageScope kt( ctx, "k:ccRelax" );
       for ( int b = 0; b < 3; ++b )
         hipLaunchKernelGGL( ccRelaxKernel<16>, grdT, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p,
                             d_root.p, perm, chunked, n, d_lab.p, d_small.p, ++relaxToken, agentScope );
-      ctx->stageEnd( kt );
+      kt.end();
       hipLaunchKernelGGL( ccLabelCountKernel, grdN, blk, 0, s, d_raw.p, d_root.p, d_lab.p, n,
                           uint32_t( sp->minPointCountPerCCPatchSegmentation ), d_label.p, d_ccCount.p );
       hipLaunchKernelGGL( ccSeedFlagKernel, grdN, blk, 0, s, d_label.p, d_ccCount.p,
@@ -891,10 +891,10 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
       // (ccCount is an accumulation: start it over before labelling again)
       TMC2_HIP( hipMemsetAsync( d_ccCount.p, 0, size_t( n ) * 4, s ) );
     }
-    ctx->stageEnd( sid );
+    cc.end();
     if ( P == 0 ) break;
     // ---- S8 -----------------------------------------------------------------------------------------
-    sid = ctx->stageBegin( "patches_build" );
+    StageScope build( ctx, "patches_build" );
     TMC2_TRY( d_minUv.alloc( 2 * size_t( P ) ) );
     TMC2_TRY( d_bbox.alloc( 7 * size_t( P ) ) );           // boxes, then the views: one copy to the host
     const size_t statWords = 2 * size_t( P ) + size_t( kRawCounters ) * 32;  // counters, then the round's counts of points still raw: one copy
@@ -1009,7 +1009,7 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     TMC2_HIP( hipStreamSynchronize( s ) );
     rawCount = 0;
     for ( uint32_t c = 0; c < kRawCounters; ++c ) rawCount += uint32_t( h_stat[2 * size_t( P ) + size_t( c ) * 32] );
-    ctx->stageEnd( sid );
+    build.end();
     for ( uint32_t p = 0; p < P; ++p ) {
       tmc2_patch& T = f->patches[patchBase + p];
       const int   sizeD = h_stat[2 * p];

@@ -348,10 +348,9 @@ int identifyBoundaryPoints( tmc2_frame* f ) {
   tmc2_ctx*      ctx = f->ctx;
   const uint32_t M   = uint32_t( f->reconCount );
   TMC2_TRY( f->d_boundaryType.alloc( M ) );
-  const int sid = ctx->stageBegin( "boundary_points" );
+  StageScope stage( ctx, "boundary_points" );
   hipLaunchKernelGGL( boundaryTypeKernel, dim3( ( M + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, f->d_pointToPixel.p, M,
                       f->d_occVideo.p, f->canvasW, f->canvasH, f->occPrecision, f->d_boundaryType.p );
-  ctx->stageEnd( sid );
   TMC2_HIP( hipGetLastError() );
   f->haveBoundaryTypes = true;
   f->haveSmoothed      = false;
@@ -375,10 +374,10 @@ int colorPointCloud( tmc2_frame* f, const uint16_t* attribute ) {
     return TMC2_E_STATE;
   }
   TMC2_TRY( f->d_colors16.alloc( M ) );
-  const int sid = ctx->stageBegin( "color_point_cloud" );
+  StageScope stage( ctx, "color_point_cloud" );
   hipLaunchKernelGGL( colorGatherKernel, dim3( ( M + 255 ) / 256 ), dim3( 256 ), 0, s, f->d_pointToPixel.p, M, f->d_attr16.p,
                       f->canvasW, f->canvasH, reinterpret_cast<ushort4*>( f->d_colors16.p ) );
-  ctx->stageEnd( sid );
+  stage.end();
   TMC2_HIP( hipStreamSynchronize( s ) );  // the caller's buffer is free again
   TMC2_HIP( hipGetLastError() );
   f->haveColors16  = true;
@@ -414,7 +413,7 @@ int smoothPointCloudGrid( tmc2_frame* f, int gridSize, double thresholdSmoothing
   TMC2_TRY( d_flag.alloc( cellCount ) );
   TMC2_TRY( d_slot.alloc( cellCount ) );
   TMC2_TRY( d_small.alloc( 4 ) );
-  const int sid = ctx->stageBegin( "geometry_smoothing" );
+  StageScope stage( ctx, "geometry_smoothing" );
   TMC2_HIP( hipMemsetAsync( d_flag.p, 0, cellCount * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_small.p, 0, 16, s ) );
   hipLaunchKernelGGL( markCellsKernel, grdM, blk, 0, s, f->d_recon.p, f->d_boundaryType.p, M, g, d_flag.p );
@@ -429,7 +428,7 @@ int smoothPointCloudGrid( tmc2_frame* f, int gridSize, double thresholdSmoothing
                       f->canvasW / 16, g, d_flag.p, d_slot.p, d_cells.p );
   hipLaunchKernelGGL( smoothGridKernel, grdM, blk, 0, s, f->d_recon.p, M, g, d_slot.p, d_cells.p, int( thresholdSmoothing ),
                       f->d_reconSmoothed.p, f->d_boundaryType.p, d_small.p + 1 );
-  ctx->stageEnd( sid );
+  stage.end();
   uint32_t err = 0;
   TMC2_HIP( hipMemcpyAsync( &err, d_small.p + 1, 4, hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
@@ -457,14 +456,14 @@ int transferColors16bitBP( tmc2_frame* f ) {
   TMC2_TRY( d_flag.alloc( M ) );
   TMC2_TRY( d_rank.alloc( M ) );
   TMC2_TRY( d_small.alloc( 4 ) );
-  int sid = ctx->stageBegin( "transfer_colors16" );
+  StageScope count( ctx, "transfer_colors16" );
   TMC2_HIP( hipMemsetAsync( d_small.p, 0, 16, s ) );
   hipLaunchKernelGGL( movedFlagKernel, grdM, blk, 0, s, f->d_boundaryType.p, M, d_flag.p );
   TMC2_TRY( exclusiveScanU32( ctx, d_flag.p, d_rank.p, M, d_small.p ) );
   uint32_t K = 0;
   TMC2_HIP( hipMemcpyAsync( &K, d_small.p, 4, hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
-  ctx->stageEnd( sid );
+  count.end();
   if ( K == 0 ) return TMC2_OK;  // nothing moved: every point keeps its colour
   if ( M < 8 ) {
     setError( "transferColors16bitBP: fewer than 8 points" );
@@ -473,9 +472,8 @@ int transferColors16bitBP( tmc2_frame* f ) {
   // the tree over the smoothed cloud (the one over the cloud before smoothing is S18's)
   DeviceTree smoothed;
   {
-    const int kt = ctx->stageBegin( "kdtree_build_smoothed" );
+    StageScope stage( ctx, "kdtree_build_smoothed" );
     TMC2_TRY( buildKdTreeDevice( ctx, f->d_reconSmoothed.p, M, smoothed ) );
-    ctx->stageEnd( kt );
   }
   const uint32_t entries = K * 8;
   DevBuf<uint32_t> d_moved, d_idx8, d_dist8, d_nn1, d_nn1Dist, d_count, d_offset, d_cursor;
@@ -500,13 +498,14 @@ int transferColors16bitBP( tmc2_frame* f ) {
                       d_queries.p );
   // (the queries of both trees are points of the reconstruction before / after smoothing)
   TMC2_TRY( launchKnnTree( ctx, f->reconTree.view( QueryBox::Bounded ), d_queries.p, K, 8, d_idx8.p, d_dist8.p, "knn8_moved_in_recon" ) );
-  sid = ctx->stageBegin( "transfer_colors16" );
-  hipLaunchKernelGGL( forwardColor16Kernel, grdK, blk, 0, s, d_idx8.p, d_dist8.p, colors, f->d_recon.p, K,
-                      reinterpret_cast<ushort4*>( d_refined.p ), d_partPts.p );
-  ctx->stageEnd( sid );
+  {
+    StageScope stage( ctx, "transfer_colors16" );
+    hipLaunchKernelGGL( forwardColor16Kernel, grdK, blk, 0, s, d_idx8.p, d_dist8.p, colors, f->d_recon.p, K,
+                        reinterpret_cast<ushort4*>( d_refined.p ), d_partPts.p );
+  }
   TMC2_TRY( launchKnnTree( ctx, smoothed.view( QueryBox::Bounded ), d_partPts.p, entries, 1, d_nn1.p, d_nn1Dist.p,
                            "knn1_neighbours_in_smoothed" ) );
-  sid = ctx->stageBegin( "transfer_colors16" );
+  StageScope votes( ctx, "transfer_colors16" );
   TMC2_HIP( hipMemsetAsync( d_count.p, 0, size_t( K ) * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_cursor.p, 0, size_t( K ) * 4, s ) );
   hipLaunchKernelGGL( backwardVoteKernel<false>, grdE, blk, 0, s, d_idx8.p, d_nn1.p, d_nn1Dist.p, entries, colors,
@@ -519,7 +518,7 @@ int transferColors16bitBP( tmc2_frame* f ) {
                       reinterpret_cast<ushort4*>( d_refined.p ), K, d_small.p + 1 );
   hipLaunchKernelGGL( scatterColor16Kernel, grdK, blk, 0, s, d_moved.p, reinterpret_cast<const ushort4*>( d_refined.p ), K,
                       reinterpret_cast<ushort4*>( f->d_colors16.p ) );
-  ctx->stageEnd( sid );
+  votes.end();
   uint32_t err = 0;
   TMC2_HIP( hipMemcpyAsync( &err, d_small.p + 1, 4, hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
@@ -541,10 +540,9 @@ int convertYuv16ToRgb8( tmc2_frame* f ) {
   tmc2_ctx*      ctx = f->ctx;
   const uint32_t M   = uint32_t( f->reconCount );
   TMC2_TRY( f->d_rgbPost.alloc( size_t( M ) * 4 ) );
-  const int sid = ctx->stageBegin( "yuv16_to_rgb8" );
+  StageScope stage( ctx, "yuv16_to_rgb8" );
   hipLaunchKernelGGL( yuv16ToRgb8Kernel, dim3( ( M + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream,
                       reinterpret_cast<const ushort4*>( f->d_colors16.p ), M, reinterpret_cast<uchar4*>( f->d_rgbPost.p ) );
-  ctx->stageEnd( sid );
   TMC2_HIP( hipGetLastError() );
   f->haveRgbPost = true;
   return TMC2_OK;

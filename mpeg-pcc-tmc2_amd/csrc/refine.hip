@@ -1316,7 +1316,7 @@ int RefineJob::geometry( tmc2_frame* f ) {
   devRange  = voxDim >= 4 ? 1 : 2;  // PCCPatchSegmenter.cpp:1471
   devStride = devRange == 1 ? 32u : 128u;
   idBits    = r2 <= 64 ? 26 : 25;   // neighbourhood sort key: d2 above, voxel id below
-  const int sidSetup = ctx->stageBegin( "refine_setup" );
+  StageScope setup( ctx, "refine_setup" );
   {
     const size_t bitWords = size_t( g.keyCount ) / 32 + 2;  // (+ spare words: a row's second word may lie behind the last key)
     if ( ctx->gridBits.count < bitWords ) {
@@ -1440,7 +1440,6 @@ int RefineJob::geometry( tmc2_frame* f ) {
   launchNeighbourhood();
   TMC2_HIP( hipMemcpyAsync( res, d_small.p + 1, 20, hipMemcpyDeviceToHost, s ) );  // (read in finish(), after a synchronisation)
   TMC2_HIP( hipMemcpyAsync( rowCtlHost.data(), d_rowCtl.p, kRowRegions * 32 * 4, hipMemcpyDeviceToHost, s ) );
-  ctx->stageEnd( sidSetup );
   TMC2_HIP( hipGetLastError() );
   return TMC2_OK;
 }
@@ -1451,7 +1450,7 @@ int RefineJob::finish() {
     setError( "refineSegmentationGridBased: normals / partition missing" );
     return TMC2_E_STATE;
   }
-  const int  sidSetup = ctx->stageBegin( "refine_setup" );
+  StageScope setup( ctx, "refine_setup" );
   const dim3 blk( 256 ), grdN( ( n + 255 ) / 256 );
   uint8_t *d_edge = d_state.p, *d_ppi = d_state.p + Vp;
   uint32_t* d_active = d_activeBuf.p;
@@ -1506,9 +1505,9 @@ int RefineJob::finish() {
   TMC2_TRY( d_rec.alloc( 2 * size_t( V ) ) );
   hipLaunchKernelGGL( smoothInitKernel, grdV16, blk, 0, s, reinterpret_cast<const uint4*>( d_hist.p ), d_adjOff.p,
                       d_rowLen.p, d_adj.p, V, d_rec.p );
-  ctx->stageEnd( sidSetup );
+  setup.end();
   TMC2_HIP( hipGetLastError() );
-  const int sidSweep = ctx->stageBegin( "refine_sweeps" );
+  StageScope sweeps( ctx, "refine_sweeps" );
   // closureKernel: a run of voxels per workgroup; LDS = the run's active voxels + the ring
   // (test hooks: TMC2_REFINE_CLOSURE_BLOCKS = its grid, TMC2_REFINE_CLOSURE_THREADS = its workgroup; TMC2_REFINE_RING = room
   // of the LDS ring beyond the run -- 1 sends nearly every fan-out through the spill ring)
@@ -1580,7 +1579,7 @@ int RefineJob::finish() {
       fprintf( stderr, "refine: sweep %d sweep done (%d)\n", iter, int( e ) );
     }
   }
-  ctx->stageEnd( sidSweep );
+  sweeps.end();
   TMC2_HIP( hipGetLastError() );
   ctx->stageAddHostMs( "refine_sweeps_executed", double( iterationCount ) );  // (counts, not milliseconds: what the
   ctx->stageAddHostMs( "refine_voxels", double( V ) );                        //  roofline of a sweep is quoted on,
@@ -1625,13 +1624,12 @@ int refineGridBased( tmc2_frame* f, int maxNNCount, double lambda, int iteration
     setError( "refineSegmentationGridBased: normals / partition missing" );
     return TMC2_E_STATE;
   }
-  std::shared_ptr<RefineJob> job = std::static_pointer_cast<RefineJob>( f->refineJob );
-  f->refineJob.reset();
+  std::shared_ptr<RefineJob> job;
+  job.swap( f->refineJob );
   if ( !job || !job->matches( maxNNCount, lambda, iterationCount < 1 ? 1 : iterationCount, voxDim, searchRadius ) ) {
     job.reset();
     TMC2_TRY( refinePrepareGeometry( f, maxNNCount, lambda, iterationCount, voxDim, searchRadius ) );
-    job = std::static_pointer_cast<RefineJob>( f->refineJob );
-    f->refineJob.reset();
+    job.swap( f->refineJob );
   }
   return job->finish();
 }

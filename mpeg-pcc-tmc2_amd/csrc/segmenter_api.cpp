@@ -74,20 +74,19 @@ int tmc2_segmenter_compute( tmc2_frame* f, const tmc2_segmenter_params* p ) {
   // chain and costs throughput when the chip is full: round 4, four frames in flight (one rank's share of an 8-GPU run):
   // longdress 30.8 -> 30.4 ms, loot (voxels of 2: 5 ms of geometry) 57.8 -> 52.0 ms; sixteen in flight: 173.5 -> 174.0 and
   // 91.5 -> 90.1 frames/s.  The GOF host (tmc2_amd/gof.py, integration/tmc2_encode_gof.cpp) turns it on for <= 4 frames in flight.
-  struct HookGuard {  // on every way out: no hook left behind, and no half-used refine job (it holds the context's dense voxel table
-    tmc2_frame* f;    // filled: another frame's refinement on this context would look its cells up in a dirty table)
+  struct JobGuard {  // on every way out: no half-used refine job (it holds the context's dense voxel table filled: another
+    tmc2_frame* f;   // frame's refinement on this context would look its cells up in a dirty table)
     bool        done = false;
-    ~HookGuard() {
-      f->beforeHostWalk = nullptr;
+    ~JobGuard() {
       if ( !done ) f->refineJob.reset();
     }
   } guard{f};
-  if ( p->gridBasedRefineSegmentation && tmc2::refineOverlap( f->ctx ) )
-    f->beforeHostWalk = [f, p]() {
-      return tmc2::refinePrepareGeometry( f, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
-                                          p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,
-                                          p->searchRadiusRefineSegmentation );
-    };
+  const std::function<int()> prepareRefine = [f, p]() {
+    return tmc2::refinePrepareGeometry( f, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
+                                        p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,
+                                        p->searchRadiusRefineSegmentation );
+  };
+  const bool overlap = p->gridBasedRefineSegmentation && tmc2::refineOverlap( f->ctx );
   // Option FRAME_START_DELAY_US (few frames in flight: a rank of the 8-GPU run has four).  Frames that start together reach their
   // host-resident step -- S3's walk, ~ 3 ms -- together, and the GPU has nothing to do meanwhile (profiles/r06_rank_concurrency.txt:
   // a hole of ~ 3 ms in every 27 ms step).  A host that delays the start of half of its frames by about that long has one half
@@ -96,8 +95,7 @@ int tmc2_segmenter_compute( tmc2_frame* f, const tmc2_segmenter_params* p ) {
     const int us = atoi( delay->c_str() );
     if ( us > 0 ) std::this_thread::sleep_for( std::chrono::microseconds( std::min( us, 100000 ) ) );
   }
-  TMC2_TRY( tmc2_normals_compute( f, p->nnNormalEstimation, p->normalOrientation ) );
-  f->beforeHostWalk = nullptr;
+  TMC2_TRY( tmc2::normalsCompute( f, p->nnNormalEstimation, p->normalOrientation, overlap ? &prepareRefine : nullptr ) );
   TMC2_TRY( tmc2_segmenter_initial_segmentation( f, p->weightNormal ) );
   TMC2_TRY( tmc2_segmenter_refine_grid_based( f, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
                                               p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,

@@ -52,12 +52,12 @@ int weightNormal( tmc2_frame* f, int bits, double minWeightEPP, double w[3] ) {
   TMC2_TRY( d_bits.alloc( size_t( wordsPerPlane ) * 3 + 4 ) );
   uint32_t*   d_counts = d_bits.p + size_t( wordsPerPlane ) * 3;
   hipStream_t s        = f->ctx->stream;
-  const int   sid      = f->ctx->stageBegin( "weight_normal" );
+  StageScope  stage( f->ctx, "weight_normal" );
   TMC2_HIP( hipMemsetAsync( d_bits.p, 0, d_bits.bytes(), s ) );
   hipLaunchKernelGGL( footprintKernel, dim3( uint32_t( ( f->n + 255 ) / 256 ) ), dim3( 256 ), 0, s, f->d_pts.p,
                       uint32_t( f->n ), M, d_bits.p );
   hipLaunchKernelGGL( popcountKernel, dim3( 128, 3 ), dim3( 256 ), 0, s, d_bits.p, wordsPerPlane, d_counts );
-  f->ctx->stageEnd( sid );
+  stage.end();
   uint32_t counts[3];
   TMC2_HIP( hipMemcpyAsync( counts, d_counts, sizeof( counts ), hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );

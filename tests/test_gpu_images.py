@@ -24,7 +24,7 @@ def gpu_phase_a(ctx, frames, iterations, occ_precision=4, min_w=1280, min_h=1280
         fr.encoder_generate_geometry_images(W, H, occ_precision)
         img = fr.get_geometry_images()
         patches = fr.get_patches()[0][fr.get_patch_order()]
-        img.update(patches=patches, width=W, height=H)
+        img.update(patches=patches, width=W, height=H, frame=fr)
         out.append(img)
     return out
 
@@ -63,6 +63,51 @@ def test_gpu_phase_a_full_size_properties(gpu_ctx):
     unocc_cell = ~np.repeat(np.repeat(ov, 4, 0), 4, 1)
     assert np.array_equal(g0[unocc_cell], g1[unocc_cell])                      # group dilation equalised D0/D1
     # idempotence: a second generation from the same packing gives the same canvases
+    img["frame"].encoder_generate_geometry_images(W, H, 4)
+    assert all(np.array_equal(v, img[k]) for k, v in img["frame"].get_geometry_images().items())
+
+
+E_STATE = r"tmc2hip error -5: "                        # TMC2_E_STATE, as lib._check words it
+
+
+def _packed_frame_with_canvases(ctx, name):
+    xyz, rgb = synth_cloud(name)
+    fr = ctx.frame(xyz, rgb)
+    p = T.ctc_params(10, 11, fr.weight_normal(11, 0.6))
+    fr.segmenter_compute(p)
+    h = fr.encoder_pack_flexible(1280, 2, 1.0)
+    W, H = T.encoder_canvas_size([h], 1280, 1280, 1280)
+    fr.encoder_generate_geometry_images(W, H, 4)
+    return fr, p, (W, H), fr.get_geometry_images()
+
+
+@pytest.mark.parametrize("name", ["tiny", "small"])
+def test_gpu_resegmentation_leaves_no_stale_product(gpu_ctx, name):
+    """A new patch list without a frame reset in between: the packing and the canvases of the old list are gone with it (they
+    index the old list), and come back the same once the stages have run again in order."""
+    fr, p, (W, H), first = _packed_frame_with_canvases(gpu_ctx, name)
+    fr.segmenter_segment_patches(p)
+    with pytest.raises(T.Tmc2Error, match=E_STATE + ".*frame not packed"):
+        fr.encoder_generate_geometry_images(W, H, 4)
+    with pytest.raises(T.Tmc2Error, match=E_STATE + ".*not generated"):
+        fr.get_geometry_images()
+    with pytest.raises(T.Tmc2Error, match=E_STATE + ".*canvases not generated"):
+        fr.set_decoded_geometry(first["occ_video"], np.stack([first["geo0"], first["geo1"]]))
+    h = fr.encoder_pack_flexible(1280, 2, 1.0)
+    assert T.encoder_canvas_size([h], 1280, 1280, 1280) == (W, H)
+    fr.encoder_generate_geometry_images(W, H, 4)
+    again = fr.get_geometry_images()
+    assert set(again) == set(first)
+    for k in first:
+        assert again[k].tobytes() == first[k].tobytes(), k
+
+
+@pytest.mark.parametrize("name", ["tiny", "small"])
+def test_gpu_repacking_leaves_no_stale_canvases(gpu_ctx, name):
+    fr, _, _, _ = _packed_frame_with_canvases(gpu_ctx, name)
+    fr.encoder_pack_flexible(1280, 2, 1.0)
+    with pytest.raises(T.Tmc2Error, match=E_STATE + ".*not generated"):
+        fr.get_geometry_images()
 
 
 def gpu_phase_b(ctx_frames):
