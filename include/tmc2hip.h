@@ -205,6 +205,16 @@ int tmc2_frame_set_partition( tmc2_frame* f, const uint32_t* partition );
 int tmc2_segmenter_segment_patches( tmc2_frame* f, const tmc2_segmenter_params* p );
 /* replaces: PCCPatchSegmenter3::compute (PCCPatchSegmenter.cpp:53-150) = S1..S9 end to end.           */
 int tmc2_segmenter_compute( tmc2_frame* f, const tmc2_segmenter_params* p );
+/* TMC2_OK, or TMC2_E_UNSUPPORTED with a message "params: ..." naming the field.  Refused: options the path does not implement
+ * (k-NN counts other than 16, normalOrientation other than 0 / 1, gridBasedRefineSegmentation off, occupancyResolution other
+ * than 16, mapCountMinus1 other than 1); values no stage can compute (minLevel < 1 or beyond the geometry bit depth, bit
+ * depths outside 1..16, negative surfaceThickness / minPointCount / quantizer sizes, maxPatchSize < 1, raw-point thresholds
+ * outside 0..27, maxNNCountRefineSegmentation < 1, negative lambda, a voxel size that is no power of two >= 2, a search
+ * radius below one voxel or whose ball the LDS tile does not hold: radius >> log2(voxel) > 97); and
+ * maxAllowedDepth < surfaceThickness + minLevel - 1, where the reference's own loop over the raw points never ends.
+ * Two inputs on which that loop never ends depend on the cloud and cannot be refused here: tmc2_segmenter_segment_patches /
+ * tmc2_segmenter_compute end with TMC2_E_UNSUPPORTED when patch splitting keeps no point of a component, or when a round
+ * takes no point off the raw list.                                                                                         */
 int tmc2_segmenter_params_check( const tmc2_segmenter_params* p );
 
 /* patch list of the frame (after segment_patches / compute) */

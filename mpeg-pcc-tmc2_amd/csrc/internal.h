@@ -522,6 +522,17 @@ int yuv420ToYuv444Device( tmc2_ctx* ctx, const uint8_t* d_yuv, int W, int H, int
 int refineGridBased( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount, int voxDim, int searchRadius );
 // the point-only half of it ahead of time (voxels, neighbourhood rows): queued, not waited for; refineGridBased picks it up
 void setRefineOverlapDefault( int on );
+// the refinement's search ball: cells with squared cell distance < r2 (r2 = searchRadius >> log2(voxel)); the neighbourhood
+// kernels keep a ball in an LDS tile of 4 096 words less 160 of their own (r2 = 97: 3 911 cells, the last that fits)
+inline int refineBallCells( int r2 ) {
+  int R = 0, ball = 0;
+  while ( R * R < r2 ) ++R;
+  for ( int dz = -R; dz <= R; ++dz )
+    for ( int dy = -R; dy <= R; ++dy )
+      for ( int dx = -R; dx <= R; ++dx ) ball += dx * dx + dy * dy + dz * dz < r2;
+  return ball;
+}
+inline bool refineBallFits( int r2 ) { return r2 >= 1 && r2 <= 128 && refineBallCells( r2 ) <= 4096 - 160; }
 bool refineOverlap( const tmc2_ctx* ctx );  // option REFINE_OVERLAP; unset: the process default of tmc2_set_refine_overlap
 int refinePrepareGeometry( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount, int voxDim, int searchRadius );
 // exclusive prefix sum of n uint32 (in -> out, may alias); returns the total through *d_total (device) if non-null

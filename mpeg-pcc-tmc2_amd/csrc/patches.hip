@@ -920,6 +920,19 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     TMC2_HIP( hipMemcpyAsync( h_records, d_bbox.p, 7 * size_t( P ) * 4, hipMemcpyDeviceToHost, s ) );
     const int32_t* h_view = h_bbox + 6 * size_t( P );
     TMC2_HIP( hipStreamSynchronize( s ) );
+    // A component of which patch splitting kept no point (none lies within maxPatchSize of its (min u, min v) corner: an L, a
+    // diagonal band) has no box.  The reference makes an empty patch of it, the component stays raw, and its loop over the raw
+    // points repeats that round for ever: the call ends here, before a size is derived from a box that does not exist.
+    for ( uint32_t p = 0; p < P; ++p )
+      if ( h_bbox[6 * p] > h_bbox[6 * p + 3] ) {
+        f->patches.clear();
+        f->depthCount = f->occCount = 0;
+        f->havePatches              = false;
+        setError( "segmentPatches: patch splitting with maxPatchSize=%d keeps no point of a connected component (round %d); "
+                  "the reference does not terminate on this input",
+                  sp->maxPatchSize, rounds );
+        return TMC2_E_UNSUPPORTED;
+      }
     // patch geometry on the host (P is a few hundred): axes, sizes, depth origin, pool offsets, tile list
     static const int       AX[3][3] = {{0, 2, 1}, {1, 2, 0}, {2, 0, 1}};
     std::vector<PatchDev>  h_pdLocal( P );
@@ -1007,9 +1020,21 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
                         int( offsets.size() ), thrSel, d_dist.p, d_raw.p, d_rawCount );
     TMC2_HIP( hipMemcpyAsync( h_stat, d_patchStat.p, statWords * 4, hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
+    const uint32_t rawBefore = rawCount;
     rawCount = 0;
     for ( uint32_t c = 0; c < kRawCounters; ++c ) rawCount += uint32_t( h_stat[2 * size_t( P ) + size_t( c ) * 32] );
     build.end();
+    // A pixel that passes the depth filter holds an input point that was raw and now lies on the resampled cloud, so a round with
+    // one such pixel shortens the list.  A round that does not has changed nothing and would be repeated for ever (the
+    // reference's loop is; tmc2_segmenter_params_check refuses the parameter range in which that can happen).
+    if ( rawCount >= rawBefore ) {
+      f->patches.clear();
+      f->depthCount = f->occCount = 0;
+      f->havePatches              = false;
+      setError( "segmentPatches: round %d took no point off the raw list (%u left); the reference does not terminate on this input",
+                rounds, rawCount );
+      return TMC2_E_UNSUPPORTED;
+    }
     for ( uint32_t p = 0; p < P; ++p ) {
       tmc2_patch& T = f->patches[patchBase + p];
       const int   sizeD = h_stat[2 * p];

@@ -1309,8 +1309,8 @@ int RefineJob::geometry( tmc2_frame* f ) {
         if ( xr >= 0 ) rows.push_back( ( dy + 128 ) | ( ( dz + 128 ) << 8 ) | ( xr << 16 ) );
       }
   }
-  if ( ball > 4096 - 160 || r2 > 128 ) {  // (the neighbourhood kernel keeps 160 words of its 2048 / 4096 for its own use)  // (search radius 192: r2 = 48 with voxels of 4, 96 with voxels of 2 -> 3 911 cells)
-    setError( "refineSegmentationGridBased: search radius %d too large for the LDS neighbourhood tile", searchRadius );
+  if ( !refineBallFits( r2 ) ) {  // (the neighbourhood kernel keeps 160 words of its 2048 / 4096 for its own use)  // (search radius 192: r2 = 48 with voxels of 4, 96 with voxels of 2 -> 3 911 cells)
+    setError( "refineSegmentationGridBased: search radius %d below one voxel or too large for the LDS neighbourhood tile", searchRadius );
     return TMC2_E_UNSUPPORTED;
   }
   devRange  = voxDim >= 4 ? 1 : 2;  // PCCPatchSegmenter.cpp:1471

@@ -55,6 +55,76 @@ int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) {
     setError( "params: mapCountMinus1 must be 1 (two maps, absoluteD1)" );
     return TMC2_E_UNSUPPORTED;
   }
+  // values the stages cannot compute: refused here, before anything is launched
+  if ( p->minLevel < 1 ) {
+    setError( "params: minLevel %d must be at least 1 (the depth origin is a multiple of it)", p->minLevel );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->geometryBitDepth2D < 1 || p->geometryBitDepth2D > 16 || p->geometryBitDepth3D < 1 || p->geometryBitDepth3D > 16 ||
+       ( int64_t( 1 ) << std::min( p->geometryBitDepth2D, p->geometryBitDepth3D ) ) < p->minLevel ) {
+    setError( "params: geometryBitDepth2D %d / geometryBitDepth3D %d must lie in 1..16 and hold minLevel %d", p->geometryBitDepth2D,
+              p->geometryBitDepth3D, p->minLevel );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->surfaceThickness < 0 || p->surfaceThickness > 16383 ) {
+    setError( "params: surfaceThickness %d outside 0..16383 (depths are 16-bit)", p->surfaceThickness );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->maxAllowedDepth > 16383 ) {
+    setError( "params: maxAllowedDepth %d above 16383 (depths are 16-bit)", p->maxAllowedDepth );
+    return TMC2_E_UNSUPPORTED;
+  }
+  // Below this bound a connected component can hold a point whose depth, counted from the patch's quantised origin, never passes
+  // the filter "surfaceThickness + d > d1 + maxAllowedDepth", not even in a patch of its own: it stays raw, every later round
+  // builds the same patch around it, and the reference's loop over the raw points never ends.  From the bound on, the extreme point
+  // of every component passes, and every round takes at least that point off the list.
+  if ( int64_t( p->maxAllowedDepth ) < int64_t( p->surfaceThickness ) + p->minLevel - 1 ) {
+    setError( "params: maxAllowedDepth %d below surfaceThickness + minLevel - 1 = %d (the patch loop would never end)",
+              p->maxAllowedDepth, p->surfaceThickness + p->minLevel - 1 );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->maxPatchSize < 1 ) {
+    setError( "params: maxPatchSize %d must be at least 1", p->maxPatchSize );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->minPointCountPerCCPatchSegmentation < 0 ) {
+    setError( "params: minPointCountPerCCPatchSegmentation %d is negative", p->minPointCountPerCCPatchSegmentation );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->quantizerSizeX < 0 || p->quantizerSizeY < 0 ) {
+    setError( "params: quantizerSizeX %d / quantizerSizeY %d is negative", p->quantizerSizeX, p->quantizerSizeY );
+    return TMC2_E_UNSUPPORTED;
+  }
+  // (written so that a NaN is refused too)
+  if ( !( p->maxAllowedDist2RawPointsDetection >= 0.0 && p->maxAllowedDist2RawPointsDetection < 28.0 ) ||
+       !( p->maxAllowedDist2RawPointsSelection >= 0.0 && p->maxAllowedDist2RawPointsSelection < 28.0 ) ) {
+    setError( "params: maxAllowedDist2RawPointsDetection %g / maxAllowedDist2RawPointsSelection %g outside 0..27 (the probe "
+              "around a point is a ball of squared radius 27)",
+              p->maxAllowedDist2RawPointsDetection, p->maxAllowedDist2RawPointsSelection );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( p->maxNNCountRefineSegmentation < 1 ) {
+    setError( "params: maxNNCountRefineSegmentation %d must be at least 1", p->maxNNCountRefineSegmentation );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( !( p->lambdaRefineSegmentation >= 0.0 ) ) {
+    setError( "params: lambdaRefineSegmentation %g is negative or not a number", p->lambdaRefineSegmentation );
+    return TMC2_E_UNSUPPORTED;
+  }
+  const int voxDim = p->voxelDimensionRefineSegmentation;
+  if ( voxDim < 2 || voxDim > 1024 || ( voxDim & ( voxDim - 1 ) ) ) {
+    setError( "params: voxelDimensionRefineSegmentation %d unsupported (power of two >= 2)", voxDim );
+    return TMC2_E_UNSUPPORTED;
+  }
+  int voxShift = 0;
+  for ( int i = voxDim; i > 1; ++voxShift, i >>= 1 ) {}
+  if ( p->searchRadiusRefineSegmentation < voxDim ||
+       !tmc2::refineBallFits( p->searchRadiusRefineSegmentation >> voxShift ) ) {
+    setError( "params: searchRadiusRefineSegmentation %d with voxels of %d unsupported (at least one voxel, and a ball that the "
+              "LDS neighbourhood tile holds: radius >> log2(voxel) <= 97)",
+              p->searchRadiusRefineSegmentation, voxDim );
+    return TMC2_E_UNSUPPORTED;
+  }
   return TMC2_OK;
 }
 

@@ -33,6 +33,11 @@ struct orc_seg_result {
   std::vector<int16_t>   resampled;  // xyz triples
   std::vector<uint32_t>  rawPoints;
   std::vector<int32_t>   roundRaw;   // raw-point count after each round
+  // 0, or why the loop was left early: on these inputs the reference itself never returns (its loop "while there are raw points"
+  // repeats a round that changes nothing), the restatement says so instead of following it
+  //   1 = patch splitting left a component without a point (nothing of it lies in the corner box of maxPatchSize)
+  //   2 = a round took no point off the raw list (every pixel of its patches failed the depth filter)
+  int32_t stalled = 0;
 };
 
 namespace {
@@ -102,6 +107,10 @@ orc_seg_result* orc_segment_patches( const int16_t* xyz, const uint8_t* rgb, siz
           if ( xyz[3 * size_t( i ) + ax[1]] - minU < sp->maxPatchSize && xyz[3 * size_t( i ) + ax[2]] - minV < sp->maxPatchSize )
             kept.push_back( i );
         cc.swap( kept );
+        if ( cc.empty() ) {
+          R->stalled = 1;
+          return R;
+        }
       }
       int bbMin[3] = {1 << 30, 1 << 30, 1 << 30}, bbMax[3] = {0, 0, 0};
       for ( uint32_t i : cc )
@@ -230,18 +239,24 @@ orc_seg_result* orc_segment_patches( const int16_t* xyz, const uint8_t* rgb, siz
     std::vector<double>   dist( n );
     orc_knn( t, xyz, n, 1, nn.data(), dist.data() );
     orc_kdtree_free( t );
+    const size_t rawBefore = raw.size();
     raw.clear();
     for ( size_t i = 0; i < n; ++i ) {
       rawDist[i] = dist[i];
       if ( dist[i] > sp->maxAllowedDist2RawPointsSelection ) raw.push_back( uint32_t( i ) );
     }
     R->roundRaw.push_back( int32_t( raw.size() ) );
+    if ( raw.size() >= rawBefore ) {
+      R->stalled = 2;
+      break;
+    }
   }
   R->rawPoints = raw;
   return R;
 }
 
 void orc_seg_result_free( orc_seg_result* r ) { delete r; }
+int  orc_seg_result_stalled( const orc_seg_result* r ) { return r->stalled; }
 int  orc_seg_result_sizes( const orc_seg_result* r, int32_t* patches, int64_t* depthCount, int64_t* occCount,
                            int64_t* resampledCount, int32_t* rounds ) {
   *patches        = int32_t( r->patches.size() );

@@ -156,8 +156,9 @@ class Oracle:
         res = np.zeros((rc.value, 3), np.int16)
         rr = np.zeros(rounds.value, np.int32)
         self.L.orc_seg_result_copy(r, _p(patches), _p(d0), _p(d1), _p(occ), _p(res), _p(rr))
+        stalled = int(self.L.orc_seg_result_stalled(r))    # 0, or why the loop was left where the reference's never ends
         self.L.orc_seg_result_free(r)
-        return dict(patches=patches, depth0=d0, depth1=d1, occupancy=occ, resampled=res, round_raw=rr)
+        return dict(patches=patches, depth0=d0, depth1=d1, occupancy=occ, resampled=res, round_raw=rr, stalled=stalled)
 
     def segment_patches(self, xyz, rgb, knn, partition, params):
         xyz = _i16(xyz)
@@ -260,12 +261,13 @@ class Oracle:
         L.orc_gpa_free(h)
         return out
 
-    def phase_a(self, frames, iterations=10, bits3d=11, occ_precision=4, min_w=1280, min_h=1280, constrained_pack=False, vox_dim=4):
+    def phase_a(self, frames, iterations=10, bits3d=11, occ_precision=4, min_w=1280, min_h=1280, constrained_pack=False, vox_dim=4,
+                params=None):
         """S0..S16 for a GOF given as [(xyz, rgb), ...]; mirrors Reference.phase_a.  constrained_pack: True = the low-delay
         condition (frames after the first packed against their predecessor, S10'); 2 = the random-access condition
-        (the same chain followed by the global patch allocation)."""
+        (the same chain followed by the global patch allocation).  params: a whole SegParams instead of the CTC's."""
         w = self.weight_normal(frames[0][0], bits3d, 0.6)
-        sp = seg_params(iterations, bits3d, w, vox_dim)
+        sp = seg_params(iterations, bits3d, w, vox_dim) if params is None else params
         per = []
         for xyz, rgb in frames:
             seg = self.segment(xyz, rgb, sp)
@@ -413,15 +415,15 @@ class Oracle:
         self.L.orc_convert_yuv16_to_rgb8(_p(c16), C.c_int64(len(c16)), _p(out))
         return out
 
-    def phase_c(self, phase_a_out, phase_b_out, decoded_attribute, occ_precision=4):
-        """Post-reconstruction tail on top of phase_a() / phase_b() output; mirrors Reference.phase_c."""
+    def phase_c(self, phase_a_out, phase_b_out, decoded_attribute, occ_precision=4, grid_size=8, threshold=64.0):
+        """Post-reconstruction tail on top of phase_a() / phase_b() output; mirrors Reference.phase_c (grid 8, threshold 64)."""
         out = []
         for a, b, att in zip(phase_a_out, phase_b_out, decoded_attribute):
             p2p = b["point_to_pixel"]
             bt0 = self.identify_boundary_points(p2p, a["occ_video"], a["width"], a["height"], occ_precision)
             part = (a["block_to_patch"][p2p[:, 1] // 16, p2p[:, 0] // 16] - 1).astype(np.uint32)
             c16 = self.color_point_cloud(p2p, att)
-            xyz, bt = self.smooth_point_cloud_grid(b["recon_xyz"], bt0, part)
+            xyz, bt = self.smooth_point_cloud_grid(b["recon_xyz"], bt0, part, grid_size, threshold)
             c16 = self.transfer_colors16_bp(b["recon_xyz"], c16, xyz, bt)
             out.append(dict(boundary_before=bt0, partition=part, xyz=xyz, colors16=c16, rgb=self.convert_yuv16_to_rgb8(c16), boundary=bt))
         return out

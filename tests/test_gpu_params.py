@@ -1,0 +1,252 @@
+"""GPU tier (-m gpu): the HIP path OFF the CTC parameter point -- the table of tests/param_cases.py through
+Frame.segmenter_compute against the oracle and against the digests of the unmodified reference, and the smaller accepted values
+around it (k = 8 / 4 / 1, the refinement's arguments on their own, the tail's grid sizes and thresholds, projection weights and
+metric resolutions).  Everything is exact equality.  Every call here has been shown to return on the CPU, in the reference and in
+the oracle (tests/test_oracle_golden.py runs the same points); the points on which the reference does not return
+(param_cases.OUTSIDE) are run nowhere in this file."""
+import numpy as np
+import pytest
+
+import param_cases as pc
+import tmc2_amd as T
+from test_oracle_golden import (REFINE_CASES, SMALL_K_CLOUDS, TAIL_GRIDS, TAIL_THRESHOLDS, check_segmentation_against_params_fixture,
+                                params_fixture, small_k_cloud, small_k_queries)
+
+pytestmark = pytest.mark.gpu
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _both_params(oracle, fr, p):
+    """(library struct, oracle struct) of a point: CTC, the frame's projection weights (checked), the point's overrides"""
+    import oracle_binding as ob
+    xyz, _ = pc.cloud(p["cloud"])
+    bits3d = p["overrides"].get("geometryBitDepth3D", pc.CTC["geometryBitDepth3D"])
+    w = fr.weight_normal(bits3d, 0.6)
+    assert np.array_equal(bits(w), bits(oracle.weight_normal(xyz, bits3d, 0.6)))
+    return pc.apply(T.ctc_params(p["iterations"], bits3d, w), p), pc.apply(ob.seg_params(p["iterations"], bits3d, w), p)
+
+
+def _assert_segmentation_equal(got, seg):
+    patches, d0, d1, occ = got
+    assert len(patches) == len(seg["patches"])
+    for n in pc.PATCH_FIELDS:
+        assert np.array_equal(patches[n], seg["patches"][n]), n
+    assert np.array_equal(d0, seg["depth0"]) and np.array_equal(d1, seg["depth1"]) and np.array_equal(occ, seg["occupancy"])
+
+
+@pytest.mark.parametrize("p", pc.POINTS, ids=pc.point_id)
+def test_gpu_segmenter_compute_off_ctc(gpu_ctx, oracle, p):
+    """PCCPatchSegmenter3::compute (S1..S9) through the C-ABI on every point of the table: patch records, depth maps, occupancy
+    and the number of rounds against the oracle, and the same against the reference's digests."""
+    xyz, rgb = pc.cloud(p["cloud"])
+    fr = gpu_ctx.frame(xyz, rgb)
+    hp, op = _both_params(oracle, fr, p)
+    T.segmenter_params_check(hp)
+    seg = oracle.segment(xyz, rgb, op)
+    assert seg["stalled"] == 0
+    gpu_ctx.stage_reset()
+    fr.segmenter_compute(hp)
+    got = fr.get_patches()
+    _assert_segmentation_equal(got, seg)
+    assert gpu_ctx.stage_calls().get("patches_build", 0) == len(seg["round_raw"])
+    check_segmentation_against_params_fixture(params_fixture(), p, dict(patches=got[0], depth0=got[1], depth1=got[2], occupancy=got[3]))
+
+
+def _refine_inputs(oracle, name):
+    xyz, rgb = pc.cloud(name)
+    nrm = oracle.normals(xyz)
+    return xyz, rgb, nrm, oracle.initial_segmentation(nrm, oracle.weight_normal(xyz))
+
+
+@pytest.mark.parametrize("rowcap", [None, "tiny"])
+@pytest.mark.parametrize("name", ["tiny", "small"])
+def test_gpu_refine_off_ctc(gpu_ctx, oracle, ctx_options, name, rowcap):
+    """S5 alone with maxNN / lambda / radius / iterations off their defaults on voxels of 4, 2 and 8 (the cases the CPU tier
+    holds against the reference).  rowcap tiny: the neighbourhood rows get no room and the pass is repeated -- with the cases
+    that truncate the rows to maxNN, since the retry and the truncation interact."""
+    if rowcap:
+        ctx_options.setenv("TMC2_REFINE_ROWCAP", rowcap)
+    xyz, rgb, nrm, p0 = _refine_inputs(oracle, name)
+    for kw in REFINE_CASES:
+        if rowcap and "max_nn" not in kw:
+            continue
+        a = dict(dict(max_nn=1024, lam=3.0, iterations=10, vox_dim=4, radius=192), **kw)
+        fr = gpu_ctx.frame(xyz, rgb)
+        fr.set_normals(nrm)
+        fr.set_partition(p0)
+        fr.segmenter_refine_grid_based(a["max_nn"], a["lam"], a["iterations"], a["vox_dim"], a["radius"])
+        assert np.array_equal(fr.get_partition(), oracle.refine_grid(xyz, nrm, p0, **kw)), kw
+
+
+def test_gpu_refine_refuses_a_ball_beyond_the_lds_tile(gpu_ctx, oracle):
+    xyz, rgb, nrm, p0 = _refine_inputs(oracle, "tiny")
+    for vox, radius in ((4, 392), (2, 196), (4, 3)):
+        fr = gpu_ctx.frame(xyz, rgb)
+        fr.set_normals(nrm)
+        fr.set_partition(p0)
+        with pytest.raises(T.Tmc2Error) as e:
+            fr.segmenter_refine_grid_based(1024, 3.0, 3, vox, radius)
+        assert "search radius" in str(e.value)
+        p = T.ctc_params(3, 11, (1.0, 1.0, 1.0), vox)
+        p.searchRadiusRefineSegmentation = radius
+        with pytest.raises(T.Tmc2Error) as e:
+            fr.segmenter_compute(p)                        # refused by the parameter check, before anything is launched
+        assert "params: searchRadiusRefineSegmentation" in str(e.value)
+        assert np.array_equal(fr.get_partition(), p0)
+
+
+@pytest.mark.parametrize("name", ["maxPatchSize=32-tiny", "minPointCountPerCC=1-tiny", "surfaceThickness=0-tiny",
+                                  "maxPatchSize=64-small", "minPointCountPerCC=1-small", "surfaceThickness=0-small"])
+def test_gpu_whole_path_off_ctc(gpu_ctx, oracle, name):
+    """The points that change the patch list most, carried on through packing, geometry images at occupancy precision 1, 2 and
+    4, attribute images, the colour conversion round trip and the tail: those stages have only ever seen CTC-shaped patch lists
+    (many small patches; single-pixel components; depth1 == depth0 everywhere)."""
+    p = pc.BY_NAME[name]
+    xyz, rgb = pc.cloud(p["cloud"])
+    for prec in (1, 2, 4):
+        fr = gpu_ctx.frame(xyz, rgb)
+        hp, op = _both_params(oracle, fr, p)
+        fr.segmenter_compute(hp)
+        h = fr.encoder_pack_flexible(1280, 2, 1.0)
+        W, H = T.encoder_canvas_size([h], 1280, 1280, 1280)
+        o_a = oracle.phase_a([(xyz, rgb)], occ_precision=prec, params=op)
+        o_b = oracle.phase_b([(xyz, rgb)], o_a, prec)
+        assert (W, H) == (o_a[0]["width"], o_a[0]["height"])
+        fr.encoder_generate_geometry_images(W, H, prec)
+        fr.encoder_generate_attribute_images()
+        img, att = fr.get_geometry_images(), fr.get_attribute_images()
+        lst = fr.get_patches()[0][fr.get_patch_order()]
+        for n in ("index", "u0", "v0", "patchOrientation", "sizeU0", "sizeV0"):
+            assert np.array_equal(lst[n], o_a[0]["patches"][n]), (prec, n)
+        for k in ("occupancy", "occ_video", "block_to_patch", "geo0", "geo1"):
+            assert np.array_equal(img[k], o_a[0][k]), (prec, k)
+        rec, col, p2p = fr.get_reconstruction()
+        assert np.array_equal(rec, o_b[0]["recon_xyz"]) and np.array_equal(col, o_b[0]["recon_rgb"])
+        assert np.array_equal(p2p, o_b[0]["point_to_pixel"])
+        assert np.array_equal(att, o_b[0]["attribute"]), prec
+        fr.codec_set_decoded_attribute_yuv420(fr.encoder_attribute_to_yuv420(4), 0)
+        dec = np.stack([oracle.convert_yuv420_to_yuv444(*oracle.convert_rgb444_to_yuv420(att[m])) for m in range(2)])
+        assert np.array_equal(fr.get_decoded_attribute(), dec)
+        fr.codec_post_reconstruct(None)
+        post = fr.get_post_reconstruction()
+        o_c = oracle.phase_c(o_a, o_b, [dec], prec)[0]
+        for k in ("xyz", "colors16", "rgb", "boundary"):
+            assert np.array_equal(post[k], o_c[k]), (prec, k)
+
+
+@pytest.mark.parametrize("name", SMALL_K_CLOUDS)
+def test_gpu_normals_with_eight_neighbours(gpu_ctx, oracle, name):
+    """normalsKernel<8>: adjacency, raw and oriented normal bits and the initial partition with k = 8; the patch segmentation
+    then refuses the frame (its connected components need the 16 neighbours) with its message."""
+    xyz = small_k_cloud(name)
+    rgb = np.zeros((len(xyz), 3), np.uint8)
+    knn = oracle.knn_self(xyz, 8)
+    raw = oracle.compute_normals(xyz, knn)
+    ori = oracle.orient_normals(xyz, knn, raw)
+    fr = gpu_ctx.frame(xyz, rgb)
+    fr.normals_compute_normals(8)
+    assert np.array_equal(fr.get_adjacency(8), knn)
+    assert np.array_equal(bits(fr.get_normals()), bits(raw))
+    fr.normals_orient()
+    assert np.array_equal(bits(fr.get_normals()), bits(ori))
+    fr2 = gpu_ctx.frame(xyz, rgb)
+    fr2.normals_compute(8, 1)
+    assert np.array_equal(fr2.get_adjacency(8), knn) and np.array_equal(bits(fr2.get_normals()), bits(ori))
+    w = fr2.weight_normal(11, 0.6)
+    assert np.array_equal(bits(w), bits(oracle.weight_normal(xyz, 11, 0.6)))
+    fr2.segmenter_initial_segmentation(w)
+    assert np.array_equal(fr2.get_partition(), oracle.initial_segmentation(ori, w))
+    with pytest.raises(T.Tmc2Error) as e:
+        fr2.segmenter_segment_patches(T.ctc_params(3, 11, w))
+    assert "maxNNCountPatchSegmentation" in str(e.value) and "k=8" in str(e.value)
+    fr3 = gpu_ctx.frame(xyz, rgb)
+    fr3.normals_compute(8, 0)                                  # no orientation: the raw normals stay
+    assert np.array_equal(bits(fr3.get_normals()), bits(raw))
+
+
+@pytest.mark.parametrize("k", [4, 1, 8])
+@pytest.mark.parametrize("name", SMALL_K_CLOUDS)
+def test_gpu_kdtree_search_small_k(gpu_ctx, oracle, name, k):
+    """tmc2_kdtree_search with k = 4 (never called before), 1 and 8, with distances: on-cloud and off-cloud queries and the far /
+    wide queries of test_gpu_knn_edge_cases."""
+    xyz = small_k_cloud(name)
+    fr = gpu_ctx.frame(xyz)
+    for q in small_k_queries(xyz):
+        idx, d = fr.kdtree_search(q, k, with_dist=True)
+        oi, od = oracle.knn(xyz, q, k, with_dist=True)
+        assert np.array_equal(idx, oi)
+        assert np.array_equal(d.astype(np.float64), od)              # (squared distances below 2^32: exact as 32-bit integers)
+        assert np.array_equal(fr.kdtree_search(q, k), oi)
+
+
+def _encoded_frame(gpu_ctx, oracle, xyz, rgb):
+    """a frame through S0..S22 at the CTC point with its decoded attribute on the device, and the oracle's phases"""
+    fr = gpu_ctx.frame(xyz, rgb)
+    fr.segmenter_compute(T.ctc_params(3, 11, fr.weight_normal(11, 0.6)))
+    h = fr.encoder_pack_flexible(1280, 2, 1.0)
+    W, H = T.encoder_canvas_size([h], 1280, 1280, 1280)
+    fr.encoder_generate_geometry_images(W, H, 4)
+    fr.encoder_generate_attribute_images()
+    fr.codec_set_decoded_attribute_yuv420(fr.encoder_attribute_to_yuv420(4), 0)
+    return fr
+
+
+@pytest.fixture(scope="module")
+def tail_phases(oracle):
+    xyz, rgb = pc.cloud("tiny")
+    o_a = oracle.phase_a([(xyz, rgb)], 3, 11, 4)
+    o_b = oracle.phase_b([(xyz, rgb)], o_a, 4)
+    dec = np.stack([oracle.convert_yuv420_to_yuv444(*oracle.convert_rgb444_to_yuv420(o_b[0]["attribute"][m])) for m in range(2)])
+    return o_a, o_b, dec
+
+
+@pytest.mark.parametrize("threshold", TAIL_THRESHOLDS)
+@pytest.mark.parametrize("grid", TAIL_GRIDS)
+def test_gpu_tail_grid_sizes_and_thresholds(gpu_ctx, oracle, tail_phases, grid, threshold):
+    """tmc2_codec_smooth_point_cloud_postprocess beside (8, 64): the smallest and the largest grid it accepts, a threshold every
+    boundary point exceeds and one none does -- moved points, their colours and the boundary types against the oracle."""
+    xyz, rgb = pc.cloud("tiny")
+    o_a, o_b, dec = tail_phases
+    fr = _encoded_frame(gpu_ctx, oracle, xyz, rgb)
+    assert np.array_equal(fr.get_decoded_attribute(), dec)
+    fr.codec_post_reconstruct(None, grid, threshold)
+    post = fr.get_post_reconstruction()
+    o_c = oracle.phase_c(o_a, o_b, [dec], 4, grid, threshold)[0]
+    for k in ("xyz", "colors16", "rgb", "boundary"):
+        assert np.array_equal(post[k], o_c[k]), k
+    assert threshold < 1e9 or int((o_c["boundary"] == 3).sum()) == 0
+
+
+def test_gpu_tail_refuses_grid_sizes_outside_2_to_64(gpu_ctx, oracle):
+    xyz, rgb = pc.cloud("tiny")
+    fr = _encoded_frame(gpu_ctx, oracle, xyz, rgb)
+    fr.codec_identify_boundary_points()
+    fr.codec_color_point_cloud(None)
+    for grid in (1, 65, 0, -8):
+        with pytest.raises(T.Tmc2Error):
+            fr.codec_smooth_point_cloud_postprocess(grid, 64.0)
+
+
+@pytest.mark.parametrize("name", SMALL_K_CLOUDS)
+def test_gpu_weight_normal_off_ctc(gpu_ctx, oracle, name):
+    xyz = small_k_cloud(name)
+    fr = gpu_ctx.frame(xyz)
+    for bits3d in (10, 11, 12):
+        for mw in (0.0, 0.6, 1.0):
+            assert np.array_equal(bits(fr.weight_normal(bits3d, mw)), bits(oracle.weight_normal(xyz, bits3d, mw))), (bits3d, mw)
+
+
+@pytest.mark.parametrize("resolution", [511.0, 2047.0])
+def test_gpu_metrics_off_ctc_resolution(gpu_ctx, oracle, resolution):
+    xyz, rgb = pc.cloud("tiny")
+    rng = np.random.default_rng(3)
+    rec = np.clip(xyz[rng.integers(0, len(xyz), len(xyz) // 2)] + rng.integers(-1, 2, (len(xyz) // 2, 3)), 0, 2047).astype(np.int16)
+    rc = rng.integers(0, 256, (len(rec), 3), dtype=np.uint8)
+    nrm = oracle.normals(xyz, 16, True)
+    for normals in (None, nrm):
+        q, c = gpu_ctx.metrics_compute(xyz, rgb, rec, rc, normals, resolution)
+        oq, oc = oracle.metrics(xyz, rgb, rec, rc, normals, resolution)
+        assert np.array_equal(c, oc) and np.array_equal(bits(q), bits(oq))

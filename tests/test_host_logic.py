@@ -582,6 +582,42 @@ def test_segmenter_params_check_accepts_ctc_and_names_what_it_refuses():
         with pytest.raises(T.Tmc2Error) as e:
             T.segmenter_params_check(p)
         assert "params" in str(e.value)
+    # values no stage can compute (a division by minLevel, negative sizes and counts, thresholds cast to unsigned, a ball the
+    # LDS tile does not hold), and the range in which the reference's own patch loop never ends: refused by name, before a launch
+    for field, value in (("minLevel", 0), ("minLevel", -64), ("minLevel", 512), ("surfaceThickness", -1), ("maxPatchSize", 0),
+                         ("maxPatchSize", -1024), ("minPointCountPerCCPatchSegmentation", -1), ("quantizerSizeX", -16),
+                         ("quantizerSizeY", -1), ("maxAllowedDist2RawPointsDetection", -1.0), ("maxAllowedDist2RawPointsSelection", -0.5),
+                         ("maxAllowedDist2RawPointsDetection", 28.0), ("maxAllowedDist2RawPointsSelection", float("nan")),
+                         ("maxAllowedDepth", 66), ("maxAllowedDepth", 63), ("maxAllowedDepth", -1), ("surfaceThickness", 193),
+                         ("geometryBitDepth2D", 0), ("geometryBitDepth3D", 17), ("maxNNCountRefineSegmentation", 0),
+                         ("lambdaRefineSegmentation", -1.0), ("voxelDimensionRefineSegmentation", 3),
+                         ("voxelDimensionRefineSegmentation", 1), ("voxelDimensionRefineSegmentation", 0),
+                         ("searchRadiusRefineSegmentation", 392), ("searchRadiusRefineSegmentation", 3),
+                         ("searchRadiusRefineSegmentation", -192)):
+        p = T.ctc_params()
+        setattr(p, field, value)
+        with pytest.raises(T.Tmc2Error) as e:
+            T.segmenter_params_check(p)
+        assert "params: " in str(e.value) and field in str(e.value), (field, value, str(e.value))
+    for field, value in (("maxAllowedDepth", 67), ("searchRadiusRefineSegmentation", 391), ("minLevel", 128),
+                         ("maxAllowedDist2RawPointsDetection", 27.9), ("surfaceThickness", 192)):
+        p = T.ctc_params()
+        setattr(p, field, value)
+        T.segmenter_params_check(p)                 # the last value on the accepted side of each bound
+
+
+def test_segmenter_params_check_accepts_the_parameter_table_and_refuses_what_never_ends():
+    """Every point of tests/param_cases.py passes the check; of the points on which the reference does not return, those whose
+    cause lies in the parameters alone (the depth filter) are refused -- the others depend on the cloud, and the patch loop ends
+    the call when it meets them."""
+    import param_cases as pc
+    for p in pc.POINTS:
+        T.segmenter_params_check(pc.apply(T.ctc_params(), p))
+    for p in pc.OUTSIDE:
+        if pc.OUTSIDE_STALL[p["name"]] == 2:
+            with pytest.raises(T.Tmc2Error) as e:
+                T.segmenter_params_check(pc.apply(T.ctc_params(), p))
+            assert "params: maxAllowedDepth" in str(e.value)
 
 
 @pytest.mark.parametrize("seed", list(range(30)) + [1574])

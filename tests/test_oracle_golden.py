@@ -553,3 +553,254 @@ def test_oracle_metrics_wide_groups_match_reference(oracle, reference):
         qa, ca = oracle.metrics(src, sc, rec, rc, normals)
         qb, cb = reference.metrics(src, sc, rec, rc, normals)
         assert np.array_equal(ca, cb) and np.array_equal(bits(qa), bits(qb)), (qa, qb)
+
+
+# ---- off the CTC parameter point (tests/param_cases.py) -----------------------------------------------------------------------
+import param_cases as pc  # noqa: E402
+
+
+def params_fixture():
+    return np.load(os.path.join(GOLD, "segmenter_params.npz"))
+
+
+def check_segmentation_against_params_fixture(g, p, seg):
+    """Shared by the CPU (oracle) and GPU tiers: a segmentation (dict with patches, depth0, depth1, occupancy) of a point of the
+    parameter table against what the unmodified reference made of it."""
+    name = p["name"]
+    assert str(g[name + "/input_md5"]) == pc.input_digest(p), "the clouds of tests/param_cases.py drifted from the fixture"
+    d = pc.result_digests(seg)
+    assert d["patch_count"] == int(g[name + "/patch_count"])
+    for k in ("patches", "depth0", "depth1", "occupancy"):
+        assert d[k] == str(g["%s/%s_md5" % (name, k)]), k
+
+
+def test_params_fixture_covers_the_table():
+    g = params_fixture()
+    assert sorted(g["names"].tolist()) == sorted(p["name"] for p in pc.POINTS)
+    for field, values in pc.SINGLE:                          # every listed field keeps at least two values off CTC (or all it has)
+        kept = [v for v in values if any(p["name"].startswith("%s=%s-" % (field, pc._fmt(v))) for p in pc.POINTS)]
+        assert len(kept) >= min(2, len(values)), field
+    assert not {p["name"] for p in pc.OUTSIDE} & set(g["names"].tolist())
+
+
+@pytest.mark.parametrize("p", pc.POINTS, ids=pc.point_id)
+def test_oracle_segmenter_matches_params_fixture(oracle, p):
+    """Runs without the compiled reference: the oracle on every point of the table against the reference's digests."""
+    import oracle_binding as ob
+    xyz, rgb = pc.cloud(p["cloud"])
+    seg = oracle.segment(xyz, rgb, pc.oracle_params(oracle, p, ob.seg_params))
+    assert seg["stalled"] == 0
+    check_segmentation_against_params_fixture(params_fixture(), p, seg)
+
+
+@pytest.mark.parametrize("p", pc.POINTS, ids=pc.point_id)
+def test_oracle_segmenter_matches_reference_off_ctc(oracle, reference, p):
+    """Oracle against the compiled reference on every point of the table: every patch field except the two pool offsets, depth0,
+    depth1, occupancy -- integers and bit patterns, exact.  (The reference's segmenter does not report its rounds; the oracle's
+    round count is what the GPU tier compares, and here it must be a whole number of productive rounds: stalled == 0.)"""
+    import oracle_binding as ob
+    xyz, rgb = pc.cloud(p["cloud"])
+    sp = pc.oracle_params(oracle, p, ob.seg_params)
+    a, b = oracle.segment(xyz, rgb, sp), reference.segment(xyz, rgb, sp)
+    assert len(a["patches"]) == len(b["patches"])
+    for n in pc.PATCH_FIELDS:
+        assert np.array_equal(a["patches"][n], b["patches"][n]), n
+    for k in ("depth0", "depth1", "occupancy"):
+        assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+    assert a["stalled"] == 0 and len(a["round_raw"]) >= 1 and np.all(np.diff(a["round_raw"]) < 0)
+
+
+def test_params_fixture_is_not_vacuous():
+    """A point that silently changed nothing must not count as coverage: for every value of every field, the reference's result
+    differs from its result at the CTC point on at least one cloud.  geometryBitDepth3D is the exception that the segmenter's
+    definition makes: it enters through the projection weights (equal on these clouds) and through min(2D, 3D) bits of the depth
+    range (8 either way); its effect is checked where it has one (weight_normal below, the tail's grid in the GPU tier).
+    enablePatchSplitting: see below."""
+    g = params_fixture()
+
+    def same_as_ctc(p):
+        return all(str(g["%s/%s_md5" % (p["name"], k)]) == str(g["ctc-%s/%s_md5" % (p["cloud"], k)])
+                   for k in ("patches", "depth0", "depth1", "occupancy"))
+
+    for field, values in pc.SINGLE:
+        if field in ("geometryBitDepth3D", "enablePatchSplitting"):
+            continue
+        for v in values:
+            pts = [p for p in pc.POINTS if p["name"].startswith("%s=%s-" % (field, pc._fmt(v)))]
+            if (field, v) == ("maxAllowedDist2RawPointsDetection", 9.5):
+                assert pts and all(same_as_ctc(p) for p in pts)      # squared distances are whole numbers: 9.5 must act as 9 does
+                continue
+            assert pts and not all(same_as_ctc(p) for p in pts), (field, v)
+    several = sorted({p["name"].rsplit("-", 1)[0] for p in pc.POINTS if len(p["overrides"]) > 1 and not p["name"].startswith("enablePatchSplitting=0")})
+    assert len(several) >= 12 + 8
+    for prefix in several:                                   # the points with several fields off CTC, the seeded ones among them
+        pts = [p for p in pc.POINTS if p["name"].rsplit("-", 1)[0] == prefix]
+        assert pts and not all(same_as_ctc(p) for p in pts), prefix
+    # surfaceThickness inside the depth filter: next to a small maxAllowedDepth the result depends on it beyond what it does to depth1
+    for st, mad in ((0, 67), (8, 71)):
+        a, b = "surfaceThickness=%d,maxAllowedDepth=%d-small" % (st, mad), "maxAllowedDepth=67-small"
+        assert str(g[a + "/depth0_md5"]) != str(g[b + "/depth0_md5"])
+    # enablePatchSplitting = 0 alone changes nothing on clouds narrower than maxPatchSize = 1 024; what it governs shows with a
+    # small maxPatchSize: ignored when splitting is off (the CTC result), obeyed when it is on
+    for p in pc.POINTS:
+        if p["name"].startswith("enablePatchSplitting=0"):
+            assert same_as_ctc(p), p["name"]
+    count = lambda name: int(g[name + "/patch_count"])
+    for cloud in ("tiny", "small"):
+        assert count("minPointCountPerCC=1-" + cloud) > count("ctc-" + cloud) >= count("minPointCountPerCC=300-" + cloud)
+    assert count("maxPatchSize=32-tiny") > count("maxPatchSize=64-tiny") > count("ctc-tiny")
+    assert count("maxPatchSize=64-small") > count("ctc-small")
+
+
+@pytest.mark.parametrize("p", [q for q in pc.POINTS if len(q["overrides"]) == 1 or q["name"].startswith(("quantizer", "combined"))],
+                         ids=pc.point_id)
+def test_oracle_off_ctc_points_show_what_their_field_governs(oracle, p):
+    """What each field means, read off the result: a kernel that had the CTC value of a field built in would fail these even if
+    the fixture were regenerated from it."""
+    import oracle_binding as ob
+    xyz, rgb = pc.cloud(p["cloud"])
+    seg = oracle.segment(xyz, rgb, pc.oracle_params(oracle, p, ob.seg_params))
+    o, pt = dict(pc.CTC, **p["overrides"]), seg["patches"]
+    valid = seg["depth0"] < 32767
+    thick = (seg["depth1"].astype(np.int32) - seg["depth0"])[valid]
+    assert thick.min() >= 0 and thick.max() <= o["surfaceThickness"]
+    if "surfaceThickness" in p["overrides"] and p["cloud"] in ("tiny", "small") and o["surfaceThickness"] > 0:
+        assert thick.max() > (0 if o["surfaceThickness"] <= 4 else 4)       # (the clouds are shells several voxels thick)
+    assert np.all(pt["d1"] % o["minLevel"] == 0)
+    if o["minLevel"] < 64 and p["cloud"] in ("tiny", "small"):
+        assert np.any(pt["d1"] % 64 != 0)
+    if o["enablePatchSplitting"]:
+        assert pt["sizeU"].max() <= o["maxPatchSize"] and pt["sizeV"].max() <= o["maxPatchSize"]
+    for q, size, px in ((o["quantizerSizeX"], "sizeU", "size2DXInPixel"), (o["quantizerSizeY"], "sizeV", "size2DYInPixel")):
+        assert np.all(pt[px] % q == 0) and np.all(pt[px] >= pt[size]) and np.all(pt[px] - pt[size] < q)
+    assert np.all(seg["depth1"][valid] <= o["maxAllowedDepth"]) and np.all(pt["sizeDPixel"] <= o["maxAllowedDepth"])
+    bits = min(o["geometryBitDepth2D"], o["geometryBitDepth3D"])
+    assert np.all(pt["sizeD"] < (1 << bits)) and np.all((pt["sizeD"] == 0) | ((pt["sizeD"] + 1) % o["minLevel"] == 0))
+
+
+@pytest.mark.parametrize("p", pc.OUTSIDE, ids=pc.point_id)
+def test_oracle_leaves_the_patch_loop_where_the_reference_never_returns(p):
+    """The points left out of the table (the unmodified reference does not return on them): the oracle, in a CHILD process under
+    a time limit, leaves its loop over the raw points and says why -- 1: patch splitting kept no point of a component, 2: a
+    round took no point off the raw list.  The library's host loop carries the same two tests (csrc/patches.hip); nothing runs
+    these points on a GPU."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(GOLD, "make_segmenter_params_golden.py"), "--point", p["name"], "--engine", "oracle"],
+                       timeout=300, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["stalled"] == pc.OUTSIDE_STALL[p["name"]]
+
+
+@pytest.mark.parametrize("name", ["tiny", "small", "plane", "two_sheets", "lattice"])
+def test_oracle_refine_matches_reference_off_ctc(oracle, reference, name):
+    """S5 alone with maxNN / lambda / radius / voxel size off their defaults, one at a time and together."""
+    xyz, _ = pc.cloud(name)
+    nrm = reference.normals(xyz, 16, True)
+    p0 = reference.initial_segmentation(nrm, reference.weight_normal(xyz, 11, 0.6))
+    base = oracle.refine_grid(xyz, nrm, p0, iterations=3)
+    changed = 0
+    for kw in REFINE_CASES:
+        a, b = oracle.refine_grid(xyz, nrm, p0, **kw), reference.refine_grid(xyz, nrm, p0, **kw)
+        assert np.array_equal(a, b), kw
+        changed += not np.array_equal(a, base)
+    assert changed >= (len(REFINE_CASES) // 2 if name in ("tiny", "small") else 0), changed      # (a flat cloud has nothing to refine)
+
+
+def _refine_cases():
+    """maxNN, lambda and radius off their defaults on voxels of 4 and of 2 (radius >> log2(voxel) <= 97 is what the library's
+    neighbourhood tile holds: 391 / 195), voxels of 8, no and one iteration, and a few of them together."""
+    out = []
+    for vox, largest in ((4, pc.LARGEST_RADIUS_VOX4), (2, 195)):
+        out += [dict(iterations=3, vox_dim=vox, max_nn=m) for m in (16, 64, 256)]
+        out += [dict(iterations=3, vox_dim=vox, lam=x) for x in (0.0, 1.5, 10.0)]
+        out += [dict(iterations=3, vox_dim=vox, radius=r) for r in (32, 64, 96, largest)]
+    return out + [dict(iterations=3, vox_dim=8), dict(iterations=1), dict(iterations=0),
+                  dict(iterations=4, max_nn=64, lam=1.5, radius=96), dict(iterations=2, max_nn=256, lam=10.0, radius=64, vox_dim=2),
+                  dict(iterations=5, max_nn=16, lam=0.0, vox_dim=8)]
+
+
+REFINE_CASES = _refine_cases()
+SMALL_K_CLOUDS = ["tiny", "small", "plane", "two_sheets", "lattice", "degenerate0", "degenerate6", "degenerate8"]
+
+
+def small_k_cloud(name):
+    """the clouds of param_cases plus three of degenerate_cloud's by seed (dust, a line, a dense cube)"""
+    if name.startswith("degenerate"):
+        return degenerate_cloud(np.random.default_rng(9000 + int(name[10:])))
+    return pc.cloud(name)[0]
+
+
+@pytest.mark.parametrize("name", SMALL_K_CLOUDS)
+def test_oracle_normals_and_knn_small_k_match_reference(oracle, reference, name):
+    """k = 8 through normal estimation and orientation (bit patterns), k = 4 and k = 1 through the search with distances: on-cloud
+    and off-cloud queries, far and wide ones."""
+    xyz = small_k_cloud(name)
+    for oriented in (False, True):
+        assert np.array_equal(bits(oracle.normals(xyz, 8, oriented)), bits(reference.normals(xyz, 8, oriented))), oriented
+    assert not np.array_equal(bits(oracle.normals(xyz, 8, False)), bits(oracle.normals(xyz, 16, False)))
+    for q in small_k_queries(xyz)[:3]:
+        for k in (4, 1, 8):
+            (ia, da), (ib, db) = oracle.knn(xyz, q, k, True), reference.knn(xyz, q, k, True)
+            assert np.array_equal(ia, ib) and np.array_equal(bits(da), bits(db)), k
+    # the wide queries lie so far out that squared distances pass 2^24, where the reference's single-precision arithmetic rounds
+    # them (and with them the order of near-ties); the oracle and the library are exact there and are held against each other
+    # (tests/test_gpu_segmenter.py::test_gpu_knn_edge_cases, tests/test_gpu_params.py) and here against the definition
+    wide = small_k_queries(xyz)[3]
+    d2 = ((xyz.astype(np.int64)[None] - wide.astype(np.int64)[:, None]) ** 2).sum(-1)
+    for k in (4, 1, 8):
+        ia, da = oracle.knn(xyz, wide, k, True)
+        assert np.array_equal(da, np.sort(d2, 1)[:, :k]) and np.array_equal(np.take_along_axis(d2, ia.astype(np.int64), 1), da)
+
+
+def small_k_queries(xyz):
+    """Shared with the GPU tier: the cloud's own points, points off the cloud, and the far / wide queries of
+    test_gpu_knn_edge_cases (outside the root box; beyond the packed-offset range)."""
+    return (xyz[::3], (xyz[::5] + np.array([3, -2, 5], np.int16)).astype(np.int16),
+            np.array([[0, 0, 0], [1023, 1023, 1023], [500, -20, 2000]], np.int16),
+            np.array([[-6000, 10, 10], [20000, 5, 5], [512, 512, -32768]], np.int16))
+
+
+@pytest.mark.parametrize("name", ["tiny", "small", "plane", "two_sheets", "lattice"])
+def test_oracle_weight_normal_matches_reference_off_ctc(oracle, reference, name):
+    xyz, _ = pc.cloud(name)
+    seen = set()
+    for bits3d in (10, 11, 12):
+        for mw in (0.0, 0.6, 1.0):
+            a, b = oracle.weight_normal(xyz, bits3d, mw), reference.weight_normal(xyz, bits3d, mw)
+            assert np.array_equal(bits(a), bits(b)), (bits3d, mw)
+            seen.add(bits(a).tobytes())
+    assert len(seen) > 1 or name in ("tiny", "small")     # (a flat cloud's weights depend on both; a shell's may not)
+
+
+TAIL_GRIDS, TAIL_THRESHOLDS = (2, 4, 16, 64), (0.0, 8.0, 64.0, 1e9)
+
+
+@pytest.mark.parametrize("grid", TAIL_GRIDS)
+@pytest.mark.parametrize("threshold", TAIL_THRESHOLDS)
+def test_oracle_tail_matches_reference_off_ctc(oracle, reference, grid, threshold):
+    """smoothPointCloudPostprocess + transferColors16bitBP over the grid sizes and thresholds the C-ABI accepts beside (8, 64):
+    the smallest and the largest grid, a threshold nothing passes and one everything passes."""
+    moved = 0
+    for seed in range(4):
+        xyz, bt, part, c16 = random_tail_cloud(np.random.default_rng(7100 + seed))
+        rx, rb, rc = reference.smooth_and_transfer(xyz, bt, part, c16, grid, threshold)
+        ox, ob_ = oracle.smooth_point_cloud_grid(xyz, bt, part, grid, threshold)
+        assert np.array_equal(rx, ox) and np.array_equal(rb, ob_)
+        assert np.array_equal(rc, oracle.transfer_colors16_bp(xyz, c16, ox, ob_))
+        moved += int((ob_ == 3).sum())
+    assert moved == 0 if threshold == 1e9 else (moved > 0 or grid < 64), moved     # (the largest grid moves points at every other threshold)
+
+
+@pytest.mark.parametrize("resolution", [511.0, 2047.0])
+def test_oracle_metrics_match_reference_off_ctc_resolution(oracle, reference, resolution):
+    xyz, rgb = pc.cloud("tiny")
+    rng = np.random.default_rng(3)
+    rec = np.clip(xyz[rng.integers(0, len(xyz), len(xyz) // 2)] + rng.integers(-1, 2, (len(xyz) // 2, 3)), 0, 2047).astype(np.int16)
+    rc = rng.integers(0, 256, (len(rec), 3), dtype=np.uint8)
+    nrm = reference.normals(xyz, 16, True)
+    qa, ca = oracle.metrics(xyz, rgb, rec, rc, nrm, resolution)
+    qb, cb = reference.metrics(xyz, rgb, rec, rc, nrm, resolution)
+    assert np.array_equal(bits(qa), bits(qb)) and np.array_equal(ca, cb)
+    assert not np.array_equal(bits(qa), bits(oracle.metrics(xyz, rgb, rec, rc, nrm, 1023.0)[0]))
