@@ -9,6 +9,7 @@ import os as _os
 # set before the HIP runtime initialises; an explicit setting of the user wins.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import os
+import re
 import threading
 import numpy as np
 
@@ -44,8 +45,7 @@ class Patch(C.Structure):
         "eomAndD1Count", "u0", "v0", "patchOrientation")] + [("depthOffset", C.c_int64), ("occOffset", C.c_int64)]
 
 
-PATCH_DTYPE = np.dtype([(n, t) for n, t in [(f[0], np.int32) for f in Patch._fields_[:22]] +
-                        [("depthOffset", np.int64), ("occOffset", np.int64)]])
+PATCH_DTYPE = np.dtype(Patch._fields_)
 
 
 def ctc_params(iterations=10, bits3d=11, weight=(1.0, 1.0, 1.0), vox_dim=4):
@@ -121,6 +121,34 @@ def _guard_finish():
             a.reshape(-1).view(np.uint8)[:] = g[_GUARD:_GUARD + n]
 
 
+# The C-ABI as ctypes has to be told it: TMC2HIP (at the end of this file) has one row per function of include/tmc2hip.h, in the
+# header's order and spelling, parameter names dropped (native_gof.TMC2GOF: include/tmc2gof.h).  Without a prototype every Python int
+# travels as a 32-bit C int and every return value is read as one: wrong for each uint64_t / int64_t / size_t / double.  A new entry
+# point gets a row; tests/test_host_logic.py compares the rows, and what declare() installed, with the headers -- which a copy of
+# the package away from the repository cannot read: hence a table.
+# The one mapping rule: scalars by their exact width; `const char*` is c_char_p; every other pointer -- handles, out-parameters,
+# arrays such as `double[3]`, struct pointers, a returned `void*` -- is c_void_p, which takes None, byref(x), a ctypes array, a
+# c_void_p, a plain address and bytes; a function that returns void has restype None.
+_SCALARS = {"void": None, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+            "long": C.c_long, "double": C.c_double}
+
+
+def _ctype(c_type):
+    if c_type == "const char*":
+        return C.c_char_p
+    return C.c_void_p if c_type[-1] in "*]" else _SCALARS[c_type]
+
+
+def declare(handle, rows):
+    """Install the prototypes of `rows` on a CDLL handle (a function the library does not export is an AttributeError)."""
+    for row in rows:
+        ret, name, params = re.fullmatch(r"(.+?) (tmc2_\w+)\((.*)\)", row).groups()
+        fn = getattr(handle, name)
+        fn.restype = _ctype(ret)
+        fn.argtypes = [] if params == "void" else [_ctype(t) for t in params.split(", ")]
+    return handle
+
+
 def load_library():
     """Load libtmc2hip.so; raises if it has not been built (no silent fallback)."""
     global _LIB
@@ -129,32 +157,8 @@ def load_library():
     path = library_path()
     if not os.path.exists(path):
         raise Tmc2Error("libtmc2hip.so not built: run `python __graft_entry__.py build` (hipcc, gfx950)")
-    L = C.CDLL(path)
-    L.tmc2_last_error.restype = C.c_char_p
-    L.tmc2_set_kdtree_placement.restype = None
-    L.tmc2_set_refine_overlap.restype = None
-    L.tmc2_ctx_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-    L.tmc2_ctx_reserve.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.tmc2_ctx_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.tmc2_ctx_device_free.argtypes = [C.c_void_p, C.c_void_p]
-    L.tmc2_ctx_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.tmc2_ctx_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.tmc2_ctx_stream.argtypes = [C.c_void_p]
-    L.tmc2_ctx_device.argtypes = [C.c_void_p]
-    L.tmc2_ctx_make_current.argtypes = [C.c_void_p]
-    L.tmc2_ctx_pool_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tmc2_ctx_get_option.argtypes = [C.c_void_p, C.c_char_p]
-    L.tmc2_ctx_get_option.restype = C.c_char_p
-    L.tmc2_set_host_parallelism.restype = None
-    L.tmc2_host_gate_create.argtypes = [C.c_int, C.c_void_p]
-    L.tmc2_host_gate_destroy.argtypes = [C.c_void_p]
-    L.tmc2_host_gate_destroy.restype = None
-    L.tmc2_ctx_set_host_gate.argtypes = [C.c_void_p, C.c_void_p]
-    L.tmc2_ctx_stage_name.restype = C.c_char_p
-    L.tmc2_ctx_stage_ms.restype = C.c_double
-    L.tmc2_frame_point_count.restype = C.c_uint64
-    _LIB = L
-    return L
+    _LIB = declare(C.CDLL(path), TMC2HIP)
+    return _LIB
 
 
 def _check(rc):
@@ -220,13 +224,13 @@ class Context:
 
     def reserve(self, max_points, vox_dim, bits3d, max_w, max_h):
         """tmc2_ctx_reserve: the device memory of the sequence's largest frame, allocated now (no first-use hipMalloc later)."""
-        _check(self.L.tmc2_ctx_reserve(self.h, C.c_uint64(int(max_points)), int(vox_dim), int(bits3d), int(max_w), int(max_h)))
+        _check(self.L.tmc2_ctx_reserve(self.h, int(max_points), int(vox_dim), int(bits3d), int(max_w), int(max_h)))
 
     # device staging (what libtmc2gof.so's RCCL mode uses between its collectives): raw device memory of this context's device,
     # copies ordered on its stream
     def device_alloc(self, nbytes):
         p = C.c_void_p()
-        _check(self.L.tmc2_ctx_device_alloc(self.h, C.c_size_t(int(nbytes)), C.byref(p)))
+        _check(self.L.tmc2_ctx_device_alloc(self.h, int(nbytes), C.byref(p)))
         return p
 
     def device_free(self, p):
@@ -234,14 +238,13 @@ class Context:
 
     def upload(self, device_ptr, array):
         a = np.ascontiguousarray(array)
-        _check(self.L.tmc2_ctx_upload(self.h, device_ptr, _ptr(a), C.c_size_t(a.nbytes)))
+        _check(self.L.tmc2_ctx_upload(self.h, device_ptr, _ptr(a), a.nbytes))
 
     def download(self, array, device_ptr):
-        _check(self.L.tmc2_ctx_download(self.h, _ptr(array), device_ptr, C.c_size_t(array.nbytes)))
+        _check(self.L.tmc2_ctx_download(self.h, _ptr(array), device_ptr, array.nbytes))
         return array
 
     def stream(self):
-        self.L.tmc2_ctx_stream.restype = C.c_void_p
         return self.L.tmc2_ctx_stream(self.h)
 
     def device(self):
@@ -260,7 +263,6 @@ class Context:
                 for i in range(self.L.tmc2_ctx_stage_count(self.h))}
 
     def stage_calls(self):
-        self.L.tmc2_ctx_stage_calls.restype = C.c_long
         return {self.L.tmc2_ctx_stage_name(self.h, i).decode(): self.L.tmc2_ctx_stage_calls(self.h, i)
                 for i in range(self.L.tmc2_ctx_stage_count(self.h))}
 
@@ -281,7 +283,7 @@ class Context:
         if a.shape != b.shape:                                    # (the C entry takes ONE count for both: a short colour array is read past its end)
             raise Tmc2Error("transfer_colors: %d source points, %d source colours" % (len(a), len(b)))
         out = np.zeros((len(c), 3), np.uint8)
-        _check(self.L.tmc2_transfer_colors(self.h, _ptr(a), _ptr(b), C.c_uint64(len(a)), _ptr(c), C.c_uint64(len(c)), _ptr(out)))
+        _check(self.L.tmc2_transfer_colors(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), len(c), _ptr(out)))
         return out
 
     # PCCCodec::colorSmoothing
@@ -289,8 +291,8 @@ class Context:
                         thr_variation=6.0):
         """tmc2_color_smoothing on host arrays: the smoothed 16-bit colours (a copy)."""
         a = _color_smoothing_arrays(xyz, colors16, boundary, patch_index)
-        _check(self.L.tmc2_color_smoothing(self.h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.c_uint64(len(a[0])), int(grid_size),
-                                          int(bits3d), C.c_double(thr_smoothing), C.c_double(thr_difference), C.c_double(thr_variation)))
+        _check(self.L.tmc2_color_smoothing(self.h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), len(a[0]), int(grid_size),
+                                          int(bits3d), thr_smoothing, thr_difference, thr_variation))
         return a[1]
 
     # PCCMetrics::compute (one frame)
@@ -335,8 +337,8 @@ class Context:
         nm = None if normals is None else np.ascontiguousarray(normals, np.float64)
         out = np.zeros((3, 8), np.float64)
         counts = np.zeros(2, np.int64)
-        _check(self.L.tmc2_metrics_compute(self.h, _ptr(a), _ptr(b), C.c_uint64(len(a)), _ptr(c), _ptr(d), C.c_uint64(len(c)),
-                                           None if nm is None else _ptr(nm), C.c_double(resolution), _ptr(out), _ptr(counts)))
+        _check(self.L.tmc2_metrics_compute(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), _ptr(d), len(c),
+                                           None if nm is None else _ptr(nm), resolution, _ptr(out), _ptr(counts)))
         return out, counts
 
     def metrics_ordered_sums(self, terms_a, terms_b):
@@ -344,8 +346,7 @@ class Context:
         a = np.ascontiguousarray(terms_a, np.float64).reshape(-1, 5)
         b = np.ascontiguousarray(terms_b, np.float64).reshape(-1, 5)
         out = np.zeros(10, np.float64)
-        _check(self.L.tmc2_metrics_ordered_sums(self.h, _ptr(a) if len(a) else None, C.c_uint64(len(a)),
-                                                _ptr(b) if len(b) else None, C.c_uint64(len(b)), _ptr(out)))
+        _check(self.L.tmc2_metrics_ordered_sums(self.h, _ptr(a) if len(a) else None, len(a), _ptr(b) if len(b) else None, len(b), _ptr(out)))
         return out
 
 
@@ -360,8 +361,7 @@ class Frame:
         self._xyz = xyz
         self._rgb = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.uint8)
         self.h = C.c_void_p()
-        _check(self.L.tmc2_frame_create(ctx.h, _ptr(xyz), None if rgb is None else _ptr(self._rgb),
-                                        C.c_uint64(self.n), C.byref(self.h)))
+        _check(self.L.tmc2_frame_create(ctx.h, _ptr(xyz), None if rgb is None else _ptr(self._rgb), self.n, C.byref(self.h)))
 
     def close(self):
         if self.h:
@@ -382,8 +382,7 @@ class Frame:
         the attribute-image step, 1: the finished cloud of the post-reconstruction tail.  Returns (q[3][8], counts[2])."""
         out = np.zeros((3, 8), np.float64)
         counts = np.zeros(2, np.int64)
-        _check(self.L.tmc2_metrics_compute_frame(self.h, C.c_int(which), C.c_int(1 if use_normals else 0), C.c_double(resolution),
-                                                 _ptr(out), _ptr(counts)))
+        _check(self.L.tmc2_metrics_compute_frame(self.h, which, 1 if use_normals else 0, resolution, _ptr(out), _ptr(counts)))
         return out, counts
 
     def metrics_compute_source(self, src_xyz, src_rgb, normals=None, which=1, resolution=1023.0):
@@ -393,8 +392,8 @@ class Frame:
         nm = None if normals is None else np.ascontiguousarray(normals, np.float64)
         out = np.zeros((3, 8), np.float64)
         counts = np.zeros(2, np.int64)
-        _check(self.L.tmc2_metrics_compute_frame_source(self.h, C.c_int(which), _ptr(a), _ptr(b), C.c_uint64(len(a)),
-                                                        None if nm is None else _ptr(nm), C.c_double(resolution), _ptr(out), _ptr(counts)))
+        _check(self.L.tmc2_metrics_compute_frame_source(self.h, which, _ptr(a), _ptr(b), len(a),
+                                                        None if nm is None else _ptr(nm), resolution, _ptr(out), _ptr(counts)))
         return out, counts
 
     def kdtree_build(self):
@@ -424,8 +423,7 @@ class Frame:
         q = np.ascontiguousarray(queries, dtype=np.int16)
         idx = np.empty((len(q), k), np.uint32)
         d = np.empty((len(q), k), np.uint32) if with_dist else None
-        _check(self.L.tmc2_kdtree_search(self.h, _ptr(q), C.c_uint64(len(q)), int(k), _ptr(idx),
-                                         None if d is None else _ptr(d)))
+        _check(self.L.tmc2_kdtree_search(self.h, _ptr(q), len(q), int(k), _ptr(idx), None if d is None else _ptr(d)))
         return (idx, d) if with_dist else idx
 
     # PCCNormalsGenerator3
@@ -455,7 +453,7 @@ class Frame:
     # PCCEncoder::calculateWeightNormal
     def weight_normal(self, bits3d=11, min_weight_epp=0.6):
         w = (C.c_double * 3)()
-        _check(self.L.tmc2_weight_normal(self.h, int(bits3d), C.c_double(min_weight_epp), w))
+        _check(self.L.tmc2_weight_normal(self.h, int(bits3d), min_weight_epp, w))
         return np.array([w[0], w[1], w[2]])
 
     # PCCPatchSegmenter3
@@ -464,8 +462,7 @@ class Frame:
         _check(self.L.tmc2_segmenter_initial_segmentation(self.h, w))
 
     def segmenter_refine_grid_based(self, max_nn=1024, lam=3.0, iterations=10, vox_dim=4, radius=192):
-        _check(self.L.tmc2_segmenter_refine_grid_based(self.h, int(max_nn), C.c_double(lam), int(iterations),
-                                                       int(vox_dim), int(radius)))
+        _check(self.L.tmc2_segmenter_refine_grid_based(self.h, int(max_nn), lam, int(iterations), int(vox_dim), int(radius)))
 
     def get_partition(self):
         out = np.empty(self.n, np.uint32)
@@ -508,20 +505,19 @@ class Frame:
         p = np.ascontiguousarray(patch_list, dtype=PATCH_DTYPE)
         occ = np.ascontiguousarray(occupancy, dtype=np.uint8)
         m = None if matches is None else np.ascontiguousarray(matches, dtype=np.int32)
-        _check(self.L.tmc2_frame_set_packing(self.h, _ptr(p), len(p), None if m is None else _ptr(m), _ptr(occ), C.c_int64(len(occ)),
+        _check(self.L.tmc2_frame_set_packing(self.h, _ptr(p), len(p), None if m is None else _ptr(m), _ptr(occ), len(occ),
                                              int(packed_width), int(packed_height)))
 
     # PCCEncoder image generation, phase A
     def encoder_pack_flexible(self, preset_width=1280, tiles_hor=2, ratio=1.0):
         h = C.c_int32()
-        _check(self.L.tmc2_encoder_pack_flexible(self.h, int(preset_width), int(tiles_hor), C.c_double(ratio), C.byref(h)))
+        _check(self.L.tmc2_encoder_pack_flexible(self.h, int(preset_width), int(tiles_hor), ratio, C.byref(h)))
         return h.value
 
     def encoder_pack_spatial_consistency(self, previous, preset_width=1280, tiles_hor=2, ratio=1.0):
         """S10' (constrainedPack): pack against the previous frame of the GOF (which must be packed already)."""
         h = C.c_int32()
-        _check(self.L.tmc2_encoder_pack_spatial_consistency(self.h, previous.h, int(preset_width), int(tiles_hor),
-                                                            C.c_double(ratio), C.byref(h)))
+        _check(self.L.tmc2_encoder_pack_spatial_consistency(self.h, previous.h, int(preset_width), int(tiles_hor), ratio, C.byref(h)))
         return h.value
 
     def get_packed_size(self):
@@ -561,11 +557,9 @@ class Frame:
 
     def recon_count(self):
         """Points of the reconstructed cloud (0 before the reconstruction)."""
-        self.L.tmc2_frame_recon_count.restype = C.c_int64
-        return int(self.L.tmc2_frame_recon_count(self.h))
+        return self.L.tmc2_frame_recon_count(self.h)
 
     def get_reconstruction(self, colors=True):
-        self.L.tmc2_frame_recon_count.restype = C.c_int64
         M = self.L.tmc2_frame_recon_count(self.h)
         xyz, rgb, p2p = np.zeros((M, 3), np.int16), (np.zeros((M, 3), np.uint8) if colors else None), np.zeros((M, 3), np.uint32)
         _check(self.L.tmc2_frame_get_reconstruction(self.h, _ptr(xyz), None if rgb is None else _ptr(rgb), _ptr(p2p)))
@@ -614,7 +608,7 @@ class Frame:
         _check(self.L.tmc2_codec_color_point_cloud(self.h, _ptr(att)))
 
     def codec_smooth_point_cloud_postprocess(self, grid_size=8, threshold=64.0):
-        _check(self.L.tmc2_codec_smooth_point_cloud_postprocess(self.h, int(grid_size), C.c_double(threshold)))
+        _check(self.L.tmc2_codec_smooth_point_cloud_postprocess(self.h, int(grid_size), threshold))
 
     def codec_transfer_colors_16bit_bp(self):
         _check(self.L.tmc2_codec_transfer_colors_16bit_bp(self.h))
@@ -629,8 +623,7 @@ class Frame:
     def codec_color_smoothing(self, grid_size, thr_smoothing=10.0, thr_difference=10.0, thr_variation=6.0):
         """PCCCodec::colorSmoothing on the finished cloud (after codec_transfer_colors_16bit_bp, before codec_convert_yuv16_to_rgb8);
         grid_size = occupancyPrecision; the thresholds default as PCCEncoderParameters does."""
-        _check(self.L.tmc2_codec_color_smoothing(self.h, int(grid_size), C.c_double(thr_smoothing), C.c_double(thr_difference),
-                                                C.c_double(thr_variation)))
+        _check(self.L.tmc2_codec_color_smoothing(self.h, int(grid_size), thr_smoothing, thr_difference, thr_variation))
 
     def codec_post_reconstruct(self, attribute16=None, grid_size=8, threshold=64.0, color_smoothing=None):
         """The whole tail in the reference's order: boundary points, 16-bit colours from the decoded attribute frames, grid
@@ -645,7 +638,6 @@ class Frame:
         self.codec_convert_yuv16_to_rgb8()
 
     def get_post_reconstruction(self, xyz=True, colors16=True, rgb=True, boundary=True):
-        self.L.tmc2_frame_recon_count.restype = C.c_int64
         M = self.L.tmc2_frame_recon_count(self.h)
         out = dict(xyz=np.zeros((M, 3), np.int16) if xyz else None, colors16=np.zeros((M, 3), np.uint16) if colors16 else None,
                    rgb=np.zeros((M, 3), np.uint8) if rgb else None, boundary=np.zeros(M, np.uint16) if boundary else None)
@@ -671,7 +663,7 @@ class _Pinned:
 
     def __init__(self, nbytes):
         self.L, self.p, self.nbytes = load_library(), C.c_void_p(), int(nbytes)
-        _check(self.L.tmc2_host_alloc(C.c_size_t(self.nbytes), C.byref(self.p)))
+        _check(self.L.tmc2_host_alloc(self.nbytes, C.byref(self.p)))
         self.__array_interface__ = dict(shape=(self.nbytes,), typestr="|u1", data=(self.p.value, False), version=3)
 
     def __del__(self):
@@ -700,7 +692,7 @@ class SharedHostArray:
         self.array = np.frombuffer(self.map, dtype=np.uint8)
         if register:
             # (the mapping's own address, never a red-zone copy of the guard mode: the call page-locks the memory, it moves no payload)
-            _check(load_library().tmc2_host_register(C.c_void_p(self.array.ctypes.data), C.c_size_t(self.nbytes)))
+            _check(load_library().tmc2_host_register(C.c_void_p(self.array.ctypes.data), self.nbytes))
             self.registered = True
 
     def close(self):
@@ -740,7 +732,7 @@ def host_kdtree_build(xyz):
     xyz = np.ascontiguousarray(xyz, dtype=np.int16)
     perm = np.empty(len(xyz), np.uint32)
     nodes, depth = C.c_uint64(), C.c_int32()
-    _check(L.tmc2_host_kdtree_build(_ptr(xyz), C.c_uint64(len(xyz)), _ptr(perm), C.byref(nodes), C.byref(depth)))
+    _check(L.tmc2_host_kdtree_build(_ptr(xyz), len(xyz), _ptr(perm), C.byref(nodes), C.byref(depth)))
     return perm, nodes.value, depth.value
 
 
@@ -750,7 +742,7 @@ def host_pack_flexible(patches, occupancy, preset_width=1280, tiles_hor=2, ratio
     p = np.array(patches, dtype=PATCH_DTYPE, order="C", copy=True)
     occ = np.ascontiguousarray(occupancy, dtype=np.uint8)
     order, h = np.zeros(len(p), np.int32), C.c_int32()
-    _check(L.tmc2_host_pack_flexible(_ptr(p), len(p), _ptr(occ), int(preset_width), int(tiles_hor), C.c_double(ratio), _ptr(order),
+    _check(L.tmc2_host_pack_flexible(_ptr(p), len(p), _ptr(occ), int(preset_width), int(tiles_hor), ratio, _ptr(order),
                                      C.byref(h)))
     return p, order, h.value
 
@@ -763,7 +755,7 @@ def host_pack_spatial_consistency(patches, occupancy, previous_list, preset_widt
     occ = np.ascontiguousarray(occupancy, dtype=np.uint8)
     order, match, h = np.zeros(len(p), np.int32), np.zeros(len(p), np.int32), C.c_int32()
     _check(L.tmc2_host_pack_spatial_consistency(_ptr(p), len(p), _ptr(occ), _ptr(prev), len(prev), int(preset_width),
-                                                int(tiles_hor), C.c_double(ratio), _ptr(order), _ptr(match), C.byref(h)))
+                                                int(tiles_hor), ratio, _ptr(order), _ptr(match), C.byref(h)))
     return p, order, match, h.value
 
 
@@ -795,7 +787,7 @@ def host_global_patch_allocation(lists, pools, matches, tile_w, tile_h, min_w=12
     out, out_base = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.int64)
     w, h = np.zeros(n, np.int32), np.zeros(n, np.int32)
     _check(L.tmc2_host_global_patch_allocation(n, _ptr(counts), _ptr(patches), _ptr(occ), _ptr(base), _ptr(m), int(tile_w),
-                                               int(tile_h), int(min_w), int(min_h), _ptr(out), C.c_int64(cap), _ptr(out_base),
+                                               int(tile_h), int(min_w), int(min_h), _ptr(out), cap, _ptr(out_base),
                                                _ptr(w), _ptr(h)))
     res, at = [], 0
     for f in range(n):
@@ -827,7 +819,7 @@ def host_pack_gof_records(records, mode, min_w=1280, min_h=1280, tiles_hor=2, ra
     m = np.zeros(max(len(patches), 1), np.int32)
     w, h = np.zeros(n, np.int32), np.zeros(n, np.int32)
     _check(L.tmc2_host_place_segments(n, _ptr(counts), _ptr(patches), _ptr(occ), _ptr(base), int(mode), int(min_w), int(min_h),
-                                      int(tiles_hor), C.c_double(ratio), _ptr(m), _ptr(out), C.c_int64(cap), _ptr(out_base), _ptr(w), _ptr(h)))
+                                      int(tiles_hor), ratio, _ptr(m), _ptr(out), cap, _ptr(out_base), _ptr(w), _ptr(h)))
     res, at = [], 0
     for f in range(n):
         c = int(counts[f])
@@ -847,11 +839,11 @@ def metrics_display(out, source_points, reconstruct_points, counts, resolution=1
     q = np.ascontiguousarray(out, dtype=np.float64)
     c = np.ascontiguousarray(counts, dtype=np.int64)
     need = C.c_uint64()
-    _check(L.tmc2_metrics_display(_ptr(q), C.c_uint64(int(source_points)), C.c_uint64(int(reconstruct_points)), _ptr(c),
-                                  C.c_uint64(int(resolution)), int(bool(with_c2p)), int(precision), None, C.c_uint64(0), C.byref(need)))
+    _check(L.tmc2_metrics_display(_ptr(q), int(source_points), int(reconstruct_points), _ptr(c), int(resolution), int(bool(with_c2p)),
+                                  int(precision), None, 0, C.byref(need)))
     buf = C.create_string_buffer(need.value)
-    _check(L.tmc2_metrics_display(_ptr(q), C.c_uint64(int(source_points)), C.c_uint64(int(reconstruct_points)), _ptr(c),
-                                  C.c_uint64(int(resolution)), int(bool(with_c2p)), int(precision), buf, C.c_uint64(need.value), None))
+    _check(L.tmc2_metrics_display(_ptr(q), int(source_points), int(reconstruct_points), _ptr(c), int(resolution), int(bool(with_c2p)),
+                                  int(precision), buf, need.value, None))
     return buf.value.decode()
 
 
@@ -859,15 +851,15 @@ def checksum_file_write(path, digests):
     """PCCChecksum::write: digests = list of 16-byte MD5s, one per frame."""
     L = load_library()
     d = np.frombuffer(b"".join(digests), np.uint8).copy() if len(digests) else np.zeros(0, np.uint8)
-    _check(L.tmc2_checksum_file_write(str(path).encode(), _ptr(d) if len(d) else None, C.c_uint64(len(digests))))
+    _check(L.tmc2_checksum_file_write(str(path).encode(), _ptr(d) if len(d) else None, len(digests)))
 
 
 def checksum_file_read(path):
     L = load_library()
     n = C.c_uint64()
-    _check(L.tmc2_checksum_file_read(str(path).encode(), None, C.c_uint64(0), C.byref(n)))
+    _check(L.tmc2_checksum_file_read(str(path).encode(), None, 0, C.byref(n)))
     d = np.zeros(16 * max(1, n.value), np.uint8)
-    _check(L.tmc2_checksum_file_read(str(path).encode(), _ptr(d), C.c_uint64(n.value), C.byref(n)))
+    _check(L.tmc2_checksum_file_read(str(path).encode(), _ptr(d), n.value, C.byref(n)))
     return [d[16 * f:16 * f + 16].tobytes() for f in range(n.value)]
 
 
@@ -893,7 +885,7 @@ def ply_read(path, read_normals=False, threads=0, out=None):
     nrm = np.zeros((n, 3), np.float64) if has_nrm else None
     cnt = C.c_uint64()
     _check(L.tmc2_ply_read(str(path).encode(), _ptr(xyz), None if rgb is None or not has_rgb else _ptr(rgb),
-                           None if nrm is None else _ptr(nrm), C.c_uint64(len(xyz)), int(threads), C.byref(cnt)))
+                           None if nrm is None else _ptr(nrm), len(xyz), int(threads), C.byref(cnt)))
     return xyz[:n], (rgb[:n] if rgb is not None and has_rgb else None), nrm
 
 
@@ -904,7 +896,7 @@ def ply_write(path, xyz, rgb=None, normals=None, ascii=True):
     rgb = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.uint8)
     nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
     _check(L.tmc2_ply_write(str(path).encode(), _ptr(xyz), None if rgb is None else _ptr(rgb), None if nrm is None else _ptr(nrm),
-                            C.c_uint64(len(xyz)), int(bool(ascii))))
+                            len(xyz), int(bool(ascii))))
 
 
 def point_set_checksum(xyz, rgb=None, reorder=False):
@@ -913,7 +905,7 @@ def point_set_checksum(xyz, rgb=None, reorder=False):
     xyz = np.ascontiguousarray(xyz, dtype=np.int16)
     rgb = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.uint8)
     d = np.zeros(16, np.uint8)
-    _check(L.tmc2_point_set_checksum(_ptr(xyz), None if rgb is None else _ptr(rgb), C.c_uint64(len(xyz)), int(bool(reorder)), _ptr(d)))
+    _check(L.tmc2_point_set_checksum(_ptr(xyz), None if rgb is None else _ptr(rgb), len(xyz), int(bool(reorder)), _ptr(d)))
     return d.tobytes()
 
 
@@ -922,7 +914,7 @@ def host_orient_normals(xyz, knn, normals):
     xyz = np.ascontiguousarray(xyz, dtype=np.int16)
     knn = np.ascontiguousarray(knn, dtype=np.uint32)
     out = np.array(normals, dtype=np.float64, order="C", copy=True)
-    _check(L.tmc2_host_orient_normals(_ptr(xyz), C.c_uint64(len(xyz)), _ptr(knn), int(knn.shape[1]), _ptr(out)))
+    _check(L.tmc2_host_orient_normals(_ptr(xyz), len(xyz), _ptr(knn), int(knn.shape[1]), _ptr(out)))
     return out
 
 
@@ -941,6 +933,118 @@ def host_color_smoothing(xyz, colors16, boundary, patch_index, grid_size, bits3d
     """tmc2_host_color_smoothing: PCCCodec::colorSmoothing restated on the host (no device); returns the smoothed colours."""
     L = load_library()
     a = _color_smoothing_arrays(xyz, colors16, boundary, patch_index)
-    _check(L.tmc2_host_color_smoothing(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.c_uint64(len(a[0])), int(grid_size), int(bits3d),
-                                       C.c_double(thr_smoothing), C.c_double(thr_difference), C.c_double(thr_variation)))
+    _check(L.tmc2_host_color_smoothing(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), len(a[0]), int(grid_size), int(bits3d),
+                                       thr_smoothing, thr_difference, thr_variation))
     return a[1]
+
+
+# ---- the prototypes of include/tmc2hip.h (declare, above) ---------------------------------------------
+TMC2HIP = """
+int tmc2_ctx_create(int, tmc2_ctx**)
+void tmc2_ctx_destroy(tmc2_ctx*)
+const char* tmc2_last_error(void)
+int tmc2_ctx_synchronize(tmc2_ctx*)
+int tmc2_host_alloc(size_t, void**)
+void tmc2_host_free(void*)
+int tmc2_host_register(void*, size_t)
+int tmc2_host_unregister(void*)
+int tmc2_host_gate_create(int, tmc2_host_gate**)
+void tmc2_host_gate_destroy(tmc2_host_gate*)
+int tmc2_ctx_set_host_gate(tmc2_ctx*, tmc2_host_gate*)
+void tmc2_set_host_parallelism(int)
+int tmc2_ctx_set_option(tmc2_ctx*, const char*, const char*)
+const char* tmc2_ctx_get_option(tmc2_ctx*, const char*)
+int tmc2_ctx_reserve(tmc2_ctx*, uint64_t, int, int, int, int)
+int tmc2_ctx_pool_stats(tmc2_ctx*, uint64_t*, uint64_t*, double*, uint64_t*)
+int tmc2_ctx_device_alloc(tmc2_ctx*, size_t, void**)
+int tmc2_ctx_device_free(tmc2_ctx*, void*)
+int tmc2_ctx_upload(tmc2_ctx*, void*, const void*, size_t)
+int tmc2_ctx_download(tmc2_ctx*, void*, const void*, size_t)
+void* tmc2_ctx_stream(tmc2_ctx*)
+int tmc2_ctx_device(tmc2_ctx*)
+int tmc2_ctx_make_current(tmc2_ctx*)
+int tmc2_ctx_stage_count(tmc2_ctx*)
+const char* tmc2_ctx_stage_name(tmc2_ctx*, int)
+double tmc2_ctx_stage_ms(tmc2_ctx*, int)
+long tmc2_ctx_stage_calls(tmc2_ctx*, int)
+void tmc2_ctx_stage_reset(tmc2_ctx*)
+void tmc2_ctx_set_timing(tmc2_ctx*, int)
+int tmc2_frame_create(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, tmc2_frame**)
+void tmc2_frame_destroy(tmc2_frame*)
+int tmc2_kdtree_build(tmc2_frame*)
+void tmc2_set_kdtree_placement(int)
+void tmc2_set_refine_overlap(int)
+int tmc2_frame_get_kdtree_order(tmc2_frame*, uint32_t*, int32_t*)
+uint64_t tmc2_frame_point_count(const tmc2_frame*)
+int tmc2_frame_reset(tmc2_frame*)
+int tmc2_kdtree_search(tmc2_frame*, const int16_t*, uint64_t, int, uint32_t*, uint32_t*)
+int tmc2_normals_compute_normals(tmc2_frame*, int)
+int tmc2_normals_orient(tmc2_frame*)
+int tmc2_normals_compute(tmc2_frame*, int, int)
+int tmc2_frame_get_normals(tmc2_frame*, double*)
+int tmc2_frame_set_normals(tmc2_frame*, const double*)
+int tmc2_frame_get_adjacency(tmc2_frame*, uint32_t*)
+int tmc2_weight_normal(tmc2_frame*, int, double, double[3])
+int tmc2_segmenter_initial_segmentation(tmc2_frame*, const double[3])
+int tmc2_segmenter_refine_grid_based(tmc2_frame*, int, double, int, int, int)
+int tmc2_frame_get_partition(tmc2_frame*, uint32_t*)
+int tmc2_frame_set_partition(tmc2_frame*, const uint32_t*)
+int tmc2_segmenter_segment_patches(tmc2_frame*, const tmc2_segmenter_params*)
+int tmc2_segmenter_compute(tmc2_frame*, const tmc2_segmenter_params*)
+int tmc2_segmenter_params_check(const tmc2_segmenter_params*)
+int tmc2_frame_patch_count(tmc2_frame*)
+int tmc2_frame_patch_pool_sizes(tmc2_frame*, int64_t*, int64_t*)
+int tmc2_frame_get_patches(tmc2_frame*, tmc2_patch*, int16_t*, int16_t*, uint8_t*)
+int tmc2_encoder_pack_flexible(tmc2_frame*, int, int, double, int32_t*)
+int tmc2_encoder_pack_spatial_consistency(tmc2_frame*, tmc2_frame*, int, int, double, int32_t*)
+int tmc2_frame_get_packed_size(tmc2_frame*, int32_t*, int32_t*)
+int tmc2_frame_get_patch_matches(tmc2_frame*, int32_t*)
+int tmc2_encoder_global_patch_allocation(tmc2_frame**, int, int, int, int32_t*, int32_t*)
+int tmc2_frame_set_packing(tmc2_frame*, const tmc2_patch*, int, const int32_t*, const uint8_t*, int64_t, int, int)
+int tmc2_frame_get_patch_order(tmc2_frame*, int32_t*)
+int tmc2_encoder_canvas_size(const int32_t*, int, int, int, int, int32_t*, int32_t*)
+int tmc2_encoder_generate_geometry_images(tmc2_frame*, int, int, int)
+int tmc2_frame_get_geometry_images(tmc2_frame*, uint8_t*, uint8_t*, uint32_t*, uint16_t*, uint16_t*)
+int tmc2_encoder_generate_attribute_images(tmc2_frame*)
+int tmc2_transfer_colors(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, const int16_t*, uint64_t, uint8_t*)
+int64_t tmc2_frame_recon_count(tmc2_frame*)
+int tmc2_frame_get_reconstruction(tmc2_frame*, int16_t*, uint8_t*, uint32_t*)
+int tmc2_frame_get_attribute_images(tmc2_frame*, uint8_t*)
+int tmc2_frame_set_decoded_geometry(tmc2_frame*, const uint8_t*, const uint16_t*)
+int tmc2_frame_device_images(tmc2_frame*, void**, void**, void**, void**)
+int tmc2_frame_device_attribute(tmc2_frame*, void**)
+int tmc2_color_convert_rgb444_to_yuv420(tmc2_ctx*, const uint8_t*, int, int, int, uint8_t*)
+int tmc2_color_convert_yuv420_to_yuv444(tmc2_ctx*, const uint8_t*, int, int, int, uint16_t*)
+int tmc2_encoder_attribute_to_yuv420(tmc2_frame*, int, uint8_t*)
+int tmc2_codec_set_decoded_attribute_yuv420(tmc2_frame*, const uint8_t*, int)
+int tmc2_frame_get_decoded_attribute(tmc2_frame*, uint16_t*)
+int tmc2_decoder_frame_create(tmc2_ctx*, const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, tmc2_frame**)
+int tmc2_codec_generate_point_cloud(tmc2_frame*)
+int tmc2_codec_identify_boundary_points(tmc2_frame*)
+int tmc2_codec_color_point_cloud(tmc2_frame*, const uint16_t*)
+int tmc2_codec_smooth_point_cloud_postprocess(tmc2_frame*, int, double)
+int tmc2_codec_transfer_colors_16bit_bp(tmc2_frame*)
+int tmc2_codec_color_smoothing(tmc2_frame*, int, double, double, double)
+int tmc2_frame_set_geometry_bit_depth_3d(tmc2_frame*, int)
+int tmc2_color_smoothing(tmc2_ctx*, const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
+int tmc2_codec_convert_yuv16_to_rgb8(tmc2_frame*)
+int tmc2_frame_get_post_reconstruction(tmc2_frame*, int16_t*, uint16_t*, uint8_t*, uint16_t*)
+int tmc2_metrics_compute(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, const int16_t*, const uint8_t*, uint64_t, const double*, double, double*, int64_t*)
+int tmc2_metrics_compute_frame(tmc2_frame*, int, int, double, double*, int64_t*)
+int tmc2_metrics_compute_frame_source(tmc2_frame*, int, const int16_t*, const uint8_t*, uint64_t, const double*, double, double*, int64_t*)
+int tmc2_metrics_ordered_sums(tmc2_ctx*, const double*, uint64_t, const double*, uint64_t, double*)
+int tmc2_metrics_display(const double*, uint64_t, uint64_t, const int64_t*, uint64_t, int, int, char*, uint64_t, uint64_t*)
+int tmc2_ply_info(const char*, int, uint64_t*, int*, int*)
+int tmc2_ply_read(const char*, int16_t*, uint8_t*, double*, uint64_t, int, uint64_t*)
+int tmc2_ply_write(const char*, const int16_t*, const uint8_t*, const double*, uint64_t, int)
+int tmc2_point_set_checksum(const int16_t*, const uint8_t*, uint64_t, int, uint8_t[16])
+int tmc2_checksum_file_write(const char*, const uint8_t*, uint64_t)
+int tmc2_checksum_file_read(const char*, uint8_t*, uint64_t, uint64_t*)
+int tmc2_host_kdtree_build(const int16_t*, uint64_t, uint32_t*, uint64_t*, int32_t*)
+int tmc2_host_pack_flexible(tmc2_patch*, int, const uint8_t*, int, int, double, int32_t*, int32_t*)
+int tmc2_host_global_patch_allocation(int, int32_t*, tmc2_patch*, const uint8_t*, const int64_t*, int32_t*, int, int, int, int, uint8_t*, int64_t, int64_t*, int32_t*, int32_t*)
+int tmc2_host_pack_spatial_consistency(tmc2_patch*, int, const uint8_t*, const tmc2_patch*, int, int, int, double, int32_t*, int32_t*, int32_t*)
+int tmc2_host_place_segments(int, const int32_t*, tmc2_patch*, const uint8_t*, const int64_t*, int, int, int, int, double, int32_t*, uint8_t*, int64_t, int64_t*, int32_t*, int32_t*)
+int tmc2_host_orient_normals(const int16_t*, uint64_t, const uint32_t*, int, double*)
+int tmc2_host_color_smoothing(const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
+""".strip().split("\n")

@@ -25,6 +25,24 @@ def library_path():
     return os.path.join(os.path.dirname(_lib.library_path()), "libtmc2gof.so")
 
 
+# the prototypes of include/tmc2gof.h, as lib.TMC2HIP is for include/tmc2hip.h
+TMC2GOF = """
+int tmc2_gof_encode(tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*)
+int tmc2_gof_encode_resume(tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*)
+const char* tmc2_gof_last_error(void)
+int tmc2_gof_comm_create(int, int, tmc2_ctx*, const char*, tmc2_gof_comm**)
+void tmc2_gof_comm_destroy(tmc2_gof_comm*)
+int tmc2_gof_encode_sharded(tmc2_gof_comm*, tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*, int32_t, tmc2_patch*, int64_t*)
+int tmc2_gof_encode_sharded_resume(tmc2_gof_comm*, tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*, int32_t, tmc2_patch*, int64_t*)
+""".strip().split("\n")
+
+
+def declare(G):
+    """The prototypes of include/tmc2gof.h on a handle of libtmc2gof.so -- or of another build of the runner (the tests' one against
+    recorders of the C-ABI)."""
+    return _lib.declare(G, TMC2GOF)
+
+
 def load_library():
     """Load libtmc2gof.so (after libtmc2hip.so, which it links against); raises if it has not been built."""
     global _GOF
@@ -33,12 +51,7 @@ def load_library():
         path = library_path()
         if not os.path.exists(path):
             raise _lib.Tmc2Error("libtmc2gof.so not built: run `python __graft_entry__.py build` (make -C mpeg-pcc-tmc2_amd/host)")
-        G = C.CDLL(path)
-        G.tmc2_gof_last_error.restype = C.c_char_p
-        G.tmc2_gof_comm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p]
-        G.tmc2_gof_comm_destroy.argtypes = [C.c_void_p]
-        G.tmc2_gof_comm_destroy.restype = None
-        _GOF = G
+        _GOF = declare(C.CDLL(path))
     return _GOF
 
 

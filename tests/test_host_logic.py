@@ -61,6 +61,78 @@ def test_every_declared_symbol_is_bound_and_documented():
     assert not [n for n in names if n not in binding], "not bound in lib.py"
 
 
+def _header(name):
+    """include/<name> without its comments and preprocessor lines"""
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+    return re.sub(r"^\s*#.*$", "", text, flags=re.M)
+
+
+def _c_type(declarator):
+    """'const int16_t* xyz' -> 'const int16_t*', 'double weight[3]' -> 'double[3]': a parameter's type without its name"""
+    base, dim = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d+\])?", " ".join(declarator.split())).groups()
+    return re.sub(r"\s*\*", "*", base) + (dim or "")
+
+
+def _declared_prototypes(name):
+    """{function: 'ret function(type, ...)'} of a header, spelled as the rows of tmc2_amd/lib.py are"""
+    out = {}
+    for ret, fn, params in re.findall(r"([\w\s*]+?)\b(tmc2_\w+)\s*\(([^)]*)\)\s*;", _header(name)):
+        types = "void" if params.strip() == "void" else ", ".join(_c_type(p) for p in params.split(","))
+        assert fn not in out, "%s is declared twice" % fn
+        out[fn] = "%s %s(%s)" % (re.sub(r"\s*\*", "*", " ".join(ret.split())), fn, types)
+    return out
+
+
+# The rule of tmc2_amd/lib.py, restated: scalars by their exact width; `const char*` is c_char_p; every other pointer (handles,
+# out-parameters, arrays, struct pointers, a returned void*) is c_void_p; a function that returns void has restype None.
+_C_SCALARS = {"void": None, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+              "size_t": ctypes.c_size_t, "long": ctypes.c_long, "double": ctypes.c_double}
+
+
+def _expected_ctype(c_type):
+    if c_type == "const char*":
+        return ctypes.c_char_p
+    return ctypes.c_void_p if c_type[-1] in "*]" else _C_SCALARS[c_type]
+
+
+def test_installed_prototypes_match_the_headers():
+    """Types, not only names: the table of tmc2_amd/lib.py has exactly the functions the two headers declare, with the header's
+    return and parameter types, and what load_library() installed on each function is what the mapping rule gives for them."""
+    from tmc2_amd import lib as binding, native_gof
+    for header, rows, lib in (("tmc2hip.h", binding.TMC2HIP, T.load_library()), ("tmc2gof.h", native_gof.TMC2GOF, native_gof.load_library())):
+        declared = _declared_prototypes(header)
+        assert set(declared) == set(re.findall(r"\b(tmc2_[a-z0-9_]+)\s*\(", _header(header))), "a declaration the parser missed"
+        table = {re.search(r"\b(tmc2_\w+)\(", row).group(1): row for row in rows}
+        assert len(table) == len(rows), "a function has two rows"
+        assert table == declared, "%s and its table in tmc2_amd/lib.py disagree" % header
+        for fn, row in declared.items():
+            ret, params = re.fullmatch(r"(.+?) %s\((.*)\)" % fn, row).groups()
+            want = [] if params == "void" else [_expected_ctype(t) for t in params.split(", ")]
+            got = getattr(lib, fn)
+            assert got.restype is _expected_ctype(ret) and got.argtypes == want, \
+                "%s: installed %s %s, the header says %s" % (fn, got.restype, got.argtypes, row)
+
+
+def test_struct_mirrors_match_the_headers():
+    """SegmenterParams, Patch and GofConfig have the fields of the header's structs -- names, order, types -- and PATCH_DTYPE lays a
+    record out as Patch does."""
+    from tmc2_amd import lib, native_gof
+    scalar = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
+    for header, struct, mirror in (("tmc2hip.h", "tmc2_segmenter_params", T.SegmenterParams), ("tmc2hip.h", "tmc2_patch", T.Patch),
+                                   ("tmc2gof.h", "tmc2_gof_config", native_gof.GofConfig)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), _header(header), flags=re.S).group(1)
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            c_type, names = decl.split(" ", 1)
+            for name, dim in re.findall(r"(\w+)(?:\[(\d+)\])?", names):
+                fields.append((name, scalar[c_type] * int(dim) if dim else scalar[c_type]))
+        assert len(fields) >= 8 and mirror._fields_ == fields, "%s and %s disagree" % (struct, mirror.__name__)
+    dt = lib.PATCH_DTYPE
+    assert dt.names == tuple(n for n, _ in T.Patch._fields_) and dt.itemsize == ctypes.sizeof(T.Patch)
+    for n, t in T.Patch._fields_:
+        assert dt.fields[n] == (np.dtype(t), getattr(T.Patch, n).offset), n
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():

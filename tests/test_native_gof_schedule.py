@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tmc2_amd import native_gof
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 (RESET, WEIGHT, SEGMENT, PACK_FLEXIBLE, PACK_CHAIN, GPA, PACKED_SIZE, GEOMETRY, ATTRIBUTE, GET_GEOMETRY, GET_ATTRIBUTE, PLACE,
  SET_PACKING) = range(1, 14)
@@ -32,10 +34,9 @@ def runner(tmp_path_factory):
                    [os.path.join(ROOT, "mpeg-pcc-tmc2_amd", "host", "gof_runner.cpp"), "-o", os.path.join(d, "libtmc2gofmock.so"),
                     "-L" + d, "-ltmc2hipmock", "-Wl,-rpath," + d, "-pthread", "-ldl"], check=True)
     M = C.CDLL(os.path.join(d, "libtmc2hipmock.so"), mode=C.RTLD_GLOBAL)
-    G = C.CDLL(os.path.join(d, "libtmc2gofmock.so"))
+    G = native_gof.declare(C.CDLL(os.path.join(d, "libtmc2gofmock.so")))
     M.mock_frame.restype = C.c_void_p
     M.mock_frame_free.argtypes = [C.c_void_p]
-    G.tmc2_gof_last_error.restype = C.c_char_p
     return M, G
 
 
@@ -217,10 +218,9 @@ def _sharded_rank(args):
     if rank == 0:
         os.environ.update(opt.get("env0", {}))
     M = C.CDLL(os.path.join(d, "libtmc2hipmock.so"), mode=C.RTLD_GLOBAL)
-    G = C.CDLL(os.path.join(d, "libtmc2gofmock.so"))
+    G = native_gof.declare(C.CDLL(os.path.join(d, "libtmc2gofmock.so")))
     M.mock_frame.restype = C.c_void_p
     M.mock_ctx.restype = C.c_void_p
-    G.tmc2_gof_last_error.restype = C.c_char_p
     ctx = C.c_void_p(M.mock_ctx(rank))
     comm = C.c_void_p()
     if rank == 0 and opt.get("rank0_late"):
