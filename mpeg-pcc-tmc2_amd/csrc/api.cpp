@@ -590,6 +590,22 @@ bool unionCheck( const tmc2_ctx* ctx ) {
   const auto e = ctxOption( ctx, "UF_CHECK" );
   return e && ( *e )[0] == '1';
 }
+int unionCheckResult( hipStream_t s, const uint32_t* d_bad, const std::string& what ) {
+  uint32_t bad[2] = {0, 0};
+  TMC2_HIP( hipMemcpyAsync( bad, d_bad, 8, hipMemcpyDeviceToHost, s ) );
+  TMC2_HIP( hipStreamSynchronize( s ) );
+  if ( bad[0] | bad[1] ) {
+    setError( "%s (%u bad links, %u split edges)", what.c_str(), bad[0], bad[1] );
+    return TMC2_E_HIP;
+  }
+  return TMC2_OK;
+}
+PassOrder passOrder( const tmc2_frame* f, const char* option ) {
+  const auto order = ctxOption( f->ctx, option );
+  const char o     = order ? ( *order )[0] : 'c';
+  const bool tree  = o == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= f->n;
+  return {o != 'i', tree ? f->tree.perm.p : nullptr};
+}
 void setRefineOverlapDefault( int on ) { g_refineOverlap.store( on ? 1 : 0, std::memory_order_relaxed ); }
 void setKdtreePlacement( int mode ) { g_kdtreeOnHost.store( mode < 0 || mode > 2 ? 0 : mode, std::memory_order_relaxed ); }
 int buildKdTreePlaced( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, const int16_t* hostXyz, const char* stage, DeviceTree& tree ) {

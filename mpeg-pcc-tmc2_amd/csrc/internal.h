@@ -156,17 +156,33 @@ __device__ __forceinline__ T loadStaleOk( const T* p, bool agent = false ) {
 }
 #endif
 
-// The element of this lane in a one-element-per-lane pass whose grid is a multiple of 8 blocks: XCD x works through the x-th eighth
-// of the blocks (block b runs on XCD b % 8 -- observed, not promised: only speed depends on it), so that neighbouring blocks --
-// neighbouring regions of the cloud in every array that is in scan order -- share an L2 instead of being dealt round-robin over
-// the eight.  Any other grid: the blocks as they come.  (chunkedGrid rounds a grid up; the surplus blocks find no element.)
+// ---- the XCD work mapping -------------------------------------------------------------------------------------------
+// Workgroups are handed to the eight XCDs round-robin: block b runs on XCD b % 8 (observed, not promised: only speed depends on
+// it).  A pass that takes its blocks as they come therefore deals neighbouring blocks -- neighbouring regions of the cloud in
+// every array that is in scan or tree order -- over eight L2s that do not share lines, and every L2 streams everything.  Chunked,
+// XCD x works through the x-th EIGHTH of the work instead: what a workgroup needs is what its neighbours on the same L2 have just
+// fetched.  The grid of a chunked pass is a multiple of 8 blocks (chunkedGrid rounds one up; the surplus blocks find no element).
+constexpr uint32_t chunkedGrid( uint32_t blocks ) { return ( blocks + 7u ) & ~7u; }
 #if defined( __HIPCC__ )
-__device__ __forceinline__ uint32_t chunkedIndex() {
-  const uint32_t b = ( gridDim.x & 7u ) ? blockIdx.x : ( blockIdx.x & 7u ) * ( gridDim.x >> 3 ) + ( blockIdx.x >> 3 );
-  return b * blockDim.x + threadIdx.x;
+struct XcdPlace {
+  uint32_t xcd, perXcd, slot;  // this workgroup is the slot-th of the perXcd that XCD xcd is dealt
+};
+__device__ __forceinline__ XcdPlace xcdPlace() { return {blockIdx.x & 7u, gridDim.x >> 3, blockIdx.x >> 3}; }
+// The logical block of this workgroup.  Chunked: the slot-th block of its XCD's eighth, perXcd blocks to an eighth (the grid's, or
+// fewer where only the first 8 * perXcd blocks are live: knnKernel); else the blocks as they come.
+__device__ __forceinline__ uint32_t chunkedBlock( uint32_t perXcd ) {
+  const XcdPlace at = xcdPlace();
+  return at.xcd * perXcd + at.slot;
+}
+__device__ __forceinline__ uint32_t logicalBlock( bool chunked ) { return chunked ? chunkedBlock( xcdPlace().perXcd ) : blockIdx.x; }
+// The element of this lane in a one-element-per-lane pass: chunked if the grid is a multiple of 8 blocks.
+__device__ __forceinline__ uint32_t chunkedIndex() { return logicalBlock( !( gridDim.x & 7u ) ) * blockDim.x + threadIdx.x; }
+// The point of this lane in a one-point-per-lane pass over n points (n: none); perm: the points in tree order, not input order.
+__device__ __forceinline__ uint32_t pointOfLane( const uint32_t* __restrict__ perm, bool chunked, uint32_t n ) {
+  const uint32_t at = logicalBlock( chunked ) * blockDim.x + threadIdx.x;
+  return at < n ? ( perm ? perm[at] : at ) : n;
 }
 #endif
-inline uint32_t chunkedGrid( uint32_t blocks ) { return ( blocks + 7u ) & ~7u; }
 
 // pointToPixel of a reconstructed point in one word: canvas x, y (15 bits each: canvases up to kMaxCanvasDim pixels a side,
 // enforced where a canvas size enters -- generateGeometryImages, the decoder frame), map layer, "a D1 point follows"
@@ -551,6 +567,17 @@ int  kdtreePlacement( const tmc2_ctx* ctx );  // 0 device, 1 host, 2 adaptive (h
 int  unionPrecheck( const tmc2_ctx* ctx );
 bool unionCheck( const tmc2_ctx* ctx );
 bool unionAgentScope( const tmc2_ctx* ctx );  // TMC2_UF_SCOPE=agent: every load of the union passes at agent scope (the formally clean form)
+// after a check kernel (UF_CHECK) has counted into d_bad[0] (broken links) and d_bad[1] (split edges): a round trip; TMC2_E_HIP and
+// the error "<what> (<n> bad links, <n> split edges)" if either is non-zero
+int unionCheckResult( hipStream_t s, const uint32_t* d_bad, const std::string& what );
+// An order option of a pass over the frame's points (MUTUAL_ORDER, ORIENT_ORDER): "input" = index order, blocks as they come;
+// "chunk" (and unset) = index order, XCD x on the x-th eighth of the blocks; "tree" = tree order (perm != nullptr; index order if
+// the frame has no tree of its own points), same eighths.
+struct PassOrder {
+  bool            chunked;
+  const uint32_t* perm;
+};
+PassOrder passOrder( const tmc2_frame* f, const char* option );
 int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, DeviceTree& tree );
 // the frame's tree and the reconstruction's, built where kdtreePlacement says.  hostXyz: the same points as int16 triples on the
 // host, or null (they are read back from d_pts).  Stage `stage` times a device build, `stage` + "_host" a host build

@@ -86,16 +86,13 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
   const int      offBits = ( 64 - nodeBits ) / 3, sh0 = nodeBits, sh1 = nodeBits + offBits, sh2 = nodeBits + 2 * offBits;
   const uint32_t nodeMask = ( 1u << nodeBits ) - 1u, offMask = ( 1u << offBits ) - 1u;
   (void)sh0, (void)sh1, (void)sh2, (void)nodeMask, (void)offMask;
-  // Which 256 queries this workgroup takes.  Workgroups are handed to the eight XCDs round-robin (block b runs on XCD b % 8:
-  // observed, not promised -- only speed depends on it), so consecutive blocks -- neighbours in tree order, walking the same
-  // part of the tree -- land on eight different L2s, and every L2 ends up streaming the whole tree (9.4 MB at longdress size
-  // against 4 MB of L2: 9.5 x the algorithmic bytes reached HBM).  With the mapping below XCD x works through the x-th eighth
-  // of the queries: its L2 holds an eighth of the tree.  (The grid is a multiple of 8 blocks; blocks past the end leave.)
-  // (a compacted list: the eighths are eighths of the LIVE blocks, the grid was sized for the worst case)
+  // Which 256 queries this workgroup takes: chunked (internal.h: the XCD work mapping).  Consecutive blocks are neighbours in
+  // tree order and walk the same part of the tree; dealt as they come, every L2 ended up streaming the whole tree (9.4 MB at
+  // longdress size against 4 MB of L2: 9.5 x the algorithmic bytes reached HBM); in eighths an L2 holds an eighth of the tree.
+  // (a compacted list: the eighths are eighths of the LIVE blocks, the grid was sized for the worst case; surplus blocks leave)
   const uint32_t perXcd = nqLive ? ( ( nq + 255u ) / 256u + 7u ) >> 3 : gridDim.x >> 3;
-  if ( ( blockIdx.x >> 3 ) >= perXcd ) return;
-  const uint32_t block = ( blockIdx.x & 7u ) * perXcd + ( blockIdx.x >> 3 );
-  const uint32_t j     = block * blockDim.x + threadIdx.x;
+  if ( xcdPlace().slot >= perXcd ) return;
+  const uint32_t j = chunkedBlock( perXcd ) * blockDim.x + threadIdx.x;
   if ( j >= nq ) return;
   const Pt  qp = SELF ? ptsTree[j] : queries[j];
   const int qx = qp.x, qy = qp.y, qz = qp.z;
@@ -277,7 +274,7 @@ int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, 
     rb.hi[d] = t.hi[d];
   }
   const dim3 block( 256 );
-  const dim3 grid( uint32_t( ( ( nq + 255 ) / 256 + 7 ) & ~uint64_t( 7 ) ) );  // (a multiple of 8 blocks: knnKernel's XCD mapping)
+  const dim3 grid( chunkedGrid( uint32_t( ( nq + 255 ) / 256 ) ) );  // (knnKernel's XCD mapping)
   // the packed LDS stack needs: every offset < 2^14 (tree box and queries inside a 16383-wide window -- the caller
   // vouches for the queries with t.queriesBounded), node ids < 2^22, and at most kLdsLevels pending far children
   bool lds = t.depth <= kLdsLevels && ( ( t.queriesBounded && t.n <= ( uint64_t( 1 ) << 21 ) ) || ( ( SELF || t.queriesTight ) && t.n <= ( uint64_t( 1 ) << 23 ) ) );

@@ -6,20 +6,19 @@
 // points and 13 M edges of the k-NN graph:
 //   * points joined by MUTUAL strong edges (both list each other, |n_u . n_v| >= tau) are absorbed together, and if
 //     their strong edges agree with one relative sign assignment only the sign of the whole cluster is left to decide.
-//     Clusters + relative signs = a union-find with PARITY over the mutual strong edges: lock-free, one 32-bit word
-//     per point (parent << 1 | parity-to-parent), hooking by compare-and-swap under the root of smaller hashed
-//     priority, path halving that composes parities -- every word ever stored states a true relation, so stale reads
-//     are harmless.  A second pass checks every mutual strong edge against the parities (a disagreement = a cluster
-//     whose orientation would depend on the order of the growth: the caller falls back to the point-level walk);
+//     Clusters + relative signs = a union-find with PARITY over the mutual strong edges (union_find.h).  A second pass
+//     checks every mutual strong edge against the parities (a disagreement = a cluster whose orientation would depend
+//     on the order of the growth: the caller falls back to the point-level walk);
 //   * what is left for the host are the CROSS edges (ends in different clusters): counted per source cluster, prefix
 //     summed, scattered -- about 4 % of the edges and ~18 K clusters at longdress size with tau = 0.98, 16 MB over
 //     PCIe instead of 180 MB, and a 14 ms walk instead of 180 ms.
 #include "internal.h"
+#include "union_find.h"
 
 namespace tmc2 {
 namespace {
 
-__device__ __forceinline__ uint32_t ufPriority( uint32_t x ) { return x * 2654435761u; }  // odd multiplier: a bijection
+using Uf = UnionFind<true>;  // the word of a point is parent << 1 | parity-to-parent
 
 // The kernels below that read a point's own k-NN row (16 ids = 64 bytes) and dot-product row (16 doubles = 128 bytes) give the
 // point 16 lanes, lane j holding edge j: a wavefront reads four rows back to back (fully coalesced) instead of 64 rows
@@ -39,32 +38,23 @@ __device__ __forceinline__ double edgeDotOf( const double* __restrict__ normals,
   return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
 }
 
-// Which 16-point group a workgroup takes next.  The passes over the edges walk the points in TREE order (perm: tree position ->
-// point; neighbours in space are neighbours in the tree) and XCD x works through the x-th eighth of the groups (block b runs on
-// XCD b % 8 -- observed, not promised: only speed depends on it; the mapping of knnKernel): the rows, words and cluster records a
-// group's neighbours need are the ones its own XCD's L2 has just fetched, instead of every L2 seeing every region of the cloud.
-// perm == nullptr (an adjacency that came from the caller: no tree): index order, same eighths.
+// Which 16-point group a workgroup takes next, in a stride loop.  The passes over the edges walk the points in TREE order (perm:
+// tree position -> point; neighbours in space are neighbours in the tree) or, perm == nullptr, in index order; chunked (internal.h:
+// the XCD work mapping; gridDim.x is a multiple of 8), the workgroups of XCD x share out the x-th eighth of the GROUPS: the rows,
+// words and cluster records a group's neighbours need are the ones its own XCD's L2 has just fetched.
 struct GroupWalk {
   uint32_t g, end, step;
-  __device__ __forceinline__ GroupWalk( uint32_t groups, bool chunked ) {  // (chunked: gridDim.x is a multiple of 8)
+  __device__ __forceinline__ GroupWalk( uint32_t groups, bool chunked ) {
     if ( !chunked ) {
       g = blockIdx.x, end = groups, step = gridDim.x;
       return;
     }
-    const uint32_t x = blockIdx.x & 7u, perXcd = gridDim.x >> 3;
-    const uint32_t begin = uint32_t( ( uint64_t( groups ) * x ) >> 3 );
-    end  = uint32_t( ( uint64_t( groups ) * ( x + 1u ) ) >> 3 );
-    g    = begin + ( blockIdx.x >> 3 );
-    step = perXcd;
+    const XcdPlace at = xcdPlace();
+    g    = uint32_t( ( uint64_t( groups ) * at.xcd ) >> 3 ) + at.slot;
+    end  = uint32_t( ( uint64_t( groups ) * ( at.xcd + 1u ) ) >> 3 );
+    step = at.perXcd;
   }
 };
-// ... and which point a lane of a one-point-per-lane pass takes (n: none)
-__device__ __forceinline__ uint32_t pointOfLane( const uint32_t* __restrict__ perm, bool chunked, uint32_t n ) {
-  uint32_t block = blockIdx.x;
-  if ( chunked ) block = ( blockIdx.x & 7u ) * ( gridDim.x >> 3 ) + ( blockIdx.x >> 3 );
-  const uint32_t at = block * blockDim.x + threadIdx.x;
-  return at < n ? ( perm ? perm[at] : at ) : n;
-}
 
 // Initial forest without a single atomic: every point hooks itself under the mutual strong neighbour of smallest hashed
 // priority, if that is smaller than its own (priorities strictly decrease along parent links: no cycles; the word
@@ -108,60 +98,13 @@ __global__ __launch_bounds__( 256 ) void initWordsKernel( const uint32_t* __rest
   if ( j == 0 ) {
     count[i] = 0;
     if ( prio >= ufPriority( i ) ) best = i;  // (no mutual strong neighbour of smaller priority: its own root)
-    word[i] = ( best << 1 ) | ( best == i ? 0u : parity );
+    word[i] = Uf::link( best, best == i ? 0u : parity );
   }
   }
 }
 
-// root of x and the parity of x relative to it; halves the path on the way
-// (the climb reads through the XCD's L2 -- workgroup-scope loads, a view possibly behind the other XCDs': a link read there is
-// still a link of the forest with its parity -- and only "is this a root" goes to the coherent level, climbing on if it is not)
-__device__ __forceinline__ uint32_t parityFind( uint32_t* word, uint32_t x, uint32_t& parity, bool agent ) {
-  uint32_t acc = 0;
-  for ( ;; ) {
-    const uint32_t w = loadStaleOk( &word[x], agent );
-    const uint32_t p = w >> 1;
-    if ( p == x ) break;
-    const uint32_t wp = loadStaleOk( &word[p], agent );
-    const uint32_t gp = wp >> 1;
-    if ( gp != p ) __hip_atomic_store( &word[x], ( gp << 1 ) | ( ( w ^ wp ) & 1u ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-    acc ^= w & 1u;
-    x = p;
-  }
-  for ( ;; ) {
-    const uint32_t w = __hip_atomic_load( &word[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-    const uint32_t p = w >> 1;
-    if ( p == x ) break;
-    acc ^= w & 1u;
-    x = p;
-  }
-  parity = acc;
-  return x;
-}
-
-// "Are a and b in one cluster already?" from this CU's possibly stale view, without a store or an atomic (the same walk as
-// ufSameSetStale in patches.hip: the end of larger priority climbs; true is final because every word ever stored links two
-// members of one cluster, false only sends the caller to the coherent loop).  Whether the parities along the two paths agree
-// with the edge is not this walk's business: verifyCountKernel checks every mutual strong edge on the settled forest.
-__device__ __forceinline__ bool paritySameSetStale( const uint32_t* word, uint32_t a, uint32_t b, bool agent ) {
-  uint32_t pa = ufPriority( a ), pb = ufPriority( b );
-  for ( ;; ) {
-    if ( a == b ) return true;
-    if ( pa < pb ) {
-      const uint32_t t = a;
-      a                = b;
-      b                = t;
-      const uint32_t q = pa;
-      pa               = pb;
-      pb               = q;
-    }
-    const uint32_t up = loadStaleOk( &word[a], agent ) >> 1;
-    if ( up == a ) return false;
-    a  = up;
-    pa = ufPriority( a );
-  }
-}
-
+// The unions over the mutual strong edges; the union-find itself: union_find.h.  Whether an edge whose ends are in one cluster
+// already agrees with the parities there is checked afterwards, on the settled forest (pairInsertKernel).
 template <int K>
 __global__ __launch_bounds__( 256 ) void parityUnionKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ negAll,
                                                              const uint16_t* __restrict__ mask, const uint32_t* __restrict__ perm,
@@ -178,41 +121,20 @@ __global__ __launch_bounds__( 256 ) void parityUnionKernel( const uint32_t* __re
     m &= m - 1;
     const uint32_t v = knn[size_t( u ) * K + j];
     if ( v > u ) continue;  // every mutual edge is seen from both ends: the larger one acts
-    if ( precheck && paritySameSetStale( word, u, v, agent ) ) continue;
-    const uint32_t s = ( neg >> j ) & 1u;  // 1: the two normals must get opposite signs
-    for ( ;; ) {
-      uint32_t pa, pb;
-      uint32_t a = parityFind( word, u, pa, agent ), b = parityFind( word, v, pb, agent );
-      if ( a == b ) break;  // (whether the parities agree with s is checked afterwards, on the settled forest)
-      if ( ufPriority( a ) < ufPriority( b ) ) {
-        const uint32_t t = a;
-        a                = b;
-        b                = t;
-      }
-      // hook a under b: sign(a) sign(b) = sign(u) sign(v) (-1)^(pa ^ pb) = (-1)^(s ^ pa ^ pb)
-      if ( atomicCAS( &word[a], a << 1, ( b << 1 ) | ( pa ^ pb ^ s ) ) == ( a << 1 ) ) break;
-    }
+    if ( precheck && Uf::sameSetStale( word, u, v, agent ) ) continue;
+    Uf::unite( word, u, v, ( neg >> j ) & 1u, agent );  // (s = 1: the two normals must get opposite signs)
   }
 }
 
 // Debug invariants of the settled forest (TMC2_UF_CHECK=1): links fall in priority; both ends of every mutual strong edge
-// have one root (agent-scope climbs only).  bad[0] = broken links, bad[1] = split edges.
+// have one root (Uf::rootCoherent).  bad[0] = broken links, bad[1] = split edges.
 template <int K>
 __global__ __launch_bounds__( 256 ) void parityCheckKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mask,
                                                              uint32_t n, uint32_t* word, uint32_t* __restrict__ bad ) {
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
   if ( u >= n ) return;
-  auto rootOf = [&]( uint32_t x ) {
-    for ( uint32_t hops = 0; hops <= n; ++hops ) {
-      const uint32_t q = __hip_atomic_load( &word[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ) >> 1;
-      if ( q == x ) return x;
-      if ( q >= n || ufPriority( q ) >= ufPriority( x ) ) return 0xFFFFFFFFu;
-      x = q;
-    }
-    return 0xFFFFFFFFu;
-  };
-  const uint32_t ru = rootOf( u );
-  if ( ru == 0xFFFFFFFFu ) {
+  const uint32_t ru = Uf::rootCoherent( word, u, n );
+  if ( ru == kUfBroken ) {
     atomicAdd( &bad[0], 1u );
     return;
   }
@@ -222,7 +144,7 @@ __global__ __launch_bounds__( 256 ) void parityCheckKernel( const uint32_t* __re
     m &= m - 1;
     const uint32_t v = knn[size_t( u ) * K + j];
     if ( v > u ) continue;
-    if ( rootOf( v ) != ru ) atomicAdd( &bad[1], 1u );
+    if ( Uf::rootCoherent( word, v, n ) != ru ) atomicAdd( &bad[1], 1u );
   }
 }
 
@@ -231,10 +153,10 @@ __global__ __launch_bounds__( 256 ) void flattenKernel( uint32_t n, const uint32
                                                          uint8_t* __restrict__ parity, uint32_t* __restrict__ minIdx, bool agent ) {
   const uint32_t u = pointOfLane( perm, chunked, n );  // (as parityUnionKernel)
   if ( u >= n ) return;
-  uint32_t       p;
-  const uint32_t r = parityFind( word, u, p, agent );
-  root[u]          = r;
-  parity[u]        = uint8_t( p );
+  const UfRoot   found = Uf::find( word, u, agent );  // (the flat view goes to its own arrays: union_find.h)
+  const uint32_t r     = found.root;
+  root[u]              = r;
+  parity[u]            = uint8_t( found.parity );
   // first member of the cluster (the running minimum only falls: look before the atomic -- the early points of a big cluster
   // settle it, the other hundred thousand skip)
   if ( minIdx && u < loadStaleOk( &minIdx[r] ) ) atomicMin( &minIdx[r], u );
@@ -563,31 +485,25 @@ int contractOrientationDevice( tmc2_frame* f, double tau, DevBuf<uint32_t>& d_ci
                                {d_strongFirst.p, 2 * size_t( pairCap ) * 4, 0xFF}} ) );
   TMC2_TRY( ensureMutualMask( f ) );
   // 16 lanes per point, groups of 16 points in a stride loop; the grids are multiples of 8 (GroupWalk: XCD x takes the x-th eighth)
-  const dim3 grdN16( ( cappedBlocks( ctx, ( size_t( n ) + 15 ) / 16 ) + 7u ) & ~7u ), grdN8( ( grdN.x + 7u ) & ~7u );
+  const dim3 grdN16( chunkedGrid( cappedBlocks( ctx, ( size_t( n ) + 15 ) / 16 ) ) ), grdN8( chunkedGrid( grdN.x ) );
   // option ORIENT_ORDER: "input" = index order, blocks as they come (rounds 2-5); "chunk" = index order, XCD x on the x-th eighth of
   // the blocks; "tree" = tree order (perm), same eighths.  Unset: what was fastest pass by pass with the GPU to itself
   // (profiles/r06_pass_order.txt) -- the union-find passes in eighths (their climbs touch the words of points around their own:
   // parityUnionKernel 349 -> 272 us), the pair-table passes as the blocks come (in eighths the inserts of a pair of clusters
   // meet in time: pairInsertKernel 95 -> 106 us); tree order costs every pass its coalesced own-row reads and wins nothing on
   // clouds that arrive in scan order.
-  const auto      orderOpt = ctxOption( ctx, "ORIENT_ORDER" );
-  const bool      chunked  = !( orderOpt && ( *orderOpt )[0] == 'i' );
-  const bool      chunkedPairs = orderOpt && ( *orderOpt )[0] != 'i';
-  const uint32_t* perm     = orderOpt && ( *orderOpt )[0] == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= n ? f->tree.perm.p : nullptr;
+  const PassOrder order        = passOrder( f, "ORIENT_ORDER" );
+  const bool      chunked      = order.chunked;
+  const bool      chunkedPairs = chunked && ctxOption( ctx, "ORIENT_ORDER" ).has_value();  // (unset: the pair-table passes as the blocks come)
+  const uint32_t* perm         = order.perm;
   const double*   normals  = f->d_normals.p;
   TMC2_TRY( d_count.alloc( size_t( n ) + 1 ) );  // (initWordsKernel zeroes it; later: kept edges per cluster, C + 1 used)
   hipLaunchKernelGGL( initWordsKernel<16>, grdN16, blk, 0, s, f->d_knn.p, normals, f->d_mutual.p, perm, chunked, tau, n, d_mask.p, d_strongAll.p,
                       d_negAll.p, d_word.p, d_count.p );
   hipLaunchKernelGGL( parityUnionKernel<16>, grdN8, blk, 0, s, f->d_knn.p, d_negAll.p, d_mask.p, perm, chunked, n, d_word.p, unionPrecheck( f->ctx ), unionAgentScope( f->ctx ) );
   if ( unionCheck( f->ctx ) ) {  // debug invariants (soak tests): costs a round trip
-    uint32_t bad[2] = {0, 0};
     hipLaunchKernelGGL( parityCheckKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mask.p, n, d_word.p, d_small.p + 4 );
-    TMC2_HIP( hipMemcpyAsync( bad, d_small.p + 4, 8, hipMemcpyDeviceToHost, s ) );
-    TMC2_HIP( hipStreamSynchronize( s ) );
-    if ( bad[0] | bad[1] ) {
-      setError( "orientNormals: union-find invariant broken (%u bad links, %u split edges)", bad[0], bad[1] );
-      return TMC2_E_HIP;
-    }
+    TMC2_TRY( unionCheckResult( s, d_small.p + 4, "orientNormals: union-find invariant broken" ) );
   }
   hipLaunchKernelGGL( flattenKernel, grdN8, blk, 0, s, n, perm, chunked, d_word.p, d_root.p, d_parity.p, d_minIdx.p, unionAgentScope( f->ctx ) );
   hipLaunchKernelGGL( clusterFlagKernel, grdN, blk, 0, s, d_root.p, d_minIdx.p, n, d_flag.p );

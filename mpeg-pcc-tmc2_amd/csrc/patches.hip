@@ -22,9 +22,12 @@
 #include <cmath>
 
 #include "internal.h"
+#include "union_find.h"
 
 namespace tmc2 {
 namespace {
+
+using Uf = UnionFind<false>;  // the word of a point is its parent
 
 constexpr uint32_t kNoLabel = 0xFFFFFFFFu;
 constexpr uint32_t kFar     = 0xFFFFFFFFu;  // "distance to the resampled cloud unknown / beyond the probe radius"
@@ -70,9 +73,8 @@ __device__ __forceinline__ int waveMaxMasked( int v, bool mine ) {
 // restricted to raw points of one plane.  Pushing labels along edges needs as many dependent steps as
 // the graph is deep (hundreds of hops on a body-sized patch).  Instead:
 //   1. mutual edges (u in knn[v] and v in knn[u]) are bidirectional, so everything they connect is reached by
-//      exactly the same seeds: a lock-free union-find over the mutual edges (hooking with atomicCAS under the root of
-//      smaller HASHED priority -- hooking by index would grow chains as long as the scan order of the cloud -- and
-//      path halving) collapses each such group in O(log) dependent steps;
+//      exactly the same seeds: a lock-free union-find over the mutual edges (union_find.h) collapses each such group
+//      in O(log) dependent steps;
 //   2. lab[root] = smallest ELIGIBLE member (atomicMin);
 //   3. the remaining one-way edges connect groups; lab[] is relaxed along them until nothing changes -- on the
 //      condensed graph that is a handful of sweeps, each touching only the one-way edges.
@@ -80,19 +82,13 @@ __device__ __forceinline__ int waveMaxMasked( int v, bool mine ) {
 
 // bit j of mutual[u] = knn[u][j] lists u in its own row.  Depends only on the adjacency: once per call.
 // Every row is read by the point itself and by its (up to) sixteen in-neighbours: 64 N bytes if each row reached HBM once, sixteen
-// times that if none stayed cached.  Rounds 1-5 dealt the blocks round-robin over the eight XCDs: every L2 saw every region of the
-// cloud (counters: 325 MB for 55 MB of contract bytes).  Round 6: XCD x works through the x-th eighth of the blocks (the mapping of
-// knnKernel) -- the rows a workgroup needs are the rows its neighbours on the same L2 have just fetched (85 MB); perm != nullptr:
-// the points in TREE order instead of input order (no faster on clouds that arrive in scan order: option MUTUAL_ORDER=tree).
+// times that if none stayed cached.  With the blocks as they come every L2 saw every region of the cloud (counters: 325 MB for 55 MB
+// of contract bytes); chunked (internal.h: the XCD work mapping) 85 MB.  perm != nullptr: the points in TREE order instead of
+// input order (no faster on clouds that arrive in scan order: option MUTUAL_ORDER=tree).
 template <int K>
 __global__ __launch_bounds__( 256 ) void ccMutualMaskKernel( const uint32_t* __restrict__ knn, const uint32_t* __restrict__ perm, bool chunked,
                                                               uint32_t n, uint16_t* __restrict__ mutual ) {
-  uint32_t block = blockIdx.x;
-  if ( chunked ) {  // (grid: a multiple of 8 blocks; block b runs on XCD b % 8 -- observed, not promised: only speed depends on it)
-    const uint32_t perXcd = gridDim.x >> 3;
-    block                 = ( blockIdx.x & 7u ) * perXcd + ( blockIdx.x >> 3 );
-  }
-  const uint32_t at = block * blockDim.x + threadIdx.x;
+  const uint32_t at = logicalBlock( chunked ) * blockDim.x + threadIdx.x;
   if ( at >= n ) return;
   const uint32_t u = perm ? perm[at] : at;
   uint32_t     nb[K];
@@ -117,17 +113,6 @@ __global__ __launch_bounds__( 256 ) void ccMutualMaskKernel( const uint32_t* __r
     m |= hit ? ( 1u << j ) : 0u;
   }
   mutual[u] = uint16_t( m );
-}
-
-__device__ __forceinline__ uint32_t ufPriority( uint32_t x ) { return x * 2654435761u; }  // odd multiplier: a bijection
-
-// The point of this lane (n: none).  chunked: XCD x works through the x-th eighth of the blocks (block b runs on XCD b % 8 -- observed,
-// not promised: only speed depends on it; the grid is a multiple of 8 blocks); perm: the points in tree order instead of input order.
-__device__ __forceinline__ uint32_t pointOfLane( const uint32_t* __restrict__ perm, bool chunked, uint32_t n ) {
-  uint32_t block = blockIdx.x;
-  if ( chunked ) block = ( blockIdx.x & 7u ) * ( gridDim.x >> 3 ) + ( blockIdx.x >> 3 );
-  const uint32_t at = block * blockDim.x + threadIdx.x;
-  return at < n ? ( perm ? perm[at] : at ) : n;
 }
 
 // Initial forest without atomics: every raw point hooks itself under the eligible mutual neighbour of smallest hashed
@@ -160,51 +145,7 @@ __global__ __launch_bounds__( 256 ) void ccInitKernel( const uint32_t* __restric
   parent[i] = best;
 }
 
-// a parent always has a smaller priority than its child, so the forest stays acyclic and a stale read during find
-// is still an ancestor-or-self of the truth
-// The climb reads through the XCD's L2 (workgroup-scope loads: the view of this XCD, possibly behind the other seven -- still
-// ancestors); only the last step, "is this really a root", goes to the coherent level and climbs on from there if it is not.
-// An agent-scope load per hop is a trip past the L2 for every link of every path.
-__device__ __forceinline__ uint32_t ufFind( uint32_t* parent, uint32_t x, bool agent ) {
-  uint32_t p = loadStaleOk( &parent[x], agent );
-  while ( p != x ) {
-    const uint32_t g = loadStaleOk( &parent[p], agent );
-    if ( g != p ) __hip_atomic_store( &parent[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );  // path halving
-    x = p;
-    p = g;
-  }
-  for ( ;; ) {
-    const uint32_t q = __hip_atomic_load( &parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-    if ( q == x ) return x;
-    x = q;
-  }
-}
-
-// "Are a and b in one set already?" answered from this CU's possibly stale view, without a store or an atomic: the two
-// climbs advance the end of LARGER priority (priorities fall strictly along every link ever written, so the end of smaller
-// priority cannot lie below the other one's path) and meet at a common ancestor if the view has one.  true is final -- every
-// word ever stored in parent[] links two members of one set and sets only grow; false only means "not known here", and the
-// caller goes on to the coherent find / compare-and-swap loop.  Most mutual edges join points that ccInitKernel (or an
-// earlier union) has put into one tree already: they end here, a few L1 / L2 hits each.
-__device__ __forceinline__ bool ufSameSetStale( const uint32_t* parent, uint32_t a, uint32_t b, bool agent ) {
-  uint32_t pa = ufPriority( a ), pb = ufPriority( b );
-  for ( ;; ) {
-    if ( a == b ) return true;
-    if ( pa < pb ) {
-      const uint32_t t = a;
-      a                = b;
-      b                = t;
-      const uint32_t q = pa;
-      pa               = pb;
-      pb               = q;
-    }
-    const uint32_t up = loadStaleOk( &parent[a], agent );
-    if ( up == a ) return false;  // a root of larger priority than b: nothing above it in this view
-    a  = up;
-    pa = ufPriority( a );
-  }
-}
-
+// The unions over the eligible mutual edges (raw ends of one plane); the union-find itself: union_find.h.
 template <int K>
 __global__ __launch_bounds__( 256 ) void ccUnionKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mutual,
                                                          const uint8_t* __restrict__ partition,
@@ -222,44 +163,24 @@ __global__ __launch_bounds__( 256 ) void ccUnionKernel( const uint32_t* __restri
     m &= m - 1;
     const uint32_t v = row[j];
     if ( v > u || !raw[v] || partition[v] != pu ) continue;  // every mutual edge is seen from both ends: larger one acts
-    if ( precheck && ufSameSetStale( parent, u, v, agent ) ) continue;
-    uint32_t a = u, b = v;
-    while ( true ) {
-      a = ufFind( parent, a, agent );
-      b = ufFind( parent, b, agent );
-      if ( a == b ) break;
-      if ( ufPriority( a ) < ufPriority( b ) ) {
-        const uint32_t t = a;
-        a                = b;
-        b                = t;
-      }
-      if ( atomicCAS( &parent[a], a, b ) == a ) break;  // hook the root of larger priority under the other
-    }
+    if ( precheck && Uf::sameSetStale( parent, u, v, agent ) ) continue;
+    Uf::unite( parent, u, v, 0u, agent );
   }
 }
 
 // Debug invariants of the settled forest (TMC2_UF_CHECK=1, the soak tests): every link goes to a raw point of the same plane
-// and of smaller priority; the two ends of every eligible mutual edge have one root.  Climbs at agent scope only (the
-// coherent truth, no stale view involved).  bad[0] = broken links, bad[1] = edges whose ends ended up in different sets.
+// and of smaller priority; the two ends of every eligible mutual edge have one root (Uf::rootCoherent).  bad[0] = broken
+// links, bad[1] = edges whose ends ended up in different sets.
 template <int K>
 __global__ __launch_bounds__( 256 ) void ccCheckKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mutual,
                                                          const uint8_t* __restrict__ partition, const uint8_t* __restrict__ raw,
                                                          uint32_t n, uint32_t* parent, uint32_t* __restrict__ bad ) {
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
   if ( u >= n || !raw[u] ) return;
-  auto rootOf = [&]( uint32_t x ) {
-    for ( uint32_t hops = 0; hops <= n; ++hops ) {
-      const uint32_t q = __hip_atomic_load( &parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
-      if ( q == x ) return x;
-      if ( q >= n || ufPriority( q ) >= ufPriority( x ) ) return 0xFFFFFFFFu;
-      x = q;
-    }
-    return 0xFFFFFFFFu;
-  };
   const uint32_t p = __hip_atomic_load( &parent[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
   if ( p != u && ( p >= n || !raw[p] || partition[p] != partition[u] || ufPriority( p ) >= ufPriority( u ) ) ) atomicAdd( &bad[0], 1u );
-  const uint32_t ru = rootOf( u );
-  if ( ru == 0xFFFFFFFFu ) {
+  const uint32_t ru = Uf::rootCoherent( parent, u, n );
+  if ( ru == kUfBroken ) {
     atomicAdd( &bad[0], 1u );
     return;
   }
@@ -269,7 +190,7 @@ __global__ __launch_bounds__( 256 ) void ccCheckKernel( const uint32_t* __restri
     m &= m - 1;
     const uint32_t v = knn[size_t( u ) * K + j];
     if ( v > u || !raw[v] || partition[v] != partition[u] ) continue;
-    if ( rootOf( v ) != ru ) atomicAdd( &bad[1], 1u );
+    if ( Uf::rootCoherent( parent, v, n ) != ru ) atomicAdd( &bad[1], 1u );
   }
 }
 
@@ -282,11 +203,7 @@ __global__ __launch_bounds__( 256 ) void ccFlattenSeedKernel( const uint8_t* __r
   uint32_t       r    = kNoLabel;
   bool           seed = false;
   if ( u < n && raw[u] ) {
-    // The flat view goes to its OWN array.  Writing r into parent[u] raced with the path-halving stores of the finds that
-    // pass through u at the same moment: a halving store issued from a stale view (parent[u] = some ancestor) could land after
-    // this one and leave parent[u] short of the root -- and the kernels below read the array as flat.  Rare while the union
-    // pass had compressed nearly every path, frequent once most edges end in the store-free pre-check.
-    r       = ufFind( parent, u, agent );
+    r       = Uf::find( parent, u, agent ).root;  // (the flat view goes to its own array: union_find.h)
     root[u] = r;
     seed    = dist[u] > thrDetection;
   }
@@ -744,12 +661,10 @@ int ensureMutualMask( tmc2_frame* f ) {
   StageScope stage( f->ctx, "k:ccMutualMask" );
   // option MUTUAL_ORDER (this pass and S7's union / relaxation passes): "input" = index order, blocks as they come (rounds 1-5);
   // "chunk" = index order, XCD x on the x-th eighth of the blocks; "tree" = tree order, same eighths
-  const auto      order   = ctxOption( f->ctx, "MUTUAL_ORDER" );
-  const bool      chunked = !( order && ( *order )[0] == 'i' );
-  const uint32_t* perm    = order && ( *order )[0] == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= n ? f->tree.perm.p : nullptr;
-  const uint32_t  blocks  = ( n + 255 ) / 256;
-  hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( chunked ? ( ( blocks + 7 ) & ~7u ) : blocks ), dim3( 256 ), 0, f->ctx->stream, f->d_knn.p,
-                      perm, chunked, n, f->d_mutual.p );
+  const PassOrder order  = passOrder( f, "MUTUAL_ORDER" );
+  const uint32_t  blocks = ( n + 255 ) / 256;
+  hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( order.chunked ? chunkedGrid( blocks ) : blocks ), dim3( 256 ), 0, f->ctx->stream, f->d_knn.p,
+                      order.perm, order.chunked, n, f->d_mutual.p );
   TMC2_HIP( hipGetLastError() );
   f->haveMutual = true;
   return TMC2_OK;
@@ -838,32 +753,25 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   TMC2_TRY( ensureMutualMask( f ) );  // usually there already: the orientation (S3) needs the same bits
   DevBuf<uint16_t>& d_mutual   = f->d_mutual;
   const bool        agentScope = unionAgentScope( f->ctx );
-  // the union / relaxation passes: option MUTUAL_ORDER as in ensureMutualMask (here the default is "chunk")
-  const auto      ccOrder = ctxOption( ctx, "MUTUAL_ORDER" );
-  const bool      chunked = !( ccOrder && ( *ccOrder )[0] == 'i' );
-  const uint32_t* perm    = ccOrder && ( *ccOrder )[0] == 't' && f->haveTree && f->tree.perm.p && f->tree.perm.count >= n ? f->tree.perm.p : nullptr;
-  const dim3      grdT( chunked ? ( ( grdN.x + 7u ) & ~7u ) : grdN.x );
+  // the union / relaxation passes: option MUTUAL_ORDER as in ensureMutualMask (grdN is a multiple of 8 blocks either way)
+  const PassOrder order   = passOrder( f, "MUTUAL_ORDER" );
+  const bool      chunked = order.chunked;
+  const uint32_t* perm    = order.perm;
   while ( rawCount > 0 ) {
     // ---- S7 -----------------------------------------------------------------------------------------
     StageScope cc( ctx, "patches_cc" );
-    hipLaunchKernelGGL( ccInitKernel<16>, grdT, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n, d_parent.p,
+    hipLaunchKernelGGL( ccInitKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n, d_parent.p,
                         d_lab.p, d_ccCount.p );
     {
       StageScope kt( ctx, "k:ccUnion" );
-      hipLaunchKernelGGL( ccUnionKernel<16>, grdT, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n,
+      hipLaunchKernelGGL( ccUnionKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n,
                           d_parent.p, unionPrecheck( f->ctx ), agentScope );
       kt.end();
       if ( unionCheck( f->ctx ) ) {  // debug invariants (soak tests): costs a round trip
-        uint32_t bad[2] = {0, 0};
         TMC2_HIP( hipMemsetAsync( d_small.p + 8, 0, 8, s ) );
         hipLaunchKernelGGL( ccCheckKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, n,
                             d_parent.p, d_small.p + 8 );
-        TMC2_HIP( hipMemcpyAsync( bad, d_small.p + 8, 8, hipMemcpyDeviceToHost, s ) );
-        TMC2_HIP( hipStreamSynchronize( s ) );
-        if ( bad[0] | bad[1] ) {
-          setError( "segmentPatches: union-find invariant broken in round %d (%u bad links, %u split edges)", rounds, bad[0], bad[1] );
-          return TMC2_E_HIP;
-        }
+        TMC2_TRY( unionCheckResult( s, d_small.p + 8, "segmentPatches: union-find invariant broken in round " + std::to_string( rounds ) ) );
       }
       hipLaunchKernelGGL( ccFlattenSeedKernel, grdN, blk, 0, s, d_raw.p, d_dist.p, thrDet, n, d_parent.p, d_root.p, d_lab.p,
                           agentScope );
@@ -874,7 +782,7 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     for ( int guard = 0; guard < 1 << 20; ++guard ) {
       StageScope kt( ctx, "k:ccRelax" );
       for ( int b = 0; b < 3; ++b )
-        hipLaunchKernelGGL( ccRelaxKernel<16>, grdT, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p,
+        hipLaunchKernelGGL( ccRelaxKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p,
                             d_root.p, perm, chunked, n, d_lab.p, d_small.p, ++relaxToken, agentScope );
       kt.end();
       hipLaunchKernelGGL( ccLabelCountKernel, grdN, blk, 0, s, d_raw.p, d_root.p, d_lab.p, n,
