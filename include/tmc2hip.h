@@ -483,6 +483,43 @@ int tmc2_host_color_smoothing( const int16_t* xyz, uint16_t* colors16, const uin
                                uint64_t M, int gridSize, int geometryBitDepth3D, double thresholdColorSmoothing,
                                double thresholdColorDifference, double thresholdColorVariation );
 
+/* ---- the shared device primitives on their own (csrc/selftest.hip; DESIGN.md "primitives under test") ------------------- */
+/* What the stages are built on, reachable without a stage so that it can be compared with a plain loop at shapes no cloud produces.
+ * Every d_ pointer is DEVICE memory of the context's device (tmc2_ctx_device_alloc / tmc2_ctx_upload / tmc2_ctx_download); the
+ * calls are queued on the context's stream and NOT waited for.  They read the context's options as the stages do.  Not part of the
+ * drop-in boundary: the reference has no counterpart.
+ * scan: exclusiveScanU32 as the stages call it -- d_out may be d_in; d_total may be NULL; hostAnswer (page-locked: tmc2_host_alloc)
+ * may be NULL, else it receives the total and, behind it, carryWords <= 7 words of d_carry.  epoch != 0 first sets the context's
+ * scan epoch (30 bits): the wrap is 2^30 scans away otherwise.                                                          */
+int tmc2_selftest_scan( tmc2_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint64_t n, uint32_t* d_total, uint32_t* hostAnswer,
+                        const uint32_t* d_carry, int carryWords, uint64_t epoch );
+/* fill: fillRegions over regions[count][3] = (device address, bytes, byte value), a HOST array; count <= 13, of which fillRegions
+ * itself refuses the thirteenth region that is not empty.                                                                  */
+int tmc2_selftest_fill( tmc2_ctx* ctx, const uint64_t* regions, int count );
+/* work map: one lane per element on the helpers of the XCD work mapping.  d_hits[2][n] += 1 at the lane's chunkedIndex() resp.
+ * pointOfLane() element; d_logical[gridBlocks] = the logical block of each workgroup.  gridBlocks 0: chunkedGrid of the blocks n
+ * needs, as the stages size a pass.  liveBlocks != 0: the form of the k-NN kernel (a grid of a multiple of 8 blocks, the eighths
+ * are those of the live blocks, a surplus workgroup leaves and records 0xFFFFFFFF; d_hits[1] = d_hits[0]).               */
+int tmc2_selftest_work_map( tmc2_ctx* ctx, uint64_t gridBlocks, int blockThreads, uint64_t n, uint64_t liveBlocks, uint32_t* d_hits,
+                            uint32_t* d_logical );
+/* components: S7's own kernels (mutual mask, initial forest, union pass, the UF_CHECK pass if the option is set, the find of the
+ * flatten pass) on a neighbour table d_knn[n][16] (a row is padded with the point itself), planes d_partition[n], d_raw[n] (0: the
+ * point takes no part), d_perm[n] (the order MUTUAL_ORDER=tree walks; may be NULL).  d_root[u]: the root of every raw point;
+ * d_bad[2]: broken links / split edges as UF_CHECK counts them (the caller clears it).                                    */
+int tmc2_selftest_components( tmc2_ctx* ctx, const uint32_t* d_knn, const uint8_t* d_partition, const uint8_t* d_raw,
+                              const uint32_t* d_perm, uint64_t n, uint32_t* d_root, uint32_t* d_bad );
+/* union-find over an edge list: d_word[n] in: a forest whose links fall in priority (parity 0: the parent; else parent << 1 |
+ * parity), out: the settled words; d_edges[m][3] = (a, b, s: the parity of a relative to b).  One launch runs the store-free
+ * pre-check (if precheck) and the union of every edge, a second the find of every element into d_root / d_rootParity, a third the
+ * coherent climb: d_bad[0] += links that do not fall in priority or leave [0, n) and edges with an end outside it, d_bad[1] +=
+ * edges whose ends have two roots (the caller clears both).  agent: every load at agent scope.                             */
+int tmc2_selftest_union_find( tmc2_ctx* ctx, int parity, uint32_t* d_word, uint64_t n, const uint32_t* d_edges, uint64_t m, int precheck,
+                              int agent, uint32_t* d_root, uint32_t* d_rootParity, uint32_t* d_bad );
+/* CandSort::sort, one list per lane: d_lists[total][2] = (distance, payload), list l = [d_offsets[l], d_offsets[l + 1]); d_ok[l] =
+ * 0 where the depth limit was reached.  std_sort: the real std::sort( .., dist < dist ) over the same layout in HOST memory.     */
+int tmc2_selftest_cand_sort( tmc2_ctx* ctx, uint32_t* d_lists, const uint32_t* d_offsets, uint64_t lists, uint32_t* d_ok );
+int tmc2_selftest_std_sort( uint32_t* lists, const uint32_t* offsets, uint64_t count );
+
 #ifdef __cplusplus
 }
 #endif

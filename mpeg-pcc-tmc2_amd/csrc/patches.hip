@@ -967,3 +967,47 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
 }
 
 }  // namespace tmc2
+
+// S7's own kernels -- mutual mask, initial forest, union pass, the check, the find of the flatten pass -- on a neighbour table the
+// caller supplies (selftest.hip: the primitives under test), with the launch shapes and the options (MUTUAL_ORDER, UF_PRECHECK,
+// UF_SCOPE, UF_CHECK) of segmentPatches.  d_perm: the order "tree" walks (null: index order).  d_root[u] for raw points; d_bad[2] as
+// ccCheckKernel counts (left alone without UF_CHECK).  Queued, not waited for.
+extern "C" int tmc2_selftest_components( tmc2_ctx* ctx, const uint32_t* d_knn, const uint8_t* d_partition, const uint8_t* d_raw,
+                                         const uint32_t* d_perm, uint64_t n64, uint32_t* d_root, uint32_t* d_bad ) {
+  using namespace tmc2;
+  if ( !ctx || !d_knn || !d_partition || !d_raw || !d_root || !d_bad || n64 == 0 || n64 > 0x0FFFFFFFull ) {
+    setError( "selftest_components: invalid argument (null pointer, no point, or more than 2^28 - 1 points)" );
+    return TMC2_E_INVALID;
+  }
+  ApiScope         scope( ctx );
+  hipStream_t      s = ctx->stream;
+  const uint32_t   n = uint32_t( n64 );
+  DevBuf<uint16_t> d_mutual;
+  DevBuf<uint32_t> d_parent, d_lab, d_ccCount, d_dist;
+  TMC2_TRY( d_mutual.alloc( n ) );
+  TMC2_TRY( d_parent.alloc( n ) );
+  TMC2_TRY( d_lab.alloc( n ) );
+  TMC2_TRY( d_ccCount.alloc( n ) );
+  TMC2_TRY( d_dist.alloc( n ) );
+  // (a point a pass skipped must show as a wrong root, not as a link read from what the pool handed out: every link starts at 0)
+  TMC2_TRY( fillRegions( ctx, {{d_parent.p, size_t( n ) * 4, 0}, {d_mutual.p, size_t( n ) * 2, 0}, {d_dist.p, size_t( n ) * 4, 0}} ) );
+  const auto      option  = ctxOption( ctx, "MUTUAL_ORDER" );
+  const char      o       = option ? ( *option )[0] : 'c';
+  const bool      chunked = o != 'i';
+  const uint32_t* perm    = o == 't' ? d_perm : nullptr;
+  const uint32_t  blocks  = ( n + 255 ) / 256;
+  const dim3      blk( 256 ), grdN( chunkedGrid( blocks ) );
+  const bool      agentScope = unionAgentScope( ctx );
+  hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( chunked ? chunkedGrid( blocks ) : blocks ), dim3( 256 ), 0, s, d_knn, perm, chunked, n,
+                      d_mutual.p );
+  hipLaunchKernelGGL( ccInitKernel<16>, grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, perm, chunked, n, d_parent.p, d_lab.p,
+                      d_ccCount.p );
+  hipLaunchKernelGGL( ccUnionKernel<16>, grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, perm, chunked, n, d_parent.p,
+                      unionPrecheck( ctx ), agentScope );
+  if ( unionCheck( ctx ) )
+    hipLaunchKernelGGL( ccCheckKernel<16>, grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, n, d_parent.p, d_bad );
+  // (no point is a seed: no distance exceeds the threshold)
+  hipLaunchKernelGGL( ccFlattenSeedKernel, grdN, blk, 0, s, d_raw, d_dist.p, 0xFFFFFFFFu, n, d_parent.p, d_root, d_lab.p, agentScope );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}

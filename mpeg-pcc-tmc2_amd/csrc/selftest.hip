@@ -1,0 +1,215 @@
+// selftest.hip -- the shared device primitives, each reachable on its own through the C ABI (include/tmc2hip.h: tmc2_selftest_*),
+// so that the suite can compare them with a plain loop at shapes no test cloud produces: exclusiveScanU32 and fillRegions
+// (scan.hip), the XCD work mapping (internal.h), UnionFind<false / true> (union_find.h) and CandSort (cand_sort.h).  The entries
+// take DEVICE pointers and queue on the context's stream without synchronising: a test queues many calls, then reads back.
+// Nothing of the product path calls into this file.  (S7's own kernels on a caller's neighbour table: tmc2_selftest_components,
+// patches.hip -- the kernels are local to that file.)
+#include <algorithm>
+#include <utility>
+
+#include "cand_sort.h"
+#include "internal.h"
+#include "union_find.h"
+
+namespace tmc2 {
+namespace {
+
+constexpr uint32_t kNoBlock = 0xFFFFFFFFu;  // logical[b] of a surplus workgroup of the live-blocks form
+
+// One lane, one element, found with the helpers of internal.h only.  hits[0][i]: chunkedIndex() (live: knnKernel's form, perXcd
+// from the live count, surplus slots leave); hits[1][i]: pointOfLane().  logical[b]: the logical block of workgroup b.
+__global__ void workMapKernel( uint32_t n, uint32_t liveBlocks, uint32_t* __restrict__ hits, uint32_t* __restrict__ logical ) {
+  if ( liveBlocks ) {
+    const uint32_t perXcd = ( liveBlocks + 7u ) >> 3;
+    if ( xcdPlace().slot >= perXcd ) {
+      if ( threadIdx.x == 0 ) logical[blockIdx.x] = kNoBlock;
+      return;
+    }
+    const uint32_t block = chunkedBlock( perXcd ), j = block * blockDim.x + threadIdx.x;
+    if ( threadIdx.x == 0 ) logical[blockIdx.x] = block;
+    if ( j < n ) atomicAdd( &hits[j], 1u ), atomicAdd( &hits[size_t( n ) + j], 1u );
+    return;
+  }
+  const bool chunked = !( gridDim.x & 7u );
+  if ( threadIdx.x == 0 ) logical[blockIdx.x] = logicalBlock( chunked );
+  const uint32_t a = chunkedIndex(), b = pointOfLane( nullptr, chunked, n );
+  if ( a < n ) atomicAdd( &hits[a], 1u );
+  if ( b < n ) atomicAdd( &hits[size_t( n ) + b], 1u );
+}
+
+// ---- union-find over an explicit edge list (a, b, s): what a 16-NN table cannot hold (a hub of 99 999 leaves, one edge 4 096 times)
+template <bool PARITY>
+__global__ __launch_bounds__( 256 ) void ufEdgesKernel( uint32_t* word, uint32_t n, const uint32_t* __restrict__ edges, uint32_t m,
+                                                         int precheck, bool agent ) {
+  const uint32_t e = chunkedIndex();
+  if ( e >= m ) return;
+  const uint32_t a = edges[3 * size_t( e )], b = edges[3 * size_t( e ) + 1], s = edges[3 * size_t( e ) + 2] & 1u;
+  if ( a >= n || b >= n ) return;  // (counted by ufCoherentKernel)
+  if ( precheck && UnionFind<PARITY>::sameSetStale( word, a, b, agent ) ) return;
+  UnionFind<PARITY>::unite( word, a, b, s, agent );
+}
+// (the flat view goes to arrays of its own: union_find.h)
+template <bool PARITY>
+__global__ __launch_bounds__( 256 ) void ufFindKernel( uint32_t* word, uint32_t n, bool agent, uint32_t* __restrict__ root,
+                                                        uint32_t* __restrict__ rootParity ) {
+  const uint32_t x = chunkedIndex();
+  if ( x >= n ) return;
+  const UfRoot r = UnionFind<PARITY>::find( word, x, agent );
+  root[x]        = r.root;
+  rootParity[x]  = r.parity;
+}
+// bad[0]: elements whose climb meets a link that does not fall in priority or leaves [0, n), and edges with an end outside [0, n);
+// bad[1]: edges whose ends have two roots
+template <bool PARITY>
+__global__ __launch_bounds__( 256 ) void ufCoherentKernel( const uint32_t* word, uint32_t n, const uint32_t* __restrict__ edges, uint32_t m,
+                                                            uint32_t* __restrict__ bad ) {
+  const uint32_t x = chunkedIndex();
+  if ( x < n && UnionFind<PARITY>::rootCoherent( word, x, n ) == kUfBroken ) atomicAdd( &bad[0], 1u );
+  if ( x < m ) {
+    const uint32_t a = edges[3 * size_t( x )], b = edges[3 * size_t( x ) + 1];
+    if ( a >= n || b >= n ) {
+      atomicAdd( &bad[0], 1u );
+      return;
+    }
+    const uint32_t ra = UnionFind<PARITY>::rootCoherent( word, a, n ), rb = UnionFind<PARITY>::rootCoherent( word, b, n );
+    if ( ra != kUfBroken && rb != kUfBroken && ra != rb ) atomicAdd( &bad[1], 1u );
+  }
+}
+
+// ---- CandSort::sort, one list per lane, as the colour transfers run it
+__global__ __launch_bounds__( 256 ) void candSortKernel( uint2* __restrict__ lists, const uint32_t* __restrict__ offsets, uint32_t count,
+                                                          uint32_t* __restrict__ ok ) {
+  const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( l >= count ) return;
+  const CandSort cs{lists + offsets[l]};
+  ok[l] = cs.sort( int( offsets[l + 1] - offsets[l] ) ) ? 1u : 0u;
+}
+
+// fillRegions takes a braced list: one call shape per count
+template <size_t... I>
+int fillWith( tmc2_ctx* ctx, const FillRegion* r, std::index_sequence<I...> ) {
+  return fillRegions( ctx, {r[I]...} );
+}
+template <size_t N>
+int fillCount( tmc2_ctx* ctx, const FillRegion* r, size_t count ) {
+  if ( count == N ) return fillWith( ctx, r, std::make_index_sequence<N>() );
+  if constexpr ( N > 0 ) return fillCount<N - 1>( ctx, r, count );
+  return TMC2_E_INVALID;
+}
+constexpr size_t kSelftestFillMax = 13;  // one more than fillRegions takes: its refusal is reachable
+
+template <bool PARITY>
+int unionFindEdges( tmc2_ctx* ctx, uint32_t* d_word, uint32_t n, const uint32_t* d_edges, uint32_t m, int precheck, bool agent,
+                    uint32_t* d_root, uint32_t* d_rootParity, uint32_t* d_bad ) {
+  hipStream_t s = ctx->stream;
+  const dim3  blk( 256 ), grdN( chunkedGrid( ( n + 255 ) / 256 ) ), grdM( chunkedGrid( ( m + 255 ) / 256 ) ),
+      grdBoth( chunkedGrid( ( std::max( n, m ) + 255 ) / 256 ) );
+  if ( m ) hipLaunchKernelGGL( ufEdgesKernel<PARITY>, grdM, blk, 0, s, d_word, n, d_edges, m, precheck, agent );
+  hipLaunchKernelGGL( ufFindKernel<PARITY>, grdN, blk, 0, s, d_word, n, agent, d_root, d_rootParity );
+  hipLaunchKernelGGL( ufCoherentKernel<PARITY>, grdBoth, blk, 0, s, d_word, n, d_edges, m, d_bad );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+}  // namespace
+}  // namespace tmc2
+
+extern "C" {
+
+int tmc2_selftest_scan( tmc2_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint64_t n, uint32_t* d_total, uint32_t* hostAnswer,
+                        const uint32_t* d_carry, int carryWords, uint64_t epoch ) {
+  using namespace tmc2;
+  if ( !ctx || ( n && ( !d_in || !d_out ) ) || carryWords < 0 || carryWords > 7 || ( carryWords && ( !hostAnswer || !d_carry ) ) ||
+       epoch > 0x3FFFFFFFull ) {
+    setError( "selftest_scan: invalid argument (null pointer, more than 7 carry words, carry words without an answer line, or an epoch beyond 30 bits)" );
+    return TMC2_E_INVALID;
+  }
+  ApiScope scope( ctx );
+  if ( epoch ) ctx->scanEpoch = uint32_t( epoch );  // the one back door: the wrap is 2^30 scans away otherwise
+  return exclusiveScanU32( ctx, d_in, d_out, size_t( n ), d_total, ScanAnswer{hostAnswer, d_carry, carryWords} );
+}
+
+int tmc2_selftest_fill( tmc2_ctx* ctx, const uint64_t* regions, int count ) {
+  using namespace tmc2;
+  if ( !ctx || count < 0 || count > int( kSelftestFillMax ) || ( count && !regions ) ) {
+    setError( "selftest_fill: invalid argument (null pointer or more than %d regions)", int( kSelftestFillMax ) );
+    return TMC2_E_INVALID;
+  }
+  FillRegion r[kSelftestFillMax] = {};
+  for ( int k = 0; k < count; ++k ) {
+    if ( regions[3 * k + 1] && !regions[3 * k] ) {
+      setError( "selftest_fill: region %d has bytes and no address", k );
+      return TMC2_E_INVALID;
+    }
+    r[k] = FillRegion{reinterpret_cast<void*>( uintptr_t( regions[3 * k] ) ), size_t( regions[3 * k + 1] ), uint8_t( regions[3 * k + 2] )};
+  }
+  ApiScope scope( ctx );
+  return fillCount<kSelftestFillMax>( ctx, r, size_t( count ) );
+}
+
+int tmc2_selftest_work_map( tmc2_ctx* ctx, uint64_t gridBlocks, int blockThreads, uint64_t n, uint64_t liveBlocks, uint32_t* d_hits,
+                            uint32_t* d_logical ) {
+  using namespace tmc2;
+  if ( !ctx || !d_hits || !d_logical || blockThreads < 1 || blockThreads > 1024 || n > 0x7FFFFFFFull || gridBlocks > ( 1u << 20 ) ) {
+    setError( "selftest_work_map: invalid argument (null pointer, 1 .. 1024 threads, at most 2^20 blocks and 2^31 - 1 elements)" );
+    return TMC2_E_INVALID;
+  }
+  // no grid given: the grid a stage gives a chunked pass over n elements
+  const uint32_t grid = gridBlocks ? uint32_t( gridBlocks ) : chunkedGrid( uint32_t( ( n + uint64_t( blockThreads ) - 1 ) / uint64_t( blockThreads ) ) );
+  if ( grid == 0 || ( liveBlocks && ( ( grid & 7u ) || liveBlocks > grid ) ) ) {
+    setError( "selftest_work_map: an empty grid, or live blocks on a grid that is no multiple of 8 or smaller than their number" );
+    return TMC2_E_INVALID;
+  }
+  ApiScope scope( ctx );
+  hipLaunchKernelGGL( workMapKernel, dim3( grid ), dim3( uint32_t( blockThreads ) ), 0, ctx->stream, uint32_t( n ), uint32_t( liveBlocks ), d_hits,
+                      d_logical );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+int tmc2_selftest_union_find( tmc2_ctx* ctx, int parity, uint32_t* d_word, uint64_t n, const uint32_t* d_edges, uint64_t m, int precheck,
+                              int agent, uint32_t* d_root, uint32_t* d_rootParity, uint32_t* d_bad ) {
+  using namespace tmc2;
+  if ( !ctx || !d_word || !d_root || !d_rootParity || !d_bad || n == 0 || n > 0x7FFFFFFFull || m > 0x7FFFFFFFull || ( m && !d_edges ) ) {
+    setError( "selftest_union_find: invalid argument (null pointer, no element, or more than 2^31 - 1 elements or edges)" );
+    return TMC2_E_INVALID;
+  }
+  ApiScope scope( ctx );
+  return parity ? unionFindEdges<true>( ctx, d_word, uint32_t( n ), d_edges, uint32_t( m ), precheck, agent != 0, d_root, d_rootParity, d_bad )
+                : unionFindEdges<false>( ctx, d_word, uint32_t( n ), d_edges, uint32_t( m ), precheck, agent != 0, d_root, d_rootParity, d_bad );
+}
+
+int tmc2_selftest_cand_sort( tmc2_ctx* ctx, uint32_t* d_lists, const uint32_t* d_offsets, uint64_t lists, uint32_t* d_ok ) {
+  using namespace tmc2;
+  if ( !ctx || !d_lists || !d_offsets || !d_ok || lists == 0 || lists > 0x7FFFFFFFull ) {
+    setError( "selftest_cand_sort: invalid argument (null pointer, no list, or more than 2^31 - 1 lists)" );
+    return TMC2_E_INVALID;
+  }
+  ApiScope scope( ctx );
+  hipLaunchKernelGGL( candSortKernel, dim3( uint32_t( ( lists + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<uint2*>( d_lists ),
+                      d_offsets, uint32_t( lists ), d_ok );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+// the host twin: the real std::sort with the reference's comparator, on host memory
+int tmc2_selftest_std_sort( uint32_t* lists, const uint32_t* offsets, uint64_t count ) {
+  if ( !lists || !offsets ) {
+    tmc2::setError( "selftest_std_sort: invalid argument" );
+    return TMC2_E_INVALID;
+  }
+  struct Cand {
+    uint32_t dist, index;
+  };
+  Cand* c = reinterpret_cast<Cand*>( lists );
+  for ( uint64_t l = 0; l < count; ++l ) {
+    if ( offsets[l + 1] < offsets[l] ) {
+      tmc2::setError( "selftest_std_sort: offsets fall at list %llu", static_cast<unsigned long long>( l ) );
+      return TMC2_E_INVALID;
+    }
+    std::sort( c + offsets[l], c + offsets[l + 1], []( const Cand& a, const Cand& b ) { return a.dist < b.dist; } );
+  }
+  return TMC2_OK;
+}
+
+}  // extern "C"

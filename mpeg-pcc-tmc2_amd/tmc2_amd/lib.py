@@ -244,6 +244,30 @@ class Context:
         _check(self.L.tmc2_ctx_download(self.h, _ptr(array), device_ptr, array.nbytes))
         return array
 
+
+    # The shared device primitives on their own (include/tmc2hip.h: tmc2_selftest_*; csrc/selftest.hip).  Device pointers in
+    # (device_alloc / upload / download), queued on the context's stream, not waited for.
+    def selftest_scan(self, d_in, d_out, n, d_total=None, host_answer=None, d_carry=None, carry_words=0, epoch=0):
+        _check(self.L.tmc2_selftest_scan(self.h, d_in, d_out, int(n), d_total, host_answer, d_carry, int(carry_words), int(epoch)))
+
+    def selftest_fill(self, regions):
+        """regions: (device address, bytes, byte value) each"""
+        r = np.ascontiguousarray([[int(getattr(p, "value", p) or 0), int(b), int(v)] for p, b, v in regions], dtype=np.uint64).reshape(-1, 3)
+        _check(self.L.tmc2_selftest_fill(self.h, _ptr(r) if len(r) else None, len(r)))
+
+    def selftest_work_map(self, grid_blocks, block_threads, n, live_blocks, d_hits, d_logical):
+        _check(self.L.tmc2_selftest_work_map(self.h, int(grid_blocks), int(block_threads), int(n), int(live_blocks), d_hits, d_logical))
+
+    def selftest_components(self, d_knn, d_partition, d_raw, d_perm, n, d_root, d_bad):
+        _check(self.L.tmc2_selftest_components(self.h, d_knn, d_partition, d_raw, d_perm, int(n), d_root, d_bad))
+
+    def selftest_union_find(self, parity, d_word, n, d_edges, m, precheck, agent, d_root, d_root_parity, d_bad):
+        _check(self.L.tmc2_selftest_union_find(self.h, int(parity), d_word, int(n), d_edges, int(m), int(precheck), int(agent), d_root,
+                                               d_root_parity, d_bad))
+
+    def selftest_cand_sort(self, d_lists, d_offsets, lists, d_ok):
+        _check(self.L.tmc2_selftest_cand_sort(self.h, d_lists, d_offsets, int(lists), d_ok))
+
     def stream(self):
         return self.L.tmc2_ctx_stream(self.h)
 
@@ -938,6 +962,17 @@ def host_color_smoothing(xyz, colors16, boundary, patch_index, grid_size, bits3d
     return a[1]
 
 
+def selftest_std_sort(pairs, offsets):
+    """tmc2_selftest_std_sort: the real std::sort( .., dist < dist ) on every list of pairs [total][2] = (distance, payload), list l
+    = [offsets[l], offsets[l + 1]); returns the sorted copy (host only)."""
+    out = np.ascontiguousarray(pairs, dtype=np.uint32).copy()
+    off = np.ascontiguousarray(offsets, dtype=np.uint32)
+    if out.ndim != 2 or out.shape[1] != 2 or len(off) < 1 or int(off[-1]) != len(out) or (np.diff(off.astype(np.int64)) < 0).any():
+        raise Tmc2Error("selftest_std_sort: pairs [total][2] and rising offsets that end at total expected")
+    _check(load_library().tmc2_selftest_std_sort(_ptr(out), _ptr(off), len(off) - 1))
+    return out
+
+
 # ---- the prototypes of include/tmc2hip.h (declare, above) ---------------------------------------------
 TMC2HIP = """
 int tmc2_ctx_create(int, tmc2_ctx**)
@@ -1047,4 +1082,11 @@ int tmc2_host_pack_spatial_consistency(tmc2_patch*, int, const uint8_t*, const t
 int tmc2_host_place_segments(int, const int32_t*, tmc2_patch*, const uint8_t*, const int64_t*, int, int, int, int, double, int32_t*, uint8_t*, int64_t, int64_t*, int32_t*, int32_t*)
 int tmc2_host_orient_normals(const int16_t*, uint64_t, const uint32_t*, int, double*)
 int tmc2_host_color_smoothing(const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
+int tmc2_selftest_scan(tmc2_ctx*, const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, const uint32_t*, int, uint64_t)
+int tmc2_selftest_fill(tmc2_ctx*, const uint64_t*, int)
+int tmc2_selftest_work_map(tmc2_ctx*, uint64_t, int, uint64_t, uint64_t, uint32_t*, uint32_t*)
+int tmc2_selftest_components(tmc2_ctx*, const uint32_t*, const uint8_t*, const uint8_t*, const uint32_t*, uint64_t, uint32_t*, uint32_t*)
+int tmc2_selftest_union_find(tmc2_ctx*, int, uint32_t*, uint64_t, const uint32_t*, uint64_t, int, int, uint32_t*, uint32_t*, uint32_t*)
+int tmc2_selftest_cand_sort(tmc2_ctx*, uint32_t*, const uint32_t*, uint64_t, uint32_t*)
+int tmc2_selftest_std_sort(uint32_t*, const uint32_t*, uint64_t)
 """.strip().split("\n")

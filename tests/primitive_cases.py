@@ -1,0 +1,350 @@
+"""Inputs and plain references for the shared device primitives (tmc2_selftest_*: csrc/selftest.hip): the exclusive scan, the
+several-regions fill, the XCD work mapping, the two union-finds (S7's kernels over a 16-neighbour table; explicit edge lists, with
+and without parity) and CandSort.  numpy only.  tests/test_primitive_cases.py checks the references themselves (every graph family
+has a component count known in closed form); tests/test_gpu_primitives.py compares the device with them, integer for integer."""
+import functools
+
+import numpy as np
+
+K = 16                                  # neighbours per row of S7's table
+UF_MULTIPLIER = 2654435761              # ufPriority (csrc/union_find.h): x * 2654435761 mod 2^32, a bijection
+
+
+# ---- scan ---------------------------------------------------------------------------------------------------------------
+SCAN_SIZES = (0, 1, 7, 8, 9, 2047, 2048, 2049, 4096, 131072, 131073, 133121, 264197, 1000003)
+SCAN_PATTERNS = ("zero", "one", "flags", "counts", "first", "last", "max")
+
+
+def scan_input(pattern, n, seed=0):
+    rng = np.random.default_rng([seed, n, SCAN_PATTERNS.index(pattern)])
+    if pattern == "zero":
+        return np.zeros(n, np.uint32)
+    if pattern == "one":
+        return np.ones(n, np.uint32)
+    if pattern == "flags":
+        return rng.integers(0, 2, n, dtype=np.uint32)
+    if pattern == "counts":
+        return rng.integers(0, 1 << 16, n, dtype=np.uint32)
+    if pattern == "max":                                        # the sums wrap modulo 2^32, as the reference's do
+        return np.full(n, 0xFFFFFFFF, np.uint32)
+    a = np.zeros(n, np.uint32)
+    if n:
+        a[0 if pattern == "first" else n - 1] = 0x89ABCDEF
+    return a
+
+
+def scan_reference(a):
+    """(exclusive prefix sums, total) of uint32 modulo 2^32: np.cumsum in uint32, shifted by one"""
+    a = np.asarray(a, np.uint32)
+    inc = np.cumsum(a, dtype=np.uint32)
+    out = np.zeros(len(a), np.uint32)
+    out[1:] = inc[:-1]
+    return out, np.uint32(inc[-1] if len(a) else 0)
+
+
+# ---- fill ---------------------------------------------------------------------------------------------------------------
+FILL_GUARD = 0xA5
+FILL_LENGTHS = tuple(range(41)) + (16383, 16384, 16385, 32769, 100003)
+
+
+def fill_layout(gap=80):
+    """Every head offset 0..15 x every length, laid out in ONE buffer of guard bytes: [(start, length, value)], total bytes.  A
+    region starts `head` bytes into a 16-byte line; at least `gap` guard bytes lie between two regions."""
+    regions, at = [], 256
+    for head in range(16):
+        for i, length in enumerate(FILL_LENGTHS):
+            at = (at + 15) // 16 * 16 + head
+            value = 1 + 37 * len(regions) % 251                # (any twelve regions in a row: twelve values)
+            if value == FILL_GUARD:
+                value = 252
+            regions.append((at, length, value))
+            at += length + gap
+    return regions, at + 256
+
+
+def fill_reference(total, regions):
+    buf = np.full(total, FILL_GUARD, np.uint8)
+    for start, length, value in regions:
+        buf[start:start + length] = value
+    return buf
+
+
+# ---- work map -----------------------------------------------------------------------------------------------------------
+WORK_GRIDS = tuple(range(8, 65, 8)) + (1024,)
+WORK_GRIDS_UNCHUNKED = (1, 7, 9, 1001)
+
+
+def work_sizes(grid, threads):
+    """n: a full grid, one short of it, one past the last full block of an eighth, 1, 0"""
+    full = grid * threads
+    eighth = max(grid // 8, 1) * threads
+    return sorted({full, full - 1, min(full, eighth + 1), 1, 0})
+
+
+def work_map_reference(grid, live=0):
+    """logical block of every workgroup (0xFFFFFFFF: a surplus block of the live form leaves)"""
+    b = np.arange(grid, dtype=np.int64)
+    if live:
+        per = (live + 7) // 8
+        lg = (b % 8) * per + b // 8
+        return np.where(b // 8 < per, lg, 0xFFFFFFFF).astype(np.uint32)
+    if grid % 8:
+        return b.astype(np.uint32)
+    return ((b % 8) * (grid // 8) + b // 8).astype(np.uint32)
+
+
+# ---- union-find references ----------------------------------------------------------------------------------------------
+def uf_priority(x):
+    return ((np.asarray(x, np.uint64) * UF_MULTIPLIER) & 0xFFFFFFFF).astype(np.uint32)
+
+
+def components(n, a, b):
+    """label[u] = the smallest member of u's component under the undirected edges (a[i], b[i]): a sequential union-find, path
+    halving, the smaller root wins"""
+    parent = list(range(n))
+    for u, v in zip(np.asarray(a).tolist(), np.asarray(b).tolist()):
+        while parent[u] != u:
+            parent[u] = parent[parent[u]]
+            u = parent[u]
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        if u < v:
+            parent[v] = u
+        elif v < u:
+            parent[u] = v
+    label = np.empty(n, np.int64)
+    for u in range(n):                   # parents have smaller indices: one pass in index order settles everything
+        label[u] = u if parent[u] == u else label[parent[u]]
+    return label
+
+
+def components_by_sweeps(n, a, b):
+    """the same labels by another road (min-label propagation to the fixpoint, with pointer jumping): checks `components`"""
+    a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    label = np.arange(n, dtype=np.int64)
+    while True:
+        new = label.copy()
+        np.minimum.at(new, a, label[b])
+        np.minimum.at(new, b, label[a])
+        new = new[new]
+        if np.array_equal(new, label):
+            return label
+        label = new
+
+
+def same_partition(label, root, members=None):
+    """root (the device's) and label (the reference's, smallest member) describe ONE partition of `members`: root is constant on
+    every component, and the root of u lies in u's component -- so two elements share a root exactly when they share a label"""
+    label, root = np.asarray(label, np.int64), np.asarray(root, np.int64)
+    m = np.arange(len(label)) if members is None else np.asarray(members)
+    if len(m) == 0:
+        return True
+    r = root[m]
+    if r.min() < 0 or r.max() >= len(label):
+        return False
+    return bool(np.array_equal(root[label[m]], r) and np.array_equal(label[r], label[m]))
+
+
+# ---- S7's kernels: 16-neighbour tables ------------------------------------------------------------------------------------
+GRAPH_FAMILIES = ("path", "path_perm", "tree16", "grid", "groups", "twice", "one_way", "two_paths")
+
+
+def _table(n, columns):
+    """rows padded with the point itself (which the mask kernel skips); a column entry < 0 or >= n is 'no neighbour'"""
+    t = np.tile(np.arange(n, dtype=np.int64)[:, None], (1, K))
+    for j, c in enumerate(columns):
+        c = np.asarray(c, np.int64)
+        ok = (c >= 0) & (c < n)
+        t[ok, j] = c[ok]
+    return t.astype(np.uint32)
+
+
+def graph_table(family, n, seed=0):
+    """(knn [n][16], the number of components it has while every point is raw and of one plane)"""
+    i = np.arange(n, dtype=np.int64)
+    if family == "path":
+        return _table(n, [i - 1, i + 1]), 1
+    if family == "path_perm":
+        p = np.random.default_rng([seed, n, 1]).permutation(n)
+        before, after = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+        before[p[1:]], after[p[:-1]] = p[:-1], p[1:]
+        return _table(n, [before, after]), 1
+    if family == "tree16":                                       # parent + 15 children: the row is full
+        cols = [np.where(i > 0, (i - 1) // 15, -1)] + [15 * i + 1 + c for c in range(15)]
+        return _table(n, cols), 1
+    if family == "grid":
+        w = int(np.ceil(np.sqrt(n)))
+        return _table(n, [np.where(i % w > 0, i - 1, -1), np.where(i % w < w - 1, i + 1, -1), i - w, i + w]), 1
+    if family == "groups":                                       # of every six points: a pair, a triple (a path), an isolated one
+        r, base = i % 6, i - i % 6
+        c0 = np.select([r == 0, r == 1, r == 2, r == 3, r == 4], [base + 1, base, base + 3, base + 2, base + 3], -1)
+        c1 = np.where(r == 3, base + 4, -1)
+        full, rest = divmod(n, 6)
+        # the last, cut group: 1 point: itself; 2: the pair; 3: pair + a lone triple head; 4, 5: pair + (part of) the triple
+        return _table(n, [c0, c1]), 3 * full + (0, 1, 1, 2, 2, 2)[rest]
+    if family == "twice":                                        # a path whose rows list the next point twice
+        return _table(n, [i + 1, i - 1, i + 1]), 1
+    if family == "one_way":                                      # i lists i + 1, which does not list i: joins nothing
+        return _table(n, [i + 1, i + 2, i + 3]), n
+    if family == "two_paths":                                    # 0 .. h-1 and h .. n-1, joined by the edge (h-1, n-1) at the last index
+        h = n // 2
+        a = np.where((i > 0) & (i != h), i - 1, -1)
+        b = np.where((i + 1 < n) & (i + 1 != h), i + 1, -1)
+        c = np.select([i == h - 1, i == n - 1], [n - 1, h - 1], -1)
+        return _table(n, [a, b, c]), 1
+    raise ValueError(family)
+
+
+def graph_cuts(n, seed):
+    """random raw = 0 holes (one point in eight) and three planes that cut edges"""
+    rng = np.random.default_rng([seed, n, 2])
+    return (rng.random(n) >= 0.125).astype(np.uint8), rng.integers(0, 3, n).astype(np.uint8)
+
+
+def eligible_edges(knn, raw, partition):
+    """the edges S7 unites: u != v, each in the other's row, both raw, one plane; each once (u > v)"""
+    knn = np.asarray(knn, np.int64)
+    n = len(knn)
+    u = np.repeat(np.arange(n), K)
+    v = knn.reshape(-1)
+    listed = np.zeros(len(u), bool)
+    for j in range(K):                                           # is u in row v?
+        listed |= knn[v, j] == u
+    keep = listed & (u > v) & (raw[u] != 0) & (raw[v] != 0) & (partition[u] == partition[v])
+    return u[keep], v[keep]
+
+
+@functools.lru_cache(maxsize=None)
+def graph_case(family, n, cut, seed=0):
+    """(knn, partition, raw, labels of the reference, component count among the raw points); cached: computed once per session"""
+    knn, count = graph_table(family, n, seed)
+    raw, partition = graph_cuts(n, seed) if cut else (np.ones(n, np.uint8), np.zeros(n, np.uint8))
+    a, b = eligible_edges(knn, raw, partition)
+    label = components(n, a, b)
+    for x in (knn, raw, partition, label):
+        x.setflags(write=False)
+    members = np.flatnonzero(raw)
+    return knn, partition, raw, label, len(np.unique(label[members]))
+
+
+# ---- edge lists for UnionFind<false / true> -------------------------------------------------------------------------------
+UF_N = 100000
+EDGE_FAMILIES = ("star", "repeated", "loops", "path", "path_priority", "random", "cliques")
+
+
+def edge_list(family, n=UF_N, seed=0):
+    """(a, b, component count from the identity forest or None where no closed form exists)"""
+    rng = np.random.default_rng([seed, n, 3, EDGE_FAMILIES.index(family)])
+    i = np.arange(n, dtype=np.int64)
+    if family == "star":                                         # n - 1 leaves on one hub
+        hub = n // 3
+        leaves = i[i != hub]
+        return leaves, np.full(n - 1, hub), 1
+    if family == "repeated":                                     # one edge 4 096 times
+        return np.full(4096, 5), np.full(4096, n - 7), n - 1
+    if family == "loops":
+        return i, i, n
+    if family == "path":
+        return i[:-1], i[1:], 1
+    if family == "path_priority":                                # neighbours in priority: every hook races with the next
+        o = np.argsort(uf_priority(i), kind="stable")
+        return o[:-1], o[1:], 1
+    if family == "random":
+        return rng.integers(0, n, 2 * n), rng.integers(0, n, 2 * n), None
+    if family == "cliques":                                      # 1 000 cliques of 20 random members each
+        members = rng.permutation(n)[:20000].reshape(1000, 20)
+        ia, ib = np.triu_indices(20, 1)
+        return members[:, ia].reshape(-1), members[:, ib].reshape(-1), n - 1000 * 19
+    raise ValueError(family)
+
+
+def hidden_signs(n=UF_N, seed=0):
+    return np.random.default_rng([seed, n, 4]).integers(0, 2, n).astype(np.uint32)
+
+
+def initial_forest(kind, n=UF_N, seed=0, sign=None):
+    """(parent, parity-to-parent): 'identity', or 'hooked': every element under a random element at most 8 indices away if that one
+    has the smaller priority (the header's rule: links fall in priority), with the true parity sign[x] ^ sign[parent]"""
+    i = np.arange(n, dtype=np.int64)
+    if kind == "identity":
+        return i.copy(), np.zeros(n, np.uint32)
+    rng = np.random.default_rng([seed, n, 5])
+    other = np.clip(i + rng.integers(-8, 9, n), 0, n - 1)
+    prio = uf_priority(i)
+    parent = np.where(prio[other] < prio, other, i)
+    sign = np.zeros(n, np.uint32) if sign is None else sign
+    return parent, (sign ^ sign[parent]).astype(np.uint32)
+
+
+def forest_words(parent, parity, with_parity):
+    return ((parent << 1) | parity).astype(np.uint32) if with_parity else parent.astype(np.uint32)
+
+
+def word_parents(words, with_parity):
+    return (np.asarray(words, np.int64) >> 1) if with_parity else np.asarray(words, np.int64)
+
+
+def links_fall_in_priority(parent):
+    """every link goes to the element itself (a root) or to one of smaller priority"""
+    parent = np.asarray(parent, np.int64)
+    i = np.arange(len(parent))
+    if parent.min() < 0 or parent.max() >= len(parent):
+        return False
+    return bool(np.all((parent == i) | (uf_priority(parent) < uf_priority(i))))
+
+
+def parity_consistent(root, root_parity, sign):
+    """per component, root_parity[u] ^ sign[u] is one value: that of the root itself, whose parity to itself is 0"""
+    root = np.asarray(root, np.int64)
+    return bool(np.all(root_parity[root] == 0) and np.array_equal(root_parity ^ sign, sign[root]))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(family, forest, seed=0):
+    """(a, b, hidden sign, parent0, parity0 under that sign, labels of the reference over edges + forest links)"""
+    a, b, _ = edge_list(family, UF_N, seed)
+    sign = hidden_signs(UF_N, seed)
+    parent, parity = initial_forest(forest, UF_N, seed, sign)
+    label = components(UF_N, np.concatenate([a, np.arange(UF_N)]), np.concatenate([b, parent]))
+    for x in (a, b, sign, parent, parity, label):
+        x.setflags(write=False)
+    return a, b, sign, parent, parity, label
+
+
+# ---- CandSort -----------------------------------------------------------------------------------------------------------
+SORT_LENGTHS = tuple(range(18)) + (31, 32, 33, 100)
+SORT_KEYS = ("1", "2", "3", "50", "sorted", "reversed", "organ_pipe")
+SORT_LONG_KEYS = SORT_KEYS[:-1]
+
+
+def sort_keys(kind, length, rng):
+    if kind in ("1", "2", "3", "50"):
+        return rng.integers(0, int(kind), length).astype(np.uint32) * 977 + 3
+    up = np.sort(rng.integers(0, max(length // 2, 1), length)).astype(np.uint32)      # (ties within the run, too)
+    if kind == "sorted":
+        return up
+    if kind == "reversed":
+        return up[::-1].copy()
+    return np.concatenate([up[0::2], up[1::2][::-1]])                                 # rises, then falls
+
+
+def sort_lists(count=20000, seed=0):
+    """(pairs [total][2] = (key, position in its list), offsets [count + 1]): lengths 0..17, 31..33, 100 in turn, the last lists of
+    1 000 and 5 000 elements; every key pattern at every length"""
+    rng = np.random.default_rng([seed, count, 6])
+    lengths = [SORT_LENGTHS[l % len(SORT_LENGTHS)] for l in range(count)]
+    kinds = [SORT_KEYS[(l // len(SORT_LENGTHS)) % len(SORT_KEYS)] for l in range(count)]
+    # the long ones: each pattern at 1 000 and at 5 000 -- but the organ pipe, which drives libstdc++'s median of three into its
+    # depth limit from 1 000 elements on (std::sort turns to heapsort there, which CandSort does not replay: it reports it)
+    for t, kind in enumerate(SORT_LONG_KEYS):
+        lengths[count - 1 - t], kinds[count - 1 - t] = 1000, kind
+        lengths[count - 1 - len(SORT_LONG_KEYS) - t], kinds[count - 1 - len(SORT_LONG_KEYS) - t] = 5000, kind
+    offsets = np.zeros(count + 1, np.uint32)
+    offsets[1:] = np.cumsum(lengths)
+    pairs = np.zeros((int(offsets[-1]), 2), np.uint32)
+    for l in range(count):
+        lo, hi = int(offsets[l]), int(offsets[l + 1])
+        pairs[lo:hi, 0] = sort_keys(kinds[l], hi - lo, rng)
+        pairs[lo:hi, 1] = np.arange(hi - lo)
+    return pairs, offsets

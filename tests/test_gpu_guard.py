@@ -87,6 +87,49 @@ def test_gpu_guard_whole_path(gpu_ctx, oracle, guard, name, tmp_path):
             gx, gc, _ = T.ply_read(path, threads=threads)
             assert np.array_equal(gx, xyz) and np.array_equal(gc, rgb)
     T.point_set_checksum(xyz, rgb)
+    _selftest_entries_once(gpu_ctx)
+
+
+def _selftest_entries_once(ctx):
+    """one call of every tmc2_selftest_* entry: their host arrays (uploads, read-backs, the fill's region table, the lists of the
+    std::sort twin) travel between red zones like every other"""
+    import primitive_cases as pc
+    n, held = 300, []
+
+    def put(a):
+        a = np.ascontiguousarray(a)
+        held.append(ctx.device_alloc(max(a.nbytes, 1)))
+        ctx.upload(held[-1], a)
+        return held[-1]
+
+    def get(p, shape, dtype):
+        return ctx.download(np.empty(shape, dtype), p)
+
+    a = pc.scan_input("counts", 2049)
+    d_a, d_total = put(a), put(np.zeros(1, np.uint32))
+    ctx.selftest_scan(d_a, d_a, len(a), d_total)
+    assert np.array_equal(get(d_a, a.shape, np.uint32), pc.scan_reference(a)[0])
+    d_fill = put(np.full(64, pc.FILL_GUARD, np.uint8))
+    ctx.selftest_fill([(d_fill.value + 3, 17, 7), (d_fill.value + 40, 0, 9)])
+    assert np.array_equal(get(d_fill, (64,), np.uint8), pc.fill_reference(64, [(3, 17, 7)]))
+    d_hits, d_logical = put(np.zeros(2 * n, np.uint32)), put(np.zeros(8, np.uint32))
+    ctx.selftest_work_map(8, 64, n, 0, d_hits, d_logical)
+    assert (get(d_hits, (2, n), np.uint32) == 1).all() and np.array_equal(get(d_logical, (8,), np.uint32), pc.work_map_reference(8))
+    knn, partition, raw, label, _ = pc.graph_case("grid", n, True)
+    d_root, d_bad = put(np.full(n, 0xFFFFFFFF, np.uint32)), put(np.zeros(2, np.uint32))
+    ctx.selftest_components(put(knn), put(partition), put(raw), None, n, d_root, d_bad)
+    assert pc.same_partition(label, get(d_root, (n,), np.uint32), np.flatnonzero(raw))
+    edges = np.stack([np.arange(n - 1), np.arange(1, n), np.zeros(n - 1)], axis=1).astype(np.uint32)
+    d_rp = put(np.zeros(n, np.uint32))
+    ctx.selftest_union_find(1, put(np.arange(n, dtype=np.uint32) << 1), n, put(edges), len(edges), 1, 0, d_root, d_rp, d_bad)
+    assert len(np.unique(get(d_root, (n,), np.uint32))) == 1 and not get(d_rp, (n,), np.uint32).any()
+    assert get(d_bad, (2,), np.uint32).tolist() == [0, 0]
+    pairs, offsets = pc.sort_lists(200)
+    d_pairs, d_ok = put(pairs), put(np.zeros(200, np.uint32))
+    ctx.selftest_cand_sort(d_pairs, put(offsets), 200, d_ok)
+    assert np.array_equal(get(d_pairs, pairs.shape, np.uint32), lib.selftest_std_sort(pairs, offsets)) and get(d_ok, (200,), np.uint32).all()
+    for p in held:
+        ctx.device_free(p)
 
 
 @pytest.mark.gpu

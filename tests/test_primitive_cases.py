@@ -1,0 +1,168 @@
+"""CPU tier: the references of tests/primitive_cases.py checked on their own -- every graph family has a component count known in
+closed form, every reference is compared with a second, differently built one -- and the argument checks of the tmc2_selftest_*
+entries that need no device."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import primitive_cases as pc
+import tmc2_amd as T
+from tmc2_amd import lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_scan_reference_is_the_loop():
+    for pattern in pc.SCAN_PATTERNS:
+        for n in (0, 1, 9, 2049):
+            a = pc.scan_input(pattern, n)
+            out, total = pc.scan_reference(a)
+            run, want = 0, []
+            for v in a.tolist():
+                want.append(run)
+                run = (run + v) & 0xFFFFFFFF
+            assert out.dtype == np.uint32 and out.tolist() == want and int(total) == run, (pattern, n)
+    assert int(pc.scan_reference(pc.scan_input("max", 5))[1]) == 0xFFFFFFFB          # wraps modulo 2^32
+    assert len(set(pc.SCAN_SIZES)) == 14 and 131073 in pc.SCAN_SIZES
+
+
+def test_fill_layout_covers_every_head_and_length_apart():
+    regions, total = pc.fill_layout()
+    assert len(regions) == 16 * len(pc.FILL_LENGTHS) and len(pc.FILL_LENGTHS) == 46
+    assert {(s % 16, l) for s, l, _ in regions} == {(h, l) for h in range(16) for l in pc.FILL_LENGTHS}
+    assert all(v not in (0, pc.FILL_GUARD) for _, _, v in regions)
+    ends = [s + l for s, l, _ in regions]
+    assert all(s2 - e1 >= 64 for e1, (s2, _, _) in zip(ends, regions[1:])) and regions[0][0] >= 64 and total - ends[-1] >= 64
+    ref = pc.fill_reference(total, regions)
+    assert int((ref != pc.FILL_GUARD).sum()) == sum(l for _, l, _ in regions)
+
+
+def test_work_map_reference_is_a_permutation_in_eighths():
+    for grid in pc.WORK_GRIDS:
+        lg = pc.work_map_reference(grid)
+        assert sorted(lg.tolist()) == list(range(grid))
+        per = grid // 8
+        for b in range(grid):                                     # XCD x = b % 8 holds the x-th eighth
+            assert per * (b % 8) <= lg[b] < per * (b % 8 + 1)
+        for live in (1, 8, 9, grid - 1):
+            if live < 1 or live > grid:                           # (the entry refuses more live blocks than the grid has)
+                continue
+            lv = pc.work_map_reference(grid, live)
+            acting = sorted(int(x) for x in lv if x != 0xFFFFFFFF)
+            assert acting == list(range((live + 7) // 8 * 8)), (grid, live)
+    for grid in pc.WORK_GRIDS_UNCHUNKED:
+        assert pc.work_map_reference(grid).tolist() == list(range(grid))
+    assert pc.work_sizes(16, 64) == [0, 1, 129, 1023, 1024]
+
+
+def test_priority_is_the_headers_bijection():
+    x = np.arange(1 << 16)
+    p = pc.uf_priority(x)
+    assert p.dtype == np.uint32 and len(np.unique(p)) == len(x)
+    assert [int(v) for v in pc.uf_priority([0, 1, 2, 3])] == [0, 2654435761, (2 * 2654435761) % 2**32, (3 * 2654435761) % 2**32]
+    hdr = open(os.path.join(ROOT, "mpeg-pcc-tmc2_amd", "csrc", "union_find.h")).read()
+    assert re.search(r"ufPriority\( uint32_t x \) \{ return x \* (\d+)u; \}", hdr).group(1) == str(pc.UF_MULTIPLIER)
+
+
+@pytest.mark.parametrize("n", [300, 4099])
+@pytest.mark.parametrize("family", pc.GRAPH_FAMILIES)
+def test_graph_families_have_their_closed_form_count(family, n):
+    knn, count = pc.graph_table(family, n)
+    assert knn.shape == (n, pc.K) and knn.dtype == np.uint32 and knn.max() < n
+    ones, zeros = np.ones(n, np.uint8), np.zeros(n, np.uint8)
+    a, b = pc.eligible_edges(knn, ones, zeros)
+    label = pc.components(n, a, b)
+    assert len(np.unique(label)) == count
+    assert np.array_equal(label, pc.components_by_sweeps(n, a, b))
+    assert np.array_equal(label[label], label) and (label <= np.arange(n)).all()
+    if family == "one_way":
+        assert len(a) == 0
+    if family == "twice":
+        assert (knn[:-1, 0] == knn[:-1, 2]).all()                # a neighbour listed twice in a row
+    # cut by holes and planes: the two references agree, and no component crosses a plane or holds a hole
+    _, partition, raw, cut_label, comps = pc.graph_case(family, n, True)
+    ca, cb = pc.eligible_edges(knn, raw, partition)
+    assert np.array_equal(cut_label, pc.components_by_sweeps(n, ca, cb))
+    assert (partition[cut_label] == partition).all() and (cut_label[raw == 0] == np.flatnonzero(raw == 0)).all()
+    assert comps >= min(count, int(raw.sum())) and 0 < (raw == 0).sum() < n // 4
+    assert pc.same_partition(cut_label, cut_label, np.flatnonzero(raw))
+
+
+def test_same_partition_tells_partitions_apart():
+    label = np.array([0, 0, 2, 2, 4])
+    assert pc.same_partition(label, np.array([1, 1, 3, 3, 4]))
+    assert not pc.same_partition(label, np.array([1, 1, 3, 2, 4]))     # a component split
+    assert not pc.same_partition(label, np.array([1, 1, 1, 1, 4]))     # two merged
+    assert not pc.same_partition(label, np.array([1, 1, 3, 3, 5]))     # a root outside
+    assert pc.same_partition(label, np.array([9, 9, 3, 3, 9]), members=[2, 3])
+
+
+@pytest.mark.parametrize("family", pc.EDGE_FAMILIES)
+def test_edge_families_have_their_closed_form_count(family):
+    a, b, count = pc.edge_list(family)
+    assert a.min() >= 0 and max(a.max(), b.max()) < pc.UF_N and len(a) == len(b)
+    label = pc.components(pc.UF_N, a, b)
+    assert np.array_equal(label, pc.components_by_sweeps(pc.UF_N, a, b))
+    if count is not None:
+        assert len(np.unique(label)) == count
+    assert {"star": pc.UF_N - 1, "repeated": 4096, "loops": pc.UF_N, "path": pc.UF_N - 1, "path_priority": pc.UF_N - 1,
+            "random": 2 * pc.UF_N, "cliques": 190000}[family] == len(a)
+
+
+def test_initial_forest_obeys_the_headers_rule():
+    sign = pc.hidden_signs()
+    parent, parity = pc.initial_forest("hooked", sign=sign)
+    assert pc.links_fall_in_priority(parent) and (parent != np.arange(pc.UF_N)).sum() > pc.UF_N // 3
+    assert np.array_equal(parity, sign ^ sign[parent])
+    assert not pc.links_fall_in_priority(np.array([1, 0]))             # a cycle cannot fall both ways
+    ident, zero = pc.initial_forest("identity")
+    assert np.array_equal(ident, np.arange(pc.UF_N)) and not zero.any()
+    words = pc.forest_words(parent, parity, True)
+    assert np.array_equal(pc.word_parents(words, True), parent) and np.array_equal(words & 1, parity)
+    # the parity check accepts the truth and refuses one wrong bit
+    *_, label = pc.edge_case("path", "hooked")
+    rp = sign ^ sign[label]
+    assert pc.parity_consistent(label, rp, sign)
+    rp[12345] ^= 1
+    assert not pc.parity_consistent(label, rp, sign)
+
+
+def test_sort_lists_cover_the_lengths_and_tie_patterns():
+    pairs, offsets = pc.sort_lists()
+    lengths = np.diff(offsets.astype(np.int64))
+    assert len(lengths) == 20000 and set(lengths.tolist()) == set(range(18)) | {31, 32, 33, 100, 1000, 5000}
+    assert (lengths == 1000).sum() == len(pc.SORT_LONG_KEYS) == 6 and (lengths == 5000).sum() == 6
+    for l in (17, 21, 19999):
+        assert pairs[offsets[l]:offsets[l + 1], 1].tolist() == list(range(lengths[l]))   # payload = position
+    # the host twin is the real std::sort: sorted, a permutation of its input list by list, and unstable as libstdc++ is
+    got = lib.selftest_std_sort(pairs, offsets)
+    unstable = 0
+    for l in list(range(0, 20000, 97)) + list(range(19988, 20000)):
+        lo, hi = int(offsets[l]), int(offsets[l + 1])
+        assert (np.diff(got[lo:hi, 0].astype(np.int64)) >= 0).all()
+        assert sorted(map(tuple, got[lo:hi].tolist())) == sorted(map(tuple, pairs[lo:hi].tolist()))
+        stable = pairs[lo:hi][np.argsort(pairs[lo:hi, 0], kind="stable")]
+        unstable += not np.array_equal(stable, got[lo:hi])
+    assert unstable > 0
+    with pytest.raises(T.Tmc2Error):
+        lib.selftest_std_sort(pairs, offsets[:-1])
+
+
+def test_selftest_entries_refuse_bad_arguments_without_a_device():
+    L = T.load_library()
+    invalid = int(re.search(r"#define TMC2_E_INVALID (-?\d+)", open(os.path.join(ROOT, "include", "tmc2hip.h")).read()).group(1))
+    p = C.c_void_p(4096)                                              # never dereferenced: every call below stops at its arguments
+    assert L.tmc2_selftest_scan(None, p, p, 8, None, None, None, 0, 0) == invalid
+    assert L.tmc2_selftest_fill(None, p, 1) == invalid
+    assert L.tmc2_selftest_work_map(None, 8, 64, 8, 0, p, p) == invalid
+    assert L.tmc2_selftest_components(None, p, p, p, None, 8, p, p) == invalid
+    assert L.tmc2_selftest_union_find(None, 0, p, 8, p, 1, 1, 0, p, p, p) == invalid
+    assert L.tmc2_selftest_cand_sort(None, p, p, 1, p) == invalid
+    assert L.tmc2_selftest_std_sort(None, None, 0) == invalid
+    assert b"selftest_std_sort" in L.tmc2_last_error()
+    falling = np.array([0, 2, 1], np.uint32)
+    pairs = np.zeros((2, 2), np.uint32)
+    assert L.tmc2_selftest_std_sort(pairs.ctypes.data_as(C.c_void_p), falling.ctypes.data_as(C.c_void_p), 2) == invalid
