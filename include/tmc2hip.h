@@ -333,6 +333,27 @@ int tmc2_decoder_frame_create( tmc2_ctx* ctx, const tmc2_patch* patches, int cou
  * resident canvases without the encoder's colour transfer / attribute images (tmc2_encoder_generate_attribute_images runs it
  * as its first step).  tmc2_frame_get_reconstruction( f, xyz, NULL, pointToPixel ) returns the points.             */
 int tmc2_codec_generate_point_cloud( tmc2_frame* f );
+/* replaces: PCCCodec::generatePointCloud with pbfEnableFlag_ (PCCCodec.cpp:543-556, :664-669, :811) -- what the encoder
+ * (PCCEncoder.cpp:556-560) and the decoder (PCCDecoder.cpp:333, from the occupancy-synthesis SEI) run instead when the stream
+ * asks for occupancy synthesis: PatchBlockFiltering::patchBorderFiltering (PccLibCommon/source/PCCPatch.cpp:950-976, with
+ * PCCPatch::setLocalData :797, generateBorderPoints3D :851, filtering :871) filters the occupancy of every patch at full
+ * resolution against the border points of the patches next to it in 3-D, the reconstruction takes the filtered maps for its
+ * occupancy test, and every point gets its boundary type (0 / 1) from PCCPatch::isBorder (:841) -- not from
+ * identifyBoundaryPoints.  thresholdLossyOM: an occupancy-video sample counts as occupied above it (0 under the CTC);
+ * passesCount / filterSize / log2Threshold: pbfPassesCount_, pbfFilterSize_, pbfLog2Threshold_.  Points, their order and
+ * pointToPixel are those of tmc2_codec_generate_point_cloud on the filtered occupancy.  On such a frame
+ * tmc2_codec_smooth_point_cloud_postprocess starts from the filter's flags, tmc2_codec_identify_boundary_points restores them,
+ * and the colour transfer onto the moved points is not run (PCCEncoder.cpp:653, PCCDecoder.cpp:412);
+ * tmc2_codec_generate_point_cloud returns the frame to the plain rule.  TMC2_E_UNSUPPORTED, naming the parameter, for precision
+ * 16, a parameter outside 1 .. 127, filterSize + filterSize / 2 above the ring of the padded maps (8 pixels, 16 at precision 8)
+ * and more than 65535 patches.  Where the filter removes every pixel the call succeeds as the reference does: the frame has its
+ * maps and a reconstruction of no points, which the getters return as empty arrays and the tail's stages refuse by name
+ * (TMC2_E_STATE).                                                                                                      */
+int tmc2_codec_generate_point_cloud_pbf( tmc2_frame* f, int thresholdLossyOM, int passesCount, int filterSize, int log2Threshold );
+/* what the filter left, for every patch in list order back to back: the interior sizeU0*16 x sizeV0*16 of
+ * PCCPatch::getOccupancyMap( u, v ) and of PCCPatch::isBorder( u, v ), one byte per pixel, rows of v.  *pixels: their number. */
+int tmc2_frame_patch_border_filtering_size( tmc2_frame* f, int64_t* pixels );
+int tmc2_frame_get_patch_border_filtering( tmc2_frame* f, uint8_t* occupancy, uint8_t* border );
 
 /* ---- post-reconstruction tail (PCCEncoder::encode :571-719, PCCDecoder::decode :330-470) -------------------- */
 /* All of these work on the reconstruction left by tmc2_encoder_generate_attribute_images (PCCCodec::generatePointCloud on
@@ -482,6 +503,14 @@ int tmc2_host_orient_normals( const int16_t* xyz, uint64_t n, const uint32_t* kn
 int tmc2_host_color_smoothing( const int16_t* xyz, uint16_t* colors16, const uint16_t* boundaryType, const uint32_t* patchIndex,
                                uint64_t M, int gridSize, int geometryBitDepth3D, double thresholdColorSmoothing,
                                double thresholdColorDifference, double thresholdColorVariation );
+/* the exact restatement of PatchBlockFiltering::patchBorderFiltering (PCCPatch.cpp:950-976) behind
+ * tmc2_codec_generate_point_cloud_pbf, on host arrays: patch records in list order, the occupancy video (uint8 [H/p][W/p]),
+ * geometry map 0 (uint16 [H][W]), blockToPatch (uint32 [H/16][W/16], list position + 1); occupancy / border as
+ * tmc2_frame_get_patch_border_filtering returns them (either may be NULL)                                               */
+int tmc2_host_patch_border_filtering( const tmc2_patch* patches, int count, int width, int height, int occupancyPrecision,
+                                      const uint8_t* occVideo, const uint16_t* geometryD0, const uint32_t* blockToPatch,
+                                      int thresholdLossyOM, int passesCount, int filterSize, int log2Threshold, uint8_t* occupancy,
+                                      uint8_t* border );
 
 /* ---- the shared device primitives on their own (csrc/selftest.hip; DESIGN.md "primitives under test") ------------------- */
 /* What the stages are built on, reachable without a stage so that it can be compared with a plain loop at shapes no cloud produces.

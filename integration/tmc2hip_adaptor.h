@@ -143,7 +143,7 @@ class MetricsDropIn {
 // The per-frame finish of PCCDecoder::decode (PCCDecoder.cpp:325-470; the encoder's own reconstruction loop :571-719 is the
 // same code) for the CTC lossy conditions, one tile per frame: occupancy map and blockToPatch from the decoded occupancy
 // video, generatePointCloud, colorPointCloud from the decoded (colour-converted, 16-bit 4:4:4) attribute frames, grid
-// geometry smoothing, transferColors16bitBP onto the moved points, colorSmoothing where the attribute-smoothing SEI turns it on,
+// geometry smoothing, transferColors16bitBP onto the moved points (not with occupancy synthesis), colorSmoothing where the attribute-smoothing SEI turns it on,
 // convertYUV16ToRGB8 -- on the device, from the reference's own containers, into `reconstruct` (positions, 16-bit and 8-bit
 // colours, boundary point types).
 // What PCCDecoder::decode reads for `colorSmoothing( reconstruct, colorTransform, ppSEIParams )` (PCCDecoder.cpp:463): the flag
@@ -157,6 +157,18 @@ struct ColorSmoothingArgs {
   double thresholdColorDifference = 10.0;
   double thresholdColorVariation  = 6.0;
 };
+// What PCCDecoder::decode reads of the occupancy-synthesis SEI (PCCDecoder.cpp:333, :412, setPostProcessingSeiParameters :566-600):
+// the flag, the three filter parameters, and the occupancy threshold generatePointCloud hands the filter (PCCCodec.cpp:553:
+// thresholdLossyOM_, 0 with enhancedOccupancyMapCode_).  With the flag, generatePointCloud filters the occupancy of every patch
+// first (PatchBlockFiltering::patchBorderFiltering) and takes the boundary types from PCCPatch::isBorder, and the colour transfer
+// onto the moved points is skipped.
+struct PatchBorderFilteringArgs {
+  bool pbfEnableFlag    = false;
+  int  thresholdLossyOM = 0;
+  int  pbfPassesCount   = 2;
+  int  pbfFilterSize    = 4;
+  int  pbfLog2Threshold = 2;
+};
 class DecoderDropIn {
  public:
   explicit DecoderDropIn( int device );
@@ -167,6 +179,9 @@ class DecoderDropIn {
                         pcc::PCCPointSet3& reconstruct );  // flagColorSmoothing off
   int reconstructFrame( pcc::PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize, double thresholdSmoothing,
                         const ColorSmoothingArgs& colorSmoothing, pcc::PCCPointSet3& reconstruct );
+  int reconstructFrame( pcc::PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize, double thresholdSmoothing,
+                        const ColorSmoothingArgs& colorSmoothing, const PatchBorderFilteringArgs& patchBorderFiltering,
+                        pcc::PCCPointSet3& reconstruct );
   const char* lastError() const { return tmc2_last_error(); }
 
  private:

@@ -84,6 +84,12 @@ int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_
 }
 int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize,
                                      double thresholdSmoothing, const ColorSmoothingArgs& colorSmoothing, PCCPointSet3& reconstruct ) {
+  return reconstructFrame( context, frameIdx, occupancyPrecision, gridSize, thresholdSmoothing, colorSmoothing, PatchBorderFilteringArgs(),
+                           reconstruct );
+}
+int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_t occupancyPrecision, size_t gridSize,
+                                     double thresholdSmoothing, const ColorSmoothingArgs& colorSmoothing,
+                                     const PatchBorderFilteringArgs& pbf, PCCPointSet3& reconstruct ) {
   if ( !ctx_ ) return TMC2_E_NO_DEVICE;
   auto&                   tile = context[frameIdx].getTile( 0 );
   std::vector<tmc2_patch> records;
@@ -108,7 +114,10 @@ int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_
     tmc2_frame* f;
     ~Guard() { tmc2_frame_destroy( f ); }
   } guard{f};
-  if ( ( rc = tmc2_codec_generate_point_cloud( f ) ) != TMC2_OK ) return rc;
+  // generatePointCloud; with the occupancy-synthesis SEI the filtered occupancy and the filter's boundary types (PCCCodec.cpp:543-556)
+  rc = pbf.pbfEnableFlag ? tmc2_codec_generate_point_cloud_pbf( f, pbf.thresholdLossyOM, pbf.pbfPassesCount, pbf.pbfFilterSize, pbf.pbfLog2Threshold )
+                         : tmc2_codec_generate_point_cloud( f );
+  if ( rc != TMC2_OK ) return rc;
   // the decoded attribute frames after the colour conversion: 16-bit 4:4:4, frames 2f and 2f + 1 of the attribute video
   std::vector<uint16_t> att( 2 * 3 * W * H );
   for ( size_t m = 0; m < 2; ++m ) {
@@ -117,10 +126,10 @@ int DecoderDropIn::reconstructFrame( PCCContext& context, size_t frameIdx, size_
       for ( size_t v = 0; v < H; ++v )
         for ( size_t u = 0; u < W; ++u ) att[( ( m * 3 + c ) * H + v ) * W + u] = a.getValue( c, u, v );
   }
-  if ( ( rc = tmc2_codec_identify_boundary_points( f ) ) != TMC2_OK ) return rc;
+  if ( !pbf.pbfEnableFlag && ( rc = tmc2_codec_identify_boundary_points( f ) ) != TMC2_OK ) return rc;
   if ( ( rc = tmc2_codec_color_point_cloud( f, att.data() ) ) != TMC2_OK ) return rc;
   if ( ( rc = tmc2_codec_smooth_point_cloud_postprocess( f, int( gridSize ), thresholdSmoothing ) ) != TMC2_OK ) return rc;
-  if ( ( rc = tmc2_codec_transfer_colors_16bit_bp( f ) ) != TMC2_OK ) return rc;
+  if ( !pbf.pbfEnableFlag && ( rc = tmc2_codec_transfer_colors_16bit_bp( f ) ) != TMC2_OK ) return rc;  // PCCDecoder.cpp:412
   if ( colorSmoothing.flagColorSmoothing ) {  // PCCDecoder.cpp:463 (a decoder-side frame learns the cube from the SEI parameters)
     if ( ( rc = tmc2_frame_set_geometry_bit_depth_3d( f, int( colorSmoothing.geometryBitDepth3D ) ) ) != TMC2_OK ) return rc;
     if ( ( rc = tmc2_codec_color_smoothing( f, int( colorSmoothing.occupancyPrecision ), colorSmoothing.thresholdColorSmoothing,

@@ -24,6 +24,7 @@
 
 #include "internal.h"
 #include "cand_sort.h"
+#include "patch_border_filter.h"
 
 namespace tmc2 {
 namespace {
@@ -42,8 +43,18 @@ __device__ __forceinline__ int normalCoord( const PlaceDev& p, int depth ) {
   return p.mode == 0 ? depth + p.d1 : max( 0, p.d1 - depth );
 }
 
+// what the reconstruction reads instead of the occupancy video on a frame with occupancy synthesis (patch_border_filter.hip): the
+// filtered per-patch maps and their border flags, padded by `border`, patch k at offset[k]; btype: boundary type per point, out
+struct PbfMapsDev {
+  const int64_t* offset;
+  const uint8_t *occ, *flag;
+  int            border;
+  uint8_t*       btype;
+};
+
 // EMIT = false: tileCount[tile] = number of points of the tile.  EMIT = true: write them at tileOffset[tile].
-template <bool EMIT>
+// PBF: the occupancy test reads the filtered map of the patch, and both points of a pixel take its border flag as boundary type
+template <bool EMIT, bool PBF = false>
 __global__ __launch_bounds__( 256 ) void reconTileKernel( const PlaceDev* __restrict__ place,
                                                            const uint32_t* __restrict__ tilePatch,
                                                            const uint8_t* __restrict__ occVideo,
@@ -51,7 +62,7 @@ __global__ __launch_bounds__( 256 ) void reconTileKernel( const PlaceDev* __rest
                                                            const uint16_t* __restrict__ geo, int W, int H, int prec,
                                                            uint32_t* __restrict__ tileCount,
                                                            const uint32_t* __restrict__ tileOffset, Pt* __restrict__ recon,
-                                                           uint32_t* __restrict__ pointToPixel ) {
+                                                           uint32_t* __restrict__ pointToPixel, PbfMapsDev pbf = PbfMapsDev() ) {
   __shared__ uint32_t waveTotal[4];
   const uint32_t      tile  = blockIdx.x;
   const uint32_t      k     = tilePatch[tile];
@@ -65,7 +76,18 @@ __global__ __launch_bounds__( 256 ) void reconTileKernel( const PlaceDev* __rest
   toCanvasB( p, u, v, x, y );
   uint32_t cnt = 0;
   int      c0 = 0, c1 = 0;
-  if ( owned && x < W && y < H && occVideo[size_t( y / prec ) * ( W / prec ) + x / prec] ) {
+  bool    occupied = owned && x < W && y < H;
+  uint8_t flag     = 0;
+  if constexpr ( PBF ) {
+    if ( occupied ) {
+      const int64_t c = pbf.offset[k] + int64_t( v + pbf.border ) * ( p.sizeU0 * 16 + 2 * pbf.border ) + u + pbf.border;
+      occupied        = pbf.occ[c] != 0;
+      flag            = pbf.flag[c];
+    }
+  } else {
+    occupied = occupied && occVideo[size_t( y / prec ) * ( W / prec ) + x / prec];
+  }
+  if ( occupied ) {
     c0  = normalCoord( p, geo[size_t( y ) * W + x] );
     c1  = normalCoord( p, geo[size_t( W ) * H + size_t( y ) * W + x] );
     cnt = c1 != c0 ? 2u : 1u;
@@ -93,6 +115,10 @@ __global__ __launch_bounds__( 256 ) void reconTileKernel( const PlaceDev* __rest
   c[p.axN] = c0;
   recon[off]        = Pt{int16_t( c[0] ), int16_t( c[1] ), int16_t( c[2] ), 0};
   pointToPixel[off] = packPixel( x, y, 0, cnt == 2 );
+  if constexpr ( PBF ) {
+    pbf.btype[off] = flag;
+    if ( cnt == 2 ) pbf.btype[off + 1] = flag;
+  }
   if ( cnt == 2 ) {
     c[p.axN]              = c1;
     recon[off + 1]        = Pt{int16_t( c[0] ), int16_t( c[1] ), int16_t( c[2] ), 0};
@@ -471,12 +497,25 @@ int transferColorsDevice( tmc2_ctx* ctx, const TreeDev& srcTree, const Pt* d_src
 
 // S17 + the k-d tree over the reconstruction: all the decoder needs before the post-reconstruction tail, and the first half
 // of the encoder's phase B
-int reconstructPointCloud( tmc2_frame* f ) {
+int reconstructPointCloud( tmc2_frame* f, const PbfParams* pbfParams ) {
   if ( !f->haveGeometryImages ) {
     setError( "generatePointCloud: geometry images missing" );
     return TMC2_E_STATE;
   }
+  if ( pbfParams ) {  // (refused before the frame's state changes and before anything is launched)
+    if ( const char* what = pbfRefusal( f->occPrecision, *pbfParams, long( f->patches.size() ) ) ) {
+      setError( "generatePointCloud (patch border filtering): unsupported %s", what );
+      return TMC2_E_UNSUPPORTED;
+    }
+  }
+  // the attribute images are the encoder's product of the plain reconstruction: a reconstruction with occupancy synthesis (the
+  // decoder-side leg of such a stream) and the plain one that undoes it leave them standing
+  const bool keepAttributeImages = f->haveAttributeImages && ( pbfParams || f->havePbf );
   f->canvasesChanged();  // (the reconstruction is about to be replaced: what is derived from the canvases starts over)
+  f->haveAttributeImages = keepAttributeImages;
+  if ( pbfParams ) TMC2_TRY( patchBorderFilterDevice( f, *pbfParams ) );  // (refuses before anything is launched)
+  PbfMapsDev pbf;
+  if ( pbfParams ) pbf = PbfMapsDev{f->d_pbfOffset.p, f->pbfOcc, f->pbfFlag, f->pbfBorderWidth, nullptr};
   tmc2_ctx*    ctx = f->ctx;
   hipStream_t  s   = ctx->stream;
   const int    W = f->canvasW, H = f->canvasH, prec = f->occPrecision;
@@ -490,13 +529,27 @@ int reconstructPointCloud( tmc2_frame* f ) {
   TMC2_TRY( d_small.alloc( 8 ) );
   uint32_t M = 0;
   if ( tiles ) {
-    hipLaunchKernelGGL( reconTileKernel<false>, dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
-                        f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, (const uint32_t*)nullptr, (Pt*)nullptr,
-                        (uint32_t*)nullptr );
+    if ( pbfParams )
+      hipLaunchKernelGGL( ( reconTileKernel<false, true> ), dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
+                          f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, (const uint32_t*)nullptr, (Pt*)nullptr,
+                          (uint32_t*)nullptr, pbf );
+    else
+      hipLaunchKernelGGL( reconTileKernel<false>, dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
+                          f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, (const uint32_t*)nullptr, (Pt*)nullptr,
+                          (uint32_t*)nullptr, PbfMapsDev() );
     volatile uint32_t* answer = ctx->answerLine( tmc2_ctx::kAnswerRecon );  // (the point count straight to a page-locked word: no copy)
     TMC2_TRY( exclusiveScanU32( ctx, d_tileCount.p, d_tileOffset.p, tiles, d_small.p, ScanAnswer{answer, nullptr, 0} ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
     M = answer[0];
+  }
+  if ( M == 0 && pbfParams ) {
+    // the filter may remove every pixel (isolated ones have no 4-neighbour): the reference then reconstructs no point.  The frame
+    // has its maps and an empty reconstruction; the tail's stages refuse it (needReconstruction).
+    stage.end();
+    f->reconCount         = 0;
+    f->haveReconstruction = true;
+    f->haveBoundaryTypes  = true;
+    return TMC2_OK;
   }
   if ( M == 0 ) {
     setError( "generatePointCloud: empty reconstruction" );
@@ -504,14 +557,26 @@ int reconstructPointCloud( tmc2_frame* f ) {
   }
   TMC2_TRY( f->d_recon.alloc( M ) );
   TMC2_TRY( f->d_pointToPixel.alloc( M ) );
-  hipLaunchKernelGGL( reconTileKernel<true>, dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
-                      f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, d_tileOffset.p, f->d_recon.p,
-                      f->d_pointToPixel.p );
+  if ( pbfParams ) {
+    // the boundary types come with the points; a copy stays for tmc2_codec_identify_boundary_points to restore them from
+    TMC2_TRY( f->d_boundaryType.alloc( M ) );
+    TMC2_TRY( f->d_pbfBoundary.alloc( M ) );
+    pbf.btype = f->d_boundaryType.p;
+    hipLaunchKernelGGL( ( reconTileKernel<true, true> ), dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
+                        f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, d_tileOffset.p, f->d_recon.p, f->d_pointToPixel.p,
+                        pbf );
+    TMC2_HIP( hipMemcpyAsync( f->d_pbfBoundary.p, f->d_boundaryType.p, M, hipMemcpyDeviceToDevice, s ) );
+  } else {
+    hipLaunchKernelGGL( reconTileKernel<true>, dim3( tiles ), blk, 0, s, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
+                        f->d_blockToPatch.p, f->d_geo.p, W, H, prec, d_tileCount.p, d_tileOffset.p, f->d_recon.p,
+                        f->d_pointToPixel.p, PbfMapsDev() );
+  }
   stage.end();
   f->reconCount = M;
   // ---- tree over the reconstruction (like S1) --------------------------------------------------------------
   TMC2_TRY( buildKdTreePlaced( ctx, f->d_recon.p, M, nullptr, "kdtree_build_recon", f->reconTree ) );
   f->haveReconstruction = true;
+  f->haveBoundaryTypes  = pbfParams != nullptr;
   return TMC2_OK;
 }
 
@@ -717,13 +782,14 @@ int tmc2_frame_get_reconstruction( tmc2_frame* f, int16_t* xyz, uint8_t* rgb, ui
     tmc2::setError( "get_reconstruction: not generated" );
     return TMC2_E_STATE;
   }
-  if ( rgb && !f->haveAttributeImages ) {
+  if ( rgb && ( !f->haveAttributeImages || f->havePbf ) ) {  // (the colours are those of the plain reconstruction's points)
     tmc2::setError( "get_reconstruction: no transferred colours (tmc2_encoder_generate_attribute_images produces them)" );
     return TMC2_E_STATE;
   }
   tmc2::ApiScope scope( f->ctx );
   hipStream_t    s = f->ctx->stream;
   const size_t   M = f->reconCount;
+  if ( M == 0 ) return TMC2_OK;  // (occupancy synthesis removed every pixel: nothing to copy)
   std::vector<tmc2::Pt>  pts( M );
   std::vector<uint8_t>   c4( rgb ? 4 * M : 0 );
   std::vector<uint32_t>  pp( M );

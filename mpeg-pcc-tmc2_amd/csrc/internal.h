@@ -391,6 +391,7 @@ struct tmc2_frame {
   void canvasesChanged() {
     haveAttributeImages = haveReconstruction = false;
     haveBoundaryTypes = haveColors16 = haveSmoothed = haveRgbPost = false;
+    havePbf = false;  // (the filtered occupancy derives from the canvases)
   }
   // device side
   tmc2::DevBuf<tmc2::Pt>     d_pts;       // original order
@@ -440,6 +441,15 @@ struct tmc2_frame {
   bool                    haveAttr16 = false;
   bool                    haveBoundaryTypes = false, haveColors16 = false, haveSmoothed = false, haveRgbPost = false;
   tmc2::DeviceTree        reconTree;            // over d_recon (reconstructPointCloud)
+  // occupancy synthesis (patch_border_filter.hip): the padded per-patch maps of the last tmc2_codec_generate_point_cloud_pbf, all
+  // patches back to back (list order) at pbfOffset; pbfOcc / pbfFlag point into the two pools (which is which depends on the
+  // parity of the pass count); d_pbfBoundary: the boundary types the reconstruction took from the flags, per point
+  tmc2::DevBuf<uint8_t>   d_pbfMapA, d_pbfMapB, d_pbfBoundary;
+  tmc2::DevBuf<int64_t>   d_pbfOffset;
+  std::vector<int64_t>    pbfOffset;
+  const uint8_t *         pbfOcc = nullptr, *pbfFlag = nullptr;
+  int                     pbfBorderWidth = 0, pbfParams[4] = {0, 0, 0, 0};
+  bool                    havePbf = false;
   int                     geometryBitDepth3D = 0;  // the cube the colour smoothing's grid spans (segmentPatches, or tmc2_frame_set_geometry_bit_depth_3d); 0: unknown
 };
 
@@ -473,7 +483,10 @@ int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint
 int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_easy, uint32_t* d_idx,
                     uint32_t* d_dist, const char* stage, bool uniqueTreeRows = false );
 int generateAttributeImages( tmc2_frame* f );
-int reconstructPointCloud( tmc2_frame* f );
+struct PbfParams;  // patch_border_filter.h
+// pbf != nullptr: occupancy synthesis first (patchBorderFilterDevice); occupancy and boundary types then come from its maps
+int reconstructPointCloud( tmc2_frame* f, const PbfParams* pbf = nullptr );
+int patchBorderFilterDevice( tmc2_frame* f, const PbfParams& q );
 int uploadPlacement( tmc2_frame* f );
 int launchNormals( tmc2_frame* f );
 // beforeHostWalk: device work that needs the points only and may run while the host walks the orientation graph (S3); called once,

@@ -335,7 +335,11 @@ __global__ __launch_bounds__( 256 ) void yuv16ToRgb8Kernel( const ushort4* __res
 }
 
 int needReconstruction( tmc2_frame* f, const char* who ) {
-  if ( !f->haveReconstruction || f->reconCount == 0 ) {
+  if ( f->haveReconstruction && f->reconCount == 0 ) {
+    setError( "%s: the reconstruction is empty (occupancy synthesis removed every pixel)", who );
+    return TMC2_E_STATE;
+  }
+  if ( !f->haveReconstruction ) {
     setError( "%s: the frame has no reconstruction (tmc2_codec_generate_point_cloud or tmc2_encoder_generate_attribute_images first)", who );
     return TMC2_E_STATE;
   }
@@ -349,6 +353,12 @@ int identifyBoundaryPoints( tmc2_frame* f ) {
   const uint32_t M   = uint32_t( f->reconCount );
   TMC2_TRY( f->d_boundaryType.alloc( M ) );
   StageScope stage( ctx, "boundary_points" );
+  if ( f->havePbf ) {  // a frame with occupancy synthesis: the types are the filter's (PCCPatch::isBorder), never the occupancy rule's
+    TMC2_HIP( hipMemcpyAsync( f->d_boundaryType.p, f->d_pbfBoundary.p, M, hipMemcpyDeviceToDevice, ctx->stream ) );
+    f->haveBoundaryTypes = true;
+    f->haveSmoothed      = false;
+    return TMC2_OK;
+  }
   hipLaunchKernelGGL( boundaryTypeKernel, dim3( ( M + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, f->d_pointToPixel.p, M,
                       f->d_occVideo.p, f->canvasW, f->canvasH, f->occPrecision, f->d_boundaryType.p );
   TMC2_HIP( hipGetLastError() );
@@ -581,13 +591,14 @@ int tmc2_codec_convert_yuv16_to_rgb8( tmc2_frame* f ) {
 int tmc2_frame_get_post_reconstruction( tmc2_frame* f, int16_t* xyz, uint16_t* colors16, uint8_t* rgb, uint16_t* boundaryType ) {
   if ( !f ) return TMC2_E_INVALID;
   tmc2::ApiScope scope( f->ctx );
-  TMC2_TRY( tmc2::needReconstruction( f, "get_post_reconstruction" ) );
+  // (a reconstruction that occupancy synthesis left without a point is read as empty arrays; only the stages refuse it)
+  if ( !f->haveReconstruction || !f->havePbf ) TMC2_TRY( tmc2::needReconstruction( f, "get_post_reconstruction" ) );
   const size_t M = size_t( f->reconCount );
   hipStream_t  s = f->ctx->stream;
   if ( xyz ) {
     std::vector<tmc2::Pt> h( M );
     const tmc2::Pt* src = f->haveSmoothed ? f->d_reconSmoothed.p : f->d_recon.p;
-    TMC2_HIP( hipMemcpyAsync( h.data(), src, M * sizeof( tmc2::Pt ), hipMemcpyDeviceToHost, s ) );
+    if ( M ) TMC2_HIP( hipMemcpyAsync( h.data(), src, M * sizeof( tmc2::Pt ), hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
     for ( size_t i = 0; i < M; ++i ) xyz[3 * i] = h[i].x, xyz[3 * i + 1] = h[i].y, xyz[3 * i + 2] = h[i].z;
   }
@@ -597,7 +608,7 @@ int tmc2_frame_get_post_reconstruction( tmc2_frame* f, int16_t* xyz, uint16_t* c
       return TMC2_E_STATE;
     }
     std::vector<uint64_t> h( M );
-    TMC2_HIP( hipMemcpyAsync( h.data(), f->d_colors16.p, M * 8, hipMemcpyDeviceToHost, s ) );
+    if ( M ) TMC2_HIP( hipMemcpyAsync( h.data(), f->d_colors16.p, M * 8, hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
     for ( size_t i = 0; i < M; ++i )
       for ( int k = 0; k < 3; ++k ) colors16[3 * i + k] = uint16_t( h[i] >> ( 16 * k ) );
@@ -608,7 +619,7 @@ int tmc2_frame_get_post_reconstruction( tmc2_frame* f, int16_t* xyz, uint16_t* c
       return TMC2_E_STATE;
     }
     std::vector<uint8_t> h( M * 4 );
-    TMC2_HIP( hipMemcpyAsync( h.data(), f->d_rgbPost.p, M * 4, hipMemcpyDeviceToHost, s ) );
+    if ( M ) TMC2_HIP( hipMemcpyAsync( h.data(), f->d_rgbPost.p, M * 4, hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
     for ( size_t i = 0; i < M; ++i )
       for ( int k = 0; k < 3; ++k ) rgb[3 * i + k] = h[4 * i + k];
@@ -619,7 +630,7 @@ int tmc2_frame_get_post_reconstruction( tmc2_frame* f, int16_t* xyz, uint16_t* c
       return TMC2_E_STATE;
     }
     std::vector<uint8_t> h( M );
-    TMC2_HIP( hipMemcpyAsync( h.data(), f->d_boundaryType.p, M, hipMemcpyDeviceToHost, s ) );
+    if ( M ) TMC2_HIP( hipMemcpyAsync( h.data(), f->d_boundaryType.p, M, hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
     for ( size_t i = 0; i < M; ++i ) boundaryType[i] = h[i];
   }

@@ -388,7 +388,7 @@ class GofEncoder:
         """S17-S22 on the resident (decoded == generated) occupancy / geometry canvases."""
         self._per_worker(frames, lambda fr: fr.encoder_generate_attribute_images())
 
-    def phase_c(self, frames, decoded_attribute=None, grid_size=8, threshold=64.0, i420_out=None, color_smoothing=None):
+    def phase_c(self, frames, decoded_attribute=None, grid_size=8, threshold=64.0, i420_out=None, color_smoothing=None, pbf=None):
         """What follows the attribute images, per frame: the colour-space conversion to the I420 frames the video encoder
         reads, and the post-reconstruction tail (boundary points, 16-bit colours from the decoded attribute frames, grid
         geometry smoothing, colour transfer onto the moved points, YUV -> RGB).
@@ -396,13 +396,15 @@ class GofEncoder:
         video codec -- the I420 frames produced here are converted back on the device (i420_out[i], uint8 [2][H*W*3/2],
         receives them if given).
         color_smoothing: None (flagColorSmoothing off, the CTC) or the arguments of Frame.codec_color_smoothing as a tuple,
-        (grid_size[, thr_smoothing, thr_difference, thr_variation]): the stage runs between the colour transfer and YUV -> RGB."""
+        (grid_size[, thr_smoothing, thr_difference, thr_variation]): the stage runs between the colour transfer and YUV -> RGB.
+        pbf: None, or (passesCount, filterSize, log2Threshold[, thresholdLossyOM]) for a stream with occupancy synthesis (patch border
+        filtering): the tail reconstructs with the filter and skips the colour transfer (Frame.codec_post_reconstruct)."""
         if color_smoothing is None:
-            tail = lambda fr, att: fr.codec_post_reconstruct(att, grid_size, threshold)
+            tail = lambda fr, att: fr.codec_post_reconstruct(att, grid_size, threshold, pbf=pbf)
         else:
             def tail(fr, att):
                 fr.set_geometry_bit_depth_3d(self.bits3d)       # (a frame whose patches came from another rank has not been told)
-                fr.codec_post_reconstruct(att, grid_size, threshold, tuple(color_smoothing))
+                fr.codec_post_reconstruct(att, grid_size, threshold, tuple(color_smoothing), pbf=pbf)
         if decoded_attribute is not None:
             self.per_frame(frames, lambda fr, i: tail(fr, decoded_attribute[i]))
             return

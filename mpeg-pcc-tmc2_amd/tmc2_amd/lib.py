@@ -577,6 +577,7 @@ class Frame:
 
     # PCCEncoder image generation, phase B
     def encoder_generate_attribute_images(self):
+        self._pbf = False
         _check(self.L.tmc2_encoder_generate_attribute_images(self.h))
 
     def recon_count(self):
@@ -589,9 +590,25 @@ class Frame:
         _check(self.L.tmc2_frame_get_reconstruction(self.h, _ptr(xyz), None if rgb is None else _ptr(rgb), _ptr(p2p)))
         return xyz, rgb, p2p
 
-    def codec_generate_point_cloud(self):
-        """PCCCodec::generatePointCloud alone (no colour transfer, no attribute images)."""
-        _check(self.L.tmc2_codec_generate_point_cloud(self.h))
+    def codec_generate_point_cloud(self, pbf=None):
+        """PCCCodec::generatePointCloud alone (no colour transfer, no attribute images).  pbf: None, or occupancy synthesis (patch
+        border filtering) first, as (passesCount, filterSize, log2Threshold[, thresholdLossyOM]): the occupancy is then the filtered
+        one and the frame has its boundary types from the filter."""
+        self._pbf = pbf is not None
+        if pbf is None:
+            _check(self.L.tmc2_codec_generate_point_cloud(self.h))
+            return
+        passes, filter_size, log2_threshold, threshold_om = (tuple(pbf) + (0,))[:4]
+        _check(self.L.tmc2_codec_generate_point_cloud_pbf(self.h, int(threshold_om), int(passes), int(filter_size), int(log2_threshold)))
+
+    def get_patch_border_filtering(self):
+        """What the filter of codec_generate_point_cloud(pbf=...) left: (occupancy, border), uint8, the interior sizeU0*16 x sizeV0*16
+        of every patch in list order, back to back."""
+        n = C.c_int64()
+        _check(self.L.tmc2_frame_patch_border_filtering_size(self.h, C.byref(n)))
+        occ, border = np.zeros(n.value, np.uint8), np.zeros(n.value, np.uint8)
+        _check(self.L.tmc2_frame_get_patch_border_filtering(self.h, _ptr(occ), _ptr(border)))
+        return occ, border
 
     # post-reconstruction tail (PCCEncoder::encode :571-719 / PCCDecoder::decode :330-470)
     def codec_identify_boundary_points(self):
@@ -649,14 +666,23 @@ class Frame:
         grid_size = occupancyPrecision; the thresholds default as PCCEncoderParameters does."""
         _check(self.L.tmc2_codec_color_smoothing(self.h, int(grid_size), thr_smoothing, thr_difference, thr_variation))
 
-    def codec_post_reconstruct(self, attribute16=None, grid_size=8, threshold=64.0, color_smoothing=None):
+    def codec_post_reconstruct(self, attribute16=None, grid_size=8, threshold=64.0, color_smoothing=None, pbf=None):
         """The whole tail in the reference's order: boundary points, 16-bit colours from the decoded attribute frames, grid
         geometry smoothing, colour transfer onto the moved points, [colour smoothing,] YUV -> RGB.  color_smoothing: None (the
-        CTC: flagColorSmoothing off) or the arguments of codec_color_smoothing as a tuple, (grid_size[, thresholds ...])."""
-        self.codec_identify_boundary_points()
+        CTC: flagColorSmoothing off) or the arguments of codec_color_smoothing as a tuple, (grid_size[, thresholds ...]).
+        pbf: None, or the arguments of codec_generate_point_cloud(pbf=...) for a stream with occupancy synthesis: the frame is
+        reconstructed again with the filter, the boundary points are the filter's, and the colour transfer onto the moved points
+        is not run (PCCEncoder.cpp:653, PCCDecoder.cpp:412)."""
+        if pbf is not None:
+            self.codec_generate_point_cloud(pbf)
+        else:
+            if getattr(self, "_pbf", False):   # (an earlier call left the filtered reconstruction: back to the plain rule)
+                self.codec_generate_point_cloud()
+            self.codec_identify_boundary_points()
         self.codec_color_point_cloud(attribute16)
         self.codec_smooth_point_cloud_postprocess(grid_size, threshold)
-        self.codec_transfer_colors_16bit_bp()
+        if pbf is None:
+            self.codec_transfer_colors_16bit_bp()
         if color_smoothing is not None:
             self.codec_color_smoothing(*color_smoothing)
         self.codec_convert_yuv16_to_rgb8()
@@ -962,6 +988,25 @@ def host_color_smoothing(xyz, colors16, boundary, patch_index, grid_size, bits3d
     return a[1]
 
 
+def host_patch_border_filtering(patches, width, height, occ_precision, occ_video, geometry_d0, block_to_patch, passes, filter_size,
+                                log2_threshold, threshold_om=0):
+    """tmc2_host_patch_border_filtering: PatchBlockFiltering::patchBorderFiltering restated on the host (no device) -> (occupancy,
+    border) as Frame.get_patch_border_filtering returns them."""
+    L = load_library()
+    pt = np.ascontiguousarray(patches, dtype=PATCH_DTYPE)
+    ov = np.ascontiguousarray(occ_video, dtype=np.uint8)
+    geo = np.ascontiguousarray(geometry_d0, dtype=np.uint16)
+    b2p = np.ascontiguousarray(block_to_patch, dtype=np.uint32)
+    if width <= 0 or height <= 0 or occ_precision <= 0 or ov.size != (height // occ_precision) * (width // occ_precision) or \
+            geo.size != height * width or b2p.size != (height // 16) * (width // 16):
+        raise Tmc2Error("host_patch_border_filtering: canvases do not match %dx%d at precision %d" % (width, height, occ_precision))
+    n = int(sum(int(t["sizeU0"]) * int(t["sizeV0"]) * 256 for t in pt if t["sizeU0"] > 0 and t["sizeV0"] > 0))
+    occ, border = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    _check(L.tmc2_host_patch_border_filtering(_ptr(pt), len(pt), int(width), int(height), int(occ_precision), _ptr(ov), _ptr(geo), _ptr(b2p),
+                                              int(threshold_om), int(passes), int(filter_size), int(log2_threshold), _ptr(occ), _ptr(border)))
+    return occ, border
+
+
 def selftest_std_sort(pairs, offsets):
     """tmc2_selftest_std_sort: the real std::sort( .., dist < dist ) on every list of pairs [total][2] = (distance, payload), list l
     = [offsets[l], offsets[l + 1]); returns the sorted copy (host only)."""
@@ -1055,6 +1100,9 @@ int tmc2_codec_set_decoded_attribute_yuv420(tmc2_frame*, const uint8_t*, int)
 int tmc2_frame_get_decoded_attribute(tmc2_frame*, uint16_t*)
 int tmc2_decoder_frame_create(tmc2_ctx*, const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, tmc2_frame**)
 int tmc2_codec_generate_point_cloud(tmc2_frame*)
+int tmc2_codec_generate_point_cloud_pbf(tmc2_frame*, int, int, int, int)
+int tmc2_frame_patch_border_filtering_size(tmc2_frame*, int64_t*)
+int tmc2_frame_get_patch_border_filtering(tmc2_frame*, uint8_t*, uint8_t*)
 int tmc2_codec_identify_boundary_points(tmc2_frame*)
 int tmc2_codec_color_point_cloud(tmc2_frame*, const uint16_t*)
 int tmc2_codec_smooth_point_cloud_postprocess(tmc2_frame*, int, double)
@@ -1082,6 +1130,7 @@ int tmc2_host_pack_spatial_consistency(tmc2_patch*, int, const uint8_t*, const t
 int tmc2_host_place_segments(int, const int32_t*, tmc2_patch*, const uint8_t*, const int64_t*, int, int, int, int, double, int32_t*, uint8_t*, int64_t, int64_t*, int32_t*, int32_t*)
 int tmc2_host_orient_normals(const int16_t*, uint64_t, const uint32_t*, int, double*)
 int tmc2_host_color_smoothing(const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
+int tmc2_host_patch_border_filtering(const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, const uint32_t*, int, int, int, int, uint8_t*, uint8_t*)
 int tmc2_selftest_scan(tmc2_ctx*, const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, const uint32_t*, int, uint64_t)
 int tmc2_selftest_fill(tmc2_ctx*, const uint64_t*, int)
 int tmc2_selftest_work_map(tmc2_ctx*, uint64_t, int, uint64_t, uint64_t, uint32_t*, uint32_t*)
