@@ -115,16 +115,34 @@ __global__ __launch_bounds__( 256 ) void ccMutualMaskKernel( const uint32_t* __r
   mutual[u] = uint16_t( m );
 }
 
+// The point of this lane in a one-point-per-lane pass of the patch rounds (n: none).  Round 1 (LIST = false): every point is raw and
+// the pass runs over all n of them (count == n), in the order its caller chose.  Later rounds: over list[0 .. count), the points
+// still raw in ASCENDING index order (rawListScatterKernel), on a grid of count lanes -- a lane per point of the cloud would find
+// raw[i] == 0 and leave in nearly all of them.  The arrays indexed by point or seed keep their size and meaning; a pass run from
+// the list leaves the entries of the other points as they are, and nothing reads them (segmentPatches: which consumers).
+template <bool LIST>
+__device__ __forceinline__ uint32_t roundPoint( const uint32_t* __restrict__ list, uint32_t count, uint32_t n ) {
+  const uint32_t j = chunkedIndex();
+  if ( LIST ) return j < count ? list[j] : n;
+  return j < n ? j : n;
+}
+template <bool LIST>
+__device__ __forceinline__ uint32_t roundPoint( const uint32_t* __restrict__ list, uint32_t count, const uint32_t* __restrict__ perm,
+                                                bool chunked, uint32_t n ) {
+  return LIST ? roundPoint<true>( list, count, n ) : pointOfLane( perm, chunked, n );
+}
+
 // Initial forest without atomics: every raw point hooks itself under the eligible mutual neighbour of smallest hashed
 // priority, if smaller than its own (priorities strictly decrease along parent links: acyclic).  Most unions are done
 // before the first compare-and-swap, and the paths the union pass walks end at local priority minima.
-template <int K>
+template <bool LIST, int K>
 __global__ __launch_bounds__( 256 ) void ccInitKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mutual,
                                                         const uint8_t* __restrict__ partition, const uint8_t* __restrict__ raw,
-                                                        const uint32_t* __restrict__ perm, bool chunked, uint32_t n,
+                                                        const uint32_t* __restrict__ perm, bool chunked,
+                                                        const uint32_t* __restrict__ list, uint32_t count, uint32_t n,
                                                         uint32_t* __restrict__ parent, uint32_t* __restrict__ lab,
                                                         uint32_t* __restrict__ ccCount ) {
-  const uint32_t i = pointOfLane( perm, chunked, n );
+  const uint32_t i = roundPoint<LIST>( list, count, perm, chunked, n );
   if ( i >= n ) return;
   lab[i]        = kNoLabel;
   ccCount[i]    = 0;
@@ -146,13 +164,13 @@ __global__ __launch_bounds__( 256 ) void ccInitKernel( const uint32_t* __restric
 }
 
 // The unions over the eligible mutual edges (raw ends of one plane); the union-find itself: union_find.h.
-template <int K>
+template <bool LIST, int K>
 __global__ __launch_bounds__( 256 ) void ccUnionKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mutual,
                                                          const uint8_t* __restrict__ partition,
                                                          const uint8_t* __restrict__ raw, const uint32_t* __restrict__ perm,
-                                                         bool chunked, uint32_t n, uint32_t* __restrict__ parent, int precheck,
-                                                         bool agent ) {
-  const uint32_t u = pointOfLane( perm, chunked, n );
+                                                         bool chunked, const uint32_t* __restrict__ list, uint32_t count, uint32_t n,
+                                                         uint32_t* __restrict__ parent, int precheck, bool agent ) {
+  const uint32_t u = roundPoint<LIST>( list, count, perm, chunked, n );
   if ( u >= n || !raw[u] ) return;
   uint32_t m = mutual[u];
   if ( !m ) return;
@@ -171,11 +189,14 @@ __global__ __launch_bounds__( 256 ) void ccUnionKernel( const uint32_t* __restri
 // Debug invariants of the settled forest (TMC2_UF_CHECK=1, the soak tests): every link goes to a raw point of the same plane
 // and of smaller priority; the two ends of every eligible mutual edge have one root (Uf::rootCoherent).  bad[0] = broken
 // links, bad[1] = edges whose ends ended up in different sets.
-template <int K>
+template <bool LIST, int K>
 __global__ __launch_bounds__( 256 ) void ccCheckKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mutual,
                                                          const uint8_t* __restrict__ partition, const uint8_t* __restrict__ raw,
-                                                         uint32_t n, uint32_t* parent, uint32_t* __restrict__ bad ) {
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+                                                         const uint32_t* __restrict__ list, uint32_t count, uint32_t n, uint32_t* parent,
+                                                         uint32_t* __restrict__ bad ) {
+  const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( at >= count ) return;
+  const uint32_t u = LIST ? list[at] : at;
   if ( u >= n || !raw[u] ) return;
   const uint32_t p = __hip_atomic_load( &parent[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
   if ( p != u && ( p >= n || !raw[p] || partition[p] != partition[u] || ufPriority( p ) >= ufPriority( u ) ) ) atomicAdd( &bad[0], 1u );
@@ -194,11 +215,12 @@ __global__ __launch_bounds__( 256 ) void ccCheckKernel( const uint32_t* __restri
   }
 }
 
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void ccFlattenSeedKernel( const uint8_t* __restrict__ raw, const uint32_t* __restrict__ dist,
-                                                               uint32_t thrDetection, uint32_t n,
-                                                               uint32_t* __restrict__ parent, uint32_t* __restrict__ root,
-                                                               uint32_t* __restrict__ lab, bool agent ) {
-  const uint32_t u    = chunkedIndex();
+                                                               uint32_t thrDetection, const uint32_t* __restrict__ list,
+                                                               uint32_t count, uint32_t n, uint32_t* __restrict__ parent,
+                                                               uint32_t* __restrict__ root, uint32_t* __restrict__ lab, bool agent ) {
+  const uint32_t u    = roundPoint<LIST>( list, count, n );
   const int      lane = threadIdx.x & 63;
   uint32_t       r    = kNoLabel;
   bool           seed = false;
@@ -213,7 +235,8 @@ __global__ __launch_bounds__( 256 ) void ccFlattenSeedKernel( const uint8_t* __r
     const int                leader = __ffsll( (long long)todo ) - 1;
     const uint32_t           key    = __shfl( r, leader, 64 );
     const unsigned long long same   = __ballot( seed && r == key );
-    // lanes are in index order, so the leader (lowest lane of its group) holds the group's smallest index in the wave
+    // lanes are in index order (the list is ascending), so the leader (lowest lane of its group) holds the group's smallest index
+    // in the wave
     if ( lane == leader && loadStaleOk( &lab[key], agent ) > u )
       atomicMin( &lab[key], u );
     todo &= ~same;
@@ -221,14 +244,15 @@ __global__ __launch_bounds__( 256 ) void ccFlattenSeedKernel( const uint8_t* __r
 }
 
 // one relaxation sweep over the one-way edges between groups (parent = the flat roots ccFlattenSeedKernel wrote)
-template <int K>
+template <bool LIST, int K>
 __global__ __launch_bounds__( 256 ) void ccRelaxKernel( const uint32_t* __restrict__ knn, const uint16_t* __restrict__ mutual,
                                                          const uint8_t* __restrict__ partition,
                                                          const uint8_t* __restrict__ raw, const uint32_t* __restrict__ parent,
-                                                         const uint32_t* __restrict__ perm, bool chunked, uint32_t n,
+                                                         const uint32_t* __restrict__ perm, bool chunked,
+                                                         const uint32_t* __restrict__ list, uint32_t count, uint32_t n,
                                                          uint32_t* __restrict__ lab, uint32_t* __restrict__ changed, uint32_t token,
                                                          bool agent ) {
-  const uint32_t u = pointOfLane( perm, chunked, n );
+  const uint32_t u = roundPoint<LIST>( list, count, perm, chunked, n );
   if ( u >= n || !raw[u] ) return;
   uint32_t m = ~uint32_t( mutual[u] ) & ( ( 1u << K ) - 1u );
   if ( !m ) return;
@@ -251,13 +275,11 @@ __global__ __launch_bounds__( 256 ) void ccRelaxKernel( const uint32_t* __restri
   if ( any ) *changed = token;  // (which sweep changed something last: nothing to clear between sweeps)
 }
 
-constexpr uint32_t kRawCounters = 16;  // this round's count of points still raw: sixteen words 128 bytes apart, one add per workgroup
 // start of a round's per-patch accumulators: bounding box {min 3 x INT_MAX, max 3 x 0 -- the reference starts its max at 0},
-// minimum (u, v), the two resampling counters; and this round's count of points still raw
+// minimum (u, v), the two resampling counters
 __global__ __launch_bounds__( 256 ) void patchBoundsInitKernel( uint32_t P, int32_t* __restrict__ bbox, int32_t* __restrict__ minUv,
-                                                                 int32_t* __restrict__ patchStat, uint32_t* __restrict__ rawCount ) {
+                                                                 int32_t* __restrict__ patchStat ) {
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( p < kRawCounters ) rawCount[p * 32] = 0;  // (the first workgroup always exists: P >= 1)
   if ( p >= P ) return;
 #pragma unroll
   for ( int d = 0; d < 3; ++d ) {
@@ -273,10 +295,12 @@ __global__ __launch_bounds__( 256 ) void patchBoundsInitKernel( uint32_t P, int3
 // (round 6: the sizes are only ever compared with minCount -- ccSeedFlagKernel, ccAssignKernel -- so a component that has reached it
 //  stops counting: the body of a figure is ONE component of 10^5 points, and 13 000 wavefronts adding to its one word queued up for
 //  ~ 11 ns each; the look is a possibly stale view of a counter that only grows -- a stale read costs an add, never a wrong answer)
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void ccLabelCountKernel( const uint8_t* __restrict__ raw, const uint32_t* __restrict__ parent,
-                                                              const uint32_t* __restrict__ lab, uint32_t n, uint32_t minCount,
+                                                              const uint32_t* __restrict__ lab, const uint32_t* __restrict__ list,
+                                                              uint32_t count, uint32_t n, uint32_t minCount,
                                                               uint32_t* __restrict__ label, uint32_t* __restrict__ ccCount ) {
-  const uint32_t i    = chunkedIndex();
+  const uint32_t i    = roundPoint<LIST>( list, count, n );
   const int      lane = threadIdx.x & 63;
   const uint32_t l    = ( i < n && raw[i] ) ? lab[parent[i]] : kNoLabel;
   if ( i < n ) label[i] = l;
@@ -290,26 +314,42 @@ __global__ __launch_bounds__( 256 ) void ccLabelCountKernel( const uint8_t* __re
   }
 }
 
-__global__ __launch_bounds__( 256 ) void ccSeedFlagKernel( const uint32_t* __restrict__ label,
-                                                            const uint32_t* __restrict__ ccCount, uint32_t minCount,
-                                                            uint32_t n, uint32_t* __restrict__ flag ) {
-  const uint32_t i = chunkedIndex();
-  if ( i < n ) flag[i] = ( label[i] == i && ccCount[i] >= minCount ) ? 1u : 0u;
+// (ccCount is an accumulation: before a round labels again -- later rounds: the counts of the listed points, the only ones a label
+//  can name; round 1 clears all n with a memset)
+__global__ __launch_bounds__( 256 ) void ccClearCountKernel( const uint32_t* __restrict__ list, uint32_t count,
+                                                              uint32_t* __restrict__ ccCount ) {
+  const uint32_t j = chunkedIndex();
+  if ( j < count ) ccCount[list[j]] = 0;
 }
 
-// per point: patch (this round's rank of its component) or -1; per patch: plane of the seed
+// flag[j] = the j-th point of the pass (round 1: point j) is the seed of a component that becomes a patch; the scan over these gives
+// the patches their numbers: rank in ascending seed index, from the list as from all n points
+template <bool LIST>
+__global__ __launch_bounds__( 256 ) void ccSeedFlagKernel( const uint32_t* __restrict__ label,
+                                                            const uint32_t* __restrict__ ccCount, uint32_t minCount,
+                                                            const uint32_t* __restrict__ list, uint32_t count,
+                                                            uint32_t* __restrict__ flag ) {
+  const uint32_t j = chunkedIndex();
+  if ( j >= count ) return;
+  const uint32_t i = LIST ? list[j] : j;
+  flag[j]          = ( label[i] == i && ccCount[i] >= minCount ) ? 1u : 0u;
+}
+
+// per point: patch (this round's rank of its component) or -1; per patch: plane of the seed.  posOf[l]: where the list holds point l
+// (a label is a seed, a point still raw), which is where the scan left its rank
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void ccAssignKernel( const uint32_t* __restrict__ label,
                                                           const uint32_t* __restrict__ ccCount,
-                                                          const uint32_t* __restrict__ rank,
+                                                          const uint32_t* __restrict__ rank, const uint32_t* __restrict__ posOf,
                                                           const uint8_t* __restrict__ partition, uint32_t minCount,
-                                                          uint32_t n, int32_t* __restrict__ pointPatch,
-                                                          int32_t* __restrict__ patchView ) {
-  const uint32_t i = chunkedIndex();
+                                                          const uint32_t* __restrict__ list, uint32_t count, uint32_t n,
+                                                          int32_t* __restrict__ pointPatch, int32_t* __restrict__ patchView ) {
+  const uint32_t i = roundPoint<LIST>( list, count, n );
   if ( i >= n ) return;
   const uint32_t l = label[i];
   int32_t        p = -1;
   if ( l != kNoLabel && ccCount[l] >= minCount ) {
-    p = int32_t( rank[l] );
+    p = int32_t( rank[LIST ? posOf[l] : l] );
     if ( l == i ) patchView[p] = partition[i];
   }
   pointPatch[i] = p;
@@ -377,12 +417,13 @@ __device__ __forceinline__ void aggFlush( PatchAgg<FIELDS>& t, int32_t* __restri
   }
 }
 
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void patchMinUvKernel( const Pt* __restrict__ pts, const int32_t* __restrict__ pointPatch,
-                                                            const int32_t* __restrict__ patchView, uint32_t n,
-                                                            int32_t* __restrict__ minUv ) {
+                                                            const int32_t* __restrict__ patchView, const uint32_t* __restrict__ list,
+                                                            uint32_t count, uint32_t n, int32_t* __restrict__ minUv ) {
   __shared__ PatchAgg<2> agg;
   aggInit<2, 2>( agg );
-  const uint32_t i = chunkedIndex();
+  const uint32_t i = roundPoint<LIST>( list, count, n );
   const int32_t  p = i < n ? pointPatch[i] : -1;
   if ( p >= 0 ) {
     const int view = patchView[p] % 3;
@@ -394,13 +435,15 @@ __global__ __launch_bounds__( 256 ) void patchMinUvKernel( const Pt* __restrict_
   aggFlush<2, 2>( agg, minUv );
 }
 
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void patchTrimBboxKernel( const Pt* __restrict__ pts, const int32_t* __restrict__ patchView,
                                                                const int32_t* __restrict__ minUv, int splitting,
-                                                               int maxPatchSize, uint32_t n,
-                                                               int32_t* __restrict__ pointPatch, int32_t* __restrict__ bbox ) {
+                                                               int maxPatchSize, const uint32_t* __restrict__ list, uint32_t count,
+                                                               uint32_t n, int32_t* __restrict__ pointPatch,
+                                                               int32_t* __restrict__ bbox ) {
   __shared__ PatchAgg<6> agg;
   aggInit<6, 3>( agg );
-  const uint32_t i = chunkedIndex();
+  const uint32_t i = roundPoint<LIST>( list, count, n );
   int32_t        p = i < n ? pointPatch[i] : -1;
   if ( p >= 0 ) {
     const Pt q = pts[i];
@@ -421,11 +464,12 @@ __global__ __launch_bounds__( 256 ) void patchTrimBboxKernel( const Pt* __restri
 }
 
 // D0 candidates: 64-bit (depth << 32 | point) min (mode 0) / max (mode 1) per pixel
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void patchDepth0Kernel( const Pt* __restrict__ pts, const int32_t* __restrict__ pointPatch,
-                                                             const PatchDev* __restrict__ patches, uint32_t n,
-                                                             int64_t roundDepthBase,
+                                                             const PatchDev* __restrict__ patches, const uint32_t* __restrict__ list,
+                                                             uint32_t count, uint32_t n, int64_t roundDepthBase,
                                                              unsigned long long* __restrict__ map64 ) {
-  const uint32_t i = chunkedIndex();
+  const uint32_t i = roundPoint<LIST>( list, count, n );
   if ( i >= n ) return;
   const int32_t p = pointPatch[i];
   if ( p < 0 ) return;
@@ -510,13 +554,14 @@ __global__ __launch_bounds__( 256 ) void patchFilterTileKernel( const PatchDev* 
 }
 
 // D1: farthest same-pixel depth within surfaceThickness of D0, colour-similar to the D0 point
+template <bool LIST>
 __global__ __launch_bounds__( 256 ) void patchDepth1Kernel( const Pt* __restrict__ pts, const uint8_t* __restrict__ rgb4,
                                                              const int32_t* __restrict__ pointPatch,
-                                                             const PatchDev* __restrict__ patches, uint32_t n,
-                                                             int64_t roundDepthBase, int surfaceThickness,
+                                                             const PatchDev* __restrict__ patches, const uint32_t* __restrict__ list,
+                                                             uint32_t count, uint32_t n, int64_t roundDepthBase, int surfaceThickness,
                                                              const int32_t* __restrict__ d0tmp,
                                                              const uint32_t* __restrict__ d0src, int32_t* __restrict__ d1tmp ) {
-  const uint32_t i = chunkedIndex();
+  const uint32_t i = roundPoint<LIST>( list, count, n );
   if ( i >= n ) return;
   const int32_t p = pointPatch[i];
   if ( p < 0 ) return;
@@ -613,42 +658,49 @@ __global__ __launch_bounds__( 256 ) void patchResampleTileKernel( const PatchDev
 }
 
 // ---- S9 -------------------------------------------------------------------------------------------------
-// dist2 of every input point to the resampled cloud, exact up to the probe radius, kFar beyond it
-__global__ __launch_bounds__( 256 ) void rawDistanceKernel( const Pt* __restrict__ pts, uint32_t n,
+// dist2 of every point still raw to the resampled cloud, exact up to the probe radius, kFar beyond it.  A point that has come
+// within thrSelection is raw no longer and never will be again (the bitmap only gains bits), and its dist is not read again: later
+// rounds probe the points of the list alone.  keep[j] = the j-th point of the pass stays raw (the next list: rawListScatterKernel).
+template <bool LIST>
+__global__ __launch_bounds__( 256 ) void rawDistanceKernel( const Pt* __restrict__ pts, const uint32_t* __restrict__ list, uint32_t count,
                                                              const uint32_t* __restrict__ bitmap, int bitmapBits,
                                                              const int* __restrict__ offsets, int nOffsets,
                                                              uint32_t thrSelection, uint32_t* __restrict__ dist,
-                                                             uint8_t* __restrict__ raw, uint32_t* __restrict__ rawCount ) {
-  const uint32_t i = chunkedIndex();
-  bool           isRaw = false;
-  if ( i < n ) {
-    const Pt  q    = pts[i];
-    const int size = 1 << bitmapBits;
-    uint32_t  best = kFar;
-    for ( int o = 0; o < nOffsets; ++o ) {
-      const int packed = offsets[o];
-      const int dx = ( packed & 0xFF ) - 128, dy = ( ( packed >> 8 ) & 0xFF ) - 128, dz = ( ( packed >> 16 ) & 0xFF ) - 128;
-      const int x = q.x + dx, y = q.y + dy, z = q.z + dz;
-      if ( x < 0 || y < 0 || z < 0 || x >= size || y >= size || z >= size ) continue;
-      const size_t bit = size_t( x ) + ( size_t( y ) << bitmapBits ) + ( size_t( z ) << ( 2 * bitmapBits ) );
-      if ( bitmap[bit >> 5] & ( 1u << ( bit & 31 ) ) ) {
-        best = uint32_t( packed >> 24 );  // offsets are sorted by d2 and carry it in the top byte
-        break;
-      }
+                                                             uint8_t* __restrict__ raw, uint32_t* __restrict__ keep ) {
+  const uint32_t j = chunkedIndex();
+  if ( j >= count ) return;
+  const uint32_t i    = LIST ? list[j] : j;
+  const Pt       q    = pts[i];
+  const int      size = 1 << bitmapBits;
+  uint32_t       best = kFar;
+  for ( int o = 0; o < nOffsets; ++o ) {
+    const int packed = offsets[o];
+    const int dx = ( packed & 0xFF ) - 128, dy = ( ( packed >> 8 ) & 0xFF ) - 128, dz = ( ( packed >> 16 ) & 0xFF ) - 128;
+    const int x = q.x + dx, y = q.y + dy, z = q.z + dz;
+    if ( x < 0 || y < 0 || z < 0 || x >= size || y >= size || z >= size ) continue;
+    const size_t bit = size_t( x ) + ( size_t( y ) << bitmapBits ) + ( size_t( z ) << ( 2 * bitmapBits ) );
+    if ( bitmap[bit >> 5] & ( 1u << ( bit & 31 ) ) ) {
+      best = uint32_t( packed >> 24 );  // offsets are sorted by d2 and carry it in the top byte
+      break;
     }
-    dist[i] = best;
-    isRaw   = best > thrSelection;
-    raw[i]  = isRaw ? 1 : 0;
   }
-  // (rounds 1-5: one add per wavefront to ONE word -- 13 000 of them, ~ 11 ns each, in a queue; now folded per workgroup in LDS
-  //  and spread over kRawCounters words)
-  __shared__ uint32_t wgRaw;
-  if ( threadIdx.x == 0 ) wgRaw = 0;
-  __syncthreads();
-  const unsigned long long m = __ballot( isRaw );
-  if ( ( threadIdx.x & 63 ) == 0 && m ) atomicAdd( &wgRaw, uint32_t( __popcll( m ) ) );
-  __syncthreads();
-  if ( threadIdx.x == 0 && wgRaw ) atomicAdd( &rawCount[( blockIdx.x % kRawCounters ) * 32], wgRaw );
+  const bool isRaw = best > thrSelection;
+  dist[i]          = best;
+  raw[i]           = isRaw ? 1 : 0;
+  keep[j]          = isRaw ? 1u : 0u;
+}
+
+// The next round's list: the points that stay raw, in the order of this pass -- ascending, since the compaction is stable (pos = the
+// exclusive scan of keep, whose total is the new count); posOf[i] = where the list holds point i.
+template <bool LIST>
+__global__ __launch_bounds__( 256 ) void rawListScatterKernel( const uint32_t* __restrict__ list, uint32_t count,
+                                                                const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos,
+                                                                uint32_t* __restrict__ next, uint32_t* __restrict__ posOf ) {
+  const uint32_t j = chunkedIndex();
+  if ( j >= count || !keep[j] ) return;
+  const uint32_t i = LIST ? list[j] : j;
+  next[pos[j]]     = i;
+  posOf[i]         = pos[j];
 }
 
 }  // namespace
@@ -719,10 +771,9 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   const size_t bitmapWords = ( size_t( 1 ) << ( 3 * bitmapBits ) ) >> 5;
   TMC2_TRY( ctx->voxelBitmap.alloc( bitmapWords ) );
 
-  DevBuf<uint32_t> d_label, d_ccCount, d_flag, d_rank, d_dist, d_small, d_tilePatch, d_d0src, d_parent, d_root, d_lab;
-  DevBuf<uint8_t>  d_raw;
+  DevBuf<uint32_t> d_label, d_ccCount, d_flag, d_rank, d_dist, d_small, d_d0src, d_parent, d_root, d_lab, d_rawList[2], d_posOf;
+  DevBuf<uint8_t>  d_raw, d_tables;
   DevBuf<int32_t>  d_pointPatch, d_minUv, d_bbox, d_patchStat, d_d0tmp, d_d1tmp;
-  DevBuf<PatchDev> d_patches;
   DevBuf<unsigned long long> d_map64;
   TMC2_TRY( d_label.alloc( n ) );
   TMC2_TRY( d_parent.alloc( n ) );
@@ -734,6 +785,9 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   TMC2_TRY( d_dist.alloc( n ) );
   TMC2_TRY( d_raw.alloc( n ) );
   TMC2_TRY( d_pointPatch.alloc( n ) );
+  TMC2_TRY( d_rawList[0].alloc( n ) );
+  TMC2_TRY( d_rawList[1].alloc( n ) );
+  TMC2_TRY( d_posOf.alloc( n ) );
   TMC2_TRY( d_small.alloc( 16 ) );
   const int* d_offsets = ctx->constTable( ( uint64_t( 0x5339 ) << 32 ) | uint64_t( probeR2 ), offsets );  // (S9's probe offsets: a function of the thresholds)
   if ( !d_offsets ) return TMC2_E_HIP;
@@ -753,28 +807,45 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
   TMC2_TRY( ensureMutualMask( f ) );  // usually there already: the orientation (S3) needs the same bits
   DevBuf<uint16_t>& d_mutual   = f->d_mutual;
   const bool        agentScope = unionAgentScope( f->ctx );
-  // the union / relaxation passes: option MUTUAL_ORDER as in ensureMutualMask (grdN is a multiple of 8 blocks either way)
+  // the union / relaxation passes of round 1: option MUTUAL_ORDER as in ensureMutualMask (grdN is a multiple of 8 blocks either way)
   const PassOrder order   = passOrder( f, "MUTUAL_ORDER" );
   const bool      chunked = order.chunked;
   const uint32_t* perm    = order.perm;
-  while ( rawCount > 0 ) {
+  const uint32_t  minCount = uint32_t( sp->minPointCountPerCCPatchSegmentation );
+  // Round 1 runs every per-point pass over all n points: every one is raw.  Each round's raw-point update leaves the list of the points
+  // still raw (ascending) and their number, and the per-point passes of the later rounds run over that list (roundPoint).  What the
+  // n-wide form of a pass wrote for a point that is not raw -- lab / ccCount / parent (ccInit), label = kNoLabel (ccLabelCount), flag = 0
+  // (ccSeedFlag), pointPatch = -1 (ccAssign), dist and raw = 0 (rawDistance) -- is read by nobody: every per-point pass starts from
+  // a listed point; lab, root, ccCount and rank are looked up at roots, labels and seeds, which are raw points of this round;
+  // knn rows lead to other points only behind the test of raw[v], which rawDistance brings to 0 once; the tile passes read the depth
+  // maps, never a per-point array; and d_label, d_pointPatch, d_dist and d_raw do not outlive this call.
+  // ROUND_KERNEL: the instance of a per-point kernel this round launches (one body each, the index source a template argument)
+#define ROUND_KERNEL( name, ... ) ( listed ? name<true, ##__VA_ARGS__> : name<false, ##__VA_ARGS__> )
+  bool listed = false;
+  int  cur    = 0;  // d_rawList[cur]: this round's list (from round 2 on)
+  // A component needs minPointCountPerCCPatchSegmentation points to become a patch (reference :833), and a round without one ends
+  // the reference's loop (:900) with the patches made so far: with fewer points than that left raw the round is not queued at all.
+  while ( rawCount > 0 && rawCount >= minCount ) {
+    const uint32_t* list  = listed ? d_rawList[cur].p : nullptr;
+    const uint32_t  count = rawCount;  // (round 1: n)
+    const dim3      grd   = listed ? dim3( chunkedGrid( ( count + 255 ) / 256 ) ) : grdN;
     // ---- S7 -----------------------------------------------------------------------------------------
     StageScope cc( ctx, "patches_cc" );
-    hipLaunchKernelGGL( ccInitKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n, d_parent.p,
-                        d_lab.p, d_ccCount.p );
+    hipLaunchKernelGGL( ROUND_KERNEL( ccInitKernel, 16 ), grd, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked,
+                        list, count, n, d_parent.p, d_lab.p, d_ccCount.p );
     {
       StageScope kt( ctx, "k:ccUnion" );
-      hipLaunchKernelGGL( ccUnionKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm, chunked, n,
-                          d_parent.p, unionPrecheck( f->ctx ), agentScope );
+      hipLaunchKernelGGL( ROUND_KERNEL( ccUnionKernel, 16 ), grd, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, perm,
+                          chunked, list, count, n, d_parent.p, unionPrecheck( f->ctx ), agentScope );
       kt.end();
       if ( unionCheck( f->ctx ) ) {  // debug invariants (soak tests): costs a round trip
         TMC2_HIP( hipMemsetAsync( d_small.p + 8, 0, 8, s ) );
-        hipLaunchKernelGGL( ccCheckKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, n,
-                            d_parent.p, d_small.p + 8 );
+        hipLaunchKernelGGL( ROUND_KERNEL( ccCheckKernel, 16 ), grd, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p, list,
+                            count, n, d_parent.p, d_small.p + 8 );
         TMC2_TRY( unionCheckResult( s, d_small.p + 8, "segmentPatches: union-find invariant broken in round " + std::to_string( rounds ) ) );
       }
-      hipLaunchKernelGGL( ccFlattenSeedKernel, grdN, blk, 0, s, d_raw.p, d_dist.p, thrDet, n, d_parent.p, d_root.p, d_lab.p,
-                          agentScope );
+      hipLaunchKernelGGL( ROUND_KERNEL( ccFlattenSeedKernel ), grd, blk, 0, s, d_raw.p, d_dist.p, thrDet, list, count, n, d_parent.p,
+                          d_root.p, d_lab.p, agentScope );
     }
     // a few sweeps, then -- speculatively -- the labelling and the seed count, and ONE round trip for both answers: "did the
     // last sweep of the batch still change a label" (then sweep on and label again) and the number of patches
@@ -782,22 +853,24 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     for ( int guard = 0; guard < 1 << 20; ++guard ) {
       StageScope kt( ctx, "k:ccRelax" );
       for ( int b = 0; b < 3; ++b )
-        hipLaunchKernelGGL( ccRelaxKernel<16>, grdN, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p,
-                            d_root.p, perm, chunked, n, d_lab.p, d_small.p, ++relaxToken, agentScope );
+        hipLaunchKernelGGL( ROUND_KERNEL( ccRelaxKernel, 16 ), grd, blk, 0, s, f->d_knn.p, d_mutual.p, f->d_partition.p, d_raw.p,
+                            d_root.p, perm, chunked, list, count, n, d_lab.p, d_small.p, ++relaxToken, agentScope );
       kt.end();
-      hipLaunchKernelGGL( ccLabelCountKernel, grdN, blk, 0, s, d_raw.p, d_root.p, d_lab.p, n,
-                          uint32_t( sp->minPointCountPerCCPatchSegmentation ), d_label.p, d_ccCount.p );
-      hipLaunchKernelGGL( ccSeedFlagKernel, grdN, blk, 0, s, d_label.p, d_ccCount.p,
-                          uint32_t( sp->minPointCountPerCCPatchSegmentation ), n, d_flag.p );
+      hipLaunchKernelGGL( ROUND_KERNEL( ccLabelCountKernel ), grd, blk, 0, s, d_raw.p, d_root.p, d_lab.p, list, count, n, minCount,
+                          d_label.p, d_ccCount.p );
+      hipLaunchKernelGGL( ROUND_KERNEL( ccSeedFlagKernel ), grd, blk, 0, s, d_label.p, d_ccCount.p, minCount, list, count, d_flag.p );
       // (both answers in the context's page-locked line, stored by the scan's last tile: [0] the number of patches, [1] the token of
       //  the last sweep that changed a label -- no copy)
       volatile uint32_t* answer = ctx->answerLine( tmc2_ctx::kAnswerPatchRound );
-      TMC2_TRY( exclusiveScanU32( ctx, d_flag.p, d_rank.p, n, d_small.p + 1, ScanAnswer{answer, d_small.p, 1} ) );
+      TMC2_TRY( exclusiveScanU32( ctx, d_flag.p, d_rank.p, count, d_small.p + 1, ScanAnswer{answer, d_small.p, 1} ) );
       TMC2_HIP( hipStreamSynchronize( s ) );
       P = answer[0];
       if ( answer[1] != relaxToken ) break;
       // (ccCount is an accumulation: start it over before labelling again)
-      TMC2_HIP( hipMemsetAsync( d_ccCount.p, 0, size_t( n ) * 4, s ) );
+      if ( listed )
+        hipLaunchKernelGGL( ccClearCountKernel, grd, blk, 0, s, list, count, d_ccCount.p );
+      else
+        TMC2_HIP( hipMemsetAsync( d_ccCount.p, 0, size_t( n ) * 4, s ) );
     }
     cc.end();
     if ( P == 0 ) break;
@@ -805,19 +878,17 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     StageScope build( ctx, "patches_build" );
     TMC2_TRY( d_minUv.alloc( 2 * size_t( P ) ) );
     TMC2_TRY( d_bbox.alloc( 7 * size_t( P ) ) );           // boxes, then the views: one copy to the host
-    const size_t statWords = 2 * size_t( P ) + size_t( kRawCounters ) * 32;  // counters, then the round's counts of points still raw: one copy
+    const size_t statWords = 2 * size_t( P );
     TMC2_TRY( d_patchStat.alloc( statWords ) );
-    int32_t*  d_view     = d_bbox.p + 6 * size_t( P );
-    uint32_t* d_rawCount = reinterpret_cast<uint32_t*>( d_patchStat.p + 2 * size_t( P ) );
-    TMC2_TRY( d_patches.alloc( P ) );
-    hipLaunchKernelGGL( ccAssignKernel, grdN, blk, 0, s, d_label.p, d_ccCount.p, d_rank.p, f->d_partition.p,
-                        uint32_t( sp->minPointCountPerCCPatchSegmentation ), n, d_pointPatch.p, d_view );
-    hipLaunchKernelGGL( patchBoundsInitKernel, dim3( ( P + 255 ) / 256 ), blk, 0, s, P, d_bbox.p, d_minUv.p, d_patchStat.p,
-                        d_rawCount );
+    int32_t* d_view = d_bbox.p + 6 * size_t( P );
+    hipLaunchKernelGGL( ROUND_KERNEL( ccAssignKernel ), grd, blk, 0, s, d_label.p, d_ccCount.p, d_rank.p, d_posOf.p, f->d_partition.p,
+                        minCount, list, count, n, d_pointPatch.p, d_view );
+    hipLaunchKernelGGL( patchBoundsInitKernel, dim3( ( P + 255 ) / 256 ), blk, 0, s, P, d_bbox.p, d_minUv.p, d_patchStat.p );
     if ( sp->enablePatchSplitting )
-      hipLaunchKernelGGL( patchMinUvKernel, grdN, blk, 0, s, f->d_pts.p, d_pointPatch.p, d_view, n, d_minUv.p );
-    hipLaunchKernelGGL( patchTrimBboxKernel, grdN, blk, 0, s, f->d_pts.p, d_view, d_minUv.p,
-                        sp->enablePatchSplitting, sp->maxPatchSize, n, d_pointPatch.p, d_bbox.p );
+      hipLaunchKernelGGL( ROUND_KERNEL( patchMinUvKernel ), grd, blk, 0, s, f->d_pts.p, d_pointPatch.p, d_view, list, count, n,
+                          d_minUv.p );
+    hipLaunchKernelGGL( ROUND_KERNEL( patchTrimBboxKernel ), grd, blk, 0, s, f->d_pts.p, d_view, d_minUv.p, sp->enablePatchSplitting,
+                        sp->maxPatchSize, list, count, n, d_pointPatch.p, d_bbox.p );
     // (boxes + views, and further down the counters, land in the context's page-locked staging: plain DMA, no staging copy behind it)
     int32_t* h_records = ctx->hostRecords.get<int32_t>( std::max<size_t>( 7 * size_t( P ) + statWords, size_t( 1 ) << 16 ) );
     if ( !h_records ) {
@@ -906,31 +977,41 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     TMC2_TRY( d_d0tmp.alloc( roundArea ) );
     TMC2_TRY( d_d1tmp.alloc( roundArea ) );
     TMC2_TRY( d_d0src.alloc( roundArea ) );
-    TMC2_TRY( d_tilePatch.alloc( tiles ) );
-    TMC2_HIP( hipMemcpyAsync( d_patches.p, h_tables, size_t( P ) * sizeof( PatchDev ), hipMemcpyHostToDevice, s ) );
-    TMC2_HIP( hipMemcpyAsync( d_tilePatch.p, h_tilePatch, size_t( tiles ) * 4, hipMemcpyHostToDevice, s ) );
-    hipLaunchKernelGGL( patchInitTileKernel, dim3( tiles ), blk, 0, s, d_patches.p, d_tilePatch.p, roundDepthBase, occRes,
-                        d_map64.p );
-    hipLaunchKernelGGL( patchDepth0Kernel, grdN, blk, 0, s, f->d_pts.p, d_pointPatch.p, d_patches.p, n, roundDepthBase,
-                        d_map64.p );
-    hipLaunchKernelGGL( patchFilterTileKernel, dim3( tiles ), blk, 0, s, d_patches.p, d_tilePatch.p, d_map64.p,
-                        roundDepthBase, occRes, sp->surfaceThickness, sp->maxAllowedDepth, d_d0tmp.p, d_d1tmp.p,
-                        d_d0src.p );
+    // (both tables in one allocation, as they lie in the staging: one copy)
+    TMC2_TRY( d_tables.alloc( pdBytes + size_t( tiles ) * 4 ) );
+    const PatchDev* d_patches   = reinterpret_cast<const PatchDev*>( d_tables.p );
+    const uint32_t* d_tilePatch = reinterpret_cast<const uint32_t*>( d_tables.p + pdBytes );
+    TMC2_HIP( hipMemcpyAsync( d_tables.p, h_tables, pdBytes + size_t( tiles ) * 4, hipMemcpyHostToDevice, s ) );
+    hipLaunchKernelGGL( patchInitTileKernel, dim3( tiles ), blk, 0, s, d_patches, d_tilePatch, roundDepthBase, occRes, d_map64.p );
+    hipLaunchKernelGGL( ROUND_KERNEL( patchDepth0Kernel ), grd, blk, 0, s, f->d_pts.p, d_pointPatch.p, d_patches, list, count, n,
+                        roundDepthBase, d_map64.p );
+    hipLaunchKernelGGL( patchFilterTileKernel, dim3( tiles ), blk, 0, s, d_patches, d_tilePatch, d_map64.p, roundDepthBase, occRes,
+                        sp->surfaceThickness, sp->maxAllowedDepth, d_d0tmp.p, d_d1tmp.p, d_d0src.p );
     if ( sp->surfaceThickness > 0 )
-      hipLaunchKernelGGL( patchDepth1Kernel, grdN, blk, 0, s, f->d_pts.p, f->d_rgb.p, d_pointPatch.p, d_patches.p, n,
-                          roundDepthBase, sp->surfaceThickness, d_d0tmp.p, d_d0src.p, d_d1tmp.p );
-    hipLaunchKernelGGL( patchResampleTileKernel, dim3( tiles ), blk, 0, s, d_patches.p, d_tilePatch.p, roundDepthBase,
-                        occRes, d_d0tmp.p, d_d1tmp.p, bitmapBits, ctx->voxelBitmap.p, f->d_depth0.p, f->d_depth1.p,
-                        f->d_occupancy.p, d_patchStat.p );
-    int32_t* h_stat = h_records + 7 * size_t( P );  // (copied after the raw-point update below: its count rides along)
+      hipLaunchKernelGGL( ROUND_KERNEL( patchDepth1Kernel ), grd, blk, 0, s, f->d_pts.p, f->d_rgb.p, d_pointPatch.p, d_patches, list,
+                          count, n, roundDepthBase, sp->surfaceThickness, d_d0tmp.p, d_d0src.p, d_d1tmp.p );
+    hipLaunchKernelGGL( patchResampleTileKernel, dim3( tiles ), blk, 0, s, d_patches, d_tilePatch, roundDepthBase, occRes, d_d0tmp.p,
+                        d_d1tmp.p, bitmapBits, ctx->voxelBitmap.p, f->d_depth0.p, f->d_depth1.p, f->d_occupancy.p, d_patchStat.p );
+    int32_t* h_stat = h_records + 7 * size_t( P );
     // ---- S9 -----------------------------------------------------------------------------------------
-    hipLaunchKernelGGL( rawDistanceKernel, grdN, blk, 0, s, f->d_pts.p, n, ctx->voxelBitmap.p, bitmapBits, d_offsets,
-                        int( offsets.size() ), thrSel, d_dist.p, d_raw.p, d_rawCount );
+    // the points that stay raw, compacted (stable: ascending) into the next round's list; their number comes back in the answer line,
+    // whose content of this round (the number of patches, the sweep token) has been read
+    volatile uint32_t* answer = ctx->answerLine( tmc2_ctx::kAnswerPatchRound );
+    hipLaunchKernelGGL( ROUND_KERNEL( rawDistanceKernel ), grd, blk, 0, s, f->d_pts.p, list, count, ctx->voxelBitmap.p, bitmapBits,
+                        d_offsets, int( offsets.size() ), thrSel, d_dist.p, d_raw.p, d_flag.p );
+    const int scanned = exclusiveScanU32( ctx, d_flag.p, d_rank.p, count, nullptr, ScanAnswer{answer, nullptr, 0} );
+    if ( scanned != TMC2_OK ) {
+      (void)hipStreamSynchronize( s );  // (the copy from the staging above is queued: not left in flight)
+      return scanned;
+    }
+    hipLaunchKernelGGL( ROUND_KERNEL( rawListScatterKernel ), grd, blk, 0, s, list, count, d_flag.p, d_rank.p, d_rawList[cur ^ 1].p,
+                        d_posOf.p );
     TMC2_HIP( hipMemcpyAsync( h_stat, d_patchStat.p, statWords * 4, hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
     const uint32_t rawBefore = rawCount;
-    rawCount = 0;
-    for ( uint32_t c = 0; c < kRawCounters; ++c ) rawCount += uint32_t( h_stat[2 * size_t( P ) + size_t( c ) * 32] );
+    rawCount                 = answer[0];
+    cur ^= 1;
+    listed = true;
     build.end();
     // A pixel that passes the depth filter holds an input point that was raw and now lies on the resampled cloud, so a round with
     // one such pixel shortens the list.  A round that does not has changed nothing and would be repeated for ever (the
@@ -959,6 +1040,7 @@ int segmentPatches( tmc2_frame* f, const tmc2_segmenter_params* sp ) {
     }
     ++rounds;
   }
+#undef ROUND_KERNEL
   TMC2_HIP( hipGetLastError() );
   f->rounds      = rounds;
   f->havePatches = true;
@@ -1000,14 +1082,18 @@ extern "C" int tmc2_selftest_components( tmc2_ctx* ctx, const uint32_t* d_knn, c
   const bool      agentScope = unionAgentScope( ctx );
   hipLaunchKernelGGL( ccMutualMaskKernel<16>, dim3( chunked ? chunkedGrid( blocks ) : blocks ), dim3( 256 ), 0, s, d_knn, perm, chunked, n,
                       d_mutual.p );
-  hipLaunchKernelGGL( ccInitKernel<16>, grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, perm, chunked, n, d_parent.p, d_lab.p,
-                      d_ccCount.p );
-  hipLaunchKernelGGL( ccUnionKernel<16>, grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, perm, chunked, n, d_parent.p,
-                      unionPrecheck( ctx ), agentScope );
+  // (the round-1 form of the passes: over all n points, no list)
+  const uint32_t* noList = nullptr;
+  hipLaunchKernelGGL( ( ccInitKernel<false, 16> ), grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, perm, chunked, noList, n, n,
+                      d_parent.p, d_lab.p, d_ccCount.p );
+  hipLaunchKernelGGL( ( ccUnionKernel<false, 16> ), grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, perm, chunked, noList, n, n,
+                      d_parent.p, unionPrecheck( ctx ), agentScope );
   if ( unionCheck( ctx ) )
-    hipLaunchKernelGGL( ccCheckKernel<16>, grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, n, d_parent.p, d_bad );
+    hipLaunchKernelGGL( ( ccCheckKernel<false, 16> ), grdN, blk, 0, s, d_knn, d_mutual.p, d_partition, d_raw, noList, n, n, d_parent.p,
+                        d_bad );
   // (no point is a seed: no distance exceeds the threshold)
-  hipLaunchKernelGGL( ccFlattenSeedKernel, grdN, blk, 0, s, d_raw, d_dist.p, 0xFFFFFFFFu, n, d_parent.p, d_root, d_lab.p, agentScope );
+  hipLaunchKernelGGL( ccFlattenSeedKernel<false>, grdN, blk, 0, s, d_raw, d_dist.p, 0xFFFFFFFFu, noList, n, n, d_parent.p, d_root,
+                      d_lab.p, agentScope );
   TMC2_HIP( hipGetLastError() );
   return TMC2_OK;
 }
