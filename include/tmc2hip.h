@@ -216,6 +216,23 @@ int tmc2_segmenter_compute( tmc2_frame* f, const tmc2_segmenter_params* p );
  * tmc2_segmenter_compute end with TMC2_E_UNSUPPORTED when patch splitting keeps no point of a component, or when a round
  * takes no point off the raw list.                                                                                         */
 int tmc2_segmenter_params_check( const tmc2_segmenter_params* p );
+/* replaces: PCCPatchSegmenter3::compute with gridBasedSegmentation_ (PCCPatchSegmenter.cpp:78-149) -- the reference's fast mode
+ * (m56857): the cloud is voxelised (convertPointsToVoxels :152-181), tree, normals, orientation, initial segmentation and
+ * refinement run on the voxel cloud with p's values, partition and normals are copied back to the points (applyVoxelsDataToPoints
+ * :183-215); tree, k = 16 adjacency and segmentPatches then run on the full cloud.  p as for the plain call -- the reference's fast
+ * mode presets maxNNCountRefineSegmentation 384, iterationCountRefineSegmentation 5, voxelDimensionRefineSegmentation 2,
+ * searchRadiusRefineSegmentation 128 (PCCEncoderParameters.cpp:64-67), which apply to the voxel coordinates; weightNormal is that
+ * of the original cloud.  Afterwards the frame is what the plain call leaves: normals (copies of the voxels', bit for bit),
+ * partition, adjacency and tree of the full cloud, patches, pools.  TMC2_E_UNSUPPORTED, with the frame left as it was, for a
+ * voxelDimensionGridBasedSegmentation other than 2, 4 or 8, a voxel coordinate that does not fit geometryBitDepth3D bits (the
+ * reference's voxel names would collide; negative coordinates included) and a voxel cloud of fewer than 16 points.          */
+int tmc2_segmenter_compute_grid_based( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation );
+/* replaces: PCCPatchSegmenter3::convertPointsToVoxels (PCCPatchSegmenter.cpp:152-181) alone, on a host cloud, on the device: the
+ * voxel of a point is ( ( x + voxDim / 2 ) >> log2 voxDim, .. ) -- rounding, not floor; voxelXyz int16[n][3] takes the voxels in
+ * the order of their first point (the first *voxelCount rows are written), voxelOfPoint uint32[n] the rank of every point's voxel
+ * in that list.  Same status as the tmc2_selftest_ family: the new code on its own.  Refusals as above (bits = geometryBitDepth3D). */
+int tmc2_segmenter_convert_points_to_voxels( tmc2_ctx* ctx, const int16_t* xyz, uint64_t n, int voxDim, int bits, int16_t* voxelXyz,
+                                             uint64_t* voxelCount, uint32_t* voxelOfPoint );
 
 /* patch list of the frame (after segment_patches / compute) */
 int tmc2_frame_patch_count( tmc2_frame* f );
@@ -511,6 +528,9 @@ int tmc2_host_patch_border_filtering( const tmc2_patch* patches, int count, int 
                                       const uint8_t* occVideo, const uint16_t* geometryD0, const uint32_t* blockToPatch,
                                       int thresholdLossyOM, int passesCount, int filterSize, int log2Threshold, uint8_t* occupancy,
                                       uint8_t* border );
+/* the same rule compiled for the host (csrc/voxelize.h; no device): what tmc2_segmenter_convert_points_to_voxels is checked against */
+int tmc2_host_convert_points_to_voxels( const int16_t* xyz, uint64_t n, int voxDim, int bits, int16_t* voxelXyz, uint64_t* voxelCount,
+                                        uint32_t* voxelOfPoint );
 
 /* ---- the shared device primitives on their own (csrc/selftest.hip; DESIGN.md "primitives under test") ------------------- */
 /* What the stages are built on, reachable without a stage so that it can be compared with a plain loop at shapes no cloud produces.

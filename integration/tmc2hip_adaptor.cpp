@@ -7,6 +7,9 @@
 namespace tmc2hip {
 using namespace pcc;
 
+// the fast mode (gridBasedSegmentation_): the library takes voxels of 2, 4 and 8
+static bool gridBasedVoxelsAccepted( bool gridBased, size_t voxDim ) { return !gridBased || voxDim == 2 || voxDim == 4 || voxDim == 8; }
+
 bool toParams( const PCCPatchSegmenter3Parameters& params, tmc2_segmenter_params& p ) {
   p                                      = tmc2_segmenter_params{};
   p.nnNormalEstimation                   = int( params.nnNormalEstimation_ );
@@ -33,8 +36,9 @@ bool toParams( const PCCPatchSegmenter3Parameters& params, tmc2_segmenter_params
   p.maxAllowedDist2RawPointsSelection    = params.maxAllowedDist2RawPointsSelection_;
   p.lambdaRefineSegmentation             = params.lambdaRefineSegmentation_;
   for ( int c = 0; c < 3; ++c ) p.weightNormal[c] = params.weightNormal_[c];
-  // what the library does not mirror stays with the reference's own body
-  if ( params.gridBasedSegmentation_ || params.useEnhancedOccupancyMapCode_ || params.createSubPointCloud_ ||
+  // what the library does not mirror stays with the reference's own body (the fast mode, gridBasedSegmentation_, is mirrored for
+  // voxels of 2, 4 and 8: segmenterCompute calls tmc2_segmenter_compute_grid_based with voxelDimensionGridBasedSegmentation_)
+  if ( !gridBasedVoxelsAccepted( params.gridBasedSegmentation_, params.voxelDimensionGridBasedSegmentation_ ) || params.useEnhancedOccupancyMapCode_ || params.createSubPointCloud_ ||
        params.additionalProjectionPlaneMode_ != 0 || !params.absoluteD1_ || params.patchExpansion_ || params.surfaceSeparation_ ||
        params.highGradientSeparation_ || params.enablePointCloudPartitioning_ )
     return false;
@@ -51,7 +55,9 @@ int segmenterCompute( tmc2_ctx* ctx, const PCCPointSet3& geometry, size_t frameI
   tmc2_frame* f = nullptr;
   int         r = tmc2_frame_create( ctx, xyz.data(), rgb.empty() ? nullptr : rgb.data(), geometry.getPointCount(), &f );
   if ( r != TMC2_OK ) return r;
-  r = tmc2_segmenter_compute( f, &p );  // S1..S9
+  // S1..S9; with the flag: S1-S5 on the voxel cloud, the copy back, tree / adjacency / S6-S9 on the full cloud
+  r = params.gridBasedSegmentation_ ? tmc2_segmenter_compute_grid_based( f, &p, int( params.voxelDimensionGridBasedSegmentation_ ) )
+                                    : tmc2_segmenter_compute( f, &p );
   int64_t depthCount = 0, occCount = 0;
   if ( r == TMC2_OK ) r = tmc2_frame_patch_pool_sizes( f, &depthCount, &occCount );
   if ( r != TMC2_OK ) {
@@ -103,7 +109,7 @@ bool toParams( const PCCEncoderParameters& e, tmc2_segmenter_params& p ) {
   p.lambdaRefineSegmentation            = e.lambdaRefineSegmentation_;
   p.weightNormal[0] = p.weightNormal[1] = p.weightNormal[2] = 1.0;
   // everything of the reference the path does not mirror keeps the reference's own bodies
-  if ( e.gridBasedSegmentation_ || e.enhancedOccupancyMapCode_ || e.pointLocalReconstruction_ || e.singleMapPixelInterleaving_ ||
+  if ( !gridBasedVoxelsAccepted( e.gridBasedSegmentation_, e.voxelDimensionGridBasedSegmentation_ ) || e.enhancedOccupancyMapCode_ || e.pointLocalReconstruction_ || e.singleMapPixelInterleaving_ ||
        e.additionalProjectionPlaneMode_ != 0 || !e.absoluteD1_ || e.patchExpansion_ || e.surfaceSeparation_ ||
        e.highGradientSeparation_ || e.enablePointCloudPartitioning_ || e.rawPointsPatch_ || e.lossyRawPointsPatch_ ||
        e.multipleStreams_ || e.useEightOrientations_ || e.packingStrategy_ != 1 || e.safeGuardDistance_ != 0 ||
@@ -151,7 +157,10 @@ int EncoderDropIn::generateSegments( const PCCGroupOfFrames& sources, PCCContext
     TMC2HIP_TRY( tmc2_frame_create( ctx_, xyz.data(), rgb.empty() ? nullptr : rgb.data(), sources[i].getPointCount(), &frames_[i] ) );
     // calculateWeightNormal( geometryBitDepth3D, sources[0] ) :3569-3626: the axis weights of the whole GOF come from frame 0
     if ( i == 0 ) TMC2HIP_TRY( tmc2_weight_normal( frames_[0], p.geometryBitDepth3D, params.minWeightEPP_, p.weightNormal ) );
-    TMC2HIP_TRY( tmc2_segmenter_compute( frames_[i], &p ) );
+    if ( params.gridBasedSegmentation_ )  // the fast mode: the voxel size travels as an argument, not in the struct
+      TMC2HIP_TRY( tmc2_segmenter_compute_grid_based( frames_[i], &p, int( params.voxelDimensionGridBasedSegmentation_ ) ) );
+    else
+      TMC2HIP_TRY( tmc2_segmenter_compute( frames_[i], &p ) );
     int64_t depthCount = 0, occCount = 0;
     TMC2HIP_TRY( tmc2_frame_patch_pool_sizes( frames_[i], &depthCount, &occCount ) );
     const int               count = tmc2_frame_patch_count( frames_[i] );

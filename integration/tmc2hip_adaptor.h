@@ -26,7 +26,9 @@ namespace tmc2hip {
 void flatten( const pcc::PCCPointSet3& cloud, std::vector<int16_t>& xyz, std::vector<uint8_t>& rgb );
 
 // PCCPatchSegmenter3Parameters -> tmc2_segmenter_params; false if the parameter set uses something the library does not
-// mirror (the caller then keeps the reference's own body)
+// mirror (the caller then keeps the reference's own body).  gridBasedSegmentation_ (the fast mode) is mirrored for
+// voxelDimensionGridBasedSegmentation_ 2, 4 and 8; the struct has no field for it: segmenterCompute and
+// EncoderDropIn::generateSegments hand the voxel size to tmc2_segmenter_compute_grid_based.
 bool toParams( const pcc::PCCPatchSegmenter3Parameters& params, tmc2_segmenter_params& out );
 
 // patch records + pools (tmc2_frame_get_patches) -> the PCCPatch objects PCCPatchSegmenter3::compute would have appended
@@ -62,7 +64,8 @@ void toReconstruction( const int16_t* xyz, const uint8_t* rgb, const uint32_t* p
                        std::vector<pcc::PCCVector3<size_t>>& pointToPixelOut );
 
 // drop-in body of PCCPatchSegmenter3::compute (PCCPatchSegmenter.cpp:53-224) for the CTC lossy conditions: S1-S9 on the
-// device; the frame stays resident in *keep for the image-generation calls that follow.  Returns a tmc2 status.
+// device (with params.gridBasedSegmentation_: the fast mode, S1-S5 on the voxel cloud); the frame stays resident in *keep for the
+// image-generation calls that follow.  Returns a tmc2 status.
 int segmenterCompute( tmc2_ctx* ctx, const pcc::PCCPointSet3& geometry, size_t frameIndex,
                       const pcc::PCCPatchSegmenter3Parameters& params, std::vector<pcc::PCCPatch>& patches, tmc2_frame** keep );
 

@@ -321,7 +321,7 @@ struct tmc2_ctx {
   uint32_t* mailbox = nullptr;
   static constexpr size_t kMailboxWords = 1024;
   volatile uint32_t* answerLine( int line ) const { return mailbox + size_t( line ) * 16; }
-  enum { kAnswerRefineVoxels = 1, kAnswerPatchRound = 2, kAnswerRecon = 3, kAnswerOrientHead = 4, kAnswerTreeDepth = 5, kAnswerGeoError = 6, kAnswerAttrError = 7, kAnswerTreeLevels = 8 /* .. 12 */ };
+  enum { kAnswerRefineVoxels = 1, kAnswerPatchRound = 2, kAnswerRecon = 3, kAnswerOrientHead = 4, kAnswerTreeDepth = 5, kAnswerGeoError = 6, kAnswerAttrError = 7, kAnswerTreeLevels = 8 /* .. 12 */, kAnswerVoxelCount = 13 };
   // Per-context options (tmc2_ctx_set_option): key = the name of the knob without its TMC2_ prefix.  Filled ONCE, when the
   // context is created, from the process environment (every TMC2_* variable: the defaults); nothing in the library reads the
   // environment after that, and nothing is process-wide: two encoders of one process can run with different settings.
@@ -608,6 +608,16 @@ struct ScanAnswer {
   int                carryWords = 0;
 };
 int exclusiveScanU32( tmc2_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, size_t n, uint32_t* d_total, ScanAnswer answer = ScanAnswer() );
+// stable LSD radix sort of (key, payload) pairs, 8 bits per pass over the low `bits` bits of the keys (radix_sort.hip); the sorted
+// pairs end in (keyA, idxA) or (keyB, idxB): *inA says which
+int radixSortPairs( tmc2_ctx* ctx, uint64_t* keyA, uint32_t* idxA, uint64_t* keyB, uint32_t* idxB, uint32_t n, uint32_t bits, bool* inA );
+// convertPointsToVoxels on the device (voxelize.hip): the voxel cloud of d_pts in first-occurrence order and, per point, the rank of
+// its voxel.  maxCoord: the largest coordinate of the cloud (the caller has ruled out voxelizeRefusal, voxelize.h).  One host round
+// trip: the voxel count, through the context's mailbox.
+int voxelizeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint32_t n, int voxDim, int maxCoord, DevBuf<Pt>& d_voxelPts, DevBuf<uint32_t>& d_voxelOfPoint,
+                    uint32_t* voxelCount );
+// PCCPatchSegmenter3::compute with gridBasedSegmentation_ (voxelize.hip)
+int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim );
 // several device regions set to a byte value each in ONE launch (instead of one hipMemsetAsync per buffer)
 struct FillRegion {
   void*   p;

@@ -170,6 +170,17 @@ class _Done(list):
         self.event = threading.Event()
 
 
+def _segmenter(enc, weight, grid_based_segmentation=None):
+    """What a frame of the encoder's GOF is segmented with, as fn(frame): Frame.segmenter_compute with the encoder's CTC settings, or
+    -- grid_based_segmentation = the voxel size of the reference's fast mode -- with the four defaults the reference takes with the
+    flag (lib.fast_params) in their place and grid_based = that voxel size."""
+    if grid_based_segmentation is None:
+        params = lib.ctc_params(enc.iterations, enc.bits3d, weight, enc.vox_dim)
+        return lambda fr: fr.segmenter_compute(params)
+    params, grid = lib.fast_params(bits3d=enc.bits3d, weight=weight), int(grid_based_segmentation)
+    return lambda fr: fr.segmenter_compute(params, grid)
+
+
 class GofEncoder:
     """Phase A (S0-S16) and phase B (S17-S22) of a GOF on one GPU with `workers` concurrent frames.
     Worker w is pinned to a core of L3 domain (first_domain + w) % domains: the host-resident steps (orientation, the
@@ -284,7 +295,7 @@ class GofEncoder:
         return self._dispatch([(i % self.workers, (lambda fr=fr, i=i: fn(fr, i))) for i, fr in enumerate(frames)])
 
     def phase_a(self, frames, sharder=None, weight=None, constrained_pack=False, frame_count=None, records_chain=False,
-                then=None):
+                then=None, grid_based_segmentation=None):
         """constrained_pack: True = the low-delay condition -- frames after the first are packed against their predecessor
         (S10', a sequential chain over the GOF, microseconds per frame on the host); 2 = the random-access condition -- the same chain followed by the global patch allocation over the
         GOF (tracked patches share one place in all frames of a sub-context).  With several ranks (frame f on rank
@@ -292,23 +303,25 @@ class GofEncoder:
         packed lists come back (records_chain=True forces that route in a single process).
         then(frame, index, W, H): what a frame goes on with once the canvas size is settled and its geometry images exist (phase B,
         the copy of its canvases to the host, ...), on the frame's worker in the same pass -- the frames are independent from
-        there on, and every rendezvous of the GOF costs the wait for its slowest frame."""
+        there on, and every rendezvous of the GOF costs the wait for its slowest frame.
+        grid_based_segmentation: voxelDimensionGridBasedSegmentation (2, 4 or 8) -- every frame is segmented in the reference's fast
+        mode (Frame.segmenter_compute( fast_params, grid_based = .. )); None: the plain path."""
         sharder = sharder or Sharder()
         if constrained_pack and (sharder.world > 1 or records_chain):
-            size = self._phase_a_sharded_chain(frames, sharder, weight, int(constrained_pack), frame_count)
+            size = self._phase_a_sharded_chain(frames, sharder, weight, int(constrained_pack), frame_count, grid_based_segmentation)
             if then is not None:
                 self.per_frame(frames, lambda fr, i: then(fr, i, size[0], size[1]))
             return size
         if weight is None:
             w = frames[0].weight_normal(self.bits3d, 0.6) if sharder.rank == 0 else np.zeros(3)
             weight = sharder.broadcast_weight(w)
-        params = lib.ctc_params(self.iterations, self.bits3d, weight, self.vox_dim)
+        segment = _segmenter(self, weight, grid_based_segmentation)
 
         def segment_and_pack(fr):
-            fr.segmenter_compute(params)
+            segment(fr)
             return fr.encoder_pack_flexible(self.min_w, 2, 1.0)
         if constrained_pack:
-            self._per_worker(frames, lambda fr: fr.segmenter_compute(params))
+            self._per_worker(frames, segment)
             # the chain is sequential over the GOF; each call still runs on the worker thread that owns the frame's context
             heights = self._dispatch([(0, lambda: frames[0].encoder_pack_flexible(self.min_w, 2, 1.0))])
             for i in range(1, len(frames)):
@@ -365,14 +378,13 @@ class GofEncoder:
             self._dispatch([(i % self.workers, (lambda fr=fr, i=i: images(fr, i, size))) for i, fr in redo])
         return size
 
-    def _phase_a_sharded_chain(self, frames, sharder, weight, mode, frame_count):
+    def _phase_a_sharded_chain(self, frames, sharder, weight, mode, frame_count, grid_based_segmentation=None):
         if frame_count is None:                              # (uneven shards: the ranks need not hold equally many frames)
             frame_count = sharder.sum_count(len(frames))
         if weight is None:
             w = frames[0].weight_normal(self.bits3d, 0.6) if sharder.rank == 0 else np.zeros(3)
             weight = sharder.broadcast_weight(w)
-        params = lib.ctc_params(self.iterations, self.bits3d, weight, self.vox_dim)
-        self._per_worker(frames, lambda fr: fr.segmenter_compute(params))
+        self._per_worker(frames, _segmenter(self, weight, grid_based_segmentation))
         local = self._per_worker(frames, lambda fr: fr.get_patch_records())
         mine, tiles = sharder.pack_gof_records(local, frame_count, mode, self.min_w, self.min_h)
         self.per_frame(frames, lambda fr, i: fr.set_packing(mine[i][0], mine[i][2], mine[i][1], mine[i][3], mine[i][4]))

@@ -80,6 +80,16 @@ def ctc_params(iterations=10, bits3d=11, weight=(1.0, 1.0, 1.0), vox_dim=4):
     return p
 
 
+def fast_params(iterations=5, bits3d=11, weight=(1.0, 1.0, 1.0)):
+    """The CTC settings with the defaults the reference takes when gridBasedSegmentation is set (PCCEncoderParameters.cpp:64-67):
+    maxNNCountRefineSegmentation 384, iterationCountRefineSegmentation 5, voxelDimensionRefineSegmentation 2,
+    searchRadiusRefineSegmentation 128 -- for Frame.segmenter_compute( params, grid_based = voxDim )."""
+    p = ctc_params(iterations, bits3d, weight, vox_dim=2)
+    p.maxNNCountRefineSegmentation = 384
+    p.searchRadiusRefineSegmentation = 128
+    return p
+
+
 # TMC2_GUARD=1 (tests, bench.py --guard): every array handed to the C-ABI travels in a copy with a red zone of _GUARD bytes on
 # both sides, filled with a pattern; after the call (_check) the zones are verified -- the library wrote outside a buffer of the
 # caller's iff they changed -- and the payload is copied back.  Calls are synchronous on host buffers (the getters end with a
@@ -310,6 +320,16 @@ class Context:
         _check(self.L.tmc2_transfer_colors(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), len(c), _ptr(out)))
         return out
 
+    # PCCPatchSegmenter3::convertPointsToVoxels
+    def convert_points_to_voxels(self, xyz, vox_dim, bits3d):
+        """tmc2_segmenter_convert_points_to_voxels on a host cloud -> (voxel positions [V][3] in first-occurrence order, the rank of
+        every point's voxel [n])."""
+        a = np.ascontiguousarray(xyz, np.int16).reshape(-1, 3)
+        vox, rank, count = np.zeros((len(a), 3), np.int16), np.zeros(len(a), np.uint32), C.c_uint64()
+        _check(self.L.tmc2_segmenter_convert_points_to_voxels(self.h, _ptr(a), len(a), int(vox_dim), int(bits3d), _ptr(vox), C.byref(count),
+                                                              _ptr(rank)))
+        return vox[:count.value].copy(), rank
+
     # PCCCodec::colorSmoothing
     def color_smoothing(self, xyz, colors16, boundary, patch_index, grid_size, bits3d, thr_smoothing=10.0, thr_difference=10.0,
                         thr_variation=6.0):
@@ -500,8 +520,13 @@ class Frame:
     def segmenter_segment_patches(self, params):
         _check(self.L.tmc2_segmenter_segment_patches(self.h, C.byref(params)))
 
-    def segmenter_compute(self, params):
-        _check(self.L.tmc2_segmenter_compute(self.h, C.byref(params)))
+    def segmenter_compute(self, params, grid_based=None):
+        """PCCPatchSegmenter3::compute; grid_based = voxelDimensionGridBasedSegmentation (2, 4 or 8): the reference's fast mode --
+        S1-S5 on the voxel cloud, partition and normals copied back, tree / adjacency / patches on the full cloud."""
+        if grid_based is None:
+            _check(self.L.tmc2_segmenter_compute(self.h, C.byref(params)))
+        else:
+            _check(self.L.tmc2_segmenter_compute_grid_based(self.h, C.byref(params), int(grid_based)))
 
     def get_patches(self):
         cnt = self.L.tmc2_frame_patch_count(self.h)
@@ -1007,6 +1032,15 @@ def host_patch_border_filtering(patches, width, height, occ_precision, occ_video
     return occ, border
 
 
+def host_convert_points_to_voxels(xyz, vox_dim, bits3d):
+    """tmc2_host_convert_points_to_voxels: PCCPatchSegmenter3::convertPointsToVoxels restated on the host (no device) -> (voxel
+    positions [V][3] in first-occurrence order, the rank of every point's voxel [n])."""
+    a = np.ascontiguousarray(xyz, np.int16).reshape(-1, 3)
+    vox, rank, count = np.zeros((len(a), 3), np.int16), np.zeros(len(a), np.uint32), C.c_uint64()
+    _check(load_library().tmc2_host_convert_points_to_voxels(_ptr(a), len(a), int(vox_dim), int(bits3d), _ptr(vox), C.byref(count), _ptr(rank)))
+    return vox[:count.value].copy(), rank
+
+
 def selftest_std_sort(pairs, offsets):
     """tmc2_selftest_std_sort: the real std::sort( .., dist < dist ) on every list of pairs [total][2] = (distance, payload), list l
     = [offsets[l], offsets[l + 1]); returns the sorted copy (host only)."""
@@ -1072,6 +1106,8 @@ int tmc2_frame_set_partition(tmc2_frame*, const uint32_t*)
 int tmc2_segmenter_segment_patches(tmc2_frame*, const tmc2_segmenter_params*)
 int tmc2_segmenter_compute(tmc2_frame*, const tmc2_segmenter_params*)
 int tmc2_segmenter_params_check(const tmc2_segmenter_params*)
+int tmc2_segmenter_compute_grid_based(tmc2_frame*, const tmc2_segmenter_params*, int)
+int tmc2_segmenter_convert_points_to_voxels(tmc2_ctx*, const int16_t*, uint64_t, int, int, int16_t*, uint64_t*, uint32_t*)
 int tmc2_frame_patch_count(tmc2_frame*)
 int tmc2_frame_patch_pool_sizes(tmc2_frame*, int64_t*, int64_t*)
 int tmc2_frame_get_patches(tmc2_frame*, tmc2_patch*, int16_t*, int16_t*, uint8_t*)
@@ -1131,6 +1167,7 @@ int tmc2_host_place_segments(int, const int32_t*, tmc2_patch*, const uint8_t*, c
 int tmc2_host_orient_normals(const int16_t*, uint64_t, const uint32_t*, int, double*)
 int tmc2_host_color_smoothing(const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
 int tmc2_host_patch_border_filtering(const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, const uint32_t*, int, int, int, int, uint8_t*, uint8_t*)
+int tmc2_host_convert_points_to_voxels(const int16_t*, uint64_t, int, int, int16_t*, uint64_t*, uint32_t*)
 int tmc2_selftest_scan(tmc2_ctx*, const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, const uint32_t*, int, uint64_t)
 int tmc2_selftest_fill(tmc2_ctx*, const uint64_t*, int)
 int tmc2_selftest_work_map(tmc2_ctx*, uint64_t, int, uint64_t, uint64_t, uint32_t*, uint32_t*)
