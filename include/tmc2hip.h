@@ -568,6 +568,14 @@ int tmc2_selftest_union_find( tmc2_ctx* ctx, int parity, uint32_t* d_word, uint6
  * 0 where the depth limit was reached.  std_sort: the real std::sort( .., dist < dist ) over the same layout in HOST memory.     */
 int tmc2_selftest_cand_sort( tmc2_ctx* ctx, uint32_t* d_lists, const uint32_t* d_offsets, uint64_t lists, uint32_t* d_ok );
 int tmc2_selftest_std_sort( uint32_t* lists, const uint32_t* offsets, uint64_t count );
+/* marked cells: markedCells (csrc/cell_grid.hip) as T3 and T6 call it, over d_xyz4[M][4] (x, y, z, 0) and d_boundaryType[M] (bytes), on
+ * the grid of gridSize (even, 2 .. 64) over the cube of 2^bits (bits != 0, T6's) or over [0, maxCoord] (bits == 0, T3's); at most 2^31
+ * cells.  The eight cells around every type-1 point inside the faces are marked.  *cells (HOST): their number -- this entry waits
+ * for it.  d_bits / d_rank [ceil( w^3 / 32 )] (each may be NULL): one bit per cell in raster order, and per word the marked cells
+ * before it.  d_slots[keys]: slotOfKey of every cell key of d_keys -- its rank among the marked cells, 0xFFFFFFFF if not marked.  */
+int tmc2_selftest_marked_cells( tmc2_ctx* ctx, const int16_t* d_xyz4, const uint8_t* d_boundaryType, uint64_t M, int gridSize, int bits,
+                                int maxCoord, uint32_t* cells, uint32_t* d_bits, uint32_t* d_rank, const uint32_t* d_keys, uint64_t keys,
+                                uint32_t* d_slots );
 
 #ifdef __cplusplus
 }

@@ -16,14 +16,14 @@
 // list gives each tile its output offset, and a second pass emits with an in-tile prefix (wave scan).
 // S18 reuses the exact nanoflann-order k-NN kernel: 8-NN of every reconstructed point in the SOURCE tree (the frame's
 // own tree) and 1-NN of every source point in a tree built over the reconstruction; the backward votes are bucketed
-// per target (count, scan, fill), ordered by (distance, source index) -- the order the reference's insertion sort
-// leaves for its <=16-element lists -- and reduced in fp64 in that order.
+// per target (count, scan, fill), ordered as the reference's std::sort leaves them and reduced in fp64 in that order: the
+// device functions of color_transfer.h, which T4 (post_reconstruct.hip) runs on 16-bit colours.
 // S21: every pyramid level is an image-parallel kernel over all six planes (2 maps x RGB) at once.
 #include <algorithm>
 #include <cmath>
 
+#include "color_transfer.h"
 #include "internal.h"
-#include "cand_sort.h"
 #include "patch_border_filter.h"
 
 namespace tmc2 {
@@ -127,8 +127,6 @@ __global__ __launch_bounds__( 256 ) void reconTileKernel( const PlaceDev* __rest
 }
 
 // ---- S18 ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint8_t toU8( double v ) { return uint8_t( fmax( 0.0, fmin( round( v ), 255.0 ) ) ); }
-
 // easy: the first result of the queries that have an identical source point (0xFFFFFFFF for the others: only
 // their rows of idx8 / dist8 are filled -- launchKnnSplit)
 __global__ __launch_bounds__( 256 ) void forwardColorKernel( const uint32_t* __restrict__ idx8, const uint32_t* __restrict__ dist8,
@@ -146,39 +144,19 @@ __global__ __launch_bounds__( 256 ) void forwardColorKernel( const uint32_t* __r
   const uint4  i0 = ir[0], i1 = ir[1], d0 = dr[0], d1 = dr[1];
   const uint32_t id[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
   const uint32_t ds[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-  uchar4         out;
-  if ( ds[0] == 0 ) {  // "dist < 0.0001": an identical source point exists, take its colour
-    out = reinterpret_cast<const uchar4*>( srcRgb4 )[id[0]];
-  } else {
-    double r = 0.0, g = 0.0, b = 0.0, sw = 0.0;
-#pragma unroll
-    for ( int i = 0; i < 8; ++i ) {
-      const double w = __ddiv_rn( 1.0, double( ds[i] ) + 4.0 );
-      const uchar4 c = reinterpret_cast<const uchar4*>( srcRgb4 )[id[i]];
-      r += double( c.x ) * w;
-      g += double( c.y ) * w;
-      b += double( c.z ) * w;
-      sw += w;
-    }
-    out = make_uchar4( toU8( __ddiv_rn( r, sw ) ), toU8( __ddiv_rn( g, sw ) ), toU8( __ddiv_rn( b, sw ) ), 0 );
-  }
-  reinterpret_cast<uchar4*>( fwdRgb4 )[t] = out;
+  reinterpret_cast<uchar4*>( fwdRgb4 )[t] = forwardColor( id, ds, reinterpret_cast<const uchar4*>( srcRgb4 ) );
 }
 
-__global__ __launch_bounds__( 256 ) void backwardCountKernel( const uint32_t* __restrict__ idx1, uint32_t n,
-                                                               uint32_t* __restrict__ count ) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( s < n ) atomicAdd( &count[idx1[s]], 1u );
-}
-
-__global__ __launch_bounds__( 256 ) void backwardFillKernel( const uint32_t* __restrict__ idx1, const uint32_t* __restrict__ dist1,
-                                                              const uint32_t* __restrict__ offset, uint32_t n,
-                                                              uint32_t* __restrict__ cursor, uint2* __restrict__ entries ) {
+// source point s votes for its nearest reconstructed point.  FILL = false: count per target; FILL = true (count: a zeroed cursor):
+// place (dist, s) in the target's bucket
+template <bool FILL>
+__global__ __launch_bounds__( 256 ) void backwardVoteKernel( const uint32_t* __restrict__ idx1, const uint32_t* __restrict__ dist1, uint32_t n,
+                                                              uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
+                                                              uint2* __restrict__ entries ) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if ( s >= n ) return;
-  const uint32_t t          = idx1[s];
-  const uint32_t slot       = atomicAdd( &cursor[t], 1u );
-  entries[offset[t] + slot] = make_uint2( dist1[s], s );
+  const uint32_t t = idx1[s], slot = atomicAdd( &count[t], 1u );
+  if ( FILL ) entries[offset[t] + slot] = make_uint2( dist1[s], s );
 }
 
 __global__ __launch_bounds__( 256 ) void combineColorKernel( const uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
@@ -193,40 +171,10 @@ __global__ __launch_bounds__( 256 ) void combineColorKernel( const uint32_t* __r
     return;
   }
   uint2* e = entries + offset[t];
-  // (a) source-index order (keys unique): plain insertion sort
-  for ( int i = 1; i < n; ++i ) {
-    const uint2 v = e[i];
-    int         k = i - 1;
-    while ( k >= 0 && e[k].y > v.y ) {
-      e[k + 1] = e[k];
-      --k;
-    }
-    e[k + 1] = v;
-  }
-  // (b) std::sort by distance
-  const CandSort cs{e};
-  if ( !cs.sort( n ) ) *error = 1;
-  double r = 0.0, g = 0.0, b = 0.0, sw = 0.0;
-  if ( e[0].x == 0 || n == 1 ) {  // an identical source point, or a single candidate: its colour, unweighted
-    const uchar4 c = reinterpret_cast<const uchar4*>( srcRgb4 )[e[0].y];
-    r = double( c.x ), g = double( c.y ), b = double( c.z );
-  } else {
-    for ( int k = 0; k < n; ++k ) {
-      const uchar4 c = reinterpret_cast<const uchar4*>( srcRgb4 )[e[k].y];
-      const double w = __ddiv_rn( 1.0, __dsqrt_rn( double( e[k].x ) ) + 4.0 );
-      r += double( c.x ) * w;
-      g += double( c.y ) * w;
-      b += double( c.z ) * w;
-      sw += w;
-    }
-    r = __ddiv_rn( r, sw );
-    g = __ddiv_rn( g, sw );
-    b = __ddiv_rn( b, sw );
-  }
-  const uchar4 f = reinterpret_cast<const uchar4*>( fwdRgb4 )[t];
-  // fixWeight: w = 0  ->  round( 0 * centroid1 + 1 * centroid2 )
-  reinterpret_cast<uchar4*>( outRgb4 )[t] = make_uchar4( toU8( 0.0 * double( f.x ) + 1.0 * r ), toU8( 0.0 * double( f.y ) + 1.0 * g ),
-                                                         toU8( 0.0 * double( f.z ) + 1.0 * b ), 0 );
+  if ( !orderCandidates( e, n ) ) *error = 1;
+  // an identical source point comes first and counts alone, unweighted, like a single candidate
+  const ColorSum c = backwardColor( e, e[0].x == 0 ? 1 : n, reinterpret_cast<const uchar4*>( srcRgb4 ), []( uint32_t source ) { return source; } );
+  reinterpret_cast<uchar4*>( outRgb4 )[t] = combinedColor( reinterpret_cast<const uchar4*>( fwdRgb4 )[t], c );
 }
 
 // ---- S20 ------------------------------------------------------------------------------------------------
@@ -486,9 +434,9 @@ int transferColorsDevice( tmc2_ctx* ctx, const TreeDev& srcTree, const Pt* d_src
   TMC2_TRY( fillRegions( ctx, {{d_count.p, size_t( M ) * 4, 0}, {d_cursor.p, size_t( M ) * 4, 0}, {d_error, 4, 0}} ) );
   const dim3 grdM( ( M + 255 ) / 256 ), grdN( ( n + 255 ) / 256 );
   hipLaunchKernelGGL( forwardColorKernel, grdM, blk, 0, s, d_idx8.p, d_dist8.p, d_easy8.p, d_srcRgb4, M, d_fwd.p );
-  hipLaunchKernelGGL( backwardCountKernel, grdN, blk, 0, s, d_idx1.p, n, d_count.p );
+  hipLaunchKernelGGL( backwardVoteKernel<false>, grdN, blk, 0, s, d_idx1.p, d_dist1.p, n, d_count.p, d_offset.p, d_entries.p );
   TMC2_TRY( exclusiveScanU32( ctx, d_count.p, d_offset.p, M, nullptr ) );
-  hipLaunchKernelGGL( backwardFillKernel, grdN, blk, 0, s, d_idx1.p, d_dist1.p, d_offset.p, n, d_cursor.p, d_entries.p );
+  hipLaunchKernelGGL( backwardVoteKernel<true>, grdN, blk, 0, s, d_idx1.p, d_dist1.p, n, d_cursor.p, d_offset.p, d_entries.p );
   hipLaunchKernelGGL( combineColorKernel, grdM, blk, 0, s, d_count.p, d_offset.p, d_entries.p, d_srcRgb4, d_fwd.p, M,
                       d_outRgb4, d_error );
   TMC2_HIP( hipGetLastError() );

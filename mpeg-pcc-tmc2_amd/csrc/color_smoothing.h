@@ -1,6 +1,6 @@
 // color_smoothing.h -- the arithmetic of T6 (PCCCodec::colorSmoothing, PccLibCommon/source/PCCCodec.cpp:151-238) that the device
-// kernels (color_smoothing.hip) and the host restatement (color_smoothing_host.cpp) share word for word: the grid geometry,
-// the verdict on one cell (mean against median of its lumas) and the filter of one point (gridFilteringColor :1193-1277 +
+// kernels (color_smoothing.hip) and the host restatement (color_smoothing_host.cpp) share word for word, on the grid of
+// cell_grid.h: the verdict on one cell (mean against median of its lumas) and the filter of one point (gridFilteringColor :1193-1277 +
 // smoothPointCloudColorLC :1279-1317).  Everything is fp64 on values that fit an int, divided with one rounding.
 //
 // The three abs() of the reference take a double and are the INTEGER abs (the difference is truncated toward zero first):
@@ -8,18 +8,10 @@
 #pragma once
 #include <cstdint>
 
-#if defined( __HIPCC__ )
-#include <hip/hip_runtime.h>
-#define TMC2_CS_HD __host__ __device__ __forceinline__
-#else
-#define TMC2_CS_HD inline
-#endif
+#include "cell_grid.h"
 
 namespace tmc2 {
 
-struct ColorGrid {
-  int gridSize, half, w, disth, th;  // th = 2^geometryBitDepth3D, w = th / gridSize cells a side
-};
 // gridSize 2 / 4 / 8 / 16 and 3D bit depths whose grid has at most 2^31 cells (the reference names a cell by an int)
 inline bool colorGridSupported( int gridSize, int bits3d ) {
   if ( gridSize != 2 && gridSize != 4 && gridSize != 8 && gridSize != 16 ) return false;
@@ -27,38 +19,17 @@ inline bool colorGridSupported( int gridSize, int bits3d ) {
   const uint64_t w = ( uint64_t( 1 ) << bits3d ) / uint64_t( gridSize );
   return w * w * w <= ( uint64_t( 1 ) << 31 );
 }
-inline ColorGrid makeColorGrid( int gridSize, int bits3d ) {
-  ColorGrid g;
-  g.gridSize = gridSize, g.half = gridSize / 2;
-  g.th    = 1 << bits3d;
-  g.w     = g.th / gridSize;
-  g.disth = g.half > 1 ? g.half : 1;
-  return g;
-}
-TMC2_CS_HD bool csInCube( const ColorGrid& g, int x, int y, int z ) {
+TMC2_HD bool csInCube( const CellGrid& g, int x, int y, int z ) {
   return x >= 0 && y >= 0 && z >= 0 && x < g.th && y < g.th && z < g.th;
 }
-// too close to a face of the cube: such a point marks nothing and is not filtered
-TMC2_CS_HD bool csOutside( const ColorGrid& g, int x, int y, int z ) {
-  return x < g.disth || y < g.disth || z < g.disth || g.th <= x + g.disth || g.th <= y + g.disth || g.th <= z + g.disth;
-}
-// lower corner of the 2x2x2 cells around a coordinate (as T3's lowerCell)
-TMC2_CS_HD int csLowerCell( const ColorGrid& g, int p ) {
-  const int c = p / g.gridSize;
-  return c + ( ( p - c * g.gridSize < g.half ) ? -1 : 0 );
-}
-TMC2_CS_HD uint32_t csCellKey( const ColorGrid& g, int cx, int cy, int cz ) {
-  return ( uint32_t( cz ) * uint32_t( g.w ) + uint32_t( cy ) ) * uint32_t( g.w ) + uint32_t( cx );
-}
-
-TMC2_CS_HD double csDiv( double a, double b ) {
+TMC2_HD double csDiv( double a, double b ) {
 #if defined( __HIP_DEVICE_COMPILE__ )
   return __ddiv_rn( a, b );
 #else
   return a / b;
 #endif
 }
-TMC2_CS_HD double csIntAbs( double v ) {  // abs( int( v ) ): what the reference's abs() on a double is
+TMC2_HD double csIntAbs( double v ) {  // abs( int( v ) ): what the reference's abs() on a double is
   const int t = int( v );
   return double( t < 0 ? -t : t );
 }
@@ -75,7 +46,7 @@ constexpr uint32_t kCellMaxCount = 65535u;       // colorGridCount is a uint16_t
 constexpr uint32_t kCellExactSum = 1u << 24;     // below it a float sum of integers is exact in any order
 
 // lumaSum: exact sum of the cell's lumas; medianLo / medianHi: its values of rank n/2 - 1 and n/2 in sorted order
-TMC2_CS_HD uint32_t csCellFlags( uint32_t count, uint64_t lumaSum, uint32_t medianLo, uint32_t medianHi, bool twoPatches,
+TMC2_HD uint32_t csCellFlags( uint32_t count, uint64_t lumaSum, uint32_t medianLo, uint32_t medianHi, bool twoPatches,
                                  double thresholdColorVariation ) {
   uint32_t flags = twoPatches ? kCellDoSmooth : 0u;
   if ( count > 1 ) {
@@ -89,9 +60,9 @@ TMC2_CS_HD uint32_t csCellFlags( uint32_t count, uint64_t lumaSum, uint32_t medi
 // The filter of one boundary point inside the faces.  cellAt( cx, cy, cz ) returns the ColorCell of a grid cell (count 0 for
 // one that holds nothing).  Returns true and the new colour when the point changes.
 template <typename CellAt>
-TMC2_CS_HD bool csFilterPoint( const ColorGrid& g, const int P[3], const uint16_t own[3], const CellAt& cellAt, double thresholdSmoothing,
+TMC2_HD bool csFilterPoint( const CellGrid& g, const int P[3], const uint16_t own[3], const CellAt& cellAt, double thresholdSmoothing,
                                double thresholdDifference, uint16_t out[3] ) {
-  const int S[3] = {csLowerCell( g, P[0] ), csLowerCell( g, P[1] ), csLowerCell( g, P[2] )};
+  const int S[3] = {g.lowerCell( P[0] ), g.lowerCell( P[1] ), g.lowerCell( P[2] )};
   ColorCell cell[8];
   bool      other = false;
   for ( int k = 0; k < 8; ++k ) {

@@ -8,8 +8,7 @@
 //
 // The twin of T3 (post_reconstruct.hip) on colours, with three differences that shape the kernels:
 //  * the grid spans the whole cube (2^geometryBitDepth3D / gridSize cells a side, gridSize = occupancyPrecision: 512^3 at 11
-//    bits): the marked cells are one BIT each plus a rank per 32-bit word (prefix sum of the popcounts), 1 / 16 of T3's flag + slot
-//    words.  A cell's number is only a name: rank in raster order here, first touch in the reference.
+//    bits).  The marked cells are T3's form (markedCells, cell_grid.hip): one bit each plus a rank per 32-bit word.
 //  * a cell needs the median of its lumas, so the points of every marked cell are brought together first (count, prefix sum,
 //    scatter of the point indices -- the count is the only atomic) and ONE wavefront per cell makes every reduction of that
 //    cell from its segment: count, the three colour sums, "a second patch showed up", mean against median.
@@ -18,6 +17,7 @@
 // The filter of a point reads the cell table and its own colour only, so colours are rewritten in place.
 #include <algorithm>
 
+#include "cell_grid.h"
 #include "color_smoothing.h"
 #include "internal.h"
 
@@ -37,34 +37,9 @@ struct PatchSource {
   }
 };
 
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 // error words: [0] a point outside the cube, [1] the largest count of a cell beyond kCellMaxCount
-__device__ __forceinline__ uint32_t slotOfKey( const uint32_t* __restrict__ bits, const uint32_t* __restrict__ rank, uint32_t key ) {
-  const uint32_t word = bits[key >> 5], b = key & 31u;
-  if ( !( ( word >> b ) & 1u ) ) return kNoSlot;
-  return rank[key >> 5] + __popc( word & ( ( 1u << b ) - 1u ) );
-}
-
-__global__ __launch_bounds__( 256 ) void markColorCellsKernel( const Pt* __restrict__ pts, const uint8_t* __restrict__ btype, uint32_t M,
-                                                                ColorGrid g, uint32_t* __restrict__ bits ) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( i >= M || btype[i] != 1 ) return;
-  const Pt p = pts[i];
-  if ( csOutside( g, p.x, p.y, p.z ) ) return;  // (inside the faces: the eight cells lie in the grid)
-  const int qx = csLowerCell( g, p.x ), qy = csLowerCell( g, p.y ), qz = csLowerCell( g, p.z );
-  for ( int k = 0; k < 8; ++k ) {
-    const uint32_t key = csCellKey( g, qx + ( k & 1 ), qy + ( ( k >> 1 ) & 1 ), qz + ( k >> 2 ) );
-    const uint32_t bit = 1u << ( key & 31u );
-    if ( !( loadStaleOk( &bits[key >> 5] ) & bit ) ) atomicOr( &bits[key >> 5], bit );  // bits only ever get set
-  }
-}
-
-__global__ __launch_bounds__( 256 ) void popcountWordsKernel( const uint32_t* __restrict__ bits, uint32_t* __restrict__ rank, uint32_t words ) {
-  for ( uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x ) rank[i] = __popc( bits[i] );
-}
-
 // every point (any boundary type) whose own cell is marked belongs to that cell
-__global__ __launch_bounds__( 256 ) void countCellPointsKernel( const Pt* __restrict__ pts, uint32_t M, ColorGrid g,
+__global__ __launch_bounds__( 256 ) void countCellPointsKernel( const Pt* __restrict__ pts, uint32_t M, CellGrid g,
                                                                  const uint32_t* __restrict__ bits, const uint32_t* __restrict__ rank,
                                                                  uint32_t* __restrict__ pointSlot, uint32_t* __restrict__ cellCount,
                                                                  uint32_t* __restrict__ error ) {
@@ -75,7 +50,7 @@ __global__ __launch_bounds__( 256 ) void countCellPointsKernel( const Pt* __rest
   if ( !csInCube( g, p.x, p.y, p.z ) ) {
     error[0] = 1u;
   } else {
-    slot = slotOfKey( bits, rank, csCellKey( g, p.x / g.gridSize, p.y / g.gridSize, p.z / g.gridSize ) );
+    slot = slotOfKey( bits, rank, g.keyOfPoint( p.x, p.y, p.z ) );
     if ( slot != kNoSlot ) atomicAdd( &cellCount[slot], 1u );
   }
   pointSlot[i] = slot;
@@ -229,12 +204,12 @@ __global__ __launch_bounds__( 64 ) void cellStatsKernel( const uint32_t* __restr
 }
 
 struct CellLookup {
-  ColorGrid        g;
+  CellGrid         g;
   const uint32_t*  bits;
   const uint32_t*  rank;
   const ColorCell* table;
   __device__ __forceinline__ ColorCell operator()( int cx, int cy, int cz ) const {
-    const uint32_t slot = slotOfKey( bits, rank, csCellKey( g, cx, cy, cz ) );
+    const uint32_t slot = slotOfKey( bits, rank, g.key( cx, cy, cz ) );
     return slot == kNoSlot ? ColorCell{0u, {0.f, 0.f, 0.f}, 0u} : table[slot];
   }
 };
@@ -245,7 +220,7 @@ __global__ __launch_bounds__( 256 ) void filterColorsKernel( const Pt* __restric
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= M || btype[i] != 1 ) return;
   const Pt p = pts[i];
-  if ( csOutside( cells.g, p.x, p.y, p.z ) ) return;
+  if ( cells.g.outside( p.x, p.y, p.z ) ) return;
   const int      P[3]   = {p.x, p.y, p.z};
   const ushort4  c      = colors[i];
   const uint16_t own[3] = {c.x, c.y, c.z};
@@ -269,26 +244,18 @@ int colorSmoothingDevice( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype
                           int bits3d, double thrSmoothing, double thrDifference, double thrVariation ) {
   TMC2_TRY( checkParameters( "colorSmoothing", gridSize, bits3d ) );
   if ( M == 0 ) return TMC2_OK;
-  hipStream_t     s = ctx->stream;
-  const ColorGrid g = makeColorGrid( gridSize, bits3d );
-  const dim3      blk( 256 ), grdM( ( M + 255 ) / 256 );
-  const size_t    cellCount = size_t( g.w ) * g.w * g.w;
-  const uint32_t  words     = uint32_t( ( cellCount + 31 ) / 32 );
-  DevBuf<uint32_t> d_bits, d_rank, d_small, d_pointSlot, d_entries;
-  TMC2_TRY( d_bits.alloc( words ) );
-  TMC2_TRY( d_rank.alloc( words ) );
+  hipStream_t    s = ctx->stream;
+  const CellGrid g = cubeCellGrid( gridSize, bits3d );
+  const dim3     blk( 256 ), grdM( ( M + 255 ) / 256 );
+  MarkedCells      marked;
+  DevBuf<uint32_t> d_small, d_pointSlot, d_entries;
   TMC2_TRY( d_small.alloc( 4 ) );
   TMC2_TRY( d_pointSlot.alloc( M ) );
   TMC2_TRY( d_entries.alloc( M ) );
   StageScope stage( ctx, "color_smoothing" );
-  TMC2_HIP( hipMemsetAsync( d_bits.p, 0, size_t( words ) * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_small.p, 0, 16, s ) );
-  hipLaunchKernelGGL( markColorCellsKernel, grdM, blk, 0, s, d_pts, d_btype, M, g, d_bits.p );
-  hipLaunchKernelGGL( popcountWordsKernel, dim3( cappedBlocks( ctx, ( words + 255 ) / 256 ) ), blk, 0, s, d_bits.p, d_rank.p, words );
-  TMC2_TRY( exclusiveScanU32( ctx, d_rank.p, d_rank.p, words, d_small.p ) );
-  uint32_t cells = 0;
-  TMC2_HIP( hipMemcpyAsync( &cells, d_small.p, 4, hipMemcpyDeviceToHost, s ) );
-  TMC2_HIP( hipStreamSynchronize( s ) );
+  TMC2_TRY( markedCells( ctx, d_pts, d_btype, M, g, d_small.p, marked ) );
+  const uint32_t cells = marked.count;
   if ( cells == 0 ) return TMC2_OK;  // no boundary point inside the faces: nothing is filtered
   DevBuf<uint32_t>  d_count, d_offset, d_cursor;
   DevBuf<ColorCell> d_table;
@@ -298,14 +265,14 @@ int colorSmoothingDevice( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype
   TMC2_TRY( d_table.alloc( cells ) );
   TMC2_HIP( hipMemsetAsync( d_count.p, 0, size_t( cells ) * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_cursor.p, 0, size_t( cells ) * 4, s ) );
-  hipLaunchKernelGGL( countCellPointsKernel, grdM, blk, 0, s, d_pts, M, g, d_bits.p, d_rank.p, d_pointSlot.p, d_count.p, d_small.p + 1 );
+  hipLaunchKernelGGL( countCellPointsKernel, grdM, blk, 0, s, d_pts, M, g, marked.bits.p, marked.rank.p, d_pointSlot.p, d_count.p, d_small.p + 1 );
   TMC2_TRY( exclusiveScanU32( ctx, d_count.p, d_offset.p, cells, nullptr ) );
   hipLaunchKernelGGL( scatterCellPointsKernel, grdM, blk, 0, s, d_pointSlot.p, M, d_offset.p, d_cursor.p, d_entries.p );
   const PatchSource patches{d_patchIndex, d_pointToPixel, d_blockToPatch, Wb};
   ushort4*          colors = reinterpret_cast<ushort4*>( d_colors );
   hipLaunchKernelGGL( cellStatsKernel, dim3( uint32_t( std::min<size_t>( cells, size_t( 32 ) * ctx->cuCount ) ) ), dim3( 64 ), 0, s, d_count.p,
                       d_offset.p, cells, d_entries.p, colors, patches, thrVariation, d_table.p, d_small.p + 1 );
-  const CellLookup lookup{g, d_bits.p, d_rank.p, d_table.p};
+  const CellLookup lookup{g, marked.bits.p, marked.rank.p, d_table.p};
   hipLaunchKernelGGL( filterColorsKernel, grdM, blk, 0, s, d_pts, d_btype, M, lookup, thrSmoothing, thrDifference, colors );
   stage.end();
   uint32_t err[2] = {0, 0};

@@ -12,7 +12,7 @@
 namespace tmc2 {
 namespace {
 struct HostCells {
-  ColorGrid                    g;
+  CellGrid                     g;
   const std::vector<uint32_t>* keys;
   const std::vector<ColorCell>* table;
   long slot( uint32_t key ) const {
@@ -20,7 +20,7 @@ struct HostCells {
     return ( it != keys->end() && *it == key ) ? long( it - keys->begin() ) : -1;
   }
   ColorCell operator()( int cx, int cy, int cz ) const {
-    const long s = slot( csCellKey( g, cx, cy, cz ) );
+    const long s = slot( g.key( cx, cy, cz ) );
     return s < 0 ? ColorCell{0u, {0.f, 0.f, 0.f}, 0u} : ( *table )[size_t( s )];
   }
 };
@@ -33,7 +33,7 @@ int colorSmoothingHost( const int16_t* xyz, uint16_t* colors16, const uint16_t* 
               bits3d );
     return TMC2_E_UNSUPPORTED;
   }
-  const ColorGrid g = makeColorGrid( gridSize, bits3d );
+  const CellGrid g = cubeCellGrid( gridSize, bits3d );
   for ( uint64_t i = 0; i < M; ++i )
     if ( !csInCube( g, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] ) ) {
       setError( "host_color_smoothing: a point lies outside the cube of %d^3 (geometryBitDepth3D %d)", g.th, bits3d );
@@ -42,9 +42,9 @@ int colorSmoothingHost( const int16_t* xyz, uint16_t* colors16, const uint16_t* 
   std::vector<uint32_t> keys;
   for ( uint64_t i = 0; i < M; ++i ) {
     const int x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    if ( boundaryType[i] != 1 || csOutside( g, x, y, z ) ) continue;
-    const int qx = csLowerCell( g, x ), qy = csLowerCell( g, y ), qz = csLowerCell( g, z );
-    for ( int k = 0; k < 8; ++k ) keys.push_back( csCellKey( g, qx + ( k & 1 ), qy + ( ( k >> 1 ) & 1 ), qz + ( k >> 2 ) ) );
+    if ( boundaryType[i] != 1 || g.outside( x, y, z ) ) continue;
+    const int qx = g.lowerCell( x ), qy = g.lowerCell( y ), qz = g.lowerCell( z );
+    for ( int k = 0; k < 8; ++k ) keys.push_back( g.key( qx + ( k & 1 ), qy + ( ( k >> 1 ) & 1 ), qz + ( k >> 2 ) ) );
   }
   std::sort( keys.begin(), keys.end() );
   keys.erase( std::unique( keys.begin(), keys.end() ), keys.end() );
@@ -55,7 +55,7 @@ int colorSmoothingHost( const int16_t* xyz, uint16_t* colors16, const uint16_t* 
   std::vector<long>     slotOf( M );
   std::vector<uint32_t> offset( keys.size() + 1, 0u );
   for ( uint64_t i = 0; i < M; ++i ) {
-    slotOf[i] = cells.slot( csCellKey( g, xyz[3 * i] / gridSize, xyz[3 * i + 1] / gridSize, xyz[3 * i + 2] / gridSize ) );
+    slotOf[i] = cells.slot( g.keyOfPoint( xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] ) );
     if ( slotOf[i] >= 0 ) ++offset[size_t( slotOf[i] ) + 1];
   }
   for ( size_t c = 0; c < keys.size(); ++c ) {
@@ -89,7 +89,7 @@ int colorSmoothingHost( const int16_t* xyz, uint16_t* colors16, const uint16_t* 
   }
   for ( uint64_t i = 0; i < M; ++i ) {
     const int P[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-    if ( boundaryType[i] != 1 || csOutside( g, P[0], P[1], P[2] ) ) continue;
+    if ( boundaryType[i] != 1 || g.outside( P[0], P[1], P[2] ) ) continue;
     const uint16_t own[3] = {colors16[3 * i], colors16[3 * i + 1], colors16[3 * i + 2]};
     uint16_t       res[3];
     if ( csFilterPoint( g, P, own, cells, thrSmoothing, thrDifference, res ) )

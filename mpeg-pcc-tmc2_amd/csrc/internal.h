@@ -611,6 +611,16 @@ int exclusiveScanU32( tmc2_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, size
 // stable LSD radix sort of (key, payload) pairs, 8 bits per pass over the low `bits` bits of the keys (radix_sort.hip); the sorted
 // pairs end in (keyA, idxA) or (keyB, idxB): *inA says which
 int radixSortPairs( tmc2_ctx* ctx, uint64_t* keyA, uint32_t* idxA, uint64_t* keyB, uint32_t* idxB, uint32_t n, uint32_t bits, bool* inA );
+// head[i] = 1 where position i of a sorted key array starts a run of equal keys, else 0 (radix_sort.hip)
+int markRunHeads( tmc2_ctx* ctx, const uint64_t* d_key, uint32_t n, uint32_t* d_head );
+// The cells of a CellGrid (cell_grid.h) around the type-1 points inside the faces, one bit per cell and a rank per 32-bit word
+// (cell_grid.hip; slotOfKey reads them).  d_total: a device word for the count, which is also read back (one stream synchronise).
+struct CellGrid;
+struct MarkedCells {
+  DevBuf<uint32_t> bits, rank;
+  uint32_t         words = 0, count = 0;
+};
+int markedCells( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype, uint32_t M, const CellGrid& g, uint32_t* d_total, MarkedCells& out );
 // convertPointsToVoxels on the device (voxelize.hip): the voxel cloud of d_pts in first-occurrence order and, per point, the rank of
 // its voxel.  maxCoord: the largest coordinate of the cloud (the caller has ruled out voxelizeRefusal, voxelize.h).  One host round
 // trip: the voxel count, through the context's mailbox.

@@ -104,11 +104,7 @@ __global__ __launch_bounds__( 256 ) void positionKeysKernel( CloudView c, KeyBas
   index[i] = i;
 }
 
-// (the stable LSD radix sort of the (key, index) pairs: radixSortPairs, radix_sort.hip)
-__global__ __launch_bounds__( 256 ) void runHeadKernel( const uint64_t* __restrict__ key, uint32_t n, uint32_t* __restrict__ head ) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( i < n ) head[i] = ( i == 0 || key[i] != key[i - 1] ) ? 1u : 0u;
-}
+// (the stable LSD radix sort of the (key, index) pairs and the heads of its runs: radixSortPairs, markRunHeads, radix_sort.hip)
 // one thread per run: position of its first element, colour = integer mean over the run (removeDuplicate :188-206)
 __global__ __launch_bounds__( 256 ) void emitDistinctKernel( const uint64_t* __restrict__ key, const uint32_t* __restrict__ index,
                                                               const uint32_t* __restrict__ head, const uint32_t* __restrict__ rank,
@@ -181,7 +177,7 @@ int removeDuplicatesDevice( tmc2_ctx* ctx, const CloudView& c, DevCloud& out, De
   TMC2_TRY( radixSortPairs( ctx, d_keyA.p, d_idxA.p, d_keyB.p, d_idxB.p, n, kb.bits, &inA ) );
   const uint64_t* key = inA ? d_keyA.p : d_keyB.p;
   const uint32_t* idx = inA ? d_idxA.p : d_idxB.p;
-  hipLaunchKernelGGL( runHeadKernel, grd, blk, 0, s, key, n, d_head.p );
+  TMC2_TRY( markRunHeads( ctx, key, n, d_head.p ) );
   TMC2_TRY( exclusiveScanU32( ctx, d_head.p, d_rank.p, n, d_small.p + 6 ) );
   uint32_t distinct = 0;
   TMC2_HIP( hipMemcpyAsync( &distinct, d_small.p + 6, 4, hipMemcpyDeviceToHost, s ) );

@@ -15,17 +15,18 @@
 //  * T1: the staged 3x3 / 5x5 tests collapse to "within two pixels of the canvas border, or an unoccupied pixel in the 5x5
 //    window"; occupancy is the p x p-granular occupancy video, so a window is at most 3x3 cells.
 //  * T3: the reference numbers the boundary cells in first-touch order and sums their points in float, in point order.
-//    Cell numbers are only names (here: rank of the cell in raster order, by a prefix sum over the cell flags), and the
+//    Cell numbers are only names (here: rank of the cell in raster order -- markedCells, cell_grid.hip, shared with T6), and the
 //    float sums are sums of integers below 2^24, hence exact and order-free: integer atomics give the same value
 //    (checked: a cell whose sum or count leaves that range is reported, not guessed).  "doSmooth" (a second patch showed
 //    up in the cell) is min(patch) != max(patch).  The filter itself reads only the cell table and the point's own
 //    position, so moving points in place, as the reference does, does not couple the points.
 //  * T4 with filterType 1 touches only the moved points (a few percent): their 8-NN in the cloud before smoothing
 //    (the tree S18 built), the 1-NN of those neighbours in the smoothed cloud (one more tree), candidate lists bucketed
-//    per moved target, ordered as libstdc++'s std::sort leaves them (cand_sort.h), reduced in fp64 in that order.
+//    per moved target, ordered and reduced in fp64 by the text S18 runs (color_transfer.h), on ushort4 colours.
 #include <algorithm>
 
-#include "cand_sort.h"
+#include "cell_grid.h"
+#include "color_transfer.h"
 #include "internal.h"
 
 namespace tmc2 {
@@ -75,31 +76,6 @@ __global__ __launch_bounds__( 256 ) void colorGatherKernel( const uint32_t* __re
 }
 
 // ---- T3 ---------------------------------------------------------------------------------------------------
-struct GridGeom {
-  int gridSize, half, w, disth, th;
-};
-__device__ __forceinline__ bool outsideGrid( const GridGeom& g, int px, int py, int pz ) {
-  return px < g.disth || py < g.disth || pz < g.disth || g.th <= px + g.disth || g.th <= py + g.disth || g.th <= pz + g.disth;
-}
-// the lower corner of the 2x2x2 cells around a point: the point's cell, or the one before it in every direction in
-// which the point sits in the lower half of its cell
-__device__ __forceinline__ int lowerCell( const GridGeom& g, int p ) {
-  const int c = p / g.gridSize;
-  return c + ( ( p - c * g.gridSize < g.half ) ? -1 : 0 );
-}
-
-__global__ __launch_bounds__( 256 ) void markCellsKernel( const Pt* __restrict__ pts, const uint8_t* __restrict__ btype, uint32_t M,
-                                                           GridGeom g, uint32_t* __restrict__ cellFlag ) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( i >= M || btype[i] != 1 ) return;
-  const Pt p = pts[i];
-  if ( outsideGrid( g, p.x, p.y, p.z ) ) return;
-  const int qx = lowerCell( g, p.x ), qy = lowerCell( g, p.y ), qz = lowerCell( g, p.z );
-  for ( int dz = 0; dz < 2; ++dz )
-    for ( int dy = 0; dy < 2; ++dy )
-      for ( int dx = 0; dx < 2; ++dx ) cellFlag[( size_t( qz + dz ) * g.w + ( qy + dy ) ) * g.w + ( qx + dx )] = 1u;
-}
-
 struct CellAcc {  // one boundary cell: integer sums of its points, the patches seen
   uint32_t count, sx, sy, sz, patchMin, patchMax;
 };
@@ -111,18 +87,18 @@ __global__ __launch_bounds__( 256 ) void initCellsKernel( CellAcc* __restrict__ 
 
 __global__ __launch_bounds__( 256 ) void accumulateCellsKernel( const Pt* __restrict__ pts, const uint32_t* __restrict__ pointToPixel,
                                                                  uint32_t M, const uint32_t* __restrict__ blockToPatch, int Wb,
-                                                                 GridGeom g, const uint32_t* __restrict__ cellFlag,
-                                                                 const uint32_t* __restrict__ cellSlot, CellAcc* __restrict__ cells ) {
+                                                                 CellGrid g, const uint32_t* __restrict__ cellBits,
+                                                                 const uint32_t* __restrict__ cellRank, CellAcc* __restrict__ cells ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= M ) return;
   const Pt p = pts[i];
-  if ( outsideGrid( g, p.x, p.y, p.z ) ) return;
-  const size_t cell = ( size_t( p.z / g.gridSize ) * g.w + p.y / g.gridSize ) * g.w + p.x / g.gridSize;
-  if ( !cellFlag[cell] ) return;
+  if ( g.outside( p.x, p.y, p.z ) ) return;
+  const uint32_t slot = slotOfKey( cellBits, cellRank, g.keyOfPoint( p.x, p.y, p.z ) );
+  if ( slot == kNoSlot ) return;
   int x, y, layer;
   unpackPixel( pointToPixel[i], x, y, layer );
   const uint32_t patch = blockToPatch[size_t( y / 16 ) * Wb + x / 16];  // list position + 1 of the patch that emitted the point
-  CellAcc*       c     = cells + cellSlot[cell];
+  CellAcc*       c     = cells + slot;
   atomicAdd( &c->count, 1u );
   atomicAdd( &c->sx, uint32_t( p.x ) );
   atomicAdd( &c->sy, uint32_t( p.y ) );
@@ -131,25 +107,26 @@ __global__ __launch_bounds__( 256 ) void accumulateCellsKernel( const Pt* __rest
   if ( c->patchMax < patch ) atomicMax( &c->patchMax, patch );
 }
 
-__global__ __launch_bounds__( 256 ) void smoothGridKernel( const Pt* __restrict__ pts, uint32_t M, GridGeom g,
-                                                            const uint32_t* __restrict__ cellSlot, const CellAcc* __restrict__ cells,
-                                                            int threshold, Pt* __restrict__ out, uint8_t* __restrict__ btype,
-                                                            uint32_t* __restrict__ error ) {
+__global__ __launch_bounds__( 256 ) void smoothGridKernel( const Pt* __restrict__ pts, uint32_t M, CellGrid g,
+                                                            const uint32_t* __restrict__ cellBits, const uint32_t* __restrict__ cellRank,
+                                                            const CellAcc* __restrict__ cells, int threshold, Pt* __restrict__ out,
+                                                            uint8_t* __restrict__ btype, uint32_t* __restrict__ error ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= M ) return;
   const Pt p = pts[i];
   out[i]     = p;
-  if ( btype[i] != 1 || outsideGrid( g, p.x, p.y, p.z ) ) return;
+  if ( btype[i] != 1 || g.outside( p.x, p.y, p.z ) ) return;
   const int P[3] = {p.x, p.y, p.z};
-  const int S[3] = {lowerCell( g, P[0] ), lowerCell( g, P[1] ), lowerCell( g, P[2] )};
-  // the eight cells: count, centre (float division of the exact integer sums, as the reference's float centre)
+  const int S[3] = {g.lowerCell( P[0] ), g.lowerCell( P[1] ), g.lowerCell( P[2] )};
+  // the eight cells (all marked: the point itself marked them): count, centre (float division of the exact integer sums, as
+  // the reference's float centre)
   double c3[2][2][2][3];
   int    cnt8[2][2][2];
   bool   other = false;
   for ( int dz = 0; dz < 2; ++dz )
     for ( int dy = 0; dy < 2; ++dy )
       for ( int dx = 0; dx < 2; ++dx ) {
-        const CellAcc c = cells[cellSlot[( size_t( S[2] + dz ) * g.w + ( S[1] + dy ) ) * g.w + ( S[0] + dx )]];
+        const CellAcc c = cells[slotOfKey( cellBits, cellRank, g.key( S[0] + dx, S[1] + dy, S[2] + dz ) )];
         cnt8[dz][dy][dx] = int( c.count );
         if ( c.count > 65535u || c.sx >= ( 1u << 24 ) || c.sy >= ( 1u << 24 ) || c.sz >= ( 1u << 24 ) ) *error = 1;
         if ( c.count != 0 && c.patchMin != c.patchMax ) other = true;
@@ -212,7 +189,6 @@ __global__ __launch_bounds__( 256 ) void movedGatherKernel( const uint8_t* __res
   moved[rank[i]]   = i;
   queries[rank[i]] = pts[i];
 }
-__device__ __forceinline__ uint16_t toU16( double v ) { return uint16_t( fmax( 0.0, fmin( round( v ), 65535.0 ) ) ); }
 
 // forward colour of every moved point from its 8 nearest points of the cloud before smoothing; the neighbours'
 // positions become the queries of the backward search
@@ -227,20 +203,7 @@ __global__ __launch_bounds__( 256 ) void forwardColor16Kernel( const uint32_t* _
     ds[i]                      = dist8[size_t( r ) * 8 + i];
     partPts[size_t( r ) * 8 + i] = srcPts[id[i]];
   }
-  if ( ds[0] == 0 ) {  // "dist < 0.0001"
-    refined[r] = srcColors[id[0]];
-    return;
-  }
-  double c0 = 0.0, c1 = 0.0, c2 = 0.0, sw = 0.0;
-  for ( int i = 0; i < 8; ++i ) {
-    const double  w = __ddiv_rn( 1.0, double( ds[i] ) + 4.0 );
-    const ushort4 c = srcColors[id[i]];
-    c0 += double( c.x ) * w;
-    c1 += double( c.y ) * w;
-    c2 += double( c.z ) * w;
-    sw += w;
-  }
-  refined[r] = make_ushort4( toU16( __ddiv_rn( c0, sw ) ), toU16( __ddiv_rn( c1, sw ) ), toU16( __ddiv_rn( c2, sw ) ), 0 );
+  refined[r] = forwardColor( id, ds, srcColors );
 }
 
 __device__ __forceinline__ bool closeColors( const ushort4 a, const ushort4 b ) {
@@ -280,36 +243,8 @@ __global__ __launch_bounds__( 256 ) void combineColor16Kernel( const uint32_t* _
   const int n = int( count[r] );
   if ( n == 0 ) return;
   uint2* e = bucket + offset[r];
-  for ( int i = 1; i < n; ++i ) {  // the order in which the reference appended them: by entry number
-    const uint2 v = e[i];
-    int         k = i - 1;
-    while ( k >= 0 && e[k].y > v.y ) {
-      e[k + 1] = e[k];
-      --k;
-    }
-    e[k + 1] = v;
-  }
-  const CandSort cs{e};
-  if ( !cs.sort( n ) ) *error = 1;
-  double c0 = 0.0, c1 = 0.0, c2 = 0.0;
-  if ( n == 1 ) {
-    const ushort4 c = srcColors[idx8[e[0].y]];
-    c0 = double( c.x ), c1 = double( c.y ), c2 = double( c.z );
-  } else {
-    double sw = 0.0;
-    for ( int k = 0; k < n; ++k ) {
-      const ushort4 c = srcColors[idx8[e[k].y]];
-      const double  w = __ddiv_rn( 1.0, __dsqrt_rn( double( e[k].x ) ) + 4.0 );
-      c0 += double( c.x ) * w;
-      c1 += double( c.y ) * w;
-      c2 += double( c.z ) * w;
-      sw += w;
-    }
-    c0 = __ddiv_rn( c0, sw ), c1 = __ddiv_rn( c1, sw ), c2 = __ddiv_rn( c2, sw );
-  }
-  const ushort4 f = refined[r];  // fixWeight: w = 0  ->  round( 0 * centroid1 + 1 * centroid2 )
-  refined[r] = make_ushort4( toU16( 0.0 * double( f.x ) + 1.0 * c0 ), toU16( 0.0 * double( f.y ) + 1.0 * c1 ),
-                             toU16( 0.0 * double( f.z ) + 1.0 * c2 ), 0 );
+  if ( !orderCandidates( e, n ) ) *error = 1;
+  refined[r] = combinedColor( refined[r], backwardColor( e, n, srcColors, [idx8]( uint32_t entry ) { return idx8[entry]; } ) );
 }
 __global__ __launch_bounds__( 256 ) void scatterColor16Kernel( const uint32_t* __restrict__ moved, const ushort4* __restrict__ final16,
                                                                 uint32_t K, ushort4* __restrict__ colors16 ) {
@@ -408,36 +343,26 @@ int smoothPointCloudGrid( tmc2_frame* f, int gridSize, double thresholdSmoothing
   const dim3     blk( 256 ), grdM( ( M + 255 ) / 256 );
   // the tree over the reconstruction knows the bounding box: the grid spans [0, max coordinate]
   const int maxSize = std::max( std::max( f->reconTree.hi[0], f->reconTree.hi[1] ), f->reconTree.hi[2] );
-  GridGeom  g;
-  g.gridSize = gridSize, g.half = gridSize / 2;
-  g.w     = ( maxSize + gridSize - 1 ) / gridSize;
-  g.disth = std::max( gridSize / 2, 1 );
-  g.th    = gridSize * g.w;
+  const CellGrid g = extentCellGrid( gridSize, maxSize );
   TMC2_TRY( f->d_reconSmoothed.alloc( M ) );
-  const size_t cellCount = size_t( g.w ) * g.w * g.w;
-  if ( cellCount == 0 || cellCount > ( size_t( 1 ) << 31 ) ) {
+  if ( g.cells() == 0 || g.cells() > ( uint64_t( 1 ) << 31 ) ) {
     setError( "smoothPointCloudPostprocess: grid of %d^3 cells unsupported", g.w );
     return TMC2_E_UNSUPPORTED;
   }
-  DevBuf<uint32_t> d_flag, d_slot, d_small;
-  TMC2_TRY( d_flag.alloc( cellCount ) );
-  TMC2_TRY( d_slot.alloc( cellCount ) );
+  MarkedCells      marked;
+  DevBuf<uint32_t> d_small;
   TMC2_TRY( d_small.alloc( 4 ) );
   StageScope stage( ctx, "geometry_smoothing" );
-  TMC2_HIP( hipMemsetAsync( d_flag.p, 0, cellCount * 4, s ) );
   TMC2_HIP( hipMemsetAsync( d_small.p, 0, 16, s ) );
-  hipLaunchKernelGGL( markCellsKernel, grdM, blk, 0, s, f->d_recon.p, f->d_boundaryType.p, M, g, d_flag.p );
-  TMC2_TRY( exclusiveScanU32( ctx, d_flag.p, d_slot.p, cellCount, d_small.p ) );
-  uint32_t cells = 0;
-  TMC2_HIP( hipMemcpyAsync( &cells, d_small.p, 4, hipMemcpyDeviceToHost, s ) );
-  TMC2_HIP( hipStreamSynchronize( s ) );
+  TMC2_TRY( markedCells( ctx, f->d_recon.p, f->d_boundaryType.p, M, g, d_small.p, marked ) );
+  const uint32_t cells = marked.count;
   DevBuf<CellAcc> d_cells;
   TMC2_TRY( d_cells.alloc( std::max( cells, 1u ) ) );
   if ( cells ) hipLaunchKernelGGL( initCellsKernel, dim3( ( cells + 255 ) / 256 ), blk, 0, s, d_cells.p, cells );
   hipLaunchKernelGGL( accumulateCellsKernel, grdM, blk, 0, s, f->d_recon.p, f->d_pointToPixel.p, M, f->d_blockToPatch.p,
-                      f->canvasW / 16, g, d_flag.p, d_slot.p, d_cells.p );
-  hipLaunchKernelGGL( smoothGridKernel, grdM, blk, 0, s, f->d_recon.p, M, g, d_slot.p, d_cells.p, int( thresholdSmoothing ),
-                      f->d_reconSmoothed.p, f->d_boundaryType.p, d_small.p + 1 );
+                      f->canvasW / 16, g, marked.bits.p, marked.rank.p, d_cells.p );
+  hipLaunchKernelGGL( smoothGridKernel, grdM, blk, 0, s, f->d_recon.p, M, g, marked.bits.p, marked.rank.p, d_cells.p,
+                      int( thresholdSmoothing ), f->d_reconSmoothed.p, f->d_boundaryType.p, d_small.p + 1 );
   stage.end();
   uint32_t err = 0;
   TMC2_HIP( hipMemcpyAsync( &err, d_small.p + 1, 4, hipMemcpyDeviceToHost, s ) );

@@ -1,6 +1,7 @@
 // radix_sort.hip -- stable LSD radix sort of (64-bit key, 32-bit payload) pairs on gfx950.  Shared by the metric's lexicographic
 // de-duplication (metrics.hip: removeDuplicatesDevice) and the voxelisation of the grid-based segmentation (voxelize.hip): in a
 // STABLE sort of (key, input index) pairs the first element of a run of equal keys is the one with the smallest input index.
+// Both mark those first elements next (markRunHeads).
 #include "internal.h"
 
 namespace tmc2 {
@@ -56,6 +57,10 @@ __global__ __launch_bounds__( 256 ) void radixScatterKernel( const uint64_t* __r
     __syncthreads();
   }
 }
+__global__ __launch_bounds__( 256 ) void runHeadKernel( const uint64_t* __restrict__ key, uint32_t n, uint32_t* __restrict__ head ) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( i < n ) head[i] = ( i == 0 || key[i] != key[i - 1] ) ? 1u : 0u;
+}
 }  // namespace
 
 // keys / payload of `a` sorted; the result is in (keyA, idxA) or (keyB, idxB): returns which through *inA
@@ -77,6 +82,12 @@ int radixSortPairs( tmc2_ctx* ctx, uint64_t* keyA, uint32_t* idxA, uint64_t* key
   }
   TMC2_HIP( hipGetLastError() );
   *inA = fromA;
+  return TMC2_OK;
+}
+
+int markRunHeads( tmc2_ctx* ctx, const uint64_t* d_key, uint32_t n, uint32_t* d_head ) {
+  if ( n ) hipLaunchKernelGGL( runHeadKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_key, n, d_head );
+  TMC2_HIP( hipGetLastError() );
   return TMC2_OK;
 }
 

@@ -1,6 +1,7 @@
 // selftest.hip -- the shared device primitives, each reachable on its own through the C ABI (include/tmc2hip.h: tmc2_selftest_*),
 // so that the suite can compare them with a plain loop at shapes no test cloud produces: exclusiveScanU32 and fillRegions
-// (scan.hip), the XCD work mapping (internal.h), UnionFind<false / true> (union_find.h) and CandSort (cand_sort.h).  The entries
+// (scan.hip), the XCD work mapping (internal.h), UnionFind<false / true> (union_find.h), CandSort (cand_sort.h) and the marked
+// cells of a boundary-cell grid (cell_grid.h, cell_grid.hip; this one waits for its count, as the stages do).  The entries
 // take DEVICE pointers and queue on the context's stream without synchronising: a test queues many calls, then reads back.
 // Nothing of the product path calls into this file.  (S7's own kernels on a caller's neighbour table: tmc2_selftest_components,
 // patches.hip -- the kernels are local to that file.)
@@ -8,6 +9,7 @@
 #include <utility>
 
 #include "cand_sort.h"
+#include "cell_grid.h"
 #include "internal.h"
 #include "union_find.h"
 
@@ -83,6 +85,13 @@ __global__ __launch_bounds__( 256 ) void candSortKernel( uint2* __restrict__ lis
   if ( l >= count ) return;
   const CandSort cs{lists + offsets[l]};
   ok[l] = cs.sort( int( offsets[l + 1] - offsets[l] ) ) ? 1u : 0u;
+}
+
+// ---- slotOfKey of a caller's keys (a key beyond the grid: not marked)
+__global__ __launch_bounds__( 256 ) void slotOfKeysKernel( const uint32_t* __restrict__ bits, const uint32_t* __restrict__ rank, uint32_t cells,
+                                                            const uint32_t* __restrict__ keys, uint32_t count, uint32_t* __restrict__ slots ) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( k < count ) slots[k] = keys[k] < cells ? slotOfKey( bits, rank, keys[k] ) : kNoSlot;
 }
 
 // fillRegions takes a braced list: one call shape per count
@@ -188,6 +197,38 @@ int tmc2_selftest_cand_sort( tmc2_ctx* ctx, uint32_t* d_lists, const uint32_t* d
   ApiScope scope( ctx );
   hipLaunchKernelGGL( candSortKernel, dim3( uint32_t( ( lists + 255 ) / 256 ) ), dim3( 256 ), 0, ctx->stream, reinterpret_cast<uint2*>( d_lists ),
                       d_offsets, uint32_t( lists ), d_ok );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+int tmc2_selftest_marked_cells( tmc2_ctx* ctx, const int16_t* d_xyz4, const uint8_t* d_boundaryType, uint64_t M, int gridSize, int bits,
+                                int maxCoord, uint32_t* cells, uint32_t* d_bits, uint32_t* d_rank, const uint32_t* d_keys, uint64_t keys,
+                                uint32_t* d_slots ) {
+  using namespace tmc2;
+  if ( !ctx || !cells || ( M && ( !d_xyz4 || !d_boundaryType ) ) || M > 0x7FFFFFFFull || keys > 0x7FFFFFFFull || ( keys && ( !d_keys || !d_slots ) ) ||
+       gridSize < 2 || gridSize > 64 || ( gridSize & 1 ) || bits < 0 || bits > 14 || maxCoord < 0 || maxCoord > 32767 ) {
+    // (an odd gridSize: the upper cell of a point in the last cell before a face lies outside the grid)
+    setError( "selftest_marked_cells: invalid argument (null pointer, gridSize not even or outside 2 .. 64, bits beyond 14, maxCoord beyond 32767)" );
+    return TMC2_E_INVALID;
+  }
+  const CellGrid g = bits ? cubeCellGrid( gridSize, bits ) : extentCellGrid( gridSize, maxCoord );
+  if ( g.cells() == 0 || g.cells() > ( uint64_t( 1 ) << 31 ) ) {
+    setError( "selftest_marked_cells: a grid of %d^3 cells", g.w );
+    return TMC2_E_INVALID;
+  }
+  ApiScope         scope( ctx );
+  hipStream_t      s = ctx->stream;
+  MarkedCells      marked;
+  DevBuf<uint32_t> d_total;
+  TMC2_TRY( d_total.alloc( 1 ) );
+  TMC2_TRY( markedCells( ctx, reinterpret_cast<const Pt*>( d_xyz4 ), d_boundaryType, uint32_t( M ), g, d_total.p, marked ) );
+  *cells = marked.count;
+  if ( d_bits ) TMC2_HIP( hipMemcpyAsync( d_bits, marked.bits.p, size_t( marked.words ) * 4, hipMemcpyDeviceToDevice, s ) );
+  if ( d_rank ) TMC2_HIP( hipMemcpyAsync( d_rank, marked.rank.p, size_t( marked.words ) * 4, hipMemcpyDeviceToDevice, s ) );
+  if ( keys )
+    hipLaunchKernelGGL( slotOfKeysKernel, dim3( uint32_t( ( keys + 255 ) / 256 ) ), dim3( 256 ), 0, s, marked.bits.p, marked.rank.p,
+                        uint32_t( g.cells() ), d_keys, uint32_t( keys ), d_slots );
+  TMC2_HIP( hipStreamSynchronize( s ) );  // (the bit words and ranks go back to the pool with `marked`)
   TMC2_HIP( hipGetLastError() );
   return TMC2_OK;
 }

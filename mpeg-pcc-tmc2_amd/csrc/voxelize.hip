@@ -27,11 +27,6 @@ __global__ __launch_bounds__( 256 ) void voxelKeysKernel( const Pt* __restrict__
   key[i]     = voxelKey( voxelCoord( p.x, r ), voxelCoord( p.y, r ), voxelCoord( p.z, r ), axisBits );
   index[i]   = i;
 }
-// sorted order: head[j] = position j starts a run of equal keys
-__global__ __launch_bounds__( 256 ) void voxelRunHeadKernel( const uint64_t* __restrict__ key, uint32_t n, uint32_t* __restrict__ head ) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if ( j < n ) head[j] = ( j == 0 || key[j] != key[j - 1] ) ? 1u : 0u;
-}
 // sorted order -> input order: runFirst[run] = the run's first (smallest) point, isFirst[point] = the point is the first of its voxel
 // (headsBefore: the exclusive prefix sum of head -- at a head, the number of its run)
 __global__ __launch_bounds__( 256 ) void voxelRunFirstKernel( const uint32_t* __restrict__ head, const uint32_t* __restrict__ headsBefore,
@@ -100,7 +95,7 @@ int voxelizeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint32_t n, int voxDim, int 
   uint32_t* runFirst = inA ? d_idxB.p : d_idxA.p;
   uint32_t* isFirst  = reinterpret_cast<uint32_t*>( inA ? d_keyB.p : d_keyA.p );
   uint32_t* rank     = isFirst + n;
-  hipLaunchKernelGGL( voxelRunHeadKernel, grd, blk, 0, s, key, n, d_head.p );
+  TMC2_TRY( markRunHeads( ctx, key, n, d_head.p ) );  // head[j] = position j starts a run of equal keys
   TMC2_TRY( exclusiveScanU32( ctx, d_head.p, d_headsBefore.p, n, nullptr ) );
   hipLaunchKernelGGL( voxelRunFirstKernel, grd, blk, 0, s, d_head.p, d_headsBefore.p, index, n, runFirst, isFirst );
   volatile uint32_t* answer = ctx->answerLine( tmc2_ctx::kAnswerVoxelCount );  // (the voxel count straight to a page-locked word: no copy)

@@ -278,6 +278,14 @@ class Context:
     def selftest_cand_sort(self, d_lists, d_offsets, lists, d_ok):
         _check(self.L.tmc2_selftest_cand_sort(self.h, d_lists, d_offsets, int(lists), d_ok))
 
+    def selftest_marked_cells(self, d_xyz4, d_boundary_type, m, grid_size, bits=0, max_coord=0, d_bits=None, d_rank=None, d_keys=None,
+                              keys=0, d_slots=None):
+        """the number of marked cells (this one waits for it); bits != 0: the cube of 2^bits, else the grid over [0, max_coord]"""
+        cells = C.c_uint32(0)
+        _check(self.L.tmc2_selftest_marked_cells(self.h, d_xyz4, d_boundary_type, int(m), int(grid_size), int(bits), int(max_coord),
+                                                 C.byref(cells), d_bits, d_rank, d_keys, int(keys), d_slots))
+        return cells.value
+
     def stream(self):
         return self.L.tmc2_ctx_stream(self.h)
 
@@ -1175,4 +1183,5 @@ int tmc2_selftest_components(tmc2_ctx*, const uint32_t*, const uint8_t*, const u
 int tmc2_selftest_union_find(tmc2_ctx*, int, uint32_t*, uint64_t, const uint32_t*, uint64_t, int, int, uint32_t*, uint32_t*, uint32_t*)
 int tmc2_selftest_cand_sort(tmc2_ctx*, uint32_t*, const uint32_t*, uint64_t, uint32_t*)
 int tmc2_selftest_std_sort(uint32_t*, const uint32_t*, uint64_t)
+int tmc2_selftest_marked_cells(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, uint64_t, uint32_t*)
 """.strip().split("\n")

@@ -1,6 +1,6 @@
 """Inputs and plain references for the shared device primitives (tmc2_selftest_*: csrc/selftest.hip): the exclusive scan, the
 several-regions fill, the XCD work mapping, the two union-finds (S7's kernels over a 16-neighbour table; explicit edge lists, with
-and without parity) and CandSort.  numpy only.  tests/test_primitive_cases.py checks the references themselves (every graph family
+and without parity), CandSort and the marked cells of a boundary-cell grid.  numpy only.  tests/test_primitive_cases.py checks the references themselves (every graph family
 has a component count known in closed form); tests/test_gpu_primitives.py compares the device with them, integer for integer."""
 import functools
 
@@ -348,3 +348,66 @@ def sort_lists(count=20000, seed=0):
         pairs[lo:hi, 0] = sort_keys(kinds[l], hi - lo, rng)
         pairs[lo:hi, 1] = np.arange(hi - lo)
     return pairs, offsets
+
+
+# ---- marked cells of a boundary-cell grid (csrc/cell_grid.h, cell_grid.hip) ---------------------------------------------------
+CELL_POINTS = (1, 63, 64, 65, 4097)
+CELL_GRIDS = ((3, 16), (4, 4), (11, 6), (35, 2), (3, 64))       # (cells a side, gridSize): 27 cells = one partial word, 64 = two full words
+# (even grid sizes only: with an odd one a point in the last cell before a face has its upper cell outside the grid)
+CELL_CLOUDS = ("random", "one_cell", "near_faces", "word_ends")
+NO_SLOT = 0xFFFFFFFF
+
+
+def cell_geometry(w, grid_size):
+    """(half, disth, th) of the grid of w cells a side"""
+    half = grid_size // 2
+    return half, max(half, 1), grid_size * w
+
+
+def cell_cloud(kind, m, w, grid_size, seed=0):
+    """(xyz4 [m][4] int16 = (x, y, z, 0), boundary type [m] uint8) on the grid of w cells a side"""
+    rng = np.random.default_rng([seed, m, w, grid_size, CELL_CLOUDS.index(kind)])
+    half, disth, th = cell_geometry(w, grid_size)
+    btype = rng.choice(np.array([0, 1, 1, 3], np.uint8), m)      # types 0 and 3 among the 1s: they mark nothing
+    if kind == "random":                                          # some beyond the faces and below zero
+        p = rng.integers(-2, th + 3, (m, 3))
+    elif kind == "one_cell":                                      # every point in one inner cell, in either half of it
+        p = rng.integers(1, w - 1, 3) * grid_size + rng.integers(0, grid_size, (m, 3))
+        btype[:] = 1
+    elif kind == "near_faces":                                    # type 1 only within disth of a face; the others anywhere
+        p = rng.integers(0, th + 1, (m, 3))
+        axis, low = rng.integers(0, 3, m), rng.integers(0, 2, m).astype(bool)
+        near = np.where(low, rng.integers(0, disth, m), th - disth + rng.integers(0, disth + 1, m))
+        one = btype == 1
+        p[one, axis[one]] = near[one]
+    elif kind == "word_ends":                                     # the upper half of cells whose key sits on bit 0 or bit 31 of a word
+        key = np.arange(w ** 3)
+        cx, cy, cz = key % w, key // w % w, key // (w * w)
+        ends = key[((key % 32 == 0) | (key % 32 == 31)) & (cx < w - 1) & (cy < w - 1) & (cz < w - 1)]
+        pick = rng.choice(ends, m)
+        p = np.stack([pick % w, pick // w % w, pick // (w * w)], 1) * grid_size + rng.integers(half, grid_size, (m, 3))
+        btype[:] = 1
+    else:
+        raise ValueError(kind)
+    xyz4 = np.zeros((m, 4), np.int16)
+    xyz4[:, :3] = p
+    return xyz4, btype
+
+
+def marked_cells_reference(xyz4, btype, w, grid_size):
+    """(bit words [ceil(w^3 / 32)], marked cells before each word, slot of every key [w^3]: its rank in raster order, NO_SLOT if
+    not marked): the eight cells around every type-1 point inside the faces"""
+    half, disth, th = cell_geometry(w, grid_size)
+    p = np.asarray(xyz4)[:, :3].astype(np.int64)
+    inside = (np.asarray(btype) == 1) & np.all((p >= disth) & (p + disth < th), axis=1)
+    q = p[inside]
+    cell = q // grid_size
+    low = cell - (q - cell * grid_size < half)
+    marked = np.zeros((w ** 3 + 31) // 32 * 32, bool)
+    for k in range(8):
+        marked[((low[:, 2] + (k >> 2)) * w + low[:, 1] + ((k >> 1) & 1)) * w + low[:, 0] + (k & 1)] = True
+    bits = np.packbits(marked, bitorder="little").view(np.uint32)
+    per_word = marked.reshape(-1, 32).sum(axis=1)
+    rank = (np.cumsum(per_word) - per_word).astype(np.uint32)
+    slot = np.where(marked, np.cumsum(marked) - 1, NO_SLOT).astype(np.uint32)[:w ** 3]
+    return bits, rank, slot

@@ -1,7 +1,7 @@
 """GPU tier: the shared device primitives on their own (tmc2_selftest_*: csrc/selftest.hip, and S7's kernels in csrc/patches.hip)
 against the plain references of tests/primitive_cases.py -- the exclusive scan, the several-regions fill, the XCD work mapping,
-S7's union-find kernels on neighbour tables no cloud produces, both union-finds over explicit edge lists, and CandSort against the
-real std::sort.  Every comparison is exact integer equality.  The entries queue on the context's stream and do not wait: a test
+S7's union-find kernels on neighbour tables no cloud produces, both union-finds over explicit edge lists, CandSort against the
+real std::sort, and the marked cells of a boundary-cell grid.  Every comparison is exact integer equality.  The entries queue on the context's stream and do not wait: a test
 queues all its calls, then reads back."""
 import ctypes as C
 import threading
@@ -406,3 +406,49 @@ def test_gpu_cand_sort_is_std_sort_pair_for_pair(gpu_ctx, dev):
     assert (ok == 1).all(), np.flatnonzero(ok != 1)[:8]
     differ = np.flatnonzero((got != want).any(axis=1))
     assert len(differ) == 0, "first difference in list %d" % (np.searchsorted(offsets, differ[0], side="right") - 1)
+
+
+# ---- marked cells of a boundary-cell grid -----------------------------------------------------------------------------------
+def _marked_cells_case(ctx, dev, xyz4, btype, w, grid_size, bits, what):
+    want_bits, want_rank, want_slot = pc.marked_cells_reference(xyz4, btype, w, grid_size)
+    words, cells = len(want_bits), w ** 3
+    keys = np.concatenate([np.arange(cells, dtype=np.uint32), np.array([cells, cells + 31, 0x7FFFFFFF, pc.NO_SLOT], np.uint32)])
+    d_bits, d_rank = dev.put(np.full(words + 1, SENTINEL, np.uint32)), dev.put(np.full(words + 1, SENTINEL, np.uint32))
+    d_slots = dev.put(np.full(len(keys) + 1, SENTINEL, np.uint32))
+    count = ctx.selftest_marked_cells(dev.put(xyz4), dev.put(btype), len(xyz4), grid_size, bits, 0 if bits else grid_size * w, d_bits,
+                                      d_rank, dev.put(keys), len(keys), d_slots)
+    got_bits, got_rank = dev.get(d_bits, (words + 1,), np.uint32), dev.get(d_rank, (words + 1,), np.uint32)
+    got_slot = dev.get(d_slots, (len(keys) + 1,), np.uint32)
+    assert count == int((want_slot != pc.NO_SLOT).sum()), what
+    assert np.array_equal(got_bits[:words], want_bits) and np.array_equal(got_rank[:words], want_rank), what
+    assert np.array_equal(got_slot[:cells], want_slot) and (got_slot[cells:-1] == pc.NO_SLOT).all(), what
+    assert got_bits[words] == got_rank[words] == got_slot[-1] == SENTINEL, what
+    return count
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,grid_size", pc.CELL_GRIDS)
+def test_gpu_marked_cells_are_the_reference(gpu_ctx, dev, w, grid_size):
+    """bit words, ranks, the count and the slot of every key of the grid (and of keys beyond it) against the numpy reference: every
+    cloud at every size, on the grid over [0, gridSize * w] as T3 lays it"""
+    for kind in pc.CELL_CLOUDS:
+        for m in pc.CELL_POINTS:
+            xyz4, btype = pc.cell_cloud(kind, m, w, grid_size)
+            count = _marked_cells_case(gpu_ctx, dev, xyz4, btype, w, grid_size, 0, (w, grid_size, kind, m))
+            assert kind == "random" or (count == 0) == (kind == "near_faces"), (w, grid_size, kind, m)
+
+
+@pytest.mark.gpu
+def test_gpu_marked_cells_on_the_cube_and_without_outputs(gpu_ctx, dev):
+    """T6's grid (2^bits / gridSize cells a side); no point at all; the optional outputs left out"""
+    for grid_size, bits in ((4, 4), (2, 5), (16, 6)):
+        w = (1 << bits) // grid_size
+        for kind in ("random", "word_ends"):
+            xyz4, btype = pc.cell_cloud(kind, 4097, w, grid_size)
+            _marked_cells_case(gpu_ctx, dev, xyz4, btype, w, grid_size, bits, (grid_size, bits, kind))
+    xyz4, btype = pc.cell_cloud("random", 65, 11, 6)
+    want = int((pc.marked_cells_reference(xyz4, btype, 11, 6)[2] != pc.NO_SLOT).sum())
+    assert gpu_ctx.selftest_marked_cells(dev.put(xyz4), dev.put(btype), 65, 6, 0, 66) == want > 0
+    assert gpu_ctx.selftest_marked_cells(None, None, 0, 6, 0, 66) == 0
+    with pytest.raises(T.Tmc2Error, match="selftest_marked_cells"):
+        gpu_ctx.selftest_marked_cells(dev.put(xyz4), dev.put(btype), 65, 3, 0, 66)

@@ -166,3 +166,54 @@ def test_selftest_entries_refuse_bad_arguments_without_a_device():
     falling = np.array([0, 2, 1], np.uint32)
     pairs = np.zeros((2, 2), np.uint32)
     assert L.tmc2_selftest_std_sort(pairs.ctypes.data_as(C.c_void_p), falling.ctypes.data_as(C.c_void_p), 2) == invalid
+
+
+def test_marked_cells_reference_is_the_loop():
+    """the vectorised reference against a set filled point by point, cell by cell; the clouds hold what their names promise"""
+    for w, grid_size in pc.CELL_GRIDS:
+        half, disth, th = pc.cell_geometry(w, grid_size)
+        for kind in pc.CELL_CLOUDS:
+            for m in (1, 65, 4097) if w < 35 else (65,):
+                xyz4, btype = pc.cell_cloud(kind, m, w, grid_size)
+                bits, rank, slot = pc.marked_cells_reference(xyz4, btype, w, grid_size)
+                keys = set()
+                for (x, y, z, _), t in zip(xyz4.tolist(), btype.tolist()):
+                    if t != 1 or min(x, y, z) < disth or max(x, y, z) + disth >= th:
+                        continue
+                    lo = [c // grid_size - (1 if c % grid_size < half else 0) for c in (x, y, z)]
+                    keys |= {((lo[2] + dz) * w + lo[1] + dy) * w + lo[0] + dx for dz in (0, 1) for dy in (0, 1) for dx in (0, 1)}
+                what = (w, grid_size, kind, m)
+                assert all(0 <= k < w ** 3 for k in keys), what
+                order = sorted(keys)
+                assert np.flatnonzero(slot != pc.NO_SLOT).tolist() == order and slot[order].tolist() == list(range(len(order))), what
+                assert len(bits) == len(rank) == (w ** 3 + 31) // 32 and bits.dtype == rank.dtype == slot.dtype == np.uint32, what
+                assert [k for k in range(len(bits) * 32) if bits[k >> 5] >> (k & 31) & 1] == order, what
+                assert rank.tolist() == [sum(1 for k in order if k < 32 * i) for i in range(len(rank))], what
+                if kind == "near_faces":
+                    assert not keys and not bits.any(), what
+                if kind == "one_cell":
+                    assert len({tuple(c) for c in (xyz4[:, :3] // grid_size).tolist()}) == 1 and 8 <= len(keys) <= 27, what
+                if kind == "word_ends":
+                    assert any(k % 32 == 0 for k in keys) or any(k % 32 == 31 for k in keys), what
+                if kind == "random" and m == 4097:
+                    assert set(btype.tolist()) == {0, 1, 3} and keys and (xyz4[:, :3] < 0).any() and (xyz4[:, :3] >= th).any(), what
+    # both ends of a word, over all sizes of one grid; a type-1 point near a face in every near_faces cloud of some size
+    ends = set()
+    for m in pc.CELL_POINTS:
+        ends |= {int(k) % 32 for k in np.flatnonzero(pc.marked_cells_reference(*pc.cell_cloud("word_ends", m, 11, 6), 11, 6)[2] != pc.NO_SLOT)}
+    assert {0, 31} <= ends
+    assert all((pc.cell_cloud("near_faces", m, 4, 4)[1] == 1).any() for m in (63, 64, 65, 4097))
+    assert [w ** 3 % 32 for w, _ in pc.CELL_GRIDS] == [27, 0, 19, 27, 27]
+
+
+def test_marked_cells_entry_refuses_bad_arguments_without_a_device():
+    L = T.load_library()
+    invalid = int(re.search(r"#define TMC2_E_INVALID (-?\d+)", open(os.path.join(ROOT, "include", "tmc2hip.h")).read()).group(1))
+    p, cells = C.c_void_p(4096), C.c_uint32(0)                      # never dereferenced: every call below stops at its arguments
+    assert L.tmc2_selftest_marked_cells(None, p, p, 8, 4, 0, 64, C.byref(cells), p, p, p, 1, p) == invalid
+    assert b"selftest_marked_cells" in L.tmc2_last_error()
+    for grid_size, bits, max_coord in ((1, 0, 64), (66, 0, 640), (3, 0, 64), (4, 15, 0), (4, 0, 40000), (4, 0, -1)):
+        assert L.tmc2_selftest_marked_cells(p, p, p, 8, grid_size, bits, max_coord, C.byref(cells), p, p, p, 1, p) == invalid
+    for grid_size, bits, max_coord in ((2, 14, 0), (4, 0, 0), (16, 3, 0)):       # more than 2^31 cells, none, none
+        assert L.tmc2_selftest_marked_cells(p, p, p, 8, grid_size, bits, max_coord, C.byref(cells), p, p, p, 1, p) == invalid
+        assert b"cells" in L.tmc2_last_error()
