@@ -177,6 +177,13 @@ int  tmc2_frame_reset( tmc2_frame* f );
 /* replaces: PCCKdTree::search (PCCKdTree.cpp:61-66) for a batch of queries against the frame's tree.
  * idx = uint32[nq][k] in nanoflann result order; dist2 = uint32[nq][k] squared distances or NULL.   */
 int tmc2_kdtree_search( tmc2_frame* f, const int16_t* queries, uint64_t nq, int k, uint32_t* idx, uint32_t* dist2 );
+/* replaces: PCCKdTree::search for result counts beyond the per-lane kernel's (PCCPatchSegmenter3::computeAdjacencyInfo with
+ * maxNNCountRefineSegmentation, PCCPatchSegmenter.cpp:267-291).  queries NULL: the frame's own points (row i = point i; nq is then
+ * the frame's point count).  idx uint32[nq][k]: the k results of nanoflann's search as a SET -- the first k points under the key
+ * (squared distance, position in the query's depth-first visiting order); the order inside a row is unspecified.  Always the
+ * wave-per-query kernel (csrc/knn_wide.hip), whatever k.  TMC2_E_INVALID for k < 1 or k > the cloud, TMC2_E_UNSUPPORTED for
+ * k > 1024 and for a coordinate below -4096 (squared distances are 32-bit).                                                  */
+int tmc2_kdtree_search_wide( tmc2_frame* f, const int16_t* queries, uint64_t nq, int k, uint32_t* idx );
 
 /* ---- PCCNormalsGenerator3 ------------------------------------------------------------------- */
 /* replaces: PCCNormalsGenerator3::computeNormals (PccLibEncoder/source/PCCNormalsGenerator.cpp:158-185)
@@ -199,6 +206,13 @@ int tmc2_segmenter_initial_segmentation( tmc2_frame* f, const double weight[3] )
 /* replaces: PCCPatchSegmenter3::refineSegmentationGridBased (PCCPatchSegmenter.cpp:1386-1561).       */
 int tmc2_segmenter_refine_grid_based( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount,
                                       int voxDim, int searchRadius );
+/* replaces: PCCPatchSegmenter3::refineSegmentation (PCCPatchSegmenter.cpp:1322-1384) on the frame's normals and partition: the
+ * maxNNCount nearest neighbours of every point (tmc2_kdtree_search_wide's set), then iterationCount Jacobi rounds; a round that
+ * changes no point ends the loop on the device (later rounds are no-ops in the reference too).  The neighbourhoods are scratch of
+ * the context, n x maxNNCount x 4 bytes, grown on demand and NOT part of tmc2_ctx_reserve; the frame's k = 16 adjacency is left
+ * alone.  TMC2_E_UNSUPPORTED, with the frame left as it was, for maxNNCount outside 1..1024 or above the cloud's point count (the
+ * reference pads such rows with point 0), a negative iterationCount, a negative or NaN lambda.                                */
+int tmc2_segmenter_refine( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount );
 int tmc2_frame_get_partition( tmc2_frame* f, uint32_t* partition /* [n] */ );
 int tmc2_frame_set_partition( tmc2_frame* f, const uint32_t* partition );
 /* replaces: PCCPatchSegmenter3::segmentPatches (PCCPatchSegmenter.cpp:542-1320).                      */
@@ -227,6 +241,15 @@ int tmc2_segmenter_params_check( const tmc2_segmenter_params* p );
  * voxelDimensionGridBasedSegmentation other than 2, 4 or 8, a voxel coordinate that does not fit geometryBitDepth3D bits (the
  * reference's voxel names would collide; negative coordinates included) and a voxel cloud of fewer than 16 points.          */
 int tmc2_segmenter_compute_grid_based( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation );
+/* replaces: PCCPatchSegmenter3::compute with gridBasedRefineSegmentation_ off (:126-131).  p->gridBasedRefineSegmentation must be
+ * 0; voxelDimensionGridBasedSegmentation 0: the plain chain; 2, 4, 8: the fast mode with this refinement on the voxel cloud.
+ * tmc2_segmenter_params_check's rules apply with the one on gridBasedRefineSegmentation reversed; voxelDimensionRefineSegmentation
+ * and searchRadiusRefineSegmentation are not read; maxNNCountRefineSegmentation must lie in 1..1024 (the reference's default with
+ * the flag off is 256, with 100 iterations) and iterationCountRefineSegmentation must be >= 0.  A cloud, or a voxel cloud, of
+ * fewer than maxNNCountRefineSegmentation points is TMC2_E_UNSUPPORTED by name, with the frame left as it was, as are the
+ * refusals of tmc2_segmenter_compute_grid_based.  The neighbourhoods are context scratch outside tmc2_ctx_reserve
+ * (tmc2_segmenter_refine).                                                                                               */
+int tmc2_segmenter_compute_knn_refine( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation );
 /* replaces: PCCPatchSegmenter3::convertPointsToVoxels (PCCPatchSegmenter.cpp:152-181) alone, on a host cloud, on the device: the
  * voxel of a point is ( ( x + voxDim / 2 ) >> log2 voxDim, .. ) -- rounding, not floor; voxelXyz int16[n][3] takes the voxels in
  * the order of their first point (the first *voxelCount rows are written), voxelOfPoint uint32[n] the rank of every point's voxel
@@ -531,6 +554,11 @@ int tmc2_host_patch_border_filtering( const tmc2_patch* patches, int count, int 
 /* the same rule compiled for the host (csrc/voxelize.h; no device): what tmc2_segmenter_convert_points_to_voxels is checked against */
 int tmc2_host_convert_points_to_voxels( const int16_t* xyz, uint64_t n, int voxDim, int bits, int16_t* voxelXyz, uint64_t* voxelCount,
                                         uint32_t* voxelOfPoint );
+/* PCCPatchSegmenter3::refineSegmentation restated on the host (csrc/refine_knn_host.cpp; no device) over tmc2_host_kdtree_build's
+ * tree: normals double[n][3], partition uint32[n] in and out (labels 0..5); adjacency uint32[n][maxNNCount] takes the rows of
+ * nanoflann's search in its result order, or NULL.  Refusals as tmc2_segmenter_refine.                                    */
+int tmc2_host_refine_segmentation( const int16_t* xyz, uint64_t n, const double* normals, uint32_t* partition, int maxNNCount,
+                                   double lambda, int iterationCount, uint32_t* adjacency /* [n][maxNNCount], may be NULL */ );
 
 /* ---- the shared device primitives on their own (csrc/selftest.hip; DESIGN.md "primitives under test") ------------------- */
 /* What the stages are built on, reachable without a stage so that it can be compared with a plain loop at shapes no cloud produces.

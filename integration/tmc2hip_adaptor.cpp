@@ -10,6 +10,22 @@ using namespace pcc;
 // the fast mode (gridBasedSegmentation_): the library takes voxels of 2, 4 and 8
 static bool gridBasedVoxelsAccepted( bool gridBased, size_t voxDim ) { return !gridBased || voxDim == 2 || voxDim == 4 || voxDim == 8; }
 
+// The parameter rules of the entry a set goes to.  gridBasedRefineSegmentation_ off: tmc2_segmenter_compute_knn_refine, whose rules
+// are tmc2_segmenter_params_check's with that one reversed -- the refinement's voxel size and search radius are not read, and
+// maxNNCountRefineSegmentation must lie in 1..1024, iterationCountRefineSegmentation must not be negative.
+static bool paramsAccepted( const tmc2_segmenter_params& p ) {
+  if ( p.gridBasedRefineSegmentation ) return tmc2_segmenter_params_check( &p ) == TMC2_OK;
+  tmc2_segmenter_params q = p;
+  q.gridBasedRefineSegmentation = 1, q.voxelDimensionRefineSegmentation = 4, q.searchRadiusRefineSegmentation = 192;
+  return p.maxNNCountRefineSegmentation <= 1024 && p.iterationCountRefineSegmentation >= 0 && tmc2_segmenter_params_check( &q ) == TMC2_OK;
+}
+
+// S1..S9 by the entry the reference's two flags name; the voxel size of the fast mode travels as an argument, not in the struct
+static int computeSegments( tmc2_frame* f, const tmc2_segmenter_params& p, bool gridBased, size_t voxDim ) {
+  if ( !p.gridBasedRefineSegmentation ) return tmc2_segmenter_compute_knn_refine( f, &p, gridBased ? int( voxDim ) : 0 );
+  return gridBased ? tmc2_segmenter_compute_grid_based( f, &p, int( voxDim ) ) : tmc2_segmenter_compute( f, &p );
+}
+
 bool toParams( const PCCPatchSegmenter3Parameters& params, tmc2_segmenter_params& p ) {
   p                                      = tmc2_segmenter_params{};
   p.nnNormalEstimation                   = int( params.nnNormalEstimation_ );
@@ -42,7 +58,7 @@ bool toParams( const PCCPatchSegmenter3Parameters& params, tmc2_segmenter_params
        params.additionalProjectionPlaneMode_ != 0 || !params.absoluteD1_ || params.patchExpansion_ || params.surfaceSeparation_ ||
        params.highGradientSeparation_ || params.enablePointCloudPartitioning_ )
     return false;
-  return tmc2_segmenter_params_check( &p ) == TMC2_OK;
+  return paramsAccepted( p );
 }
 
 int segmenterCompute( tmc2_ctx* ctx, const PCCPointSet3& geometry, size_t frameIndex, const PCCPatchSegmenter3Parameters& params,
@@ -55,9 +71,9 @@ int segmenterCompute( tmc2_ctx* ctx, const PCCPointSet3& geometry, size_t frameI
   tmc2_frame* f = nullptr;
   int         r = tmc2_frame_create( ctx, xyz.data(), rgb.empty() ? nullptr : rgb.data(), geometry.getPointCount(), &f );
   if ( r != TMC2_OK ) return r;
-  // S1..S9; with the flag: S1-S5 on the voxel cloud, the copy back, tree / adjacency / S6-S9 on the full cloud
-  r = params.gridBasedSegmentation_ ? tmc2_segmenter_compute_grid_based( f, &p, int( params.voxelDimensionGridBasedSegmentation_ ) )
-                                    : tmc2_segmenter_compute( f, &p );
+  // S1..S9; with gridBasedSegmentation_: S1-S5 on the voxel cloud, the copy back, tree / adjacency / S6-S9 on the full cloud; with
+  // gridBasedRefineSegmentation_ off: the refinement over k-NN neighbourhoods (on the cloud or on the voxel cloud)
+  r = computeSegments( f, p, params.gridBasedSegmentation_, params.voxelDimensionGridBasedSegmentation_ );
   int64_t depthCount = 0, occCount = 0;
   if ( r == TMC2_OK ) r = tmc2_frame_patch_pool_sizes( f, &depthCount, &occCount );
   if ( r != TMC2_OK ) {
@@ -117,7 +133,7 @@ bool toParams( const PCCEncoderParameters& e, tmc2_segmenter_params& p ) {
        e.occupancyMapRefinement_ || e.geometryPadding_ != 0 || e.attributeBGFill_ != 1 || !e.groupDilation_ ||
        e.mapCountMinus1_ != 1 || e.globalPatchAllocation_ > 1 || ( e.globalPatchAllocation_ == 1 && !e.constrainedPack_ ) )
     return false;
-  return tmc2_segmenter_params_check( &p ) == TMC2_OK;
+  return paramsAccepted( p );
 }
 
 EncoderDropIn::EncoderDropIn( int device ) {
@@ -157,10 +173,7 @@ int EncoderDropIn::generateSegments( const PCCGroupOfFrames& sources, PCCContext
     TMC2HIP_TRY( tmc2_frame_create( ctx_, xyz.data(), rgb.empty() ? nullptr : rgb.data(), sources[i].getPointCount(), &frames_[i] ) );
     // calculateWeightNormal( geometryBitDepth3D, sources[0] ) :3569-3626: the axis weights of the whole GOF come from frame 0
     if ( i == 0 ) TMC2HIP_TRY( tmc2_weight_normal( frames_[0], p.geometryBitDepth3D, params.minWeightEPP_, p.weightNormal ) );
-    if ( params.gridBasedSegmentation_ )  // the fast mode: the voxel size travels as an argument, not in the struct
-      TMC2HIP_TRY( tmc2_segmenter_compute_grid_based( frames_[i], &p, int( params.voxelDimensionGridBasedSegmentation_ ) ) );
-    else
-      TMC2HIP_TRY( tmc2_segmenter_compute( frames_[i], &p ) );
+    TMC2HIP_TRY( computeSegments( frames_[i], p, params.gridBasedSegmentation_, params.voxelDimensionGridBasedSegmentation_ ) );
     int64_t depthCount = 0, occCount = 0;
     TMC2HIP_TRY( tmc2_frame_patch_pool_sizes( frames_[i], &depthCount, &occCount ) );
     const int               count = tmc2_frame_patch_count( frames_[i] );

@@ -28,7 +28,9 @@ void flatten( const pcc::PCCPointSet3& cloud, std::vector<int16_t>& xyz, std::ve
 // PCCPatchSegmenter3Parameters -> tmc2_segmenter_params; false if the parameter set uses something the library does not
 // mirror (the caller then keeps the reference's own body).  gridBasedSegmentation_ (the fast mode) is mirrored for
 // voxelDimensionGridBasedSegmentation_ 2, 4 and 8; the struct has no field for it: segmenterCompute and
-// EncoderDropIn::generateSegments hand the voxel size to tmc2_segmenter_compute_grid_based.
+// EncoderDropIn::generateSegments hand the voxel size to tmc2_segmenter_compute_grid_based.  gridBasedRefineSegmentation_ off (the
+// k-NN refinement) is mirrored for maxNNCountRefineSegmentation_ up to 1024: the two call tmc2_segmenter_compute_knn_refine, with
+// the voxel size of the fast mode or 0.
 bool toParams( const pcc::PCCPatchSegmenter3Parameters& params, tmc2_segmenter_params& out );
 
 // patch records + pools (tmc2_frame_get_patches) -> the PCCPatch objects PCCPatchSegmenter3::compute would have appended

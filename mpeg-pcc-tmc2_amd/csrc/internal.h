@@ -304,6 +304,7 @@ struct tmc2_ctx {
   tmc2::DevBuf<unsigned long long> scanState;    // look-back state of exclusiveScanU32: [0] tile tickets, [1 + t] tile t (epoch-tagged)
   uint32_t                      scanEpoch = 0, scanTickets = 0;
   tmc2::DevBuf<uint32_t>        voxelBitmap;     // dense 3-D occupancy bitmap of the resampled cloud (S9)
+  tmc2::DevBuf<uint32_t>        knnWideAdj;      // the k-NN refinement's neighbourhoods, [K][n rounded up to 64] tree positions (refine_knn.hip); grown on demand, not part of tmc2_ctx_reserve
   std::map<uint32_t, int>       kdLevelHint;     // levels of level passes the last device k-d tree of ~ this size took (by n >> 15)
   // small tables that depend on the parameters only (the probe offsets of S9, the ball rows / cells of S5): uploaded once per context
   // and key, not once per frame (round 6: each was a pageable host-to-device copy -- a staging copy and a blit -- on every frame's chain)
@@ -628,6 +629,19 @@ int voxelizeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint32_t n, int voxDim, int 
                     uint32_t* voxelCount );
 // PCCPatchSegmenter3::compute with gridBasedSegmentation_ (voxelize.hip)
 int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim );
+// the two ends of a chain on the voxel cloud (voxelize.hip): the V voxels of vox->d_pts down to vox->h_xyz / geoMax / n for the
+// host-resident steps; and applyVoxelsDataToPoints -- every point of f takes its voxel's partition and normal
+int voxelFrameHostPoints( tmc2_frame* vox, uint32_t V );
+int applyVoxelsToPoints( tmc2_frame* f, const tmc2_frame* vox, const uint32_t* d_voxelOfPoint );
+// tmc2_segmenter_params_check's rules; gridBasedRefine false: the one on gridBasedRefineSegmentation reversed, and the refinement's
+// voxel size and search radius not read (segmenter_api.cpp)
+int segmenterParamsCheck( const tmc2_segmenter_params* p, bool gridBasedRefine );
+// the wave-per-query search (knn_wide.hip), 1 <= k <= 1024, k <= tree.n.  d_queries null: the tree's own points in tree order.
+// transposed false: d_out[row][k] original indices (row: the point's index / the query's number); true: d_out[e * outStride + j] =
+// tree position of result e of tree-order point j.  Stage knn_wide.
+int launchKnnWide( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_out, bool transposed, uint32_t outStride );
+// PCCPatchSegmenter3::refineSegmentation on the frame's normals and partition (refine_knn.hip); leaves d_knn / k alone
+int refineKnn( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount );
 // several device regions set to a byte value each in ONE launch (instead of one hipMemsetAsync per buffer)
 struct FillRegion {
   void*   p;

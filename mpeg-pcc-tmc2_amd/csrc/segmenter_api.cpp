@@ -31,9 +31,7 @@ int tmc2_frame::growPools() {
   return TMC2_OK;
 }
 
-extern "C" {
-
-int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) {
+int tmc2::segmenterParamsCheck( const tmc2_segmenter_params* p, bool gridBasedRefine ) {
   if ( !p ) return TMC2_E_INVALID;
   if ( p->nnNormalEstimation != 16 || p->maxNNCountPatchSegmentation != 16 ) {
     setError( "params: nnNormalEstimation / maxNNCountPatchSegmentation must be 16 (one shared k-NN self-join)" );
@@ -43,8 +41,12 @@ int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) {
     setError( "params: normalOrientation %d unsupported (0 none, 1 spanning tree)", p->normalOrientation );
     return TMC2_E_UNSUPPORTED;
   }
-  if ( !p->gridBasedRefineSegmentation ) {
+  if ( gridBasedRefine && !p->gridBasedRefineSegmentation ) {
     setError( "params: only gridBasedRefineSegmentation=1 is implemented" );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( !gridBasedRefine && p->gridBasedRefineSegmentation ) {
+    setError( "params: gridBasedRefineSegmentation must be 0 for the k-NN refinement" );
     return TMC2_E_UNSUPPORTED;
   }
   if ( p->occupancyResolution != 16 ) {
@@ -111,6 +113,7 @@ int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) {
     setError( "params: lambdaRefineSegmentation %g is negative or not a number", p->lambdaRefineSegmentation );
     return TMC2_E_UNSUPPORTED;
   }
+  if ( !gridBasedRefine ) return TMC2_OK;  // (the k-NN refinement reads neither the voxel size nor the search radius)
   const int voxDim = p->voxelDimensionRefineSegmentation;
   if ( voxDim < 2 || voxDim > 1024 || ( voxDim & ( voxDim - 1 ) ) ) {
     setError( "params: voxelDimensionRefineSegmentation %d unsupported (power of two >= 2)", voxDim );
@@ -127,6 +130,10 @@ int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) {
   }
   return TMC2_OK;
 }
+
+extern "C" {
+
+int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) { return tmc2::segmenterParamsCheck( p, true ); }
 
 int tmc2_segmenter_segment_patches( tmc2_frame* f, const tmc2_segmenter_params* p ) {
   if ( !f || !p ) return TMC2_E_INVALID;

@@ -115,9 +115,47 @@ int voxelizeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint32_t n, int voxDim, int 
   return TMC2_OK;  // (the temporaries go back to the pool; what is queued on the stream runs before their next user's work)
 }
 
-int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim ) {
-  tmc2_ctx*   ctx = f->ctx;
+int voxelFrameHostPoints( tmc2_frame* vox, uint32_t V ) {
+  tmc2_ctx*   ctx = vox->ctx;
   hipStream_t s   = ctx->stream;
+  vox->n = V;
+  // the host-resident steps (S3's walk and its point-level fallback, a tree build of option KDTREE_HOST) read h_xyz: once down
+  Pt* hp = ctx->hostD.get<Pt>( V );
+  if ( !hp ) {
+    setError( "segmenter_compute_grid_based: hipHostMalloc failed" );
+    return TMC2_E_HIP;
+  }
+  TMC2_HIP( hipMemcpyAsync( hp, vox->d_pts.p, size_t( V ) * sizeof( Pt ), hipMemcpyDeviceToHost, s ) );
+  TMC2_HIP( hipStreamSynchronize( s ) );
+  vox->h_xyz.resize( 3 * size_t( V ) );
+  for ( uint32_t v = 0; v < V; ++v ) {
+    vox->h_xyz[3 * size_t( v )] = hp[v].x, vox->h_xyz[3 * size_t( v ) + 1] = hp[v].y, vox->h_xyz[3 * size_t( v ) + 2] = hp[v].z;
+    vox->geoMax = std::max( vox->geoMax, std::max( hp[v].x, std::max( hp[v].y, hp[v].z ) ) );
+  }
+  return TMC2_OK;
+}
+
+int applyVoxelsToPoints( tmc2_frame* f, const tmc2_frame* vox, const uint32_t* d_voxelOfPoint ) {
+  if ( !vox->haveNormals || !vox->havePartition ) {
+    setError( "segmenter_compute_grid_based: the voxel cloud has no normals / partition" );
+    return TMC2_E_STATE;
+  }
+  tmc2_ctx*      ctx = f->ctx;
+  const uint32_t n   = uint32_t( f->n );
+  TMC2_TRY( f->d_normals.alloc( 3 * size_t( n ) ) );
+  TMC2_TRY( f->d_partition.alloc( n ) );
+  {
+    StageScope span( ctx, "voxels_to_points" );
+    hipLaunchKernelGGL( applyVoxelsKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_voxelOfPoint, n, vox->d_partition.p,
+                        vox->d_normals.p, f->d_partition.p, f->d_normals.p );
+    TMC2_HIP( hipGetLastError() );
+  }
+  f->haveNormals = f->havePartition = true;
+  return TMC2_OK;
+}
+
+int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim ) {
+  tmc2_ctx* ctx = f->ctx;
   // ---- refused before anything is launched: the frame stays as it is
   TMC2_TRY( tmc2_segmenter_params_check( p ) );
   if ( f->n == 0 || f->h_xyz.size() != 3 * size_t( f->n ) || f->d_rgb.count == 0 ) {
@@ -143,22 +181,7 @@ int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, in
               voxDim, V, kMinVoxelCloud );
     return TMC2_E_UNSUPPORTED;
   }
-  vox->n = V;
-  {
-    // the host-resident steps (S3's walk and its point-level fallback, a tree build of option KDTREE_HOST) read h_xyz: once down
-    Pt* hp = ctx->hostD.get<Pt>( V );
-    if ( !hp ) {
-      setError( "segmenter_compute_grid_based: hipHostMalloc failed" );
-      return TMC2_E_HIP;
-    }
-    TMC2_HIP( hipMemcpyAsync( hp, vox->d_pts.p, size_t( V ) * sizeof( Pt ), hipMemcpyDeviceToHost, s ) );
-    TMC2_HIP( hipStreamSynchronize( s ) );
-    vox->h_xyz.resize( 3 * size_t( V ) );
-    for ( uint32_t v = 0; v < V; ++v ) {
-      vox->h_xyz[3 * size_t( v )] = hp[v].x, vox->h_xyz[3 * size_t( v ) + 1] = hp[v].y, vox->h_xyz[3 * size_t( v ) + 2] = hp[v].z;
-      vox->geoMax = std::max( vox->geoMax, std::max( hp[v].x, std::max( hp[v].y, hp[v].z ) ) );
-    }
-  }
+  TMC2_TRY( voxelFrameHostPoints( vox.get(), V ) );
   // ---- S1-S5 on the voxel cloud, with p's values: the refinement's voxel size and radius apply to the shrunk coordinates, the
   // projection weights are those of the original cloud (S0), as in the reference
   TMC2_TRY( normalsCompute( vox.get(), p->nnNormalEstimation, p->normalOrientation, nullptr ) );
@@ -166,20 +189,7 @@ int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, in
   TMC2_TRY( tmc2_segmenter_refine_grid_based( vox.get(), p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
                                               p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,
                                               p->searchRadiusRefineSegmentation ) );
-  if ( !vox->haveNormals || !vox->havePartition ) {
-    setError( "segmenter_compute_grid_based: the voxel cloud has no normals / partition" );
-    return TMC2_E_STATE;
-  }
-  // ---- copy back: every point takes its voxel's partition and normal
-  TMC2_TRY( f->d_normals.alloc( 3 * size_t( n ) ) );
-  TMC2_TRY( f->d_partition.alloc( n ) );
-  {
-    StageScope span( ctx, "voxels_to_points" );
-    hipLaunchKernelGGL( applyVoxelsKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, s, d_voxelOfPoint.p, n, vox->d_partition.p,
-                        vox->d_normals.p, f->d_partition.p, f->d_normals.p );
-    TMC2_HIP( hipGetLastError() );
-  }
-  f->haveNormals = f->havePartition = true;
+  TMC2_TRY( applyVoxelsToPoints( f, vox.get(), d_voxelOfPoint.p ) );
   vox.reset();  // (its buffers go back to the pool; the copy queued above runs before their next user's work)
   // ---- the full cloud: tree, k = 16 adjacency (no second normal estimation), patches
   TMC2_TRY( f->ensureTree() );

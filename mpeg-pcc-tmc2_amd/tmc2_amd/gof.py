@@ -170,10 +170,18 @@ class _Done(list):
         self.event = threading.Event()
 
 
-def _segmenter(enc, weight, grid_based_segmentation=None):
+def _segmenter(enc, weight, grid_based_segmentation=None, knn_refine_segmentation=None):
     """What a frame of the encoder's GOF is segmented with, as fn(frame): Frame.segmenter_compute with the encoder's CTC settings, or
     -- grid_based_segmentation = the voxel size of the reference's fast mode -- with the four defaults the reference takes with the
-    flag (lib.fast_params) in their place and grid_based = that voxel size."""
+    flag (lib.fast_params) in their place and grid_based = that voxel size.  knn_refine_segmentation = (maxNNCountRefineSegmentation,
+    iterationCountRefineSegmentation): gridBasedRefineSegmentation off (lib.knn_refine_params), on the cloud or, with
+    grid_based_segmentation, on its voxel cloud."""
+    if knn_refine_segmentation is not None:
+        max_nn, iterations = knn_refine_segmentation
+        params = lib.knn_refine_params(int(iterations), enc.bits3d, weight)
+        params.maxNNCountRefineSegmentation = int(max_nn)
+        grid = None if grid_based_segmentation is None else int(grid_based_segmentation)
+        return lambda fr: fr.segmenter_compute(params, grid)
     if grid_based_segmentation is None:
         params = lib.ctc_params(enc.iterations, enc.bits3d, weight, enc.vox_dim)
         return lambda fr: fr.segmenter_compute(params)
@@ -295,7 +303,7 @@ class GofEncoder:
         return self._dispatch([(i % self.workers, (lambda fr=fr, i=i: fn(fr, i))) for i, fr in enumerate(frames)])
 
     def phase_a(self, frames, sharder=None, weight=None, constrained_pack=False, frame_count=None, records_chain=False,
-                then=None, grid_based_segmentation=None):
+                then=None, grid_based_segmentation=None, knn_refine_segmentation=None):
         """constrained_pack: True = the low-delay condition -- frames after the first are packed against their predecessor
         (S10', a sequential chain over the GOF, microseconds per frame on the host); 2 = the random-access condition -- the same chain followed by the global patch allocation over the
         GOF (tracked patches share one place in all frames of a sub-context).  With several ranks (frame f on rank
@@ -305,17 +313,21 @@ class GofEncoder:
         the copy of its canvases to the host, ...), on the frame's worker in the same pass -- the frames are independent from
         there on, and every rendezvous of the GOF costs the wait for its slowest frame.
         grid_based_segmentation: voxelDimensionGridBasedSegmentation (2, 4 or 8) -- every frame is segmented in the reference's fast
-        mode (Frame.segmenter_compute( fast_params, grid_based = .. )); None: the plain path."""
+        mode (Frame.segmenter_compute( fast_params, grid_based = .. )); None: the plain path.
+        knn_refine_segmentation: (maxNNCountRefineSegmentation, iterationCountRefineSegmentation) -- gridBasedRefineSegmentation off:
+        every frame is refined over k-NN neighbourhoods (Frame.segmenter_compute( knn_refine_params )); combines with
+        grid_based_segmentation (the refinement then runs on the voxel cloud)."""
         sharder = sharder or Sharder()
         if constrained_pack and (sharder.world > 1 or records_chain):
-            size = self._phase_a_sharded_chain(frames, sharder, weight, int(constrained_pack), frame_count, grid_based_segmentation)
+            size = self._phase_a_sharded_chain(frames, sharder, weight, int(constrained_pack), frame_count, grid_based_segmentation,
+                                               knn_refine_segmentation)
             if then is not None:
                 self.per_frame(frames, lambda fr, i: then(fr, i, size[0], size[1]))
             return size
         if weight is None:
             w = frames[0].weight_normal(self.bits3d, 0.6) if sharder.rank == 0 else np.zeros(3)
             weight = sharder.broadcast_weight(w)
-        segment = _segmenter(self, weight, grid_based_segmentation)
+        segment = _segmenter(self, weight, grid_based_segmentation, knn_refine_segmentation)
 
         def segment_and_pack(fr):
             segment(fr)
@@ -378,13 +390,13 @@ class GofEncoder:
             self._dispatch([(i % self.workers, (lambda fr=fr, i=i: images(fr, i, size))) for i, fr in redo])
         return size
 
-    def _phase_a_sharded_chain(self, frames, sharder, weight, mode, frame_count, grid_based_segmentation=None):
+    def _phase_a_sharded_chain(self, frames, sharder, weight, mode, frame_count, grid_based_segmentation=None, knn_refine_segmentation=None):
         if frame_count is None:                              # (uneven shards: the ranks need not hold equally many frames)
             frame_count = sharder.sum_count(len(frames))
         if weight is None:
             w = frames[0].weight_normal(self.bits3d, 0.6) if sharder.rank == 0 else np.zeros(3)
             weight = sharder.broadcast_weight(w)
-        self._per_worker(frames, _segmenter(self, weight, grid_based_segmentation))
+        self._per_worker(frames, _segmenter(self, weight, grid_based_segmentation, knn_refine_segmentation))
         local = self._per_worker(frames, lambda fr: fr.get_patch_records())
         mine, tiles = sharder.pack_gof_records(local, frame_count, mode, self.min_w, self.min_h)
         self.per_frame(frames, lambda fr, i: fr.set_packing(mine[i][0], mine[i][2], mine[i][1], mine[i][3], mine[i][4]))

@@ -90,6 +90,16 @@ def fast_params(iterations=5, bits3d=11, weight=(1.0, 1.0, 1.0)):
     return p
 
 
+def knn_refine_params(iterations=100, bits3d=11, weight=(1.0, 1.0, 1.0)):
+    """The CTC settings with gridBasedRefineSegmentation off and the defaults the reference takes then: maxNNCountRefineSegmentation
+    256, iterationCountRefineSegmentation 100 -- for Frame.segmenter_compute( params[, grid_based = voxDim] ), which goes to the k-NN
+    refinement (PCCPatchSegmenter3::refineSegmentation).  The refinement's voxel size and search radius are not read."""
+    p = ctc_params(iterations, bits3d, weight)
+    p.gridBasedRefineSegmentation = 0
+    p.maxNNCountRefineSegmentation = 256
+    return p
+
+
 # TMC2_GUARD=1 (tests, bench.py --guard): every array handed to the C-ABI travels in a copy with a red zone of _GUARD bytes on
 # both sides, filled with a pattern; after the call (_check) the zones are verified -- the library wrote outside a buffer of the
 # caller's iff they changed -- and the payload is copied back.  Calls are synchronous on host buffers (the getters end with a
@@ -478,6 +488,15 @@ class Frame:
         _check(self.L.tmc2_kdtree_search(self.h, _ptr(q), len(q), int(k), _ptr(idx), None if d is None else _ptr(d)))
         return (idx, d) if with_dist else idx
 
+    def kdtree_search_wide(self, k, queries=None):
+        """tmc2_kdtree_search_wide: the k (1..1024) results of nanoflann's search per query as a SET (the order inside a row is
+        unspecified), by the wave-per-query kernel; queries None: the frame's own points, row i = point i."""
+        q = None if queries is None else np.ascontiguousarray(queries, dtype=np.int16).reshape(-1, 3)
+        nq = self.n if q is None else len(q)
+        idx = np.empty((nq, max(int(k), 0) if int(k) <= 1024 else 0), np.uint32)
+        _check(self.L.tmc2_kdtree_search_wide(self.h, None if q is None else _ptr(q), nq, int(k), _ptr(idx)))
+        return idx
+
     # PCCNormalsGenerator3
     def normals_compute_normals(self, k=16):
         _check(self.L.tmc2_normals_compute_normals(self.h, int(k)))
@@ -516,6 +535,10 @@ class Frame:
     def segmenter_refine_grid_based(self, max_nn=1024, lam=3.0, iterations=10, vox_dim=4, radius=192):
         _check(self.L.tmc2_segmenter_refine_grid_based(self.h, int(max_nn), lam, int(iterations), int(vox_dim), int(radius)))
 
+    def segmenter_refine(self, max_nn=256, lam=3.0, iterations=100):
+        """PCCPatchSegmenter3::refineSegmentation on the frame's normals and partition: max_nn nearest neighbours, Jacobi rounds."""
+        _check(self.L.tmc2_segmenter_refine(self.h, int(max_nn), lam, int(iterations)))
+
     def get_partition(self):
         out = np.empty(self.n, np.uint32)
         _check(self.L.tmc2_frame_get_partition(self.h, _ptr(out)))
@@ -530,8 +553,12 @@ class Frame:
 
     def segmenter_compute(self, params, grid_based=None):
         """PCCPatchSegmenter3::compute; grid_based = voxelDimensionGridBasedSegmentation (2, 4 or 8): the reference's fast mode --
-        S1-S5 on the voxel cloud, partition and normals copied back, tree / adjacency / patches on the full cloud."""
-        if grid_based is None:
+        S1-S5 on the voxel cloud, partition and normals copied back, tree / adjacency / patches on the full cloud.
+        params.gridBasedRefineSegmentation == 0 (knn_refine_params): the refinement over k-NN neighbourhoods, on the cloud or, with
+        grid_based, on the voxel cloud (tmc2_segmenter_compute_knn_refine)."""
+        if not params.gridBasedRefineSegmentation:
+            _check(self.L.tmc2_segmenter_compute_knn_refine(self.h, C.byref(params), 0 if grid_based is None else int(grid_based)))
+        elif grid_based is None:
             _check(self.L.tmc2_segmenter_compute(self.h, C.byref(params)))
         else:
             _check(self.L.tmc2_segmenter_compute_grid_based(self.h, C.byref(params), int(grid_based)))
@@ -1049,6 +1076,20 @@ def host_convert_points_to_voxels(xyz, vox_dim, bits3d):
     return vox[:count.value].copy(), rank
 
 
+def host_refine_segmentation(xyz, normals, partition, max_nn=256, lam=3.0, iterations=100, with_adjacency=False):
+    """tmc2_host_refine_segmentation: PCCPatchSegmenter3::refineSegmentation restated on the host (no device) -> the refined
+    partition, or (partition, adjacency [n][max_nn] in nanoflann's result order) with with_adjacency."""
+    a = np.ascontiguousarray(xyz, np.int16).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    out = np.array(partition, dtype=np.uint32, order="C", copy=True).reshape(-1)
+    if len(nrm) != len(a) or len(out) != len(a):
+        raise Tmc2Error("host_refine_segmentation: xyz [n][3], normals [n][3] and partition [n] of one n expected")
+    adj = np.zeros((len(a), max(int(max_nn), 0) if int(max_nn) <= 1024 else 0), np.uint32) if with_adjacency else None
+    _check(load_library().tmc2_host_refine_segmentation(_ptr(a), len(a), _ptr(nrm), _ptr(out), int(max_nn), lam, int(iterations),
+                                                        None if adj is None else _ptr(adj)))
+    return (out, adj) if with_adjacency else out
+
+
 def selftest_std_sort(pairs, offsets):
     """tmc2_selftest_std_sort: the real std::sort( .., dist < dist ) on every list of pairs [total][2] = (distance, payload), list l
     = [offsets[l], offsets[l + 1]); returns the sorted copy (host only)."""
@@ -1100,6 +1141,7 @@ int tmc2_frame_get_kdtree_order(tmc2_frame*, uint32_t*, int32_t*)
 uint64_t tmc2_frame_point_count(const tmc2_frame*)
 int tmc2_frame_reset(tmc2_frame*)
 int tmc2_kdtree_search(tmc2_frame*, const int16_t*, uint64_t, int, uint32_t*, uint32_t*)
+int tmc2_kdtree_search_wide(tmc2_frame*, const int16_t*, uint64_t, int, uint32_t*)
 int tmc2_normals_compute_normals(tmc2_frame*, int)
 int tmc2_normals_orient(tmc2_frame*)
 int tmc2_normals_compute(tmc2_frame*, int, int)
@@ -1109,12 +1151,14 @@ int tmc2_frame_get_adjacency(tmc2_frame*, uint32_t*)
 int tmc2_weight_normal(tmc2_frame*, int, double, double[3])
 int tmc2_segmenter_initial_segmentation(tmc2_frame*, const double[3])
 int tmc2_segmenter_refine_grid_based(tmc2_frame*, int, double, int, int, int)
+int tmc2_segmenter_refine(tmc2_frame*, int, double, int)
 int tmc2_frame_get_partition(tmc2_frame*, uint32_t*)
 int tmc2_frame_set_partition(tmc2_frame*, const uint32_t*)
 int tmc2_segmenter_segment_patches(tmc2_frame*, const tmc2_segmenter_params*)
 int tmc2_segmenter_compute(tmc2_frame*, const tmc2_segmenter_params*)
 int tmc2_segmenter_params_check(const tmc2_segmenter_params*)
 int tmc2_segmenter_compute_grid_based(tmc2_frame*, const tmc2_segmenter_params*, int)
+int tmc2_segmenter_compute_knn_refine(tmc2_frame*, const tmc2_segmenter_params*, int)
 int tmc2_segmenter_convert_points_to_voxels(tmc2_ctx*, const int16_t*, uint64_t, int, int, int16_t*, uint64_t*, uint32_t*)
 int tmc2_frame_patch_count(tmc2_frame*)
 int tmc2_frame_patch_pool_sizes(tmc2_frame*, int64_t*, int64_t*)
@@ -1176,6 +1220,7 @@ int tmc2_host_orient_normals(const int16_t*, uint64_t, const uint32_t*, int, dou
 int tmc2_host_color_smoothing(const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
 int tmc2_host_patch_border_filtering(const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, const uint32_t*, int, int, int, int, uint8_t*, uint8_t*)
 int tmc2_host_convert_points_to_voxels(const int16_t*, uint64_t, int, int, int16_t*, uint64_t*, uint32_t*)
+int tmc2_host_refine_segmentation(const int16_t*, uint64_t, const double*, uint32_t*, int, double, int, uint32_t*)
 int tmc2_selftest_scan(tmc2_ctx*, const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, const uint32_t*, int, uint64_t)
 int tmc2_selftest_fill(tmc2_ctx*, const uint64_t*, int)
 int tmc2_selftest_work_map(tmc2_ctx*, uint64_t, int, uint64_t, uint64_t, uint32_t*, uint32_t*)
