@@ -684,14 +684,20 @@ void tmc2_frame::resetDerived() {
   refineJob.reset();
 }
 
+// S1 and S2: the tree, the k-NN self-join where the resident adjacency is not of this k, the unoriented normals
+static int computeNormals( tmc2_frame* f, int k ) {
+  TMC2_TRY( f->ensureTree() );
+  if ( !f->haveKnn || f->k != k ) TMC2_TRY( launchKnnSelf( f, k ) );
+  return launchNormals( f );
+}
+
 int tmc2::normalsCompute( tmc2_frame* f, int k, int orientation, const std::function<int()>* beforeHostWalk ) {
-  TMC2_TRY( tmc2_normals_compute_normals( f, k ) );
+  TMC2_TRY( computeNormals( f, k ) );
   if ( orientation == 0 ) return TMC2_OK;
   if ( orientation != 1 ) {
     setError( "normalOrientation=%d unsupported (0 none, 1 spanning tree)", orientation );
     return TMC2_E_UNSUPPORTED;
   }
-  tmc2::ApiScope scope( f->ctx );
   return orientNormalsHost( f, beforeHostWalk );
 }
 
@@ -774,9 +780,7 @@ int tmc2_kdtree_search( tmc2_frame* f, const int16_t* queries, uint64_t nq, int 
 int tmc2_normals_compute_normals( tmc2_frame* f, int k ) {
   if ( !f ) return TMC2_E_INVALID;
   tmc2::ApiScope scope( f->ctx );
-  TMC2_TRY( f->ensureTree() );
-  if ( !f->haveKnn || f->k != k ) TMC2_TRY( launchKnnSelf( f, k ) );
-  return launchNormals( f );
+  return computeNormals( f, k );
 }
 
 int tmc2_normals_orient( tmc2_frame* f ) {
@@ -785,7 +789,11 @@ int tmc2_normals_orient( tmc2_frame* f ) {
   return orientNormalsHost( f );
 }
 
-int tmc2_normals_compute( tmc2_frame* f, int k, int orientation ) { return tmc2::normalsCompute( f, k, orientation, nullptr ); }
+int tmc2_normals_compute( tmc2_frame* f, int k, int orientation ) {
+  if ( !f ) return TMC2_E_INVALID;
+  tmc2::ApiScope scope( f->ctx );
+  return tmc2::normalsCompute( f, k, orientation, nullptr );
+}
 
 int tmc2_frame_get_normals( tmc2_frame* f, double* normals ) {
   if ( !f || !normals || !f->haveNormals ) {

@@ -627,12 +627,21 @@ int markedCells( tmc2_ctx* ctx, const Pt* d_pts, const uint8_t* d_btype, uint32_
 // trip: the voxel count, through the context's mailbox.
 int voxelizeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint32_t n, int voxDim, int maxCoord, DevBuf<Pt>& d_voxelPts, DevBuf<uint32_t>& d_voxelOfPoint,
                     uint32_t* voxelCount );
-// PCCPatchSegmenter3::compute with gridBasedSegmentation_ (voxelize.hip)
-int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim );
-// the two ends of a chain on the voxel cloud (voxelize.hip): the V voxels of vox->d_pts down to vox->h_xyz / geoMax / n for the
-// host-resident steps; and applyVoxelsDataToPoints -- every point of f takes its voxel's partition and normal
-int voxelFrameHostPoints( tmc2_frame* vox, uint32_t V );
-int applyVoxelsToPoints( tmc2_frame* f, const tmc2_frame* vox, const uint32_t* d_voxelOfPoint );
+// The voxel cloud of a frame (gridBasedSegmentation_) as a frame of its own on the same context, built from device data
+// (voxelize.hip: the only place that makes one).  Destroying it releases the voxel frame with every buffer of the stages that ran on
+// it; a refine job that was prepared and not consumed goes with it and leaves the context's dense table clean.
+struct VoxelCloud {
+  std::unique_ptr<tmc2_frame> frame;
+  DevBuf<uint32_t>            d_voxelOfPoint;  // per point of the source frame: the rank of its voxel
+  uint32_t                    count = 0;
+  // convertPointsToVoxels (span voxelize; the caller has ruled out voxelizeCheck), then the voxels down to frame->h_xyz / geoMax / n
+  // for the host-resident steps.  entry: the name its refusals carry.  A cloud of fewer voxels than the kMinVoxelCloud neighbours the
+  // normal estimation asks for, or than the refineNeighbours of the k-NN refinement (0: another refinement), is refused before
+  // anything of f is touched.
+  int build( const tmc2_frame* f, const char* entry, int voxDim, int refineNeighbours );
+  // applyVoxelsDataToPoints (span voxels_to_points): every point of f takes its voxel's partition and normal
+  int applyToPoints( tmc2_frame* f, const char* entry ) const;
+};
 // tmc2_segmenter_params_check's rules; gridBasedRefine false: the one on gridBasedRefineSegmentation reversed, and the refinement's
 // voxel size and search radius not read (segmenter_api.cpp)
 int segmenterParamsCheck( const tmc2_segmenter_params* p, bool gridBasedRefine );
@@ -642,6 +651,8 @@ int segmenterParamsCheck( const tmc2_segmenter_params* p, bool gridBasedRefine )
 int launchKnnWide( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_out, bool transposed, uint32_t outStride );
 // PCCPatchSegmenter3::refineSegmentation on the frame's normals and partition (refine_knn.hip); leaves d_knn / k alone
 int refineKnn( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount );
+// its rules for the three values alone (refine_knn.h: refineKnnRefusal), as the error "<who>: ..." and TMC2_E_UNSUPPORTED
+int refineKnnCheck( const char* who, int maxNNCount, double lambda, int iterationCount );
 // several device regions set to a byte value each in ONE launch (instead of one hipMemsetAsync per buffer)
 struct FillRegion {
   void*   p;

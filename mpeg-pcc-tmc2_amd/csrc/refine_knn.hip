@@ -1,7 +1,8 @@
 // refine_knn.hip -- the refinement of the segmentation over k-NN neighbourhoods (the reference's non-grid mode) on gfx950.
 //
-// Replaces PCCPatchSegmenter3::refineSegmentation (PccLibEncoder/source/PCCPatchSegmenter.cpp:1322-1384) and the branch of
-// PCCPatchSegmenter3::compute that calls it (:126-131), with gridBasedSegmentation_ or without.
+// Replaces PCCPatchSegmenter3::refineSegmentation (PccLibEncoder/source/PCCPatchSegmenter.cpp:1322-1384).  The branch of
+// PCCPatchSegmenter3::compute that calls it (:126-131), with gridBasedSegmentation_ or without, is segmenterCompute's
+// (segmenter_api.cpp: the one chain of the segmenter's modes).
 //
 // The neighbourhoods come from the wide search (knn_wide.hip) as TREE POSITIONS in the layout adj[e][j], j = the point's own tree
 // position: one point per lane, so the 64 lanes of a wave read 64 consecutive words per step, and the partition bytes they gather
@@ -16,11 +17,8 @@
 // round and never ends the loop early.  state[3] counts the rounds that ran.
 //
 // The adjacency (n x K x 4 bytes: 853 MB for a longdress frame at K = 256) is scratch of the context, grown on demand and kept.
-#include <memory>
-
 #include "internal.h"
 #include "refine_knn.h"
-#include "voxelize.h"
 
 namespace tmc2 {
 namespace {
@@ -70,7 +68,9 @@ __global__ __launch_bounds__( 256 ) void refineKnnRoundKernel( const uint32_t* _
   if ( moved && ( threadIdx.x & 63u ) == uint32_t( __ffsll( moved ) - 1 ) ) atomicOr( &state[round % 3u], 1u );
 }
 
-int refuse( const char* who, int maxNNCount, double lambda, int iterationCount ) {
+}  // namespace
+
+int refineKnnCheck( const char* who, int maxNNCount, double lambda, int iterationCount ) {
   int offending = 0;
   if ( const char* why = refineKnnRefusal( maxNNCount, lambda, iterationCount, &offending ) ) {
     char text[192];
@@ -81,13 +81,11 @@ int refuse( const char* who, int maxNNCount, double lambda, int iterationCount )
   return TMC2_OK;
 }
 
-}  // namespace
-
 int refineKnn( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount ) {
   tmc2_ctx*   ctx = f->ctx;
   hipStream_t s   = ctx->stream;
   // ---- refused before anything is launched: the frame stays as it is
-  TMC2_TRY( refuse( "segmenter_refine", maxNNCount, lambda, iterationCount ) );
+  TMC2_TRY( refineKnnCheck( "segmenter_refine", maxNNCount, lambda, iterationCount ) );
   if ( !f->haveNormals || !f->havePartition || f->n == 0 || f->n > 0x7FFFFFF0ull ) {
     setError( "segmenter_refine: the frame has no normals / partition" );
     return TMC2_E_STATE;
@@ -122,58 +120,6 @@ int refineKnn( tmc2_frame* f, int maxNNCount, double lambda, int iterationCount 
   return TMC2_OK;  // (the temporaries go back to the pool; what is queued on the stream runs before their next user's work)
 }
 
-// PCCPatchSegmenter3::compute with gridBasedRefineSegmentation_ off; voxDim 0: on the cloud itself, else on its voxel cloud
-int segmenterComputeKnnRefine( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim ) {
-  tmc2_ctx* ctx = f->ctx;
-  // ---- refused before anything is launched: the frame stays as it is
-  TMC2_TRY( segmenterParamsCheck( p, false ) );
-  TMC2_TRY( refuse( "segmenter_compute_knn_refine", p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
-                    p->iterationCountRefineSegmentation ) );
-  if ( f->n == 0 || f->h_xyz.size() != 3 * size_t( f->n ) || f->d_rgb.count == 0 ) {
-    setError( "segmenter_compute_knn_refine: the frame has no source cloud with colours" );
-    return TMC2_E_STATE;
-  }
-  const int K = p->maxNNCountRefineSegmentation;
-  if ( voxDim == 0 ) {
-    if ( uint64_t( K ) > f->n ) {
-      setError( "segmenter_compute_knn_refine: maxNNCountRefineSegmentation %d larger than the cloud (%llu points)", K, (unsigned long long)f->n );
-      return TMC2_E_UNSUPPORTED;
-    }
-    TMC2_TRY( normalsCompute( f, p->nnNormalEstimation, p->normalOrientation, nullptr ) );
-    TMC2_TRY( launchInitialSegmentation( f, p->weightNormal ) );
-    TMC2_TRY( refineKnn( f, K, p->lambdaRefineSegmentation, p->iterationCountRefineSegmentation ) );
-    return segmentPatches( f, p );
-  }
-  TMC2_TRY( voxelizeCheck( "segmenter_compute_knn_refine", f->h_xyz.data(), f->n, voxDim, p->geometryBitDepth3D ) );
-  const uint32_t n = uint32_t( f->n );
-  // ---- the voxel cloud: a frame of its own on the same context (voxelize.hip: the fast mode), released on every way out
-  std::unique_ptr<tmc2_frame> vox( new tmc2_frame() );
-  vox->ticket.bind( ctx );
-  vox->ctx = ctx;
-  DevBuf<uint32_t> d_voxelOfPoint;
-  uint32_t         V = 0;
-  {
-    StageScope span( ctx, "voxelize" );
-    TMC2_TRY( voxelizeDevice( ctx, f->d_pts.p, n, voxDim, f->geoMax, vox->d_pts, d_voxelOfPoint, &V ) );
-  }
-  if ( V < kMinVoxelCloud || V < uint32_t( K ) ) {  // (nothing of the frame has been touched yet)
-    setError( "segmenter_compute_knn_refine: voxelDimensionGridBasedSegmentation %d leaves a voxel cloud of %u points, fewer than "
-              "maxNNCountRefineSegmentation %d or the %u neighbours the normal estimation asks for",
-              voxDim, V, K, kMinVoxelCloud );
-    return TMC2_E_UNSUPPORTED;
-  }
-  TMC2_TRY( voxelFrameHostPoints( vox.get(), V ) );
-  TMC2_TRY( normalsCompute( vox.get(), p->nnNormalEstimation, p->normalOrientation, nullptr ) );
-  TMC2_TRY( launchInitialSegmentation( vox.get(), p->weightNormal ) );
-  TMC2_TRY( refineKnn( vox.get(), K, p->lambdaRefineSegmentation, p->iterationCountRefineSegmentation ) );
-  TMC2_TRY( applyVoxelsToPoints( f, vox.get(), d_voxelOfPoint.p ) );
-  vox.reset();  // (its buffers go back to the pool; the copy queued above runs before their next user's work)
-  // ---- the full cloud: tree, k = 16 adjacency (no second normal estimation), patches
-  TMC2_TRY( f->ensureTree() );
-  if ( !f->haveKnn || f->k != p->maxNNCountPatchSegmentation ) TMC2_TRY( launchKnnSelf( f, p->maxNNCountPatchSegmentation ) );
-  return segmentPatches( f, p );
-}
-
 }  // namespace tmc2
 
 using namespace tmc2;
@@ -184,12 +130,6 @@ int tmc2_segmenter_refine( tmc2_frame* f, int maxNNCount, double lambda, int ite
   if ( !f ) return TMC2_E_INVALID;
   ApiScope scope( f->ctx );
   return refineKnn( f, maxNNCount, lambda, iterationCount );
-}
-
-int tmc2_segmenter_compute_knn_refine( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation ) {
-  if ( !f || !p ) return TMC2_E_INVALID;
-  ApiScope scope( f->ctx );
-  return segmenterComputeKnnRefine( f, p, voxelDimensionGridBasedSegmentation );
 }
 
 }  // extern "C"

@@ -1,11 +1,10 @@
 // segmenter_api.cpp -- PCCPatchSegmenter3::compute chain, parameter validation and patch accessors.
 #include <algorithm>
-
-#include <algorithm>
 #include <chrono>
 #include <thread>
 
 #include "internal.h"
+#include "voxelize.h"
 using namespace tmc2;
 
 template <typename T>
@@ -131,6 +130,94 @@ int tmc2::segmenterParamsCheck( const tmc2_segmenter_params* p, bool gridBasedRe
   return TMC2_OK;
 }
 
+namespace {
+
+// PCCPatchSegmenter3::compute (PccLibEncoder/source/PCCPatchSegmenter.cpp:78-139) is ONE chain here; its three entries differ in
+// the refinement (S5) and in the cloud that S1-S5 run on.
+struct SegmenterMode {
+  const char* entry;            // the name the mode's refusals carry
+  bool        gridBasedRefine;  // S5: refineGridBased, else refineKnn (gridBasedRefineSegmentation_)
+  bool        onVoxelCloud;     // S1-S5 on the voxel cloud of voxDim, results copied back to the points (gridBasedSegmentation_)
+  int         voxDim;
+};
+
+// S1-S5 on the cloud to segment: the frame itself or its voxel cloud.  The refinement's voxel size and radius apply to the
+// coordinates of that cloud; the projection weights are those of the original cloud (S0), as in the reference.
+int segmentCloud( tmc2_frame* cloud, const tmc2_segmenter_params* p, bool gridBasedRefine, const std::function<int()>* beforeHostWalk ) {
+  TMC2_TRY( normalsCompute( cloud, p->nnNormalEstimation, p->normalOrientation, beforeHostWalk ) );
+  TMC2_TRY( launchInitialSegmentation( cloud, p->weightNormal ) );
+  if ( !gridBasedRefine )
+    return refineKnn( cloud, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation, p->iterationCountRefineSegmentation );
+  return refineGridBased( cloud, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation, p->iterationCountRefineSegmentation,
+                          p->voxelDimensionRefineSegmentation, p->searchRadiusRefineSegmentation );
+}
+
+int segmenterCompute( tmc2_frame* f, const tmc2_segmenter_params* p, const SegmenterMode& m ) {
+  const bool plain = m.gridBasedRefine && !m.onVoxelCloud;  // tmc2_segmenter_compute: the CTC's mode
+  const int  K     = p->maxNNCountRefineSegmentation;
+  // ---- refused before anything is launched: the frame stays as it is
+  TMC2_TRY( segmenterParamsCheck( p, m.gridBasedRefine ) );
+  if ( !m.gridBasedRefine ) TMC2_TRY( refineKnnCheck( m.entry, K, p->lambdaRefineSegmentation, p->iterationCountRefineSegmentation ) );
+  if ( !plain && ( f->n == 0 || f->h_xyz.size() != 3 * size_t( f->n ) || f->d_rgb.count == 0 ) ) {
+    setError( "%s: the frame has no source cloud with colours", m.entry );
+    return TMC2_E_STATE;
+  }
+  if ( !m.gridBasedRefine && !m.onVoxelCloud && uint64_t( K ) > f->n ) {
+    setError( "%s: maxNNCountRefineSegmentation %d larger than the cloud (%llu points)", m.entry, K, (unsigned long long)f->n );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( m.onVoxelCloud ) TMC2_TRY( voxelizeCheck( m.entry, f->h_xyz.data(), f->n, m.voxDim, p->geometryBitDepth3D ) );
+  // ---- the cloud to segment.  A voxel cloud is released on every way out; one too small for the mode is refused with nothing of
+  // the frame touched yet.
+  VoxelCloud vox;
+  if ( m.onVoxelCloud ) TMC2_TRY( vox.build( f, m.entry, m.voxDim, m.gridBasedRefine ? 0 : K ) );
+  // ---- what the plain mode alone takes: a guard for the refine job, and two scheduling options of hosts with few frames in flight.
+  // The other modes do without them on purpose.  A refine job is prepared on the cloud that S1-S5 run on: a voxel cloud takes its
+  // job with it on every way out, and the k-NN refinement prepares none.  The hook and the delay were measured on this chain
+  // alone, and the hook's geometry is the grid-based refinement's on the frame's own points: a context that sets the options
+  // leaves the other modes as they are until someone measures them there.
+  struct JobGuard {  // on every way out: no half-used refine job (it holds the context's dense voxel table filled: another
+    tmc2_frame* f;   // frame's refinement on this context would look its cells up in a dirty table)
+    ~JobGuard() {
+      if ( f ) f->refineJob.reset();
+    }
+  } guard{plain ? f : nullptr};
+  std::function<int()> prepareRefine;  // (empty: no hook)
+  if ( plain ) {
+    // tmc2_set_refine_overlap( 1 ) / TMC2_REFINE_OVERLAP=1: the refine step's geometry (voxels, neighbourhood rows forward and
+    // reverse: points only) is queued right before the orientation's host walk and built while the host walks.  It shortens a
+    // frame's chain and costs throughput when the chip is full: round 4, four frames in flight (one rank's share of an 8-GPU run):
+    // longdress 30.8 -> 30.4 ms, loot (voxels of 2: 5 ms of geometry) 57.8 -> 52.0 ms; sixteen in flight: 173.5 -> 174.0 and
+    // 91.5 -> 90.1 frames/s.  The GOF host (tmc2_amd/gof.py, integration/tmc2_encode_gof.cpp) turns it on for <= 4 frames in flight.
+    if ( refineOverlap( f->ctx ) )
+      prepareRefine = [f, p]() {
+        return refinePrepareGeometry( f, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation, p->iterationCountRefineSegmentation,
+                                      p->voxelDimensionRefineSegmentation, p->searchRadiusRefineSegmentation );
+      };
+    // Option FRAME_START_DELAY_US (few frames in flight: a rank of the 8-GPU run has four).  Frames that start together reach their
+    // host-resident step -- S3's walk, ~ 3 ms -- together, and the GPU has nothing to do meanwhile
+    // (profiles/r06_rank_concurrency.txt: a hole of ~ 3 ms in every 27 ms step).  A host that delays the start of half of its frames
+    // by about that long has one half walking while the other half's kernels run.
+    if ( const auto delay = ctxOption( f->ctx, "FRAME_START_DELAY_US" ) ) {
+      const int us = atoi( delay->c_str() );
+      if ( us > 0 ) std::this_thread::sleep_for( std::chrono::microseconds( std::min( us, 100000 ) ) );
+    }
+  }
+  // ---- S1-S5, and the way back from a voxel cloud
+  TMC2_TRY( segmentCloud( m.onVoxelCloud ? vox.frame.get() : f, p, m.gridBasedRefine, prepareRefine ? &prepareRefine : nullptr ) );
+  guard.f = nullptr;  // (the refinement consumed its job)
+  if ( m.onVoxelCloud ) {
+    TMC2_TRY( vox.applyToPoints( f, m.entry ) );
+    vox.frame.reset();  // (its buffers go back to the pool; the copy queued above runs before their next user's work)
+  }
+  // ---- the full cloud: tree, k = 16 adjacency, patches.  After S1-S5 on the frame itself the first two are resident: nothing runs.
+  TMC2_TRY( f->ensureTree() );
+  if ( !f->haveKnn || f->k != p->maxNNCountPatchSegmentation ) TMC2_TRY( launchKnnSelf( f, p->maxNNCountPatchSegmentation ) );
+  return segmentPatches( f, p );
+}
+
+}  // namespace
+
 extern "C" {
 
 int tmc2_segmenter_params_check( const tmc2_segmenter_params* p ) { return tmc2::segmenterParamsCheck( p, true ); }
@@ -145,40 +232,20 @@ int tmc2_segmenter_segment_patches( tmc2_frame* f, const tmc2_segmenter_params* 
 int tmc2_segmenter_compute( tmc2_frame* f, const tmc2_segmenter_params* p ) {
   if ( !f || !p ) return TMC2_E_INVALID;
   tmc2::ApiScope scope( f->ctx );
-  TMC2_TRY( tmc2_segmenter_params_check( p ) );
-  // tmc2_set_refine_overlap( 1 ) / TMC2_REFINE_OVERLAP=1: the refine step's geometry (voxels, neighbourhood rows forward and reverse:
-  // points only) is queued right before the orientation's host walk and built while the host walks.  It shortens a frame's
-  // chain and costs throughput when the chip is full: round 4, four frames in flight (one rank's share of an 8-GPU run):
-  // longdress 30.8 -> 30.4 ms, loot (voxels of 2: 5 ms of geometry) 57.8 -> 52.0 ms; sixteen in flight: 173.5 -> 174.0 and
-  // 91.5 -> 90.1 frames/s.  The GOF host (tmc2_amd/gof.py, integration/tmc2_encode_gof.cpp) turns it on for <= 4 frames in flight.
-  struct JobGuard {  // on every way out: no half-used refine job (it holds the context's dense voxel table filled: another
-    tmc2_frame* f;   // frame's refinement on this context would look its cells up in a dirty table)
-    bool        done = false;
-    ~JobGuard() {
-      if ( !done ) f->refineJob.reset();
-    }
-  } guard{f};
-  const std::function<int()> prepareRefine = [f, p]() {
-    return tmc2::refinePrepareGeometry( f, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
-                                        p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,
-                                        p->searchRadiusRefineSegmentation );
-  };
-  const bool overlap = p->gridBasedRefineSegmentation && tmc2::refineOverlap( f->ctx );
-  // Option FRAME_START_DELAY_US (few frames in flight: a rank of the 8-GPU run has four).  Frames that start together reach their
-  // host-resident step -- S3's walk, ~ 3 ms -- together, and the GPU has nothing to do meanwhile (profiles/r06_rank_concurrency.txt:
-  // a hole of ~ 3 ms in every 27 ms step).  A host that delays the start of half of its frames by about that long has one half
-  // walking while the other half's kernels run.
-  if ( const auto delay = tmc2::ctxOption( f->ctx, "FRAME_START_DELAY_US" ) ) {
-    const int us = atoi( delay->c_str() );
-    if ( us > 0 ) std::this_thread::sleep_for( std::chrono::microseconds( std::min( us, 100000 ) ) );
-  }
-  TMC2_TRY( tmc2::normalsCompute( f, p->nnNormalEstimation, p->normalOrientation, overlap ? &prepareRefine : nullptr ) );
-  TMC2_TRY( tmc2_segmenter_initial_segmentation( f, p->weightNormal ) );
-  TMC2_TRY( tmc2_segmenter_refine_grid_based( f, p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
-                                              p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,
-                                              p->searchRadiusRefineSegmentation ) );
-  guard.done = true;  // (the refinement consumed its job)
-  return segmentPatches( f, p );
+  return segmenterCompute( f, p, {"segmenter_compute", true, false, 0} );
+}
+
+int tmc2_segmenter_compute_grid_based( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation ) {
+  if ( !f || !p ) return TMC2_E_INVALID;
+  tmc2::ApiScope scope( f->ctx );
+  return segmenterCompute( f, p, {"segmenter_compute_grid_based", true, true, voxelDimensionGridBasedSegmentation} );
+}
+
+int tmc2_segmenter_compute_knn_refine( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation ) {
+  if ( !f || !p ) return TMC2_E_INVALID;
+  tmc2::ApiScope scope( f->ctx );
+  const int voxDim = voxelDimensionGridBasedSegmentation;  // (0: on the cloud itself)
+  return segmenterCompute( f, p, {"segmenter_compute_knn_refine", false, voxDim != 0, voxDim} );
 }
 
 int tmc2_frame_patch_count( tmc2_frame* f ) { return f ? int( f->patches.size() ) : 0; }

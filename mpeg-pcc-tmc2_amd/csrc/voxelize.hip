@@ -1,9 +1,8 @@
 // voxelize.hip -- the grid-based segmentation (the reference's fast mode, gridBasedSegmentation_) on gfx950.
 //
 // Replaces PCCPatchSegmenter3::convertPointsToVoxels and applyVoxelsDataToPoints (PccLibEncoder/source/PCCPatchSegmenter.cpp:152-215)
-// and the branch of PCCPatchSegmenter3::compute that runs between them (:78-139): tree, normals, orientation, initial segmentation
-// and refinement on the VOXEL cloud, partition and normals copied back to the points, then the tree, the adjacency and
-// segmentPatches on the full cloud.
+// as the two steps of VoxelCloud, the owner of a frame's voxel cloud.  What PCCPatchSegmenter3::compute runs between them (:78-139)
+// is segmenterCompute's (segmenter_api.cpp: the one chain of the segmenter's modes).
 //
 // The voxel list is in first-occurrence order (voxelize.h).  The first point of every voxel comes out of the stable LSD radix
 // sort the metric's de-duplication uses (radix_sort.hip): in a stable sort of (key, point index) pairs the head of a run of equal
@@ -115,29 +114,49 @@ int voxelizeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint32_t n, int voxDim, int 
   return TMC2_OK;  // (the temporaries go back to the pool; what is queued on the stream runs before their next user's work)
 }
 
-int voxelFrameHostPoints( tmc2_frame* vox, uint32_t V ) {
-  tmc2_ctx*   ctx = vox->ctx;
+int VoxelCloud::build( const tmc2_frame* f, const char* entry, int voxDim, int refineNeighbours ) {
+  tmc2_ctx*   ctx = f->ctx;
   hipStream_t s   = ctx->stream;
-  vox->n = V;
+  frame.reset( new tmc2_frame() );
+  frame->ticket.bind( ctx );
+  frame->ctx = ctx;
+  {
+    StageScope span( ctx, "voxelize" );
+    TMC2_TRY( voxelizeDevice( ctx, f->d_pts.p, uint32_t( f->n ), voxDim, f->geoMax, frame->d_pts, d_voxelOfPoint, &count ) );
+  }
+  const uint32_t V = count;
+  if ( refineNeighbours == 0 && V < kMinVoxelCloud ) {
+    setError( "%s: voxelDimensionGridBasedSegmentation %d leaves a voxel cloud of %u points, fewer than the %u neighbours the normal "
+              "estimation asks for",
+              entry, voxDim, V, kMinVoxelCloud );
+    return TMC2_E_UNSUPPORTED;
+  }
+  if ( refineNeighbours != 0 && ( V < kMinVoxelCloud || V < uint32_t( refineNeighbours ) ) ) {
+    setError( "%s: voxelDimensionGridBasedSegmentation %d leaves a voxel cloud of %u points, fewer than maxNNCountRefineSegmentation %d "
+              "or the %u neighbours the normal estimation asks for",
+              entry, voxDim, V, refineNeighbours, kMinVoxelCloud );
+    return TMC2_E_UNSUPPORTED;
+  }
+  frame->n = V;
   // the host-resident steps (S3's walk and its point-level fallback, a tree build of option KDTREE_HOST) read h_xyz: once down
   Pt* hp = ctx->hostD.get<Pt>( V );
   if ( !hp ) {
-    setError( "segmenter_compute_grid_based: hipHostMalloc failed" );
+    setError( "%s: hipHostMalloc failed", entry );
     return TMC2_E_HIP;
   }
-  TMC2_HIP( hipMemcpyAsync( hp, vox->d_pts.p, size_t( V ) * sizeof( Pt ), hipMemcpyDeviceToHost, s ) );
+  TMC2_HIP( hipMemcpyAsync( hp, frame->d_pts.p, size_t( V ) * sizeof( Pt ), hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
-  vox->h_xyz.resize( 3 * size_t( V ) );
+  frame->h_xyz.resize( 3 * size_t( V ) );
   for ( uint32_t v = 0; v < V; ++v ) {
-    vox->h_xyz[3 * size_t( v )] = hp[v].x, vox->h_xyz[3 * size_t( v ) + 1] = hp[v].y, vox->h_xyz[3 * size_t( v ) + 2] = hp[v].z;
-    vox->geoMax = std::max( vox->geoMax, std::max( hp[v].x, std::max( hp[v].y, hp[v].z ) ) );
+    frame->h_xyz[3 * size_t( v )] = hp[v].x, frame->h_xyz[3 * size_t( v ) + 1] = hp[v].y, frame->h_xyz[3 * size_t( v ) + 2] = hp[v].z;
+    frame->geoMax = std::max( frame->geoMax, std::max( hp[v].x, std::max( hp[v].y, hp[v].z ) ) );
   }
   return TMC2_OK;
 }
 
-int applyVoxelsToPoints( tmc2_frame* f, const tmc2_frame* vox, const uint32_t* d_voxelOfPoint ) {
-  if ( !vox->haveNormals || !vox->havePartition ) {
-    setError( "segmenter_compute_grid_based: the voxel cloud has no normals / partition" );
+int VoxelCloud::applyToPoints( tmc2_frame* f, const char* entry ) const {
+  if ( !frame->haveNormals || !frame->havePartition ) {
+    setError( "%s: the voxel cloud has no normals / partition", entry );
     return TMC2_E_STATE;
   }
   tmc2_ctx*      ctx = f->ctx;
@@ -146,55 +165,12 @@ int applyVoxelsToPoints( tmc2_frame* f, const tmc2_frame* vox, const uint32_t* d
   TMC2_TRY( f->d_partition.alloc( n ) );
   {
     StageScope span( ctx, "voxels_to_points" );
-    hipLaunchKernelGGL( applyVoxelsKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_voxelOfPoint, n, vox->d_partition.p,
-                        vox->d_normals.p, f->d_partition.p, f->d_normals.p );
+    hipLaunchKernelGGL( applyVoxelsKernel, dim3( ( n + 255 ) / 256 ), dim3( 256 ), 0, ctx->stream, d_voxelOfPoint.p, n, frame->d_partition.p,
+                        frame->d_normals.p, f->d_partition.p, f->d_normals.p );
     TMC2_HIP( hipGetLastError() );
   }
   f->haveNormals = f->havePartition = true;
   return TMC2_OK;
-}
-
-int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, int voxDim ) {
-  tmc2_ctx* ctx = f->ctx;
-  // ---- refused before anything is launched: the frame stays as it is
-  TMC2_TRY( tmc2_segmenter_params_check( p ) );
-  if ( f->n == 0 || f->h_xyz.size() != 3 * size_t( f->n ) || f->d_rgb.count == 0 ) {
-    setError( "segmenter_compute_grid_based: the frame has no source cloud with colours" );
-    return TMC2_E_STATE;
-  }
-  TMC2_TRY( voxelizeCheck( "segmenter_compute_grid_based", f->h_xyz.data(), f->n, voxDim, p->geometryBitDepth3D ) );
-  const uint32_t n = uint32_t( f->n );
-  // ---- the voxel cloud: a frame of its own on the same context, built from device data; released on every way out, with every
-  // buffer of the stage (a refine job that was prepared and not consumed goes with it and leaves the context's dense table clean)
-  std::unique_ptr<tmc2_frame> vox( new tmc2_frame() );
-  vox->ticket.bind( ctx );
-  vox->ctx = ctx;
-  DevBuf<uint32_t> d_voxelOfPoint;
-  uint32_t         V = 0;
-  {
-    StageScope span( ctx, "voxelize" );
-    TMC2_TRY( voxelizeDevice( ctx, f->d_pts.p, n, voxDim, f->geoMax, vox->d_pts, d_voxelOfPoint, &V ) );
-  }
-  if ( V < kMinVoxelCloud ) {  // (nothing of the frame has been touched yet)
-    setError( "segmenter_compute_grid_based: voxelDimensionGridBasedSegmentation %d leaves a voxel cloud of %u points, fewer than the "
-              "%u neighbours the normal estimation asks for",
-              voxDim, V, kMinVoxelCloud );
-    return TMC2_E_UNSUPPORTED;
-  }
-  TMC2_TRY( voxelFrameHostPoints( vox.get(), V ) );
-  // ---- S1-S5 on the voxel cloud, with p's values: the refinement's voxel size and radius apply to the shrunk coordinates, the
-  // projection weights are those of the original cloud (S0), as in the reference
-  TMC2_TRY( normalsCompute( vox.get(), p->nnNormalEstimation, p->normalOrientation, nullptr ) );
-  TMC2_TRY( tmc2_segmenter_initial_segmentation( vox.get(), p->weightNormal ) );
-  TMC2_TRY( tmc2_segmenter_refine_grid_based( vox.get(), p->maxNNCountRefineSegmentation, p->lambdaRefineSegmentation,
-                                              p->iterationCountRefineSegmentation, p->voxelDimensionRefineSegmentation,
-                                              p->searchRadiusRefineSegmentation ) );
-  TMC2_TRY( applyVoxelsToPoints( f, vox.get(), d_voxelOfPoint.p ) );
-  vox.reset();  // (its buffers go back to the pool; the copy queued above runs before their next user's work)
-  // ---- the full cloud: tree, k = 16 adjacency (no second normal estimation), patches
-  TMC2_TRY( f->ensureTree() );
-  if ( !f->haveKnn || f->k != p->maxNNCountPatchSegmentation ) TMC2_TRY( launchKnnSelf( f, p->maxNNCountPatchSegmentation ) );
-  return segmentPatches( f, p );
 }
 
 }  // namespace tmc2
@@ -202,12 +178,6 @@ int segmenterComputeGridBased( tmc2_frame* f, const tmc2_segmenter_params* p, in
 using namespace tmc2;
 
 extern "C" {
-
-int tmc2_segmenter_compute_grid_based( tmc2_frame* f, const tmc2_segmenter_params* p, int voxelDimensionGridBasedSegmentation ) {
-  if ( !f || !p ) return TMC2_E_INVALID;
-  ApiScope scope( f->ctx );
-  return segmenterComputeGridBased( f, p, voxelDimensionGridBasedSegmentation );
-}
 
 int tmc2_segmenter_convert_points_to_voxels( tmc2_ctx* ctx, const int16_t* xyz, uint64_t n, int voxDim, int bits, int16_t* voxelXyz,
                                              uint64_t* voxelCount, uint32_t* voxelOfPoint ) {

@@ -1,10 +1,13 @@
 """GPU tier (-m gpu): the HIP path, called through the C-ABI, against the oracle and the golden vectors."""
 import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
+import grid_based_cases as gc
+import knn_refine_cases as kc
 import tmc2_amd as T
 from tmc2_amd.synth import synth_cloud
 
@@ -385,6 +388,41 @@ def test_gpu_segmenter_compute_matches_oracle(gpu_ctx, oracle, name, frame, iter
     p = T.ctc_params(iters, 11, w)
     fr.segmenter_compute(p)
     _assert_patches_equal(fr.get_patches(), oracle.segment(xyz, rgb, _to_oracle_params(p)))
+
+
+def test_gpu_segmenter_chain_stages_and_results_of_every_mode(oracle):
+    """The one chain behind the three entries (csrc/segmenter_api.cpp: segmenterCompute) opens, per mode, the stage spans it opened
+    when every entry had a chain of its own: tests/golden/segmenter_chain_stages.json holds stage name -> calls (the stages that ran)
+    of five chains on the tiny cloud as recorded then, on an MI355X, twice with equal counts -- plain, grid-based with voxels of 2,
+    k-NN refinement on the cloud and with voxels of 2, and plain again on the frame the last one left, without a reset (tree and
+    adjacency resident: neither runs again).  The same five runs give the partition and the patches of the other tests' yardsticks.
+    A context of its own: what a context remembers of earlier frames (row capacities, cap tiers) decides whether a repeat stage runs."""
+    import oracle_binding as ob
+    with open(os.path.join(GOLD, "segmenter_chain_stages.json")) as fh:
+        want = json.load(fh)
+    xyz, rgb = kc.cloud("tiny")
+    ctx = T.Context(0)
+    w = ctx.frame(xyz, rgb).weight_normal(kc.BITS3D, 0.6)
+    assert np.array_equal(bits(w), bits(oracle.weight_normal(xyz, kc.BITS3D, 0.6)))
+    _, nrm, initial, _ = kc.start(oracle, "tiny")
+    plain = dict(partition=oracle.refine_grid(xyz, nrm, initial, iterations=3), seg=oracle.segment(xyz, rgb, ob.seg_params(3, kc.BITS3D, w)))
+    grid, knn, knn_vox = gc.yardstick(oracle, ("tiny", 2, 1)), kc.host_chain(oracle, ("tiny", 0, 1)), kc.host_chain(oracle, ("tiny", 2, 1))
+    chains = [("plain", lambda: T.ctc_params(3, kc.BITS3D, w), None, False, plain),
+              ("grid_based-vox2", lambda: T.fast_params(bits3d=kc.BITS3D, weight=w), 2, False, grid),
+              ("knn_refine", lambda: kc.overrides(T.knn_refine_params(kc.ITERATIONS, kc.BITS3D, w)), None, False, knn),
+              ("knn_refine-vox2", lambda: kc.overrides(T.knn_refine_params(kc.ITERATIONS, kc.BITS3D, w)), 2, False, knn_vox),
+              ("plain-after-knn_refine-vox2", lambda: T.ctc_params(3, kc.BITS3D, w), None, True, plain)]
+    assert sorted(want) == sorted(c[0] for c in chains)
+    fr = None
+    for name, params, vox_dim, same_frame, y in chains:
+        if not same_frame:
+            fr = ctx.frame(xyz, rgb)
+        ctx.stage_reset()
+        fr.segmenter_compute(params(), grid_based=vox_dim)
+        calls = {k: v for k, v in ctx.stage_calls().items() if v}
+        assert calls == want[name], name
+        assert np.array_equal(fr.get_partition(), y["partition"]), name
+        _assert_patches_equal(fr.get_patches(), y["seg"])
 
 
 def test_gpu_segmenter_full_size_properties(gpu_ctx):
