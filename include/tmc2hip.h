@@ -33,6 +33,8 @@ extern "C" {
 #define TMC2_E_INVALID -3
 #define TMC2_E_UNSUPPORTED -4
 #define TMC2_E_STATE -5
+/* a host restatement (tmc2_host_metrics_compute) whose answer would depend on the k-d tree's visiting order, which it does not know */
+#define TMC2_E_ORDER -6
 
 typedef struct tmc2_ctx   tmc2_ctx;
 typedef struct tmc2_frame tmc2_frame;
@@ -465,6 +467,36 @@ int tmc2_metrics_compute_frame( tmc2_frame* frame, int which, int useNormals, do
 int tmc2_metrics_compute_frame_source( tmc2_frame* frame, int which, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
                                        const double* srcNormals, double resolution, double* out, int64_t* counts );
 
+/* The same three entries over the parameter space of PCCMetricsParameters that PccAppMetrics takes on its command line
+ * (reflectance and lidar excepted: these clouds carry neither).  tmc2_metrics_params_default: computeC2c 1, computeC2p 1,
+ * computeColor 1, computeHausdorff 0, dropDuplicates 2, neighborsProc 1 -- with these the _ex entries run what the entries
+ * above run and return their bits in columns 0-7.
+ * out[3][14]: columns 0-7 as above; 8, 9 colorPsnr U, V; 10 c2cHausdorff, 11 c2cHausdorffPsnr, 12 c2pHausdorff, 13
+ * c2pHausdorffPsnr.  What a flag turns off stays 0, as QualityMetrics' constructor leaves it.
+ * dropDuplicates 0: no de-duplication and no reordering (counts = 0, 0; duplicated source points all take the normal of the LAST
+ * duplicate, PCCPointSet3::copyNormals); 1: a run of equal positions keeps the colour of its first point; 2: the mean colour.
+ * neighborsProc 0: the colour of the first search result; 1, 2: the rounded mean over the points at the minimum distance; 3, 4 AS
+ * THE REFERENCE IS WRITTEN (PCCMetrics.cpp:155-171: distBest and indexBest start at 0, strict comparisons, indexBest names a point
+ * of the other cloud): 3 takes the colour of that cloud's point 0, 4 the first member of the group, in ascending index, whose
+ * colour distance strictly beats every earlier one -- point 0 again if all are 0.
+ * computeHausdorff: the maxima start at DBL_MIN (two identical clouds report it).  computeC2p is ignored without normals.
+ * TMC2_E_INVALID for params == NULL; TMC2_E_UNSUPPORTED (nothing is launched) for a flag that is not 0 / 1, dropDuplicates
+ * outside 0..2, neighborsProc outside 0..4.                                                                          */
+typedef struct tmc2_metrics_params {
+  int32_t computeC2c, computeC2p, computeColor, computeHausdorff;
+  int32_t dropDuplicates;
+  int32_t neighborsProc;
+} tmc2_metrics_params;
+void tmc2_metrics_params_default( tmc2_metrics_params* params );
+int tmc2_metrics_compute_ex( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* recXyz,
+                             const uint8_t* recRgb, uint64_t m, const double* srcNormals, double resolution,
+                             const tmc2_metrics_params* params, double* out, int64_t* counts );
+int tmc2_metrics_compute_frame_ex( tmc2_frame* frame, int which, int useNormals, double resolution, const tmc2_metrics_params* params,
+                                   double* out, int64_t* counts );
+int tmc2_metrics_compute_frame_source_ex( tmc2_frame* frame, int which, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
+                                          const double* srcNormals, double resolution, const tmc2_metrics_params* params, double* out,
+                                          int64_t* counts );
+
 /* The accumulation of QualityMetrics::compute alone (`sseC2c += ..`, `sseC2p += ..`, `sseColor[i] += ..` over the points in
  * index order, PCCMetrics.cpp:187-198) for per-point terms the caller holds on the host: termsA[nA][5] / termsB[nB][5] = the
  * squared distance (an integer), the point-to-plane term and the three colour terms of every point, one direction each (either
@@ -479,6 +511,13 @@ int tmc2_metrics_ordered_sums( tmc2_ctx* ctx, const double* termsA, uint64_t nA,
  * NULL to query the size (*needed, including the terminating 0).  Host only.                                       */
 int tmc2_metrics_display( const double* out, uint64_t sourcePoints, uint64_t reconstructPoints, const int64_t* counts,
                           uint64_t resolution, int withC2p, int precision, char* text, uint64_t capacity, uint64_t* needed );
+/* ... from out[3][14] of the _ex entries and their parameters: rows 1 and 2 print the blocks the flags leave on, the Hausdorff
+ * lines among them (the "p2plane" ones print the p2point members, as QualityMetrics::print does); the symmetric row prints as
+ * the reference's does -- it is a QualityMetrics with DEFAULT parameters (operator+ sets none): all of point-to-point,
+ * point-to-plane and colour, no Hausdorff lines.  All three colour PSNR lines come from columns 7-9.  withC2p: normals were given. */
+int tmc2_metrics_display_ex( const double* out, const tmc2_metrics_params* params, uint64_t sourcePoints, uint64_t reconstructPoints,
+                             const int64_t* counts, uint64_t resolution, int withC2p, int precision, char* text, uint64_t capacity,
+                             uint64_t* needed );
 
 /* ---- point-cloud ingest and conformance checksums (host; no device needed) ------------------------------------------- */
 /* replaces: PCCPointSet3::read (PccLibCommon/source/PCCPointSet.cpp:464-757) as PCCGroupOfFrames::load (PCCGroupOfFrames.cpp:
@@ -543,6 +582,15 @@ int tmc2_host_orient_normals( const int16_t* xyz, uint64_t n, const uint32_t* kn
 int tmc2_host_color_smoothing( const int16_t* xyz, uint16_t* colors16, const uint16_t* boundaryType, const uint32_t* patchIndex,
                                uint64_t M, int gridSize, int geometryBitDepth3D, double thresholdColorSmoothing,
                                double thresholdColorDifference, double thresholdColorVariation );
+/* PCCMetrics::compute for one frame restated on the host (csrc/metrics_host.cpp; no device, brute-force neighbour search): the
+ * arguments and results of tmc2_metrics_compute_ex.  It does not know the k-d tree's visiting order; where the answer depends on
+ * it -- the first result among several equidistant points (neighborsProc 0), a minimum-distance group of more than 30 points, the
+ * floating-point sum over the nearest source points of a reconstructed point nobody voted for, unless every order of adding
+ * them gives the same doubles -- it returns
+ * TMC2_E_ORDER and leaves out untouched.                                                                              */
+int tmc2_host_metrics_compute( const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* recXyz, const uint8_t* recRgb,
+                               uint64_t m, const double* srcNormals, double resolution, const tmc2_metrics_params* params, double* out,
+                               int64_t* counts );
 /* the exact restatement of PatchBlockFiltering::patchBorderFiltering (PCCPatch.cpp:950-976) behind
  * tmc2_codec_generate_point_cloud_pbf, on host arrays: patch records in list order, the occupancy video (uint8 [H/p][W/p]),
  * geometry map 0 (uint16 [H][W]), blockToPatch (uint32 [H/16][W/16], list position + 1); occupancy / border as

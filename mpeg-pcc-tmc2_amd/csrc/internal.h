@@ -483,6 +483,8 @@ int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint
 // 0xFFFFFFFF), then the compacted rest through the ordinary kernel, rows in place (knn.hip: what a caller may do with d_easy)
 int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_easy, uint32_t* d_idx,
                     uint32_t* d_dist, const char* stage, bool uniqueTreeRows = false );
+// metrics_host.cpp: TMC2_E_INVALID for a NULL parameter set, TMC2_E_UNSUPPORTED (by name) for a value outside PCCMetricsParameters' ranges
+int checkMetricsParams( const char* who, const tmc2_metrics_params* q );
 int generateAttributeImages( tmc2_frame* f );
 struct PbfParams;  // patch_border_filter.h
 // pbf != nullptr: occupancy synthesis first (patchBorderFilterDevice); occupancy and boundary types then come from its maps

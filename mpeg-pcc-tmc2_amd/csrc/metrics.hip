@@ -18,9 +18,16 @@
 // dependent add per point each) while the rest of the workgroup streams the next chunk into LDS.  Only the 3 x 8 results cross
 // PCIe on the way back.  The clouds come either from the host (tmc2_metrics_compute) or straight from a frame's resident
 // arrays (tmc2_metrics_compute_frame: no upload at all).
+//
+// The parameter space of PCCMetricsParameters (the _ex entries): dropDuplicates 1 is a second instantiation of the emitting kernel
+// (first colour instead of the mean), 0 a bypass of the whole sort (the clouds in input order, trees with duplicate positions:
+// every search through the ordinary kernel, and copyNormals' "last point of a position wins" from one sort of the source);
+// neighborsProc is a template constant of the per-point kernel (the default instantiation is the kernel as it was); the Hausdorff
+// maxima are one more small reduction over the finished terms, launched only where they are asked for.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <numeric>
 
 #include "internal.h"
@@ -105,7 +112,9 @@ __global__ __launch_bounds__( 256 ) void positionKeysKernel( CloudView c, KeyBas
 }
 
 // (the stable LSD radix sort of the (key, index) pairs and the heads of its runs: radixSortPairs, markRunHeads, radix_sort.hip)
-// one thread per run: position of its first element, colour = integer mean over the run (removeDuplicate :188-206)
+// one thread per run: position of its first element, colour = integer mean over the run (removeDuplicate :188-206); !kAverage
+// (dropDuplicates 1): the colour of its first element, the duplicate with the smallest input index
+template <bool kAverage>
 __global__ __launch_bounds__( 256 ) void emitDistinctKernel( const uint64_t* __restrict__ key, const uint32_t* __restrict__ index,
                                                               const uint32_t* __restrict__ head, const uint32_t* __restrict__ rank,
                                                               CloudView c, Pt* __restrict__ pts, uint8_t* __restrict__ rgb4,
@@ -114,7 +123,7 @@ __global__ __launch_bounds__( 256 ) void emitDistinctKernel( const uint64_t* __r
   if ( i >= c.n || !head[i] ) return;
   const uint64_t k = key[i];
   uint32_t       r = 0, g = 0, b = 0, cnt = 0;
-  for ( uint32_t j = i; j < c.n && key[j] == k; ++j ) {
+  for ( uint32_t j = i; j < ( kAverage ? c.n : i + 1 ) && key[j] == k; ++j ) {
     const uint8_t* col = c.rgb + size_t( index[j] ) * c.rgbStride;
     r += col[0], g += col[1], b += col[2];
     ++cnt;
@@ -131,6 +140,30 @@ __global__ __launch_bounds__( 256 ) void rawPointsKernel( CloudView c, Pt* __res
   const int16_t* q = c.xyz + size_t( i ) * c.xyzStride;
   pts[i]           = Pt{q[0], q[1], q[2], 0};
 }
+// dropDuplicates 0: the cloud as it came, colours widened to the four bytes the other kernels read
+__global__ __launch_bounds__( 256 ) void rawColoursKernel( CloudView c, uint8_t* __restrict__ rgb4 ) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( i >= c.n ) return;
+  const uint8_t* col                   = c.rgb + size_t( i ) * c.rgbStride;
+  reinterpret_cast<uchar4*>( rgb4 )[i] = make_uchar4( col[0], col[1], col[2], 0 );
+}
+// copyNormals on a cloud with duplicate positions (:2295-2310): the map from a position to an index is overwritten point by point,
+// so every point of a run takes the normal of the run's LAST element -- the largest input index: the sort is stable
+__global__ __launch_bounds__( 256 ) void lastWinsNormalsKernel( const uint64_t* __restrict__ key, const uint32_t* __restrict__ index,
+                                                                 const uint32_t* __restrict__ head, uint32_t n,
+                                                                 const double* __restrict__ nrm, double* __restrict__ out ) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( i >= n || !head[i] ) return;
+  const uint64_t k   = key[i];
+  uint32_t       end = i + 1;
+  while ( end < n && key[end] == k ) ++end;
+  const size_t o = 3 * size_t( index[end - 1] );
+  const double x = nrm[o], y = nrm[o + 1], z = nrm[o + 2];
+  for ( uint32_t j = i; j < end; ++j ) {
+    const size_t t = 3 * size_t( index[j] );
+    out[t] = x, out[t + 1] = y, out[t + 2] = z;
+  }
+}
 __global__ __launch_bounds__( 256 ) void gatherPointsKernel( const Pt* __restrict__ pts, const uint32_t* __restrict__ which, uint32_t n,
                                                               Pt* __restrict__ out ) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -144,13 +177,18 @@ __global__ __launch_bounds__( 256 ) void gatherNormalsKernel( const double* __re
   out[3 * size_t( i )] = nrm[o], out[3 * size_t( i ) + 1] = nrm[o + 1], out[3 * size_t( i ) + 2] = nrm[o + 2];
 }
 
-// the cloud as its owner keeps it -> the distinct positions in (x, y, z) order with averaged colours; first[u] = input index of
-// the duplicate whose position / normal the reference keeps
-int removeDuplicatesDevice( tmc2_ctx* ctx, const CloudView& c, DevCloud& out, DevBuf<uint32_t>& d_first ) {
-  hipStream_t      s = ctx->stream;
-  const uint32_t   n = c.n;
+// the points of a cloud in (x, y, z) order: the sorted (key, input index) pairs, the heads of the runs of equal positions, their ranks
+struct SortedPositions {
   DevBuf<uint64_t> d_keyA, d_keyB;
   DevBuf<uint32_t> d_idxA, d_idxB, d_head, d_rank, d_small;
+  const uint64_t*  key      = nullptr;
+  const uint32_t*  idx      = nullptr;
+  uint32_t         distinct = 0;
+  int              sort( tmc2_ctx* ctx, const CloudView& c );
+};
+int SortedPositions::sort( tmc2_ctx* ctx, const CloudView& c ) {
+  hipStream_t    s = ctx->stream;
+  const uint32_t n = c.n;
   TMC2_TRY( d_keyA.alloc( n ) );
   TMC2_TRY( d_keyB.alloc( n ) );
   TMC2_TRY( d_idxA.alloc( n ) );
@@ -175,18 +213,52 @@ int removeDuplicatesDevice( tmc2_ctx* ctx, const CloudView& c, DevCloud& out, De
   hipLaunchKernelGGL( positionKeysKernel, grd, blk, 0, s, c, kb, d_keyA.p, d_idxA.p );
   bool inA = true;
   TMC2_TRY( radixSortPairs( ctx, d_keyA.p, d_idxA.p, d_keyB.p, d_idxB.p, n, kb.bits, &inA ) );
-  const uint64_t* key = inA ? d_keyA.p : d_keyB.p;
-  const uint32_t* idx = inA ? d_idxA.p : d_idxB.p;
+  key = inA ? d_keyA.p : d_keyB.p;
+  idx = inA ? d_idxA.p : d_idxB.p;
   TMC2_TRY( markRunHeads( ctx, key, n, d_head.p ) );
   TMC2_TRY( exclusiveScanU32( ctx, d_head.p, d_rank.p, n, d_small.p + 6 ) );
-  uint32_t distinct = 0;
   TMC2_HIP( hipMemcpyAsync( &distinct, d_small.p + 6, 4, hipMemcpyDeviceToHost, s ) );
   TMC2_HIP( hipStreamSynchronize( s ) );
-  out.n = distinct;
-  TMC2_TRY( out.pts.alloc( distinct ) );
-  TMC2_TRY( out.rgb4.alloc( 4 * size_t( distinct ) ) );
-  TMC2_TRY( d_first.alloc( distinct ) );
-  hipLaunchKernelGGL( emitDistinctKernel, grd, blk, 0, s, key, idx, d_head.p, d_rank.p, c, out.pts.p, out.rgb4.p, d_first.p );
+  return TMC2_OK;
+}
+
+// the cloud as its owner keeps it -> the distinct positions in (x, y, z) order with averaged colours (average = false: the first
+// duplicate's); first[u] = input index of the duplicate whose position / normal the reference keeps
+int removeDuplicatesDevice( tmc2_ctx* ctx, const CloudView& c, bool average, DevCloud& out, DevBuf<uint32_t>& d_first ) {
+  hipStream_t     s = ctx->stream;
+  SortedPositions sp;
+  TMC2_TRY( sp.sort( ctx, c ) );
+  const dim3 blk( 256 ), grd( ( c.n + 255 ) / 256 );
+  out.n = sp.distinct;
+  TMC2_TRY( out.pts.alloc( sp.distinct ) );
+  TMC2_TRY( out.rgb4.alloc( 4 * size_t( sp.distinct ) ) );
+  TMC2_TRY( d_first.alloc( sp.distinct ) );
+  if ( average )
+    hipLaunchKernelGGL( emitDistinctKernel<true>, grd, blk, 0, s, sp.key, sp.idx, sp.d_head.p, sp.d_rank.p, c, out.pts.p, out.rgb4.p, d_first.p );
+  else
+    hipLaunchKernelGGL( emitDistinctKernel<false>, grd, blk, 0, s, sp.key, sp.idx, sp.d_head.p, sp.d_rank.p, c, out.pts.p, out.rgb4.p, d_first.p );
+  TMC2_HIP( hipGetLastError() );
+  TMC2_HIP( hipStreamSynchronize( s ) );  // (the temporaries go back to the pool)
+  return TMC2_OK;
+}
+// dropDuplicates 0: the cloud in its input order, duplicate positions and all
+int rawCloudDevice( tmc2_ctx* ctx, const CloudView& c, DevCloud& out ) {
+  const dim3 blk( 256 ), grd( ( c.n + 255 ) / 256 );
+  out.n = c.n;
+  TMC2_TRY( out.pts.alloc( c.n ) );
+  TMC2_TRY( out.rgb4.alloc( 4 * size_t( c.n ) ) );
+  hipLaunchKernelGGL( rawPointsKernel, grd, blk, 0, ctx->stream, c, out.pts.p );
+  hipLaunchKernelGGL( rawColoursKernel, grd, blk, 0, ctx->stream, c, out.rgb4.p );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+// ... and its normals: copyNormals' last-wins rule over one sort of the source (out: fp64[c.n][3], allocated here)
+int lastWinsNormalsDevice( tmc2_ctx* ctx, const CloudView& c, const double* d_srcNormals, DevBuf<double>& out ) {
+  hipStream_t     s = ctx->stream;
+  SortedPositions sp;
+  TMC2_TRY( sp.sort( ctx, c ) );
+  TMC2_TRY( out.alloc( 3 * size_t( c.n ) ) );
+  hipLaunchKernelGGL( lastWinsNormalsKernel, dim3( ( c.n + 255 ) / 256 ), dim3( 256 ), 0, s, sp.key, sp.idx, sp.d_head.p, c.n, d_srcNormals, out.p );
   TMC2_HIP( hipGetLastError() );
   TMC2_HIP( hipStreamSynchronize( s ) );  // (the temporaries go back to the pool)
   return TMC2_OK;
@@ -274,7 +346,16 @@ __device__ __forceinline__ void yuv709( const uchar4 c, float& y, float& u, floa
   v = float( __ddiv_rn( 0.5000 * double( c.x ) - 0.4542 * double( c.y ) - 0.0458 * double( c.z ), 255.0 ) + 0.5000 );
 }
 
+// how a point of A takes its colour from B (neighborsProc_; PCCMetrics.cpp:127-176), a template constant of the per-point kernel
+enum ColourRule {
+  kColourNone   = -1,  // computeColor off: the three colour terms are 0
+  kColourFirst  = 0,   // the first result in search order
+  kColourMean   = 1,   // the rounded mean over the group (neighborsProc 1 and 2: nbdup is the constant 1)
+  kColourPoint0 = 3,   // "Min": `dist < distBest` from distBest = 0 never holds, indexBest stays 0 -- B's point 0
+  kColourMax    = 4    // "Max": the first member, in ascending index, that strictly beats every earlier one; B's point 0 if none does
+};
 // per point of A: D1 term (min squared distance), D2 term, three colour terms against its nearest group in B
+template <int kColour>
 __global__ __launch_bounds__( 256 ) void distortionTermsKernel( const Pt* __restrict__ ptsA, const uint8_t* __restrict__ rgbA,
                                                                  const Pt* __restrict__ ptsB, const uint8_t* __restrict__ rgbB,
                                                                  const double* __restrict__ nrmB,
@@ -300,6 +381,10 @@ __global__ __launch_bounds__( 256 ) void distortionTermsKernel( const Pt* __rest
   const Pt pa  = ptsA[a];
   double   c2p = 0.0;
   unsigned r = 0, gg = 0, b = 0;
+  float    ya, ua, va, yb, ub, vb;
+  if ( kColour == kColourMax ) yuv709( reinterpret_cast<const uchar4*>( rgbA )[a], ya, ua, va );
+  float    distBest  = 0.f;
+  uint32_t indexBest = 0;
   for ( int j = 0; j < g; ++j ) {
     const uint32_t ib = same[j];
     if ( nrmB ) {
@@ -308,23 +393,72 @@ __global__ __launch_bounds__( 256 ) void distortionTermsKernel( const Pt* __rest
       const double dp = e0 * nrmB[3 * size_t( ib )] + e1 * nrmB[3 * size_t( ib ) + 1] + e2 * nrmB[3 * size_t( ib ) + 2];
       c2p += dp * dp;
     }
-    const uchar4 cb = reinterpret_cast<const uchar4*>( rgbB )[ib];
-    r += cb.x, gg += cb.y, b += cb.z;
+    if ( kColour == kColourMean ) {
+      const uchar4 cb = reinterpret_cast<const uchar4*>( rgbB )[ib];
+      r += cb.x, gg += cb.y, b += cb.z;
+    }
+    if ( kColour == kColourMax ) {
+      yuv709( reinterpret_cast<const uchar4*>( rgbB )[ib], yb, ub, vb );
+      const float ey = ya - yb, eu = ua - ub, ev = va - vb;
+      const float e = float( float( ey * ey ) + float( eu * eu ) ) + float( ev * ev );
+      if ( e > distBest ) distBest = e, indexBest = ib;
+    }
   }
   if ( nrmB ) c2p = __ddiv_rn( c2p, double( g ) );
-  const uchar4 avg = make_uchar4( (unsigned char)round( __ddiv_rn( double( r ), double( g ) ) ),
-                                  (unsigned char)round( __ddiv_rn( double( gg ), double( g ) ) ),
-                                  (unsigned char)round( __ddiv_rn( double( b ), double( g ) ) ), 0 );
-  float ya, ua, va, yb, ub, vb;
-  yuv709( reinterpret_cast<const uchar4*>( rgbA )[a], ya, ua, va );
-  yuv709( avg, yb, ub, vb );
+  double* t = terms + size_t( a ) * 5;
+  t[0]      = double( d[0] );
+  t[1]      = c2p;
+  if ( kColour == kColourNone ) {
+    t[2] = 0.0, t[3] = 0.0, t[4] = 0.0;
+    return;
+  }
+  uchar4 cb;
+  if ( kColour == kColourMean )
+    cb = make_uchar4( (unsigned char)round( __ddiv_rn( double( r ), double( g ) ) ), (unsigned char)round( __ddiv_rn( double( gg ), double( g ) ) ),
+                      (unsigned char)round( __ddiv_rn( double( b ), double( g ) ) ), 0 );
+  else
+    cb = reinterpret_cast<const uchar4*>( rgbB )[kColour == kColourFirst ? idx[size_t( a ) * K] /* before the sort */ : indexBest];
+  if ( kColour != kColourMax ) yuv709( reinterpret_cast<const uchar4*>( rgbA )[a], ya, ua, va );
+  yuv709( cb, yb, ub, vb );
   const float dy = ya - yb, du = ua - ub, dv = va - vb;
-  double*     t  = terms + size_t( a ) * 5;
-  t[0]           = double( d[0] );
-  t[1]           = c2p;
   t[2]           = double( float( dy * dy ) );
   t[3]           = double( float( du * du ) );
   t[4]           = double( float( dv * dv ) );
+}
+
+// ---- the Hausdorff maxima -----------------------------------------------------------------------------------------------------
+// maxC2c / maxC2p of QualityMetrics::compute (:74-75, :188, :192): they start at DBL_MIN and move on a strict `>`, so they are
+// max( DBL_MIN, the largest term ) -- order-free.  The terms are non-negative doubles, which compare as their bit patterns do (a
+// NaN term never passes the reference's `>`: left out).  mx[4]: D1 and D2 of direction A, then of B, preset to DBL_MIN by the
+// caller.  A stride loop over at most kBoundsBlocks workgroups, folded per workgroup, four atomics per workgroup (as boundsKernel).
+__global__ __launch_bounds__( 256 ) void maxTermsKernel( const double* __restrict__ termsA, uint32_t nA, const double* __restrict__ termsB,
+                                                          uint32_t nB, unsigned long long* __restrict__ mx ) {
+  __shared__ unsigned long long sMax[4][4];
+  unsigned long long            m[4] = {0ull, 0ull, 0ull, 0ull};
+  for ( uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < uint64_t( nA ) + nB; i += gridDim.x * blockDim.x ) {
+    const int     dir = i >= nA;
+    const double* t   = dir ? termsB + 5 * ( i - nA ) : termsA + 5 * i;
+#pragma unroll
+    for ( int c = 0; c < 2; ++c ) {
+      const double v = t[c];
+      if ( v == v ) m[2 * dir + c] = max( m[2 * dir + c], (unsigned long long)__double_as_longlong( v ) );
+    }
+  }
+#pragma unroll
+  for ( int c = 0; c < 4; ++c ) {
+#pragma unroll
+    for ( int off = 32; off > 0; off >>= 1 ) m[c] = max( m[c], (unsigned long long)__shfl_xor( (long long)m[c], off, 64 ) );
+  }
+  if ( ( threadIdx.x & 63 ) == 0 ) {
+#pragma unroll
+    for ( int c = 0; c < 4; ++c ) sMax[threadIdx.x >> 6][c] = m[c];
+  }
+  __syncthreads();
+  if ( threadIdx.x < 4 ) {
+    const int                c  = threadIdx.x;
+    const unsigned long long hi = max( max( sMax[0][c], sMax[1][c] ), max( sMax[2][c], sMax[3][c] ) );
+    if ( hi > loadStaleOk( &mx[c] ) ) atomicMax( &mx[c], hi );
+  }
 }
 
 // ---- the sums over the points ---------------------------------------------------------------------------------------------
@@ -563,61 +697,102 @@ double psnr( double dist, double p, double factor ) { return 10 * std::log10( ( 
 // The metric's searches against a DE-DUPLICATED cloud (round 6: in two launches, knn.hip launchKnnSplit): most points of one cloud
 // are points of the other, and in a tree without duplicate positions the group "all points at the minimum distance" of such a
 // query is that one point.
-int metricsKnn( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int K, uint32_t* d_idx, uint32_t* d_dist ) {
+// (uniqueTree = false, dropDuplicates 0: the tree holds duplicate positions -- the ordinary search for every query)
+int metricsKnn( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int K, uint32_t* d_idx, uint32_t* d_dist,
+                bool uniqueTree = true ) {
+  if ( !uniqueTree ) return launchKnnTree( ctx, tree, d_queries, nq, K, d_idx, d_dist, "metrics_knn" );
   DevBuf<uint32_t> d_easy;
   TMC2_TRY( d_easy.alloc( std::max<uint64_t>( nq, 1 ) ) );
   return launchKnnSplit( ctx, tree, d_queries, nq, K, d_easy.p, d_idx, d_dist, "metrics_knn", true );
 }
 
 // per-point terms of one direction (A's points against their nearest neighbours in B)
-int qualityTerms( tmc2_ctx* ctx, const DevCloud& A, const DevCloud& B, bool withNormals, int K, DevBuf<double>& d_terms,
-                  uint32_t* d_error ) {
+template <int kColour>
+void launchTerms( hipStream_t s, const DevCloud& A, const DevCloud& B, bool withNormals, const uint32_t* d_idx, const uint32_t* d_dist, int K,
+                  double* d_terms, uint32_t* d_error ) {
+  const uint32_t nA = uint32_t( A.n );
+  hipLaunchKernelGGL( distortionTermsKernel<kColour>, dim3( ( nA + 255 ) / 256 ), dim3( 256 ), 0, s, A.pts.p, A.rgb4.p, B.pts.p, B.rgb4.p,
+                      withNormals ? B.nrm.p : (const double*)nullptr, d_idx, d_dist, K, nA, d_terms, d_error );
+}
+int qualityTerms( tmc2_ctx* ctx, const DevCloud& A, const DevCloud& B, bool withNormals, int K, int colour, bool uniqueTrees,
+                  DevBuf<double>& d_terms, uint32_t* d_error ) {
   hipStream_t      s  = ctx->stream;
   const uint32_t   nA = uint32_t( A.n );
   DevBuf<uint32_t> d_idx, d_dist;
   TMC2_TRY( d_idx.alloc( size_t( nA ) * K ) );
   TMC2_TRY( d_dist.alloc( size_t( nA ) * K ) );
   TMC2_TRY( d_terms.alloc( size_t( nA ) * 5 ) );
-  TMC2_TRY( metricsKnn( ctx, B.devFor( A ), A.pts.p, nA, K, d_idx.p, d_dist.p ) );
+  TMC2_TRY( metricsKnn( ctx, B.devFor( A ), A.pts.p, nA, K, d_idx.p, d_dist.p, uniqueTrees ) );
   StageScope stage( ctx, "metrics_terms" );
-  hipLaunchKernelGGL( distortionTermsKernel, dim3( ( nA + 255 ) / 256 ), dim3( 256 ), 0, s, A.pts.p, A.rgb4.p, B.pts.p, B.rgb4.p,
-                      withNormals ? B.nrm.p : (const double*)nullptr, d_idx.p, d_dist.p, K, nA, d_terms.p, d_error );
+  switch ( colour ) {
+    case kColourNone: launchTerms<kColourNone>( s, A, B, withNormals, d_idx.p, d_dist.p, K, d_terms.p, d_error ); break;
+    case kColourFirst: launchTerms<kColourFirst>( s, A, B, withNormals, d_idx.p, d_dist.p, K, d_terms.p, d_error ); break;
+    case kColourMean: launchTerms<kColourMean>( s, A, B, withNormals, d_idx.p, d_dist.p, K, d_terms.p, d_error ); break;
+    case kColourPoint0: launchTerms<kColourPoint0>( s, A, B, withNormals, d_idx.p, d_dist.p, K, d_terms.p, d_error ); break;
+    default: launchTerms<kColourMax>( s, A, B, withNormals, d_idx.p, d_dist.p, K, d_terms.p, d_error ); break;
+  }
   return TMC2_OK;
 }
 
-void qualityFromSums( const double* sse, double num, bool withNormals, double resolution, double* out ) {
-  out[0] = sse[0] / num;
-  out[1] = psnr( out[0], resolution, 3 );
-  out[2] = withNormals ? sse[1] / num : 0.0;
-  out[3] = withNormals ? psnr( out[2], resolution, 3 ) : 0.0;
-  for ( int i = 0; i < 3; ++i ) out[4 + i] = sse[2 + i] / num;
-  out[7] = psnr( out[4], 1.0, 1.0 );
+constexpr int kCols = 14;  // of a row of the _ex entries: tmc2hip.h
+// one direction's row (QualityMetrics::compute :202-224): sse[5] the sums, mx[2] the maxima (read only with computeHausdorff);
+// withNormals: normals were given AND computeC2p is on
+void qualityFromSums( const double* sse, const double* mx, double num, bool withNormals, double resolution, const tmc2_metrics_params& q,
+                      double* out ) {
+  for ( int i = 0; i < kCols; ++i ) out[i] = 0.0;
+  if ( q.computeC2c ) {
+    out[0] = sse[0] / num;
+    out[1] = psnr( out[0], resolution, 3 );
+    if ( q.computeHausdorff ) out[10] = mx[0], out[11] = psnr( out[10], resolution, 3 );
+  }
+  if ( withNormals ) {
+    out[2] = sse[1] / num;
+    out[3] = psnr( out[2], resolution, 3 );
+    if ( q.computeHausdorff ) out[12] = mx[1], out[13] = psnr( out[12], resolution, 3 );
+  }
+  if ( q.computeColor ) {
+    for ( int i = 0; i < 3; ++i ) out[4 + i] = sse[2 + i] / num;
+    out[7] = psnr( out[4], 1.0, 1.0 );
+    out[8] = psnr( out[5], 1.0, 1.0 );
+    out[9] = psnr( out[6], 1.0, 1.0 );
+  }
 }
-
 // PCCMetrics::compute for one frame from clouds resident on the device.  d_srcNormals: fp64[src.n][3] or null.
 // *overflow = true: some query's K results were all equidistant (K = 16 only): the caller repeats with K = 32.
 int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, const double* d_srcNormals, double resolution, int K,
-                   double* out, int64_t* counts, bool* overflow ) {
+                   const tmc2_metrics_params& q, double* out, int64_t* counts, bool* overflow ) {
   hipStream_t s = ctx->stream;
   *overflow     = false;
   DevCloud         dS, dR, dN;  // de-duplicated source, de-duplicated reconstruction, normal cloud (original source order)
   DevBuf<uint32_t> d_firstS, d_firstR;
-  const bool       withNormals = d_srcNormals != nullptr;
-  const dim3       blk( 256 );
+  const bool       keepDuplicates = q.dropDuplicates == 0, uniqueTrees = !keepDuplicates;
+  // (normals given with computeC2p off: copyNormals and scaleNormals would feed nothing -- only the reference's exit on a source with
+  //  duplicates remains of them)
+  const bool withNormals = d_srcNormals != nullptr && q.computeC2p;
+  const int  colour      = !q.computeColor ? kColourNone : q.neighborsProc == 2 ? kColourMean : q.neighborsProc;
+  const dim3 blk( 256 );
   {
     StageScope prep( ctx, "metrics_prepare" );
-    TMC2_TRY( removeDuplicatesDevice( ctx, src, dS, d_firstS ) );
-    TMC2_TRY( removeDuplicatesDevice( ctx, rec, dR, d_firstR ) );
-    if ( counts ) counts[0] = int64_t( dS.n ), counts[1] = int64_t( dR.n );
+    if ( keepDuplicates ) {
+      TMC2_TRY( rawCloudDevice( ctx, src, dS ) );
+      TMC2_TRY( rawCloudDevice( ctx, rec, dR ) );
+      if ( counts ) counts[0] = 0, counts[1] = 0;  // (what PCCMetrics::compute pushes, :354-355)
+    } else {
+      TMC2_TRY( removeDuplicatesDevice( ctx, src, q.dropDuplicates == 2, dS, d_firstS ) );
+      TMC2_TRY( removeDuplicatesDevice( ctx, rec, q.dropDuplicates == 2, dR, d_firstR ) );
+      if ( counts ) counts[0] = int64_t( dS.n ), counts[1] = int64_t( dR.n );
+    }
     if ( dS.n < size_t( K ) || dR.n < size_t( K ) ) {
       setError( "metrics_compute: clouds smaller than %d points unsupported", K );
       return TMC2_E_UNSUPPORTED;
     }
-    if ( withNormals ) {
-      if ( dS.n != src.n ) {
-        setError( "metrics_compute: the source has duplicate positions; normals cannot be attached (the reference exits)" );
-        return TMC2_E_INVALID;
-      }
+    if ( d_srcNormals && dS.n != src.n ) {
+      setError( "metrics_compute: the source has duplicate positions; normals cannot be attached (the reference exits)" );
+      return TMC2_E_INVALID;
+    }
+    if ( withNormals && keepDuplicates ) {
+      TMC2_TRY( lastWinsNormalsDevice( ctx, src, d_srcNormals, dS.nrm ) );
+    } else if ( withNormals ) {
       // copyNormals: the de-duplicated source is the lexicographic sort of the input
       TMC2_TRY( dS.nrm.alloc( 3 * size_t( src.n ) ) );
       hipLaunchKernelGGL( gatherNormalsKernel, dim3( ( src.n + 255 ) / 256 ), blk, 0, s, d_srcNormals, d_firstS.p, src.n, dS.nrm.p );
@@ -631,7 +806,7 @@ int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, co
   if ( withNormals ) {
     // scaleNormals
     const uint32_t mR = uint32_t( dR.n ), nS = src.n;
-    dN.n = nS;  // the normal cloud: the source in its original order (no duplicates: checked above)
+    dN.n = nS;  // the normal cloud: the source in its original order (no duplicates: checked above -- or dropDuplicates 0: dS itself)
     TMC2_TRY( dN.pts.alloc( nS ) );
     hipLaunchKernelGGL( rawPointsKernel, dim3( ( nS + 255 ) / 256 ), blk, 0, s, src, dN.pts.p );
     DevBuf<uint32_t> d_idx, d_dist, d_count, d_offset, d_cursor, d_voters, d_total;
@@ -642,7 +817,7 @@ int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, co
     TMC2_TRY( d_cursor.alloc( mR ) );
     TMC2_TRY( d_total.alloc( 1 ) );
     TMC2_TRY( dR.nrm.alloc( 3 * size_t( mR ) ) );
-    TMC2_TRY( metricsKnn( ctx, dR.devFor( dS ), dN.pts.p, nS, K, d_idx.p, d_dist.p ) );  // (dN = the points of dS)
+    TMC2_TRY( metricsKnn( ctx, dR.devFor( dS ), dN.pts.p, nS, K, d_idx.p, d_dist.p, uniqueTrees ) );  // (dN = the points of dS)
     TMC2_TRY( fillRegions( ctx, {{d_count.p, size_t( mR ) * 4, 0}, {d_cursor.p, size_t( mR ) * 4, 0}} ) );
     hipLaunchKernelGGL( votesCountKernel, dim3( ( nS + 255 ) / 256 ), blk, 0, s, d_idx.p, d_dist.p, K, nS, d_count.p, d_error.p );
     TMC2_TRY( exclusiveScanU32( ctx, d_count.p, d_offset.p, mR, d_total.p ) );
@@ -680,14 +855,26 @@ int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, co
   {
     DevBuf<double> d_termsS, d_termsR, d_sums;
     TMC2_TRY( d_sums.alloc( 16 ) );
-    TMC2_TRY( qualityTerms( ctx, dS, dR, withNormals, K, d_termsS, d_error.p ) );
-    TMC2_TRY( qualityTerms( ctx, dR, dS, withNormals, K, d_termsR, d_error.p ) );
+    TMC2_TRY( qualityTerms( ctx, dS, dR, withNormals, K, colour, uniqueTrees, d_termsS, d_error.p ) );
+    TMC2_TRY( qualityTerms( ctx, dR, dS, withNormals, K, colour, uniqueTrees, d_termsR, d_error.p ) );
     {
       StageScope stage( ctx, "metrics_sums" );
       TMC2_TRY( orderedSums( ctx, d_termsS.p, uint32_t( dS.n ), d_termsR.p, uint32_t( dR.n ), d_sums.p ) );
     }
     double   sse[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double   mx[4]   = {0, 0, 0, 0};
     uint32_t err     = 0;
+    DevBuf<unsigned long long> d_max;
+    if ( q.computeHausdorff ) {
+      StageScope stage( ctx, "metrics_maxima" );
+      for ( double& v : mx ) v = std::numeric_limits<double>::min();
+      TMC2_TRY( d_max.alloc( 4 ) );
+      TMC2_HIP( hipMemcpyAsync( d_max.p, mx, sizeof( mx ), hipMemcpyHostToDevice, s ) );
+      const uint32_t blocks = uint32_t( ( dS.n + dR.n + 255 ) / 256 );
+      hipLaunchKernelGGL( maxTermsKernel, dim3( std::min( blocks, kBoundsBlocks ) ), blk, 0, s, d_termsS.p, uint32_t( dS.n ), d_termsR.p,
+                          uint32_t( dR.n ), d_max.p );
+      TMC2_HIP( hipMemcpyAsync( mx, d_max.p, sizeof( mx ), hipMemcpyDeviceToHost, s ) );
+    }
     TMC2_HIP( hipMemcpyAsync( sse, d_sums.p, sizeof( sse ), hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipMemcpyAsync( &err, d_error.p, 4, hipMemcpyDeviceToHost, s ) );
     TMC2_HIP( hipStreamSynchronize( s ) );
@@ -696,28 +883,29 @@ int metricsDevice( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, co
       *overflow = true;
       return TMC2_OK;
     }
-    qualityFromSums( sse, double( dS.n ), withNormals, resolution, out );
-    qualityFromSums( sse + 5, double( dR.n ), withNormals, resolution, out + 8 );
+    qualityFromSums( sse, mx, double( dS.n ), withNormals, resolution, q, out );
+    qualityFromSums( sse + 5, mx + 2, double( dR.n ), withNormals, resolution, q, out + kCols );
   }
-  for ( int i = 0; i < 8; ++i ) {
-    const bool isPsnr = ( i == 1 || i == 3 || i == 7 );
-    out[16 + i]       = isPsnr ? std::min( out[i], out[8 + i] ) : std::max( out[i], out[8 + i] );
+  // operator+ (:289-322): the larger error, the smaller PSNR; what a flag turns off is 0 in both rows and stays 0
+  for ( int i = 0; i < kCols; ++i ) {
+    const bool isPsnr   = ( i == 1 || i == 3 || ( i >= 7 && i <= 9 ) || i == 11 || i == 13 );
+    out[2 * kCols + i] = isPsnr ? std::min( out[i], out[kCols + i] ) : std::max( out[i], out[kCols + i] );
   }
   return TMC2_OK;
 }
 
 // K = 16, and once more with K = 32 (the reference's 30) where a minimum-distance group filled all 16 slots
 int metricsBothWidths( tmc2_ctx* ctx, const CloudView& src, const CloudView& rec, const double* d_srcNormals, double resolution,
-                       double* out, int64_t* counts ) {
+                       const tmc2_metrics_params& q, double* out, int64_t* counts ) {
   bool overflow = false;
   // (test hook TMC2_METRICS_K=32: the wide search straight away)
   const auto kEnv = ctxOption( ctx, "METRICS_K" );
   if ( !( kEnv && atoi( kEnv->c_str() ) == 32 ) ) {
-    TMC2_TRY( metricsDevice( ctx, src, rec, d_srcNormals, resolution, 16, out, counts, &overflow ) );
+    TMC2_TRY( metricsDevice( ctx, src, rec, d_srcNormals, resolution, 16, q, out, counts, &overflow ) );
     if ( !overflow ) return TMC2_OK;
   }
   ctx->stageAddHostMs( "metrics_wide_search", 1.0 );  // (a count: how often the 30-neighbour search was needed)
-  return metricsDevice( ctx, src, rec, d_srcNormals, resolution, 32, out, counts, &overflow );
+  return metricsDevice( ctx, src, rec, d_srcNormals, resolution, 32, q, out, counts, &overflow );
 }
 
 }  // namespace
@@ -773,20 +961,48 @@ int residentReconstruction( tmc2_frame* f, int which, CloudView& rec ) {
 }  // namespace
 }  // namespace tmc2
 
-extern "C" int tmc2_metrics_compute( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
-                                     const int16_t* recXyz, const uint8_t* recRgb, uint64_t m, const double* srcNormals,
-                                     double resolution, double* out, int64_t* counts ) {
+extern "C" void tmc2_metrics_params_default( tmc2_metrics_params* params ) {
+  if ( params ) *params = tmc2_metrics_params{1, 1, 1, 0, 2, 1};
+}
+
+extern "C" int tmc2_metrics_compute_ex( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* recXyz,
+                                        const uint8_t* recRgb, uint64_t m, const double* srcNormals, double resolution,
+                                        const tmc2_metrics_params* params, double* out, int64_t* counts ) {
   using namespace tmc2;
   if ( !ctx || !srcXyz || !srcRgb || !recXyz || !recRgb || !out || n == 0 || m == 0 || n > 0x7FFFFFFFull || m > 0x7FFFFFFFull ) {
     setError( "metrics_compute: invalid argument (null pointer, empty cloud or more than 2^31 - 1 points)" );
     return TMC2_E_INVALID;
   }
+  TMC2_TRY( checkMetricsParams( "metrics_compute", params ) );
   ApiScope       scope( ctx );
   UploadedSource src, rec;  // (9 bytes per point each way; fp64 normals: 24 per source point)
   CloudView      vs{}, vr{};
   TMC2_TRY( src.put( ctx, srcXyz, srcRgb, n, srcNormals, vs ) );
   TMC2_TRY( rec.put( ctx, recXyz, recRgb, m, nullptr, vr ) );
-  return metricsBothWidths( ctx, vs, vr, srcNormals ? src.nrm.p : nullptr, resolution, out, counts );
+  return metricsBothWidths( ctx, vs, vr, srcNormals ? src.nrm.p : nullptr, resolution, *params, out, counts );
+}
+
+namespace tmc2 {
+namespace {
+// the entries without parameters: the defaults of PCCMetricsParameters through the _ex entry, columns 0-7 of its rows
+struct DefaultRows {
+  tmc2_metrics_params q;
+  double              wide[3 * kCols];
+  DefaultRows() { tmc2_metrics_params_default( &q ); }
+  int narrow( int rc, double* out ) const {
+    for ( int r = 0; rc == TMC2_OK && r < 3; ++r )
+      for ( int c = 0; c < 8; ++c ) out[8 * r + c] = wide[kCols * r + c];
+    return rc;
+  }
+};
+}  // namespace
+}  // namespace tmc2
+
+extern "C" int tmc2_metrics_compute( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
+                                     const int16_t* recXyz, const uint8_t* recRgb, uint64_t m, const double* srcNormals,
+                                     double resolution, double* out, int64_t* counts ) {
+  tmc2::DefaultRows d;  // (no out: the entry refuses it)
+  return d.narrow( tmc2_metrics_compute_ex( ctx, srcXyz, srcRgb, n, recXyz, recRgb, m, srcNormals, resolution, &d.q, out ? d.wide : nullptr, counts ), out );
 }
 
 extern "C" int tmc2_metrics_ordered_sums( tmc2_ctx* ctx, const double* termsA, uint64_t nA, const double* termsB, uint64_t nB, double* out ) {
@@ -813,12 +1029,14 @@ extern "C" int tmc2_metrics_ordered_sums( tmc2_ctx* ctx, const double* termsA, u
   return TMC2_OK;
 }
 
-extern "C" int tmc2_metrics_compute_frame( tmc2_frame* f, int which, int useNormals, double resolution, double* out, int64_t* counts ) {
+extern "C" int tmc2_metrics_compute_frame_ex( tmc2_frame* f, int which, int useNormals, double resolution, const tmc2_metrics_params* params,
+                                              double* out, int64_t* counts ) {
   using namespace tmc2;
   if ( !f || !out ) {
     setError( "metrics_compute_frame: invalid argument" );
     return TMC2_E_INVALID;
   }
+  TMC2_TRY( checkMetricsParams( "metrics_compute_frame", params ) );
   ApiScope scope( f->ctx );
   if ( f->n == 0 || f->d_rgb.count == 0 || f->n > 0x7FFFFFFFull ) {
     setError( "metrics_compute_frame: the frame has no source cloud with colours (a decoder-side frame: tmc2_metrics_compute_frame_source)" );
@@ -830,20 +1048,33 @@ extern "C" int tmc2_metrics_compute_frame( tmc2_frame* f, int which, int useNorm
   }
   CloudView src{reinterpret_cast<const int16_t*>( f->d_pts.p ), f->d_rgb.p, uint32_t( f->n ), 4, 4}, rec{};
   TMC2_TRY( residentReconstruction( f, which, rec ) );
-  return metricsBothWidths( f->ctx, src, rec, useNormals ? f->d_normals.p : nullptr, resolution, out, counts );
+  return metricsBothWidths( f->ctx, src, rec, useNormals ? f->d_normals.p : nullptr, resolution, *params, out, counts );
 }
 
-extern "C" int tmc2_metrics_compute_frame_source( tmc2_frame* f, int which, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
-                                                  const double* srcNormals, double resolution, double* out, int64_t* counts ) {
+extern "C" int tmc2_metrics_compute_frame( tmc2_frame* f, int which, int useNormals, double resolution, double* out, int64_t* counts ) {
+  tmc2::DefaultRows d;
+  return d.narrow( tmc2_metrics_compute_frame_ex( f, which, useNormals, resolution, &d.q, out ? d.wide : nullptr, counts ), out );
+}
+
+extern "C" int tmc2_metrics_compute_frame_source_ex( tmc2_frame* f, int which, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
+                                                     const double* srcNormals, double resolution, const tmc2_metrics_params* params,
+                                                     double* out, int64_t* counts ) {
   using namespace tmc2;
   if ( !f || !out || !srcXyz || !srcRgb || n == 0 || n > 0x7FFFFFFFull ) {
     setError( "metrics_compute_frame_source: invalid argument" );
     return TMC2_E_INVALID;
   }
+  TMC2_TRY( checkMetricsParams( "metrics_compute_frame_source", params ) );
   ApiScope       scope( f->ctx );
   CloudView      rec{}, vs{};
   UploadedSource src;
   TMC2_TRY( residentReconstruction( f, which, rec ) );
   TMC2_TRY( src.put( f->ctx, srcXyz, srcRgb, n, srcNormals, vs ) );
-  return metricsBothWidths( f->ctx, vs, rec, srcNormals ? src.nrm.p : nullptr, resolution, out, counts );
+  return metricsBothWidths( f->ctx, vs, rec, srcNormals ? src.nrm.p : nullptr, resolution, *params, out, counts );
+}
+
+extern "C" int tmc2_metrics_compute_frame_source( tmc2_frame* f, int which, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n,
+                                                  const double* srcNormals, double resolution, double* out, int64_t* counts ) {
+  tmc2::DefaultRows d;
+  return d.narrow( tmc2_metrics_compute_frame_source_ex( f, which, srcXyz, srcRgb, n, srcNormals, resolution, &d.q, out ? d.wide : nullptr, counts ), out );
 }

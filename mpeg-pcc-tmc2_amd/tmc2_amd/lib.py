@@ -2,6 +2,7 @@
 seams: Frame.normals_compute <-> PCCNormalsGenerator3::compute, Frame.segmenter_* <-> PCCPatchSegmenter3::*,
 Frame.kdtree_search <-> PCCKdTree::search."""
 import ctypes as C
+import dataclasses
 import os as _os
 
 # One HIP stream per in-flight frame (32 per GPU in a GOF run): the runtime multiplexes streams onto 4 hardware queues by
@@ -46,6 +47,28 @@ class Patch(C.Structure):
 
 
 PATCH_DTYPE = np.dtype(Patch._fields_)
+
+
+class _MetricsParamsStruct(C.Structure):
+    """Mirror of tmc2_metrics_params."""
+    _fields_ = [(n, C.c_int32) for n in ("computeC2c", "computeC2p", "computeColor", "computeHausdorff", "dropDuplicates", "neighborsProc")]
+
+
+@dataclasses.dataclass(frozen=True)
+class MetricsParams:
+    """The switches of PCCMetricsParameters that PccAppMetrics takes (tmc2_metrics_params; the defaults are the reference's):
+    drop_duplicates 0 keep / 1 first colour / 2 mean colour; neighbors_proc 0 first result / 1, 2 mean / 3, 4 "min" / "max" as the
+    reference is written (include/tmc2hip.h)."""
+    compute_c2c: bool = True
+    compute_c2p: bool = True
+    compute_color: bool = True
+    compute_hausdorff: bool = False
+    drop_duplicates: int = 2
+    neighbors_proc: int = 1
+
+    def struct(self):
+        return _MetricsParamsStruct(int(self.compute_c2c), int(self.compute_c2p), int(self.compute_color), int(self.compute_hausdorff),
+                                    int(self.drop_duplicates), int(self.neighbors_proc))
 
 
 def ctc_params(iterations=10, bits3d=11, weight=(1.0, 1.0, 1.0), vox_dim=4):
@@ -391,16 +414,21 @@ class Context:
         _check(self.L.tmc2_color_convert_yuv420_to_yuv444(self.h, _ptr(src), int(W), int(H), int(upsampling_filter), _ptr(out)))
         return out
 
-    def metrics_compute(self, src_xyz, src_rgb, rec_xyz, rec_rgb, normals=None, resolution=1023.0):
+    def metrics_compute(self, src_xyz, src_rgb, rec_xyz, rec_rgb, normals=None, resolution=1023.0, params=None):
+        """(q[3][8], counts[2]) with the defaults of PCCMetricsParameters; params = MetricsParams: q[3][14] (tmc2_metrics_compute_ex)."""
         a = np.ascontiguousarray(src_xyz, np.int16)
         b = np.ascontiguousarray(src_rgb, np.uint8)
         c = np.ascontiguousarray(rec_xyz, np.int16)
         d = np.ascontiguousarray(rec_rgb, np.uint8)
         nm = None if normals is None else np.ascontiguousarray(normals, np.float64)
-        out = np.zeros((3, 8), np.float64)
+        out = np.zeros((3, 8 if params is None else 14), np.float64)
         counts = np.zeros(2, np.int64)
-        _check(self.L.tmc2_metrics_compute(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), _ptr(d), len(c),
-                                           None if nm is None else _ptr(nm), resolution, _ptr(out), _ptr(counts)))
+        if params is None:
+            _check(self.L.tmc2_metrics_compute(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), _ptr(d), len(c),
+                                               None if nm is None else _ptr(nm), resolution, _ptr(out), _ptr(counts)))
+        else:
+            _check(self.L.tmc2_metrics_compute_ex(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), _ptr(d), len(c),
+                                                  None if nm is None else _ptr(nm), resolution, C.byref(params.struct()), _ptr(out), _ptr(counts)))
         return out, counts
 
     def metrics_ordered_sums(self, terms_a, terms_b):
@@ -439,23 +467,32 @@ class Frame:
     def reset(self):
         _check(self.L.tmc2_frame_reset(self.h))
 
-    def metrics_compute(self, which=0, use_normals=True, resolution=1023.0):
+    def metrics_compute(self, which=0, use_normals=True, resolution=1023.0, params=None):
         """S23 on the frame's resident clouds (nothing is uploaded): source = the frame, reconstruction = which 0: the cloud of
-        the attribute-image step, 1: the finished cloud of the post-reconstruction tail.  Returns (q[3][8], counts[2])."""
-        out = np.zeros((3, 8), np.float64)
+        the attribute-image step, 1: the finished cloud of the post-reconstruction tail.  Returns (q[3][8], counts[2]); with
+        params = MetricsParams (q[3][14], counts[2]) (tmc2_metrics_compute_frame_ex)."""
+        out = np.zeros((3, 8 if params is None else 14), np.float64)
         counts = np.zeros(2, np.int64)
-        _check(self.L.tmc2_metrics_compute_frame(self.h, which, 1 if use_normals else 0, resolution, _ptr(out), _ptr(counts)))
+        if params is None:
+            _check(self.L.tmc2_metrics_compute_frame(self.h, which, 1 if use_normals else 0, resolution, _ptr(out), _ptr(counts)))
+        else:
+            _check(self.L.tmc2_metrics_compute_frame_ex(self.h, which, 1 if use_normals else 0, resolution, C.byref(params.struct()), _ptr(out),
+                                                        _ptr(counts)))
         return out, counts
 
-    def metrics_compute_source(self, src_xyz, src_rgb, normals=None, which=1, resolution=1023.0):
-        """S23 of a source cloud held on the host against this frame's resident reconstruction (the decoder side)."""
+    def metrics_compute_source(self, src_xyz, src_rgb, normals=None, which=1, resolution=1023.0, params=None):
+        """S23 of a source cloud held on the host against this frame's resident reconstruction (the decoder side); params as above."""
         a = np.ascontiguousarray(src_xyz, np.int16)
         b = np.ascontiguousarray(src_rgb, np.uint8)
         nm = None if normals is None else np.ascontiguousarray(normals, np.float64)
-        out = np.zeros((3, 8), np.float64)
+        out = np.zeros((3, 8 if params is None else 14), np.float64)
         counts = np.zeros(2, np.int64)
-        _check(self.L.tmc2_metrics_compute_frame_source(self.h, which, _ptr(a), _ptr(b), len(a),
-                                                        None if nm is None else _ptr(nm), resolution, _ptr(out), _ptr(counts)))
+        if params is None:
+            _check(self.L.tmc2_metrics_compute_frame_source(self.h, which, _ptr(a), _ptr(b), len(a),
+                                                            None if nm is None else _ptr(nm), resolution, _ptr(out), _ptr(counts)))
+        else:
+            _check(self.L.tmc2_metrics_compute_frame_source_ex(self.h, which, _ptr(a), _ptr(b), len(a), None if nm is None else _ptr(nm),
+                                                               resolution, C.byref(params.struct()), _ptr(out), _ptr(counts)))
         return out, counts
 
     def kdtree_build(self):
@@ -943,12 +980,23 @@ def segmenter_params_check(params):
     _check(load_library().tmc2_segmenter_params_check(C.byref(params)))
 
 
-def metrics_display(out, source_points, reconstruct_points, counts, resolution=1023, with_c2p=True, precision=9):
-    """The text PCCMetrics::display() prints for one frame (what the CTC log parsers read)."""
+def metrics_display(out, source_points, reconstruct_points, counts, resolution=1023, with_c2p=True, precision=9, params=None):
+    """The text PCCMetrics::display() prints for one frame (what the CTC log parsers read); params = MetricsParams: from the
+    q[3][14] of the entries that take them (tmc2_metrics_display_ex)."""
     L = load_library()
     q = np.ascontiguousarray(out, dtype=np.float64)
     c = np.ascontiguousarray(counts, dtype=np.int64)
     need = C.c_uint64()
+    if params is not None:
+        if q.shape != (3, 14):
+            raise Tmc2Error("metrics_display: q[3][14] expected with params")
+        st = params.struct()
+        _check(L.tmc2_metrics_display_ex(_ptr(q), C.byref(st), int(source_points), int(reconstruct_points), _ptr(c), int(resolution),
+                                         int(bool(with_c2p)), int(precision), None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        _check(L.tmc2_metrics_display_ex(_ptr(q), C.byref(st), int(source_points), int(reconstruct_points), _ptr(c), int(resolution),
+                                         int(bool(with_c2p)), int(precision), buf, need.value, None))
+        return buf.value.decode()
     _check(L.tmc2_metrics_display(_ptr(q), int(source_points), int(reconstruct_points), _ptr(c), int(resolution), int(bool(with_c2p)),
                                   int(precision), None, 0, C.byref(need)))
     buf = C.create_string_buffer(need.value)
@@ -1046,6 +1094,21 @@ def host_color_smoothing(xyz, colors16, boundary, patch_index, grid_size, bits3d
     _check(L.tmc2_host_color_smoothing(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), len(a[0]), int(grid_size), int(bits3d),
                                        thr_smoothing, thr_difference, thr_variation))
     return a[1]
+
+
+def host_metrics_compute(src_xyz, src_rgb, rec_xyz, rec_rgb, normals=None, resolution=1023.0, params=None):
+    """tmc2_host_metrics_compute: PCCMetrics::compute restated on the host (no device) -> (q[3][14], counts[2]).  Raises Tmc2Error
+    with error -6 (TMC2_E_ORDER) where the answer depends on the k-d tree's visiting order."""
+    a = np.ascontiguousarray(src_xyz, np.int16)
+    b = np.ascontiguousarray(src_rgb, np.uint8)
+    c = np.ascontiguousarray(rec_xyz, np.int16)
+    d = np.ascontiguousarray(rec_rgb, np.uint8)
+    nm = None if normals is None else np.ascontiguousarray(normals, np.float64)
+    out, counts = np.zeros((3, 14), np.float64), np.zeros(2, np.int64)
+    st = (params or MetricsParams()).struct()
+    _check(load_library().tmc2_host_metrics_compute(_ptr(a), _ptr(b), len(a), _ptr(c), _ptr(d), len(c), None if nm is None else _ptr(nm),
+                                                    resolution, C.byref(st), _ptr(out), _ptr(counts)))
+    return out, counts
 
 
 def host_patch_border_filtering(patches, width, height, occ_precision, occ_video, geometry_d0, block_to_patch, passes, filter_size,
@@ -1203,8 +1266,13 @@ int tmc2_frame_get_post_reconstruction(tmc2_frame*, int16_t*, uint16_t*, uint8_t
 int tmc2_metrics_compute(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, const int16_t*, const uint8_t*, uint64_t, const double*, double, double*, int64_t*)
 int tmc2_metrics_compute_frame(tmc2_frame*, int, int, double, double*, int64_t*)
 int tmc2_metrics_compute_frame_source(tmc2_frame*, int, const int16_t*, const uint8_t*, uint64_t, const double*, double, double*, int64_t*)
+void tmc2_metrics_params_default(tmc2_metrics_params*)
+int tmc2_metrics_compute_ex(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, const int16_t*, const uint8_t*, uint64_t, const double*, double, const tmc2_metrics_params*, double*, int64_t*)
+int tmc2_metrics_compute_frame_ex(tmc2_frame*, int, int, double, const tmc2_metrics_params*, double*, int64_t*)
+int tmc2_metrics_compute_frame_source_ex(tmc2_frame*, int, const int16_t*, const uint8_t*, uint64_t, const double*, double, const tmc2_metrics_params*, double*, int64_t*)
 int tmc2_metrics_ordered_sums(tmc2_ctx*, const double*, uint64_t, const double*, uint64_t, double*)
 int tmc2_metrics_display(const double*, uint64_t, uint64_t, const int64_t*, uint64_t, int, int, char*, uint64_t, uint64_t*)
+int tmc2_metrics_display_ex(const double*, const tmc2_metrics_params*, uint64_t, uint64_t, const int64_t*, uint64_t, int, int, char*, uint64_t, uint64_t*)
 int tmc2_ply_info(const char*, int, uint64_t*, int*, int*)
 int tmc2_ply_read(const char*, int16_t*, uint8_t*, double*, uint64_t, int, uint64_t*)
 int tmc2_ply_write(const char*, const int16_t*, const uint8_t*, const double*, uint64_t, int)
@@ -1218,6 +1286,7 @@ int tmc2_host_pack_spatial_consistency(tmc2_patch*, int, const uint8_t*, const t
 int tmc2_host_place_segments(int, const int32_t*, tmc2_patch*, const uint8_t*, const int64_t*, int, int, int, int, double, int32_t*, uint8_t*, int64_t, int64_t*, int32_t*, int32_t*)
 int tmc2_host_orient_normals(const int16_t*, uint64_t, const uint32_t*, int, double*)
 int tmc2_host_color_smoothing(const int16_t*, uint16_t*, const uint16_t*, const uint32_t*, uint64_t, int, int, double, double, double)
+int tmc2_host_metrics_compute(const int16_t*, const uint8_t*, uint64_t, const int16_t*, const uint8_t*, uint64_t, const double*, double, const tmc2_metrics_params*, double*, int64_t*)
 int tmc2_host_patch_border_filtering(const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, const uint32_t*, int, int, int, int, uint8_t*, uint8_t*)
 int tmc2_host_convert_points_to_voxels(const int16_t*, uint64_t, int, int, int16_t*, uint64_t*, uint32_t*)
 int tmc2_host_refine_segmentation(const int16_t*, uint64_t, const double*, uint32_t*, int, double, int, uint32_t*)
