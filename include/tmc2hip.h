@@ -652,6 +652,15 @@ int tmc2_selftest_std_sort( uint32_t* lists, const uint32_t* offsets, uint64_t c
 int tmc2_selftest_marked_cells( tmc2_ctx* ctx, const int16_t* d_xyz4, const uint8_t* d_boundaryType, uint64_t M, int gridSize, int bits,
                                 int maxCoord, uint32_t* cells, uint32_t* d_bits, uint32_t* d_rank, const uint32_t* d_keys, uint64_t keys,
                                 uint32_t* d_slots );
+/* wave: the cross-lane idioms of csrc/wave.h, one per call, over n elements (at most 2^24, a whole number of groups).
+ * op 0 .. 5: waveInclusive, waveInclusive<16>, waveSum, waveSum<16>, waveMin, waveMax on d_in[n] -> d_out[n], one value per lane,
+ *   workgroups of 256; param = the element type (0: uint32, 1: int32, 2: double).
+ * op 6: laneRank through a compaction, workgroups of 256: every wavefront writes the numbers of its lanes with d_in[i] != 0 back to
+ *   back into its 64 words of d_out (the rest: 0xFFFFFFFF); d_aux[i] = the wavefront's count.
+ * op 7: ldsBitonicSort of lists of param keys (a power of two, 64 .. 8192), one wavefront each: d_in[n] -> d_out[n].
+ * op 8: blockExclusive over workgroups of param (1, 2, 4, 16) wavefronts: d_out[i] = the sum of the workgroup's values before
+ *   thread i, d_aux[i] = the workgroup's total.  (uint32 for op 6 .. 8; d_aux may be NULL for op 0 .. 5 and 7.)               */
+int tmc2_selftest_wave( tmc2_ctx* ctx, int op, int param, const void* d_in, void* d_out, uint32_t* d_aux, uint64_t n );
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@
 
 #include "color_transfer.h"
 #include "internal.h"
+#include "wave.h"
 #include "patch_border_filter.h"
 
 namespace tmc2 {
@@ -93,13 +94,8 @@ __global__ __launch_bounds__( 256 ) void reconTileKernel( const PlaceDev* __rest
     cnt = c1 != c0 ? 2u : 1u;
   }
   // inclusive scan of cnt over the 256 lanes (pixel raster order == lane order)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t  inc  = cnt;
-#pragma unroll
-  for ( int off = 1; off < 64; off <<= 1 ) {
-    const uint32_t t = __shfl_up( inc, off, 64 );
-    if ( lane >= off ) inc += t;
-  }
+  const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t inc  = waveInclusive( cnt, lane );
   if ( lane == 63 ) waveTotal[wave] = inc;
   __syncthreads();
   if ( !EMIT ) {

@@ -20,6 +20,7 @@
 #include "cell_grid.h"
 #include "color_smoothing.h"
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -65,22 +66,6 @@ __global__ __launch_bounds__( 256 ) void scatterCellPointsKernel( const uint32_t
   if ( slot != kNoSlot ) entries[cellOffset[slot] + atomicAdd( &cursor[slot], 1u )] = i;
 }
 
-__device__ __forceinline__ uint32_t waveAdd( uint32_t v ) {
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) v += __shfl_xor( v, off, 64 );
-  return v;
-}
-__device__ __forceinline__ uint32_t waveMin( uint32_t v ) {
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) v = min( v, uint32_t( __shfl_xor( v, off, 64 ) ) );
-  return v;
-}
-__device__ __forceinline__ uint32_t waveMax( uint32_t v ) {
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) v = max( v, uint32_t( __shfl_xor( v, off, 64 ) ) );
-  return v;
-}
-
 // The value of rank k (0-based, sorted ascending) among the lumas of a segment of more than 64 points: two passes of a
 // 256-bin histogram in LDS (high byte, then low byte among the values of that high byte).  One wavefront = one workgroup.
 __device__ uint32_t selectLuma( const uint32_t* __restrict__ seg, uint32_t n, const ushort4* __restrict__ colors, uint32_t k,
@@ -100,12 +85,7 @@ __device__ uint32_t selectLuma( const uint32_t* __restrict__ seg, uint32_t n, co
     __syncthreads();
     // lane l owns bins 4l .. 4l+3: the bin in which the running count passes k
     const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-    uint32_t       inc = h0 + h1 + h2 + h3;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t t = __shfl_up( inc, off, 64 );
-      if ( lane >= off ) inc += t;
-    }
+    const uint32_t inc = waveInclusive( h0 + h1 + h2 + h3, lane );
     const unsigned long long past  = __ballot( inc > k );
     const int                owner = __ffsll( static_cast<long long>( past ) ) - 1;  // (k < n: some lane passes it)
     uint32_t                 bin = 0, before = 0;
@@ -160,7 +140,7 @@ __global__ __launch_bounds__( 64 ) void cellStatsKernel( const uint32_t* __restr
       pMin = min( pMin, p ), pMax = max( pMax, p );
       mine = c.x;
     }
-    s0 = waveAdd( s0 ), s1 = waveAdd( s1 ), s2 = waveAdd( s2 );
+    s0 = waveSum( s0 ), s1 = waveSum( s1 ), s2 = waveSum( s2 );
     pMin = waveMin( pMin ), pMax = waveMax( pMax );
     uint32_t medianLo = 0, medianHi = 0;
     if ( n > 1 ) {

@@ -36,6 +36,7 @@
 #include <cstring>
 
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -178,12 +179,7 @@ __device__ __forceinline__ uint32_t blockClassLists( const Pt* pts, uint32_t cou
       ge[j]            = in && x >= c;
       cGE += uint32_t( ge[j] ), cIn += uint32_t( in );
     }
-    uint32_t inc = cGE | ( cIn << 16 );  // (a wave holds at most 256 elements: both counts fit 16 bits)
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t t = __shfl_up( inc, off, 64 );
-      if ( lane >= off ) inc += t;
-    }
+    const uint32_t inc = waveInclusive( cGE | ( cIn << 16 ), lane );  // (a wave holds at most 256 elements: both counts fit 16 bits)
     if ( lane == 63 ) waveCnt[buf * kHugeWaves + wave] = inc;
     __syncthreads();  // (the other buffer is written next: whoever still reads this one has passed this barrier by then)
     uint32_t before = 0, total = 0;
@@ -414,12 +410,7 @@ __device__ __forceinline__ int      pkHi( uint32_t v ) { return int( int16_t( v 
 template <int WAVES>
 __device__ __forceinline__ uint32_t pieceScan( uint32_t v, uint32_t* waveTot ) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t  inc  = v;
-#pragma unroll
-  for ( int off = 1; off < 64; off <<= 1 ) {
-    const uint32_t t = __shfl_up( inc, off, 64 );
-    if ( lane >= off ) inc += t;
-  }
+  const uint32_t inc = waveInclusive( v, lane );
   if ( lane == 63 ) waveTot[wave] = inc;
   pieceBarrier();
   uint32_t before = 0;
@@ -532,11 +523,8 @@ __global__ __launch_bounds__( kBlock ) void lvInitKernel( BuildArgs a ) {
     mnx = min( mnx, int( p.x ) ), mny = min( mny, int( p.y ) ), mnz = min( mnz, int( p.z ) );
     mxx = max( mxx, int( p.x ) ), mxy = max( mxy, int( p.y ) ), mxz = max( mxz, int( p.z ) );
   }
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) {
-    mnx = min( mnx, __shfl_xor( mnx, off, 64 ) ), mny = min( mny, __shfl_xor( mny, off, 64 ) ), mnz = min( mnz, __shfl_xor( mnz, off, 64 ) );
-    mxx = max( mxx, __shfl_xor( mxx, off, 64 ) ), mxy = max( mxy, __shfl_xor( mxy, off, 64 ) ), mxz = max( mxz, __shfl_xor( mxz, off, 64 ) );
-  }
+  mnx = waveMin( mnx ), mny = waveMin( mny ), mnz = waveMin( mnz );
+  mxx = waveMax( mxx ), mxy = waveMax( mxy ), mxz = waveMax( mxz );
   if ( lane == 0 ) {
     int* w = blockRange + 6 * wave;
     w[0] = mnx, w[1] = mny, w[2] = mnz, w[3] = mxx, w[4] = mxy, w[5] = mxz;
@@ -673,12 +661,7 @@ __global__ __launch_bounds__( kDecideThreads ) void lvDecideKernel( BuildArgs a,
       }
       if ( !split ) q->cutInfo = 0;
     }
-    uint32_t inc = split;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t t = __shfl_up( inc, off, 64 );
-      if ( lane >= off ) inc += t;
-    }
+    const uint32_t inc = waveInclusive( split, lane );
     if ( lane == 63 ) waveTot[wave] = inc;
     __syncthreads();
     uint32_t before = sCarry, all = 0;
@@ -707,9 +690,8 @@ __global__ __launch_bounds__( kDecideThreads ) void lvDecideKernel( BuildArgs a,
 // (tile-local + tile totals scanned by the block that finishes last), and the tile's list of the positions NOT of the class
 template <bool FIRST>
 __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t level ) {
-  __shared__ uint32_t waveSum[kWaves];
+  __shared__ uint32_t waveTot[kWaves];
   const uint32_t n = a.n, tiles = a.tiles;
-  const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   LvSeg*         cur   = ( level & 1 ) ? a.lvB : a.lvA;
   LvSeg*         next  = ( level & 1 ) ? a.lvA : a.lvB;
   const uint32_t count = a.counts[level];
@@ -744,16 +726,7 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
       v[k] = f;
       run += f;
     }
-    uint32_t inc = run;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t u = __shfl_up( inc, off, 64 );
-      if ( lane >= off ) inc += u;
-    }
-    if ( lane == 63 ) waveSum[wave] = inc;
-    __syncthreads();
-    uint32_t offset = inc - run;
-    for ( int w = 0; w < wave; ++w ) offset += waveSum[w];
+    uint32_t offset = blockExclusive<kWaves>( run, waveTot );
 #pragma unroll
     for ( int k = 0; k < 8; ++k ) {
       if ( base + k < n ) {
@@ -772,24 +745,15 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
 // a ticket, a hand-off to the workgroup that finishes last and ITS scan, with the whole chip waiting.
 template <int BLOCK>
 __device__ __forceinline__ void lvLoadSums( uint32_t* sums, const uint32_t* __restrict__ raw, uint32_t tiles ) {
-  __shared__ uint32_t waveSum[BLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t  carry = 0;
+  __shared__ uint32_t waveTot[BLOCK / 64];
+  uint32_t            carry = 0;
   for ( uint32_t base = 0; base < tiles; base += BLOCK ) {
     const uint32_t i   = base + threadIdx.x;
     const uint32_t v   = i < tiles ? raw[i] : 0u;
-    uint32_t       inc = v;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t u = __shfl_up( inc, off, 64 );
-      if ( lane >= off ) inc += u;
-    }
-    if ( lane == 63 ) waveSum[wave] = inc;
-    __syncthreads();
-    uint32_t offset = carry + inc - v;
-    for ( int w = 0; w < wave; ++w ) offset += waveSum[w];
+    uint32_t       all;
+    const uint32_t offset = carry + blockExclusive<BLOCK / 64>( v, waveTot, all );
     if ( i < tiles ) sums[i] = offset;
-    for ( int w = 0; w < BLOCK / 64; ++w ) carry += waveSum[w];
+    carry += all;
     __syncthreads();
   }
   if ( threadIdx.x == 0 ) sums[tiles] = carry;
@@ -928,10 +892,7 @@ __global__ __launch_bounds__( kLandBlock ) void lvSwapTwoKernel( BuildArgs a, ui
         v[3] = pkMin( right ? A : pk2( 0x7FFF, 0x7FFF ), A2 ), v[4] = pkMax( right ? B : pk2( -0x8000, -0x8000 ), B2 ),
         v[5] = pkMin( right ? C : pk2( 0x7FFF, 0x7FFF ), C2 );
 #pragma unroll
-        for ( int off = 32; off > 0; off >>= 1 ) {
-          v[0] = pkMin( v[0], __shfl_xor( v[0], off, 64 ) ), v[1] = pkMax( v[1], __shfl_xor( v[1], off, 64 ) ), v[2] = pkMin( v[2], __shfl_xor( v[2], off, 64 ) );
-          v[3] = pkMin( v[3], __shfl_xor( v[3], off, 64 ) ), v[4] = pkMax( v[4], __shfl_xor( v[4], off, 64 ) ), v[5] = pkMin( v[5], __shfl_xor( v[5], off, 64 ) );
-        }
+        for ( int k = 0; k < 6; ++k ) v[k] = ( k % 3 ) == 1 ? waveReduce( v[k], pkMax ) : waveReduce( v[k], pkMin );
         if ( lane == 0 )
           for ( int k = 0; k < 6; ++k ) red[wave][k] = v[k];
         __syncthreads();

@@ -18,6 +18,7 @@
 // Squared distances are 32-bit unsigned: every coordinate, of the tree and of the queries, must be >= -4096 (3 x 36863^2 < 2^32).
 #include "internal.h"
 #include "refine_knn.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -109,7 +110,7 @@ __global__ __launch_bounds__( 64 * kWideWaves ) void knnWideKernel( const Pt* __
     }
     const uint32_t first = min( centre > K / 2u ? centre - K / 2u : 0u, nTree - K );
     for ( uint32_t e = lane; e < K; e += 64u ) cap = max( cap, wideDist( qx, qy, qz, ptsTree[first + e] ) );
-    for ( int off = 32; off > 0; off >>= 1 ) cap = max( cap, uint32_t( __shfl_xor( int( cap ), off ) ) );
+    cap = waveMax( cap );
   }
   __builtin_amdgcn_wave_barrier();
 

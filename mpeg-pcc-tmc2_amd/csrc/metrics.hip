@@ -31,6 +31,7 @@
 #include <numeric>
 
 #include "internal.h"
+#include "wave.h"
 #include "ordered_sum.h"
 
 namespace tmc2 {
@@ -86,10 +87,7 @@ __global__ __launch_bounds__( 256 ) void boundsKernel( CloudView c, int* __restr
     }
   }
 #pragma unroll
-  for ( int d = 0; d < 3; ++d ) {
-#pragma unroll
-    for ( int off = 32; off > 0; off >>= 1 ) mn[d] = min( mn[d], __shfl_xor( mn[d], off, 64 ) ), mx[d] = max( mx[d], __shfl_xor( mx[d], off, 64 ) );
-  }
+  for ( int d = 0; d < 3; ++d ) mn[d] = waveMin( mn[d] ), mx[d] = waveMax( mx[d] );
   if ( ( threadIdx.x & 63 ) == 0 ) {
 #pragma unroll
     for ( int d = 0; d < 3; ++d ) sMin[threadIdx.x >> 6][d] = mn[d], sMax[threadIdx.x >> 6][d] = mx[d];
@@ -445,10 +443,7 @@ __global__ __launch_bounds__( 256 ) void maxTermsKernel( const double* __restric
     }
   }
 #pragma unroll
-  for ( int c = 0; c < 4; ++c ) {
-#pragma unroll
-    for ( int off = 32; off > 0; off >>= 1 ) m[c] = max( m[c], (unsigned long long)__shfl_xor( (long long)m[c], off, 64 ) );
-  }
+  for ( int c = 0; c < 4; ++c ) m[c] = waveMax( m[c] );
   if ( ( threadIdx.x & 63 ) == 0 ) {
 #pragma unroll
     for ( int c = 0; c < 4; ++c ) sMax[threadIdx.x >> 6][c] = m[c];
@@ -528,8 +523,7 @@ __global__ __launch_bounds__( 256 ) void osumBlockKernel( const double* __restri
 #pragma unroll
       for ( int off = 32; off > 0; off >>= 1 ) v[c] += __shfl_xor( v[c], off, 64 );
     }
-#pragma unroll
-    for ( int off = 32; off > 0; off >>= 1 ) d1 += __shfl_xor( d1, off, 64 );
+    d1 = waveSum( d1 );
     if ( lane == 0 ) {
 #pragma unroll
       for ( int c = 0; c < 4; ++c ) sSum[wave][c] = v[c];
@@ -590,12 +584,7 @@ __global__ __launch_bounds__( 64 ) void osumGuessKernel( OsumBufs o, int trustNo
   for ( uint32_t k0 = 0; k0 < nb; k0 += 64 ) {
     const uint32_t k = k0 + uint32_t( lane );
     const double   v = k < nb ? o.approx[size_t( chain ) * o.nbMax + k] : 0.0;
-    double         incl = v;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const double t = __shfl_up( incl, off, 64 );
-      if ( lane >= off ) incl += t;
-    }
+    const double   incl = waveInclusive( v, lane );
     double excl = __shfl_up( incl, 1, 64 );
     if ( lane == 0 ) excl = 0.0;
     const double lo = carry + excl, hi = carry + incl;  // (approximate on purpose: the chain checks the guess on the exact values)
@@ -654,8 +643,7 @@ __global__ __launch_bounds__( 64 ) void osumChainKernel( const double* __restric
   if ( col == 0 ) {  // D1: integers
     unsigned long long d1 = 0;
     for ( uint32_t k = uint32_t( lane ); k < nb; k += 64 ) d1 += o.d1[size_t( dir ) * o.nbMax + k];
-#pragma unroll
-    for ( int off = 32; off > 0; off >>= 1 ) d1 += __shfl_xor( d1, off, 64 );
+    d1 = waveSum( d1 );
     if ( lane == 0 ) out[5 * dir] = double( d1 );
   }
 }

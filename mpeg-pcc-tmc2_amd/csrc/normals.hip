@@ -12,6 +12,7 @@
 // One point per lane.  HBM traffic per point: 4k B of neighbour ids in, 24 B normal out; the 16
 // neighbour positions are gathers that stay in L1/L2 because the ids are spatial neighbours.
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 
@@ -255,9 +256,7 @@ __global__ __launch_bounds__( 256 ) void applySignsKernel( const Pt* __restrict_
 
 __global__ __launch_bounds__( 256 ) void majorityFlipKernel( const uint32_t* __restrict__ negCount, uint32_t n,
                                                               double* __restrict__ normals ) {
-  uint32_t neg = negCount[( threadIdx.x & 63 ) * 32];  // (kNegCounters = a wavefront's lanes)
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) neg += __shfl_xor( neg, off, 64 );
+  const uint32_t neg = waveSum( negCount[( threadIdx.x & 63 ) * 32] );  // (kNegCounters = a wavefront's lanes)
   if ( neg <= ( n + 1 ) / 2 ) return;
   const size_t i = size_t( blockIdx.x ) * blockDim.x + threadIdx.x;
   if ( i < 3 * size_t( n ) ) normals[i] = -normals[i];

@@ -24,6 +24,7 @@
 
 #include "internal.h"
 #include "patch_border_filter.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -112,7 +113,7 @@ __global__ __launch_bounds__( 256 ) void pbfBorderPointsKernel( const PlaceDev* 
     pt.patch  = uint16_t( k );
     pt.raster = uint32_t( v ) * uint32_t( p.sizeU0 * 16 ) + uint32_t( u );
     pt.pad    = 0;
-    points[base + uint32_t( __popcll( mask & ( ( 1ull << lane ) - 1ull ) ) )] = pt;
+    points[base + uint32_t( laneRank( mask, lane ) )] = pt;
   }
   __syncthreads();
   if ( threadIdx.x < 3 && sbox[threadIdx.x] != 32767 ) atomicMin( &box[k * 6 + threadIdx.x], sbox[threadIdx.x] );

@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "internal.h"
+#include "wave.h"
 #include "union_find.h"
 
 namespace tmc2 {
@@ -54,18 +55,6 @@ __device__ __forceinline__ void lazyAtomicMin( int32_t* a, int v ) {
 }
 __device__ __forceinline__ void lazyAtomicMax( int32_t* a, int v ) {
   if ( v > loadStaleOk( a ) ) atomicMax( a, v );
-}
-__device__ __forceinline__ int waveMinMasked( int v, bool mine ) {
-  v = mine ? v : 0x7FFFFFFF;
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) v = min( v, __shfl_xor( v, off, 64 ) );
-  return v;
-}
-__device__ __forceinline__ int waveMaxMasked( int v, bool mine ) {
-  v = mine ? v : int( 0x80000000 );
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) v = max( v, __shfl_xor( v, off, 64 ) );
-  return v;
 }
 
 // ---- S7 ---------------------------------------------------------------------------------------------
@@ -527,11 +516,7 @@ __global__ __launch_bounds__( 256 ) void patchFilterTileKernel( const PatchDev* 
   }
   // block peak: min depth (mode 0) or max depth (mode 1) over valid pixels
   int pk = depth == INF ? ( pd.mode == 0 ? INF : 0 ) : depth;
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) {
-    const int o = __shfl_xor( pk, off, 64 );
-    pk          = pd.mode == 0 ? min( pk, o ) : max( pk, o );
-  }
+  pk = waveReduce( pk, [&]( int a, int b ) { return pd.mode == 0 ? min( a, b ) : max( a, b ); } );
   if ( ( threadIdx.x & 63 ) == 0 ) wavePeak[threadIdx.x >> 6] = pk;
   __syncthreads();
   pk = wavePeak[0];
@@ -635,9 +620,7 @@ __global__ __launch_bounds__( 256 ) void patchResampleTileKernel( const PatchDev
   }
   // reductions over the tile
   const unsigned long long m  = __ballot( valid );
-  int                      mx = valid ? max( l0, l1 ) : 0;
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) mx = max( mx, __shfl_xor( mx, off, 64 ) );
+  const int                mx = waveMax( valid ? max( l0, l1 ) : 0 );
   // (one report per TILE -- rounds 1-5: one per wavefront -- and the maximum only if it can raise the patch's: a big patch is
   //  thousands of tiles adding to the same two words, ~ 11 ns each, one after the other; the look is a possibly stale view of a
   //  word that only grows)

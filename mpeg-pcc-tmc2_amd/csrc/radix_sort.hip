@@ -3,6 +3,7 @@
 // STABLE sort of (key, input index) pairs the first element of a run of equal keys is the one with the smallest input index.
 // Both mark those first elements next (markRunHeads).
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -43,7 +44,7 @@ __global__ __launch_bounds__( 256 ) void radixScatterKernel( const uint64_t* __r
       const unsigned long long m = __ballot( ( d >> bit ) & 1u );
       peers &= ( ( d >> bit ) & 1u ) ? m : ~m;
     }
-    const uint32_t rankInWave = uint32_t( __popcll( peers & ( ( 1ull << lane ) - 1ull ) ) );
+    const uint32_t rankInWave = uint32_t( laneRank( peers, lane ) );
     if ( valid && rankInWave == 0 ) waveCount[wave][d] = uint32_t( __popcll( peers ) );
     __syncthreads();
     if ( valid ) {

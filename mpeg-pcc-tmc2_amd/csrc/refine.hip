@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -67,33 +68,22 @@ __global__ __launch_bounds__( 256 ) void bitsBlockCountKernel( const uint2* __re
 #pragma unroll
   for ( int j = 0; j < kBitsPerThread; ++j )
     if ( base + j < words ) sum += __popc( bits[base + j].x );
-  __shared__ uint32_t waveSum[4];
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) sum += __shfl_xor( sum, off, 64 );
-  if ( ( threadIdx.x & 63 ) == 0 ) waveSum[threadIdx.x >> 6] = sum;
+  __shared__ uint32_t waveTot[4];
+  sum = waveSum( sum );
+  if ( ( threadIdx.x & 63 ) == 0 ) waveTot[threadIdx.x >> 6] = sum;
   __syncthreads();
-  if ( threadIdx.x == 0 ) blockTotal[blockIdx.x] = waveSum[0] + waveSum[1] + waveSum[2] + waveSum[3];
+  if ( threadIdx.x == 0 ) blockTotal[blockIdx.x] = waveTot[0] + waveTot[1] + waveTot[2] + waveTot[3];
 }
 __global__ __launch_bounds__( 256 ) void bitsPrefixKernel( uint2* __restrict__ bits, uint32_t words, const uint32_t* __restrict__ blockBase ) {
   const uint32_t base = blockIdx.x * kBitsBlock + threadIdx.x * kBitsPerThread;
-  const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t       cnt[kBitsPerThread], sum = 0;
 #pragma unroll
   for ( int j = 0; j < kBitsPerThread; ++j ) {
     cnt[j] = base + j < words ? uint32_t( __popc( bits[base + j].x ) ) : 0u;
     sum += cnt[j];
   }
-  uint32_t inc = sum;
-#pragma unroll
-  for ( int off = 1; off < 64; off <<= 1 ) {
-    const uint32_t t = __shfl_up( inc, off, 64 );
-    if ( lane >= off ) inc += t;
-  }
-  __shared__ uint32_t waveSum[4];
-  if ( lane == 63 ) waveSum[wave] = inc;
-  __syncthreads();
-  uint32_t at = blockBase[blockIdx.x] + inc - sum;
-  for ( int w = 0; w < wave; ++w ) at += waveSum[w];
+  __shared__ uint32_t waveTot[4];
+  uint32_t            at = blockBase[blockIdx.x] + blockExclusive<4>( sum, waveTot );
 #pragma unroll
   for ( int j = 0; j < kBitsPerThread; ++j ) {
     if ( base + j < words ) bits[base + j].y = at;
@@ -281,12 +271,7 @@ __device__ __forceinline__ int collectBall( const Pt c, const Pt* __restrict__ c
     for ( int k = 0; k < kRowBatch; ++k ) {
       uint32_t w = uint32_t( ( ( (unsigned long long)hi[k] << 32 ) | lo[k] ) >> sh[k] ) & ( len[k] >= 32 ? 0xFFFFFFFFu : ( ( 1u << len[k] ) - 1u ) );
       const int mine = __popc( w );
-      int       inc  = mine;
-#pragma unroll
-      for ( int off = 1; off < 64; off <<= 1 ) {
-        const int t = __shfl_up( inc, off, 64 );
-        if ( lane >= off ) inc += t;
-      }
+      const int inc   = waveInclusive( mine, lane );
       const int total = __shfl( inc, 63, 64 );
       int       at    = cand + inc - mine;
       while ( w ) {
@@ -340,7 +325,7 @@ __device__ __forceinline__ int collectBall( const Pt c, const Pt* __restrict__ c
 #pragma unroll
     for ( int k = 0; k < kBatch; ++k ) {
       const unsigned long long m = __ballot( key[k] != 0xFFFFFFFFu );
-      if ( key[k] != 0xFFFFFFFFu ) keys[hits + __popcll( m & ( ( 1ull << lane ) - 1ull ) )] = key[k];
+      if ( key[k] != 0xFFFFFFFFu ) keys[hits + laneRank( m, lane )] = key[k];
       hits += __popcll( m );
     }
     __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
@@ -417,12 +402,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
     __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
     const uint32_t w0 = bins[2 * lane], w1 = bins[2 * lane + 1];
     const uint32_t b0 = w0 & 0xFFFFFu, b1 = w1 & 0xFFFFFu, e0 = w0 >> 20, e1 = w1 >> 20;
-    uint32_t       inc = b0 + b1, einc = e0 + e1;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t t = __shfl_up( inc, off, 64 ), te = __shfl_up( einc, off, 64 );
-      if ( lane >= off ) inc += t, einc += te;
-    }
+    const uint32_t inc = waveInclusive( b0 + b1, lane ), einc = waveInclusive( e0 + e1, lane );
     const uint32_t           before  = inc - ( b0 + b1 ), ebefore = einc - ( e0 + e1 );
     const unsigned long long reached = __ballot( inc >= uint32_t( maxNN ) );
     uint32_t                 cutoff  = 127;  // (fewer members than maxNN in the whole ball: everything stays)
@@ -444,36 +424,20 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
         const int      i   = base + lane;
         const uint32_t key = i < hits ? keys[i] : 0xFFFFFFFFu;
         const bool     isFront = i < hits && ( key >> idBits ) < cutoff, isCut = i < hits && ( key >> idBits ) == cutoff;
-        const unsigned long long mF = __ballot( isFront ), mC = __ballot( isCut ), below = ( 1ull << lane ) - 1ull;
+        const unsigned long long mF = __ballot( isFront ), mC = __ballot( isCut );
         __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-        if ( isFront ) keys[front + __popcll( mF & below )] = key;
-        if ( isCut ) cut[tail + __popcll( mC & below )] = key;
+        if ( isFront ) keys[front + laneRank( mF, lane )] = key;
+        if ( isCut ) cut[tail + laneRank( mC, lane )] = key;
         front += __popcll( mF ), tail += __popcll( mC );
       }
       for ( int i = int( hitsCut ) + lane; i < Pc; i += 64 ) cut[i] = 0xFFFFFFFFu;
       __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-      for ( int k = 2; k <= Pc; k <<= 1 )
-        for ( int j = k >> 1; j > 0; j >>= 1 ) {
-          for ( int i = lane; i < Pc; i += 64 ) {
-            const int partner = i ^ j;
-            if ( partner > i ) {
-              const uint32_t a = cut[i], b = cut[partner];
-              if ( ( a > b ) == ( ( i & k ) == 0 ) ) cut[i] = b, cut[partner] = a;
-            }
-          }
-          __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-        }
+      ldsBitonicSort( cut, Pc, lane );
       // where the row ends inside the cut distance
       uint32_t running = membersBefore, m = hitsCut;
       for ( int base = 0; base < int( hitsCut ); base += 64 ) {
         const int i   = base + lane;
-        uint32_t  inc = i < int( hitsCut ) ? ( count[cut[i] & idMask] & 0xFFu ) : 0u;
-#pragma unroll
-        for ( int off = 1; off < 64; off <<= 1 ) {
-          const uint32_t t = __shfl_up( inc, off, 64 );
-          if ( lane >= off ) inc += t;
-        }
-        inc += running;
+        const uint32_t inc = running + waveInclusive( i < int( hitsCut ) ? ( count[cut[i] & idMask] & 0xFFu ) : 0u, lane );
         const unsigned long long reachedHere = __ballot( i < int( hitsCut ) && inc >= uint32_t( maxNN ) );
         if ( reachedHere ) {
           const int firstLane = __ffsll( (long long)reachedHere ) - 1;
@@ -496,15 +460,13 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
       const bool     stay = i < hits && ( key >> idBits ) <= cutoff;
       const unsigned long long m = __ballot( stay );
       __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-      if ( stay ) keys[kept + __popcll( m & ( ( 1ull << lane ) - 1ull ) )] = key;
+      if ( stay ) keys[kept + laneRank( m, lane )] = key;
       kept += __popcll( m );
     }
     if ( !partial ) hits = kept;
     __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
   }
-  // pad to a power of two and sort ascending (wave-private LDS: no barrier needed beyond wave lockstep,
-  // but LDS visibility between lanes needs the s_waitcnt the compiler inserts for __syncthreads-free code:
-  // use __builtin_amdgcn_wave_barrier to keep the order of LDS operations)
+  // pad to a power of two and sort ascending
   int P = 64;
   while ( P < hits ) P <<= 1;
   if ( partial ) P = 0;  // (nothing left to sort)
@@ -517,22 +479,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
   }
   for ( int i = hits + lane; i < P; i += 64 ) keys[i] = 0xFFFFFFFFu;
   __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-  for ( int k = 2; k <= P; k <<= 1 ) {
-    for ( int j = k >> 1; j > 0; j >>= 1 ) {
-      for ( int i = lane; i < P; i += 64 ) {
-        const int partner = i ^ j;
-        if ( partner > i ) {
-          const uint32_t a = keys[i], b = keys[partner];
-          const bool     up = ( i & k ) == 0;
-          if ( ( a > b ) == up ) {
-            keys[i]       = b;
-            keys[partner] = a;
-          }
-        }
-      }
-      __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-    }
-  }
+  ldsBitonicSort( keys, P, lane );
   // truncation: first position where the running member count reaches maxNN (inclusive).  The cut falls in the last distance
   // kept (that is how it was chosen): everything before it counts whole -- members and hits are known from the bins -- and only
   // the hits of that distance, sorted by voxel id, are walked.
@@ -543,20 +490,12 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
   if ( partial ) nn = membersBefore, done = true;  // (found above: the row is keys[0 .. hits))
   if ( !cutFound ) {  // fewer members than maxNN in the whole ball: the row is the ball
     for ( int b = lane; b < 128; b += 64 ) nn += bins[b] & 0xFFFFFu;
-#pragma unroll
-    for ( int off = 32; off > 0; off >>= 1 ) nn += __shfl_xor( nn, off, 64 );
+    nn   = waveSum( nn );
     done = true;
   }
   for ( int base = int( hitsBefore ); base < hits && !done; base += 64 ) {
     const int i   = base + lane;
-    uint32_t  cnt = ( i < hits ) ? ( count[keys[i] & idMask] & 0xFFu ) : 0u;
-    uint32_t  inc = cnt;
-#pragma unroll
-    for ( int off = 1; off < 64; off <<= 1 ) {
-      const uint32_t t = __shfl_up( inc, off, 64 );
-      if ( lane >= off ) inc += t;
-    }
-    inc += running;
+    const uint32_t inc = running + waveInclusive( ( i < hits ) ? ( count[keys[i] & idMask] & 0xFFu ) : 0u, lane );
     const unsigned long long m = __ballot( i < hits && inc >= uint32_t( maxNN ) );
     if ( m ) {
       const int firstLane = __ffsll( (long long)m ) - 1;
@@ -600,7 +539,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
       const bool near = i < used && ( keys[i] >> idBits ) <= d2Max;
       const unsigned long long m = __ballot( near );
       if ( near ) {
-        const int at = nNear + __popcll( m & ( ( 1ull << lane ) - 1ull ) );
+        const int at = nNear + laneRank( m, lane );
         if ( at < kNearRoom ) nearList[at] = keys[i] & idMask;
       }
       nNear += __popcll( m );
@@ -625,7 +564,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
     for ( int k = 0; k < 3; ++k ) {
       const unsigned long long m = __ballot( in[k] );
       if ( in[k] ) {
-        const uint32_t pos = nDev + uint32_t( __popcll( m & ( ( 1ull << lane ) - 1ull ) ) );
+        const uint32_t pos = nDev + uint32_t( laneRank( m, lane ) );
         if ( pos < devStride ) drow[pos] = u[k];
       }
       nDev += uint32_t( __popcll( m ) );
@@ -644,7 +583,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
     }
     const unsigned long long m = __ballot( in );
     if ( in ) {
-      const uint32_t pos = nDev + uint32_t( __popcll( m & ( ( 1ull << lane ) - 1ull ) ) );
+      const uint32_t pos = nDev + uint32_t( laneRank( m, lane ) );
       if ( pos < devStride ) drow[pos] = u;
     }
     nDev += uint32_t( __popcll( m ) );
@@ -690,7 +629,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void r
       const uint32_t v   = key & idMask;
       const bool     in  = i < len && ( ( key & ~idMask ) | u ) <= lastKey[v];
       const unsigned long long m = __ballot( in );
-      if ( in ) keys[kept + __popcll( m & ( ( 1ull << lane ) - 1ull ) )] = v;
+      if ( in ) keys[kept + laneRank( m, lane )] = v;
       kept += __popcll( m );
     }
     __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
@@ -704,7 +643,7 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void r
       const bool     in  = i < hits && ( ( key & ~idMask ) | u ) <= lastKey[v];
       const unsigned long long m = __ballot( in );
       __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
-      if ( in ) keys[kept + __popcll( m & ( ( 1ull << lane ) - 1ull ) )] = v;
+      if ( in ) keys[kept + laneRank( m, lane )] = v;
       kept += __popcll( m );
     }
     __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
@@ -776,12 +715,7 @@ __global__ __launch_bounds__( 256 ) void smoothInitKernel( const uint4* __restri
     s1 += h.y;
     s2 += h.z;
   }
-#pragma unroll
-  for ( int off = 8; off > 0; off >>= 1 ) {
-    s0 += __shfl_xor( s0, off, 64 );
-    s1 += __shfl_xor( s1, off, 64 );
-    s2 += __shfl_xor( s2, off, 64 );
-  }
+  s0 = waveSum<16>( s0 ), s1 = waveSum<16>( s1 ), s2 = waveSum<16>( s2 );
   if ( lane == 0 ) rec[v] = make_uint4( s0, s1, s2, 1u );
 }
 
@@ -1054,12 +988,7 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
   // the sub-lists as one index space: pre[s] = entries of the sub-lists before s
   __shared__ uint32_t pre[kSubLists + 1];
   if ( threadIdx.x < 64 ) {
-    uint32_t inc = threadIdx.x < kSubLists ? counts[threadIdx.x * 32] : 0u;
-#pragma unroll
-    for ( int off = 1; off < kSubLists; off <<= 1 ) {
-      const uint32_t t = __shfl_up( inc, off, 64 );
-      if ( int( threadIdx.x ) >= off ) inc += t;
-    }
+    const uint32_t inc = waveInclusive<kSubLists>( threadIdx.x < kSubLists ? counts[threadIdx.x * 32] : 0u, int( threadIdx.x ) );
     if ( threadIdx.x < kSubLists ) pre[threadIdx.x + 1] = inc;
     if ( threadIdx.x == 0 ) pre[0] = 0;
   }
@@ -1122,13 +1051,7 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
         h1 += ( best >> 1 ) == 1 ? one : 0u;
         h2 += ( best >> 1 ) == 2 ? one : 0u;
       }
-#pragma unroll
-      for ( int off = 8; off > 0; off >>= 1 ) {
-        h0 += __shfl_xor( h0, off, 64 );
-        h1 += __shfl_xor( h1, off, 64 );
-        h2 += __shfl_xor( h2, off, 64 );
-        moved += __shfl_xor( moved, off, 64 );
-      }
+      h0 = waveSum<16>( h0 ), h1 = waveSum<16>( h1 ), h2 = waveSum<16>( h2 ), moved = waveSum<16>( moved );
       if ( sub == 0 ) lastRescore[v] = uint32_t( iter ) + 1u;
       if ( moved ) {  // (a changed histogram needs a moved point)
         // packed u16 pairs: the difference is added modulo 2^32 per word; every true field stays within 0 .. 65535, so

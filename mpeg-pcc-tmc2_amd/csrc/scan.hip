@@ -3,25 +3,11 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
 constexpr int kTile = 2048;  // 256 threads x 8
-
-__device__ __forceinline__ uint32_t waveInclusive( uint32_t v, int lane ) {
-#pragma unroll
-  for ( int off = 1; off < 64; off <<= 1 ) {
-    const uint32_t t = __shfl_up( v, off, 64 );
-    if ( lane >= off ) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t waveSum( uint32_t v ) {
-#pragma unroll
-  for ( int off = 32; off > 0; off >>= 1 ) v += __shfl_xor( v, off, 64 );
-  return v;
-}
 
 // One launch: every tile scans its 2048 elements, publishes its total, and finds the sum of everything before it by looking
 // back over the totals / running sums its predecessors have published (decoupled look-back, one wavefront reads 64
@@ -47,11 +33,7 @@ __global__ __launch_bounds__( 256 ) void scanLookBackKernel( const uint32_t* __r
     v[k] = ( base + k < n ) ? in[base + k] : 0u;
     run += v[k];
   }
-  const uint32_t inc = waveInclusive( run, lane );
-  if ( lane == 63 ) waveTotal[wave] = inc;
-  __syncthreads();
-  uint32_t offset = inc - run;
-  for ( int w = 0; w < wave; ++w ) offset += waveTotal[w];
+  uint32_t offset = blockExclusive<4>( run, waveTotal );
   if ( wave == 0 ) {
     const uint32_t           aggregate = waveTotal[0] + waveTotal[1] + waveTotal[2] + waveTotal[3];
     const unsigned long long tag       = static_cast<unsigned long long>( epoch ) << 34;

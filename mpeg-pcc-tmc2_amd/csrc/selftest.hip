@@ -1,8 +1,9 @@
 // selftest.hip -- the shared device primitives, each reachable on its own through the C ABI (include/tmc2hip.h: tmc2_selftest_*),
 // so that the suite can compare them with a plain loop at shapes no test cloud produces: exclusiveScanU32 and fillRegions
-// (scan.hip), the XCD work mapping (internal.h), UnionFind<false / true> (union_find.h), CandSort (cand_sort.h) and the marked
-// cells of a boundary-cell grid (cell_grid.h, cell_grid.hip; this one waits for its count, as the stages do).  The entries
-// take DEVICE pointers and queue on the context's stream without synchronising: a test queues many calls, then reads back.
+// (scan.hip), the XCD work mapping (internal.h), UnionFind<false / true> (union_find.h), CandSort (cand_sort.h), the marked
+// cells of a boundary-cell grid (cell_grid.h, cell_grid.hip; this one waits for its count, as the stages do) and the cross-lane
+// idioms of wave.h.  The entries take DEVICE pointers and queue on the context's stream without synchronising: a test queues many
+// calls, then reads back.
 // Nothing of the product path calls into this file.  (S7's own kernels on a caller's neighbour table: tmc2_selftest_components,
 // patches.hip -- the kernels are local to that file.)
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include "cell_grid.h"
 #include "internal.h"
 #include "union_find.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -92,6 +94,70 @@ __global__ __launch_bounds__( 256 ) void slotOfKeysKernel( const uint32_t* __res
                                                             const uint32_t* __restrict__ keys, uint32_t count, uint32_t* __restrict__ slots ) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if ( k < count ) slots[k] = keys[k] < cells ? slotOfKey( bits, rank, keys[k] ) : kNoSlot;
+}
+
+// ---- wave.h, one primitive per launch (the op codes of tmc2_selftest_wave)
+enum WaveOp { kWaveScan, kWaveScan16, kWaveSum, kWaveSum16, kWaveMin, kWaveMax, kWaveCompact, kWaveSort, kWaveBlockScan };
+
+// out[i] = the primitive's value on lane i; workgroups of 256: four wavefronts with data of their own
+template <int OP, typename T>
+__global__ __launch_bounds__( 256 ) void waveLaneKernel( const T* __restrict__ in, T* __restrict__ out ) {
+  const uint32_t i    = blockIdx.x * 256 + threadIdx.x;
+  const int      lane = threadIdx.x & 63;
+  const T        v    = in[i];
+  if constexpr ( OP == kWaveScan ) out[i] = waveInclusive( v, lane );
+  if constexpr ( OP == kWaveScan16 ) out[i] = waveInclusive<16>( v, lane );
+  if constexpr ( OP == kWaveSum ) out[i] = waveSum( v );
+  if constexpr ( OP == kWaveSum16 ) out[i] = waveSum<16>( v );
+  if constexpr ( OP == kWaveMin ) out[i] = waveMin( v );
+  if constexpr ( OP == kWaveMax ) out[i] = waveMax( v );
+}
+template <typename T>
+void waveLaneLaunch( int op, uint32_t blocks, hipStream_t s, const void* d_in, void* d_out ) {
+  const T* in  = static_cast<const T*>( d_in );
+  T*       out = static_cast<T*>( d_out );
+  switch ( op ) {
+    case kWaveScan: hipLaunchKernelGGL( ( waveLaneKernel<kWaveScan, T> ), dim3( blocks ), dim3( 256 ), 0, s, in, out ); break;
+    case kWaveScan16: hipLaunchKernelGGL( ( waveLaneKernel<kWaveScan16, T> ), dim3( blocks ), dim3( 256 ), 0, s, in, out ); break;
+    case kWaveSum: hipLaunchKernelGGL( ( waveLaneKernel<kWaveSum, T> ), dim3( blocks ), dim3( 256 ), 0, s, in, out ); break;
+    case kWaveSum16: hipLaunchKernelGGL( ( waveLaneKernel<kWaveSum16, T> ), dim3( blocks ), dim3( 256 ), 0, s, in, out ); break;
+    case kWaveMin: hipLaunchKernelGGL( ( waveLaneKernel<kWaveMin, T> ), dim3( blocks ), dim3( 256 ), 0, s, in, out ); break;
+    default: hipLaunchKernelGGL( ( waveLaneKernel<kWaveMax, T> ), dim3( blocks ), dim3( 256 ), 0, s, in, out ); break;
+  }
+}
+// laneRank through a stream compaction: a wavefront's lanes with in != 0 write their lane number back to back from the wavefront's
+// first slot on (the other slots: 0xFFFFFFFF); aux[i] = the wavefront's count
+__global__ __launch_bounds__( 256 ) void waveCompactKernel( const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t* __restrict__ aux ) {
+  __shared__ uint32_t slots[256];
+  const uint32_t i    = blockIdx.x * 256 + threadIdx.x;
+  const int      lane = threadIdx.x & 63;
+  const bool     mine = in[i] != 0;
+  slots[threadIdx.x]  = 0xFFFFFFFFu;
+  __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
+  const unsigned long long m = __ballot( mine );
+  if ( mine ) slots[( threadIdx.x & ~63u ) + laneRank( m, lane )] = uint32_t( lane );
+  __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
+  out[i] = slots[threadIdx.x];
+  aux[i] = uint32_t( __popcll( m ) );
+}
+// one wavefront per list of P keys
+__global__ __launch_bounds__( 64 ) void waveSortKernel( const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int P ) {
+  extern __shared__ uint32_t sortKeys[];
+  const int    lane = threadIdx.x;
+  const size_t base = size_t( blockIdx.x ) * P;
+  for ( int i = lane; i < P; i += 64 ) sortKeys[i] = in[base + i];
+  __builtin_amdgcn_fence( __ATOMIC_ACQ_REL, "wavefront" );
+  ldsBitonicSort( sortKeys, P, lane );
+  for ( int i = lane; i < P; i += 64 ) out[base + i] = sortKeys[i];
+}
+// out[i] = the values before thread i in its workgroup, aux[i] = the workgroup's total as thread i has it
+template <int WAVES>
+__global__ __launch_bounds__( 64 * WAVES ) void waveBlockScanKernel( const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t* __restrict__ aux ) {
+  __shared__ uint32_t waveTot[WAVES];
+  const uint32_t      i = blockIdx.x * ( 64 * WAVES ) + threadIdx.x;
+  uint32_t            total;
+  out[i] = blockExclusive<WAVES>( in[i], waveTot, total );
+  aux[i] = total;
 }
 
 // fillRegions takes a braced list: one call shape per count
@@ -229,6 +295,42 @@ int tmc2_selftest_marked_cells( tmc2_ctx* ctx, const int16_t* d_xyz4, const uint
     hipLaunchKernelGGL( slotOfKeysKernel, dim3( uint32_t( ( keys + 255 ) / 256 ) ), dim3( 256 ), 0, s, marked.bits.p, marked.rank.p,
                         uint32_t( g.cells() ), d_keys, uint32_t( keys ), d_slots );
   TMC2_HIP( hipStreamSynchronize( s ) );  // (the bit words and ranks go back to the pool with `marked`)
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+int tmc2_selftest_wave( tmc2_ctx* ctx, int op, int param, const void* d_in, void* d_out, uint32_t* d_aux, uint64_t n ) {
+  using namespace tmc2;
+  const bool     perLane = op >= kWaveScan && op <= kWaveMax;
+  const bool     sizeOk  = op == kWaveSort        ? param >= 64 && param <= 8192 && !( param & ( param - 1 ) )
+                           : op == kWaveBlockScan ? param == 1 || param == 2 || param == 4 || param == 16
+                                                  : !perLane || ( param >= 0 && param <= 2 );
+  const uint64_t group   = op == kWaveSort ? uint64_t( param ) : op == kWaveBlockScan ? 64u * uint64_t( param ) : 256u;
+  if ( !ctx || !d_in || !d_out || op < kWaveScan || op > kWaveBlockScan || !sizeOk || n == 0 || n > ( 1u << 24 ) || n % group ||
+       ( ( op == kWaveCompact || op == kWaveBlockScan ) && !d_aux ) ) {
+    setError( "selftest_wave: invalid argument (null pointer, unknown op, a type beyond 2, a sort length that is no power of two in 64 .. 8192, "
+              "a workgroup of other than 1, 2, 4 or 16 wavefronts, no element, more than 2^24, or no whole number of groups)" );
+    return TMC2_E_INVALID;
+  }
+  ApiScope        scope( ctx );
+  hipStream_t     s      = ctx->stream;
+  const uint32_t  blocks = uint32_t( n / group );
+  const uint32_t* in     = static_cast<const uint32_t*>( d_in );
+  uint32_t*       out    = static_cast<uint32_t*>( d_out );
+  if ( perLane ) {
+    if ( param == 0 ) waveLaneLaunch<uint32_t>( op, blocks, s, d_in, d_out );
+    if ( param == 1 ) waveLaneLaunch<int>( op, blocks, s, d_in, d_out );
+    if ( param == 2 ) waveLaneLaunch<double>( op, blocks, s, d_in, d_out );
+  } else if ( op == kWaveCompact ) {
+    hipLaunchKernelGGL( waveCompactKernel, dim3( blocks ), dim3( 256 ), 0, s, in, out, d_aux );
+  } else if ( op == kWaveSort ) {
+    hipLaunchKernelGGL( waveSortKernel, dim3( blocks ), dim3( 64 ), size_t( param ) * 4, s, in, out, param );
+  } else {
+    if ( param == 1 ) hipLaunchKernelGGL( waveBlockScanKernel<1>, dim3( blocks ), dim3( 64 ), 0, s, in, out, d_aux );
+    if ( param == 2 ) hipLaunchKernelGGL( waveBlockScanKernel<2>, dim3( blocks ), dim3( 128 ), 0, s, in, out, d_aux );
+    if ( param == 4 ) hipLaunchKernelGGL( waveBlockScanKernel<4>, dim3( blocks ), dim3( 256 ), 0, s, in, out, d_aux );
+    if ( param == 16 ) hipLaunchKernelGGL( waveBlockScanKernel<16>, dim3( blocks ), dim3( 1024 ), 0, s, in, out, d_aux );
+  }
   TMC2_HIP( hipGetLastError() );
   return TMC2_OK;
 }

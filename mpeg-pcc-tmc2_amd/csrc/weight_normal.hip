@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "wave.h"
 
 namespace tmc2 {
 namespace {
@@ -35,7 +36,7 @@ __global__ __launch_bounds__( 256 ) void popcountKernel( const uint32_t* __restr
   uint32_t       acc   = 0;
   for ( uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < wordsPerPlane; w += gridDim.x * blockDim.x )
     acc += __popc( bits[plane * wordsPerPlane + w] );
-  for ( int off = 32; off > 0; off >>= 1 ) acc += __shfl_down( acc, off, 64 );
+  acc = waveSum( acc );
   if ( ( threadIdx.x & 63 ) == 0 && acc ) atomicAdd( &counts[plane], acc );
 }
 

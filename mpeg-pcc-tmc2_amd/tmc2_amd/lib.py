@@ -319,6 +319,10 @@ class Context:
                                                  C.byref(cells), d_bits, d_rank, d_keys, int(keys), d_slots))
         return cells.value
 
+    def selftest_wave(self, op, param, d_in, d_out, n, d_aux=None):
+        """one idiom of csrc/wave.h per call (include/tmc2hip.h: the op codes)"""
+        _check(self.L.tmc2_selftest_wave(self.h, int(op), int(param), d_in, d_out, d_aux, int(n)))
+
     def stream(self):
         return self.L.tmc2_ctx_stream(self.h)
 
@@ -1298,4 +1302,5 @@ int tmc2_selftest_union_find(tmc2_ctx*, int, uint32_t*, uint64_t, const uint32_t
 int tmc2_selftest_cand_sort(tmc2_ctx*, uint32_t*, const uint32_t*, uint64_t, uint32_t*)
 int tmc2_selftest_std_sort(uint32_t*, const uint32_t*, uint64_t)
 int tmc2_selftest_marked_cells(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, uint64_t, uint32_t*)
+int tmc2_selftest_wave(tmc2_ctx*, int, int, const void*, void*, uint32_t*, uint64_t)
 """.strip().split("\n")

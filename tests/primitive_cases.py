@@ -1,6 +1,6 @@
 """Inputs and plain references for the shared device primitives (tmc2_selftest_*: csrc/selftest.hip): the exclusive scan, the
 several-regions fill, the XCD work mapping, the two union-finds (S7's kernels over a 16-neighbour table; explicit edge lists, with
-and without parity), CandSort and the marked cells of a boundary-cell grid.  numpy only.  tests/test_primitive_cases.py checks the references themselves (every graph family
+and without parity), CandSort, the marked cells of a boundary-cell grid and the cross-lane idioms of csrc/wave.h.  numpy only.  tests/test_primitive_cases.py checks the references themselves (every graph family
 has a component count known in closed form); tests/test_gpu_primitives.py compares the device with them, integer for integer."""
 import functools
 
@@ -411,3 +411,114 @@ def marked_cells_reference(xyz4, btype, w, grid_size):
     rank = (np.cumsum(per_word) - per_word).astype(np.uint32)
     slot = np.where(marked, np.cumsum(marked) - 1, NO_SLOT).astype(np.uint32)[:w ** 3]
     return bits, rank, slot
+
+
+# ---- the cross-lane idioms of csrc/wave.h (tmc2_selftest_wave) -------------------------------------------------------------
+WAVE_OPS = {"scan": 0, "scan16": 1, "sum": 2, "sum16": 3, "min": 4, "max": 5, "compact": 6, "sort": 7, "block_scan": 8}
+WAVE_TYPES = {"uint32": 0, "int32": 1, "float64": 2}
+WAVE_U32_PATTERNS = ("zero", "one", "index", "max", "first", "last", "middle", "random")
+WAVE_PREDICATES = ("none", "all", "alternating", "lane0", "lane63", "random")
+WAVE_SORT_LENGTHS = (64, 128, 2048)
+WAVE_SORT_KINDS = ("duplicates", "padded", "sorted", "reversed")
+WAVE_BLOCK_WAVES = (1, 2, 4, 16)
+WAVE_NO_LANE = 0xFFFFFFFF
+
+
+def wave_u32(size, groups=4, seed=0):
+    """every pattern, `groups` groups of `size` values each, back to back: zeros, ones, the index in the group (plus 1000 per
+    group), 0xFFFFFFFF everywhere (the sums wrap), one non-zero at the first, the last and the middle place, random words"""
+    rng = np.random.default_rng([seed, size, groups])
+    out = np.zeros((len(WAVE_U32_PATTERNS), groups, size), np.uint32)
+    out[1] = 1
+    out[2] = np.arange(size, dtype=np.uint32)[None, :] + 1000 * np.arange(groups, dtype=np.uint32)[:, None]
+    out[3] = 0xFFFFFFFF
+    for row, place in ((4, 0), (5, size - 1), (6, size // 2)):
+        out[row, :, place] = 0x89ABCDEF + np.arange(groups, dtype=np.uint32)
+    out[7] = rng.integers(0, 1 << 32, (groups, size), dtype=np.uint32)
+    return out.reshape(-1)
+
+
+def wave_i32(extremes, blocks=2, seed=0):
+    """mixed signs, four wavefronts of their own per block; extremes: the whole range with INT_MIN and INT_MAX in every wavefront
+    (for min and max), else small enough that no sum overflows"""
+    rng = np.random.default_rng([seed, int(extremes), blocks])
+    if not extremes:
+        return rng.integers(-(1 << 20), 1 << 20, blocks * 256).astype(np.int32)
+    a = rng.integers(-(1 << 31), 1 << 31, (blocks * 4, 64)).astype(np.int32)
+    for w in range(len(a)):
+        a[w, (7 * w) % 64], a[w, (7 * w + 33) % 64] = -(1 << 31), (1 << 31) - 1
+    a[0, :] = np.where(np.arange(64) % 2, -(1 << 31), (1 << 31) - 1)      # (nothing but the two ends)
+    return a.reshape(-1)
+
+
+def wave_f64(blocks=2, seed=0):
+    """magnitudes 2^-40 .. 2^40 with full mantissas and mixed signs: the order of a sum shows in its low bits"""
+    rng = np.random.default_rng([seed, blocks, 64])
+    n = blocks * 256
+    return np.ldexp(rng.uniform(1.0, 2.0, n), rng.integers(-40, 41, n)) * rng.choice([-1.0, 1.0], n)
+
+
+def wave_scan_reference(a, width=64):
+    """the shuffle loop itself: for off = 1, 2, 4 .. < width, lanes at or past off in their group add the value off lanes below"""
+    v = np.array(a)
+    place = np.arange(len(v)) % width
+    off = 1
+    while off < width:
+        t = np.roll(v, off)
+        v = np.where(place >= off, v + t, v)
+        off <<= 1
+    return v
+
+
+def wave_reduce_reference(a, op, width=64):
+    """the butterfly itself: for off = width / 2 .. 1, v = op( v, v[lane ^ off] ); op: np.add, np.minimum, np.maximum"""
+    v = np.array(a)
+    lane = np.arange(len(v))
+    off = width // 2
+    while off:
+        v = op(v, v[lane ^ off])
+        off >>= 1
+    return v
+
+
+def wave_predicates(blocks=1, seed=0):
+    """every predicate pattern over `blocks` workgroups of four wavefronts each, as uint32 0 / 1"""
+    rng = np.random.default_rng([seed, blocks, 6])
+    out = np.zeros((len(WAVE_PREDICATES), blocks * 4, 64), np.uint32)
+    out[1] = 1
+    out[2, :, ::2] = 1
+    out[2, 1::2] ^= 1                                             # (odd wavefronts: the odd lanes)
+    out[3, :, 0] = 1
+    out[4, :, 63] = 1
+    out[5] = rng.integers(0, 2, out[5].shape, dtype=np.uint32)
+    return out.reshape(-1)
+
+
+def wave_compact_reference(pred):
+    """(per wavefront: the set lanes back to back, then WAVE_NO_LANE; per lane: the wavefront's count)"""
+    p = np.asarray(pred).reshape(-1, 64) != 0
+    out = np.full(p.shape, WAVE_NO_LANE, np.uint32)
+    for w, row in enumerate(p):
+        lanes = np.flatnonzero(row)
+        out[w, :len(lanes)] = lanes
+    return out.reshape(-1), np.repeat(p.sum(axis=1), 64).astype(np.uint32)
+
+
+def wave_sort_lists(length, seed=0):
+    """one list of `length` keys per kind: few distinct keys; a valid length that is no power of two, padded with 0xFFFFFFFF (which
+    is also one of the valid keys); already sorted; reverse sorted"""
+    rng = np.random.default_rng([seed, length])
+    dup = rng.integers(0, 7, length, dtype=np.uint32) * 0x10000001
+    valid = length - length // 4 - 3
+    padded = np.full(length, 0xFFFFFFFF, np.uint32)
+    padded[:valid] = rng.integers(0, 1 << 32, valid, dtype=np.uint32)
+    padded[valid // 2] = 0xFFFFFFFF
+    rising = np.sort(rng.integers(0, 1 << 32, length, dtype=np.uint32))
+    return np.concatenate([dup, padded, rising, rising[::-1]])
+
+
+def wave_block_scan_reference(a, waves):
+    """(per thread: the sum of the workgroup's values before it, per thread: the workgroup's total), uint32 modulo 2^32"""
+    g = np.asarray(a, np.uint32).reshape(-1, 64 * waves)
+    inc = np.cumsum(g, axis=1, dtype=np.uint32)
+    return (inc - g).reshape(-1), np.repeat(inc[:, -1], 64 * waves)

@@ -1,7 +1,8 @@
 """GPU tier: the shared device primitives on their own (tmc2_selftest_*: csrc/selftest.hip, and S7's kernels in csrc/patches.hip)
 against the plain references of tests/primitive_cases.py -- the exclusive scan, the several-regions fill, the XCD work mapping,
 S7's union-find kernels on neighbour tables no cloud produces, both union-finds over explicit edge lists, CandSort against the
-real std::sort, and the marked cells of a boundary-cell grid.  Every comparison is exact integer equality.  The entries queue on the context's stream and do not wait: a test
+real std::sort, the marked cells of a boundary-cell grid, and the cross-lane idioms of csrc/wave.h.  Every comparison is exact: integer
+equality, float64 as bit patterns.  The entries queue on the context's stream and do not wait: a test
 queues all its calls, then reads back."""
 import ctypes as C
 import threading
@@ -452,3 +453,65 @@ def test_gpu_marked_cells_on_the_cube_and_without_outputs(gpu_ctx, dev):
     assert gpu_ctx.selftest_marked_cells(None, None, 0, 6, 0, 66) == 0
     with pytest.raises(T.Tmc2Error, match="selftest_marked_cells"):
         gpu_ctx.selftest_marked_cells(dev.put(xyz4), dev.put(btype), 65, 3, 0, 66)
+
+
+# ---- the cross-lane idioms of csrc/wave.h --------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_gpu_wave_scans_and_reductions_are_the_shuffle_loops(gpu_ctx, dev):
+    """waveInclusive and waveSum / waveMin / waveMax at width 64 and 16 (four groups per wavefront) on uint32, int32 and float64:
+    workgroups of four wavefronts with data of their own; float64 compared as bit patterns"""
+    u32, small, extremes, f64 = pc.wave_u32(64), pc.wave_i32(False), pc.wave_i32(True), pc.wave_f64()
+    jobs = []
+    for a, names in ((u32, ("scan", "scan16", "sum", "sum16", "min", "max")), (small, ("scan", "scan16", "sum", "sum16")),
+                     (extremes, ("min", "max")), (f64, ("scan", "scan16", "sum", "sum16"))):
+        d_in = dev.put(a)
+        for name in names:
+            width = 16 if name.endswith("16") else 64
+            if name.startswith("scan"):
+                want = pc.wave_scan_reference(a, width)
+            else:
+                want = pc.wave_reduce_reference(a, {"sum": np.add, "min": np.minimum, "max": np.maximum}[name.rstrip("16")], width)
+            d_out = dev.put(np.full(a.nbytes // 4, SENTINEL, np.uint32))
+            gpu_ctx.selftest_wave(pc.WAVE_OPS[name], pc.WAVE_TYPES[a.dtype.name], d_in, d_out, len(a))
+            jobs.append((name, a, d_out, want))
+        jobs.append(("input", a, d_in, a))
+    bits = {4: np.uint32, 8: np.uint64}
+    for name, a, d_out, want in jobs:
+        assert want.dtype == a.dtype
+        got = dev.get(d_out, a.shape, a.dtype)
+        assert np.array_equal(got.view(bits[a.itemsize]), want.view(bits[a.itemsize])), (name, a.dtype.name)
+
+
+@pytest.mark.gpu
+def test_gpu_lane_rank_compacts_in_lane_order(gpu_ctx, dev):
+    """no lane, every lane, alternating lanes, lane 0 alone, lane 63 alone (the mask of all 63 lanes below), a random mask per
+    wavefront: the compacted order and the count"""
+    pred = pc.wave_predicates(2)
+    want, count = pc.wave_compact_reference(pred)
+    d_out, d_aux = dev.put(np.full(len(pred), SENTINEL, np.uint32)), dev.put(np.full(len(pred), SENTINEL, np.uint32))
+    gpu_ctx.selftest_wave(pc.WAVE_OPS["compact"], 0, dev.put(pred), d_out, len(pred), d_aux)
+    assert np.array_equal(dev.get(d_out, pred.shape, np.uint32), want)
+    assert np.array_equal(dev.get(d_aux, pred.shape, np.uint32), count)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("length", pc.WAVE_SORT_LENGTHS)
+def test_gpu_lds_bitonic_sort_is_np_sort(gpu_ctx, dev, length):
+    """keys with duplicates, a padded list, sorted and reverse sorted input, one wavefront per list; the input stays as it was"""
+    lists = pc.wave_sort_lists(length)
+    d_in, d_out = dev.put(lists), dev.put(np.full(len(lists), SENTINEL, np.uint32))
+    gpu_ctx.selftest_wave(pc.WAVE_OPS["sort"], length, d_in, d_out, len(lists))
+    assert np.array_equal(dev.get(d_out, (len(pc.WAVE_SORT_KINDS), length), np.uint32), np.sort(lists.reshape(-1, length), axis=1))
+    assert np.array_equal(dev.get(d_in, lists.shape, np.uint32), lists)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", pc.WAVE_BLOCK_WAVES)
+def test_gpu_block_exclusive_is_the_cumsum(gpu_ctx, dev, waves):
+    """every integer pattern, one workgroup each: the offsets per thread and the total as every thread has it"""
+    a = pc.wave_u32(64 * waves, groups=1)
+    before, total = pc.wave_block_scan_reference(a, waves)
+    d_out, d_aux = dev.put(np.full(len(a), SENTINEL, np.uint32)), dev.put(np.full(len(a), SENTINEL, np.uint32))
+    gpu_ctx.selftest_wave(pc.WAVE_OPS["block_scan"], waves, dev.put(a), d_out, len(a), d_aux)
+    assert np.array_equal(dev.get(d_out, a.shape, np.uint32), before)
+    assert np.array_equal(dev.get(d_aux, a.shape, np.uint32), total)

@@ -217,3 +217,82 @@ def test_marked_cells_entry_refuses_bad_arguments_without_a_device():
     for grid_size, bits, max_coord in ((2, 14, 0), (4, 0, 0), (16, 3, 0)):       # more than 2^31 cells, none, none
         assert L.tmc2_selftest_marked_cells(p, p, p, 8, grid_size, bits, max_coord, C.byref(cells), p, p, p, 1, p) == invalid
         assert b"cells" in L.tmc2_last_error()
+
+
+# ---- the cross-lane idioms of csrc/wave.h ------------------------------------------------------------------------------------
+def test_wave_inputs_hold_what_the_cases_need():
+    a = pc.wave_u32(64).reshape(len(pc.WAVE_U32_PATTERNS), 4, 64)
+    assert not a[0].any() and (a[1] == 1).all() and (a[3] == 0xFFFFFFFF).all() and a[2, 3].tolist() == list(range(3000, 3064))
+    for row, place in ((4, 0), (5, 63), (6, 32)):
+        assert (np.count_nonzero(a[row], axis=1) == 1).all() and a[row, :, place].all() and len(set(a[row, :, place].tolist())) == 4
+    assert len({w.tobytes() for w in a[7]}) == 4
+    e = pc.wave_i32(True).reshape(-1, 64)
+    assert e.dtype == np.int32 and all(w.min() == -(1 << 31) and w.max() == (1 << 31) - 1 for w in e) and set(e[0].tolist()) == {-(1 << 31), (1 << 31) - 1}
+    s = pc.wave_i32(False)
+    assert (s < 0).any() and (s > 0).any() and np.abs(s.astype(np.int64)).max() * 64 < 1 << 31
+    d = pc.wave_f64()
+    ex = np.frexp(np.abs(d))[1] - 1
+    assert d.dtype == np.float64 and ex.min() <= -38 and ex.max() >= 38 and -40 <= ex.min() and ex.max() <= 40 and (d < 0).any() and (d > 0).any()
+    p = pc.wave_predicates().reshape(len(pc.WAVE_PREDICATES), 4, 64)
+    assert p.sum(axis=2).tolist()[:5] == [[0] * 4, [64] * 4, [32] * 4, [1] * 4, [1] * 4] and p[2, 0, 0] and p[2, 1, 1] and p[4, 0, 63]
+    assert len(set(p[5].sum(axis=1).tolist())) > 1
+
+
+def test_wave_references_are_the_plain_loops():
+    """integers: the shuffle loop and the butterfly give the cumsum and the one sum / min / max of the group on every lane; float64:
+    lane by lane in Python floats, the adds in the order of the loop -- and that order shows (not the left-to-right sum)"""
+    for width in (64, 16):
+        for a in (pc.wave_u32(64), pc.wave_i32(False), pc.wave_i32(True)):
+            g = a.reshape(-1, width)
+            if a.dtype == np.uint32 or np.abs(a.astype(np.int64)).max() < 1 << 24:
+                assert np.array_equal(pc.wave_scan_reference(a, width), np.cumsum(g, axis=1, dtype=a.dtype).reshape(-1))
+                assert np.array_equal(pc.wave_reduce_reference(a, np.add, width), np.repeat(g.sum(axis=1, dtype=a.dtype), width))
+            assert np.array_equal(pc.wave_reduce_reference(a, np.minimum, width), np.repeat(g.min(axis=1), width))
+            assert np.array_equal(pc.wave_reduce_reference(a, np.maximum, width), np.repeat(g.max(axis=1), width))
+    d = pc.wave_f64(1)[:64]
+    v = d.tolist()
+    for off in (1, 2, 4, 8, 16, 32):
+        v = [v[i] + v[i - off] if i >= off else v[i] for i in range(64)]
+    assert pc.wave_scan_reference(d).view(np.uint64).tolist() == np.array(v).view(np.uint64).tolist()
+    b = d.tolist()
+    for off in (32, 16, 8, 4, 2, 1):
+        b = [b[i] + b[i ^ off] for i in range(64)]
+    got = pc.wave_reduce_reference(d, np.add)
+    assert got.view(np.uint64).tolist() == np.array(b).view(np.uint64).tolist() and len(set(got.view(np.uint64).tolist())) == 1
+    full = pc.wave_f64()
+    left_to_right = np.array([sum(w.tolist()) for w in full.reshape(-1, 64)])
+    assert (pc.wave_reduce_reference(full, np.add)[::64].view(np.uint64) != left_to_right.view(np.uint64)).any()
+
+
+def test_wave_compaction_sort_and_block_scan_references():
+    pred = pc.wave_predicates()
+    out, count = pc.wave_compact_reference(pred)
+    for w, (p, o, c) in enumerate(zip(pred.reshape(-1, 64).tolist(), out.reshape(-1, 64).tolist(), count.reshape(-1, 64).tolist())):
+        lanes = [i for i in range(64) if p[i]]
+        assert o == lanes + [pc.WAVE_NO_LANE] * (64 - len(lanes)) and c == [len(lanes)] * 64, w
+    for length in pc.WAVE_SORT_LENGTHS:
+        lists = pc.wave_sort_lists(length).reshape(len(pc.WAVE_SORT_KINDS), length)
+        assert len(set(lists[0].tolist())) <= 7 and (np.diff(lists[2].astype(np.int64)) >= 0).all() and (np.diff(lists[3].astype(np.int64)) <= 0).all()
+        valid = length - length // 4 - 3
+        assert valid & (valid - 1) and (lists[1, valid:] == 0xFFFFFFFF).all() and (lists[1, :valid] == 0xFFFFFFFF).sum() >= 1
+    for waves in pc.WAVE_BLOCK_WAVES:
+        a = pc.wave_u32(64 * waves, groups=1)
+        before, total = pc.wave_block_scan_reference(a, waves)
+        for g, b, t in zip(a.reshape(-1, 64 * waves), before.reshape(-1, 64 * waves), total.reshape(-1, 64 * waves)):
+            want, ref_total = pc.scan_reference(g)
+            assert np.array_equal(b, want) and (t == ref_total).all(), waves
+
+
+def test_wave_entry_refuses_bad_arguments_without_a_device():
+    L = T.load_library()
+    invalid = int(re.search(r"#define TMC2_E_INVALID (-?\d+)", open(os.path.join(ROOT, "include", "tmc2hip.h")).read()).group(1))
+    p = C.c_void_p(4096)                                              # never dereferenced: every call below stops at its arguments
+    ops = pc.WAVE_OPS
+    assert L.tmc2_selftest_wave(None, ops["scan"], 0, p, p, None, 256) == invalid
+    assert b"selftest_wave" in L.tmc2_last_error()
+    for op, param, n, aux in ((-1, 0, 256, p), (9, 0, 256, p), (ops["sum"], 3, 256, None), (ops["min"], 0, 255, None), (ops["max"], 0, 0, None),
+                              (ops["compact"], 0, 256, None), (ops["compact"], 0, 64, p), (ops["sort"], 32, 64, None), (ops["sort"], 96, 96, None),
+                              (ops["sort"], 16384, 16384, None), (ops["sort"], 128, 192, None), (ops["block_scan"], 3, 192, p),
+                              (ops["block_scan"], 4, 256, None), (ops["block_scan"], 16, 512, p), (ops["scan"], 0, (1 << 24) + 256, None)):
+        assert L.tmc2_selftest_wave(p, op, param, p, p, aux, n) == invalid, (op, param, n)
+    assert L.tmc2_selftest_wave(p, ops["scan"], 0, None, p, None, 256) == invalid and L.tmc2_selftest_wave(p, ops["scan"], 0, p, None, None, 256) == invalid
