@@ -331,6 +331,42 @@ int     tmc2_encoder_generate_attribute_images( tmc2_frame* f );
  * arguments PCCEncoder::generateAttributeVideo passes under the CTC (PCCEncoder.cpp:6679-6697); tgtRgb = uint8[m][3]      */
 int     tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* tgtXyz,
                               uint64_t m, uint8_t* tgtRgb );
+/* The two entries above over the arguments of PCCPointSet3::transferColors, in its order -- the sixteen encoder options that
+ * PCCEncoder::generateAttributeVideo hands over (PCCEncoder.cpp:6679-6697; defaults PCCEncoderParameters.cpp:96-110).
+ * tmc2_color_transfer_params_default fills the CTC point, what the entries above compute: 0, 0, 8, 1, 1, 1, 1, 1, 4, 4, 1000,
+ * 1000, 1000, 1000, 0, 10 -- with it the _ex entries run what the entries above run.
+ * As the reference reads them: a threshold of 512 or more is none; the geometry threshold never drops the first forward result
+ * but may drop every backward candidate (the target then keeps its forward colour); the pairwise colour maximum starts at
+ * DBL_MIN, so a colour threshold of 0 always leaves the nearest colour alone; without the skip flag an identical point is
+ * averaged with weight 1 / distOffset; a single remaining candidate counts unweighted; the outlier pass (weighted means only)
+ * compares the dropped count with the shrunk length in both directions; the best-colour search visits the clipped cube
+ * (2 searchRange + 1)^3 in lexicographic order and keeps the first strict minimum.
+ * tmc2_color_transfer_params_check needs no device: TMC2_OK, TMC2_E_INVALID for NULL, or TMC2_E_UNSUPPORTED with the field named
+ * in tmc2_last_error -- a neighbour count outside 1..32, searchRange outside 0..8, a distOffset that is not > 0, a negative or NaN
+ * threshold or thresholdColorOutlierDist.  The entries refuse these, and a neighbour count above the searched cloud's size
+ * (numNeighborsColorTransferFwd against the source, ..Bwd against the target), before the frame changes: the frame entry holds a
+ * backward count above 1 against the size of the reconstruction it is about to make by counting the tiles first (one launch and a
+ * scan that the CTC point does not pay), so a refused call leaves the previous reconstruction, colours and images in place.  A
+ * source of more than 2^26 - 1 points is refused off the CTC point (backward entries are numbered source * K + rank in 32 bits).
+ * No search asks for more results than its tree holds: a count between two search widths (1, 4, 8, 16, 32) runs the next wider
+ * search and reads its first K; where that width is above the cloud's size the search runs at K itself.                     */
+typedef struct tmc2_color_transfer_params {
+  int32_t searchRange;
+  int32_t losslessAttribute;
+  int32_t numNeighborsColorTransferFwd, numNeighborsColorTransferBwd;
+  int32_t useDistWeightedAverageFwd, useDistWeightedAverageBwd;
+  int32_t skipAvgIfIdenticalSourcePointPresentFwd, skipAvgIfIdenticalSourcePointPresentBwd;
+  double  distOffsetFwd, distOffsetBwd;
+  double  maxGeometryDist2Fwd, maxGeometryDist2Bwd;
+  double  maxColorDist2Fwd, maxColorDist2Bwd;
+  int32_t excludeColorOutlier;
+  double  thresholdColorOutlierDist;
+} tmc2_color_transfer_params;
+void tmc2_color_transfer_params_default( tmc2_color_transfer_params* params );
+int  tmc2_color_transfer_params_check( const tmc2_color_transfer_params* params );
+int  tmc2_transfer_colors_ex( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* tgtXyz,
+                              uint64_t m, const tmc2_color_transfer_params* params, uint8_t* tgtRgb );
+int  tmc2_encoder_generate_attribute_images_ex( tmc2_frame* f, const tmc2_color_transfer_params* params );
 int64_t tmc2_frame_recon_count( tmc2_frame* f );
 /* reconstruction: xyz int16[M][3], rgb uint8[M][3], pointToPixel uint32[M][3] = (x, y, layer); any may be NULL */
 int     tmc2_frame_get_reconstruction( tmc2_frame* f, int16_t* xyz, uint8_t* rgb, uint32_t* pointToPixel );
@@ -607,6 +643,11 @@ int tmc2_host_convert_points_to_voxels( const int16_t* xyz, uint64_t n, int voxD
  * nanoflann's search in its result order, or NULL.  Refusals as tmc2_segmenter_refine.                                    */
 int tmc2_host_refine_segmentation( const int16_t* xyz, uint64_t n, const double* normals, uint32_t* partition, int maxNNCount,
                                    double lambda, int iterationCount, uint32_t* adjacency /* [n][maxNNCount], may be NULL */ );
+/* PCCPointSet3::transferColors restated on the host (csrc/color_transfer_host.cpp; no device): nanoflann's searches over
+ * tmc2_host_kdtree_build's trees, libstdc++'s std::sort of the backward lists replayed, and the per-target rules of
+ * csrc/color_transfer_rules.h -- the text the device kernels run.  Arguments and refusals as tmc2_transfer_colors_ex.        */
+int tmc2_host_transfer_colors( const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* tgtXyz, uint64_t m,
+                               const tmc2_color_transfer_params* params, uint8_t* tgtRgb );
 
 /* ---- the shared device primitives on their own (csrc/selftest.hip; DESIGN.md "primitives under test") ------------------- */
 /* What the stages are built on, reachable without a stage so that it can be compared with a plain loop at shapes no cloud produces.

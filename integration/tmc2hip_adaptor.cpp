@@ -148,9 +148,34 @@ void EncoderDropIn::release() {
     if ( f ) tmc2_frame_destroy( f );
   frames_.clear();
 }
+
+// the sixteen arguments PCCEncoder::generateAttributeVideo hands to PCCPointSet3::transferColors (PCCEncoder.cpp:6679-6697); a set
+// the library does not take comes back as TMC2_E_UNSUPPORTED with the field named, never as the CTC's colours
+static tmc2_color_transfer_params toColorTransferParams( const PCCEncoderParameters& params ) {
+  tmc2_color_transfer_params transfer;
+  transfer.searchRange                             = int32_t( params.bestColorSearchRange_ );
+  transfer.losslessAttribute                       = params.rawPointsPatch_ ? 1 : 0;
+  transfer.numNeighborsColorTransferFwd            = int32_t( params.numNeighborsColorTransferFwd_ );
+  transfer.numNeighborsColorTransferBwd            = int32_t( params.numNeighborsColorTransferBwd_ );
+  transfer.useDistWeightedAverageFwd               = params.useDistWeightedAverageFwd_ ? 1 : 0;
+  transfer.useDistWeightedAverageBwd               = params.useDistWeightedAverageBwd_ ? 1 : 0;
+  transfer.skipAvgIfIdenticalSourcePointPresentFwd = params.skipAvgIfIdenticalSourcePointPresentFwd_ ? 1 : 0;
+  transfer.skipAvgIfIdenticalSourcePointPresentBwd = params.skipAvgIfIdenticalSourcePointPresentBwd_ ? 1 : 0;
+  transfer.distOffsetFwd                           = params.distOffsetFwd_;
+  transfer.distOffsetBwd                           = params.distOffsetBwd_;
+  transfer.maxGeometryDist2Fwd                     = params.maxGeometryDist2Fwd_;
+  transfer.maxGeometryDist2Bwd                     = params.maxGeometryDist2Bwd_;
+  transfer.maxColorDist2Fwd                        = params.maxColorDist2Fwd_;
+  transfer.maxColorDist2Bwd                        = params.maxColorDist2Bwd_;
+  transfer.excludeColorOutlier                     = params.excludeColorOutlier_ ? 1 : 0;
+  transfer.thresholdColorOutlierDist               = params.thresholdColorOutlierDist_;
+  return transfer;
+}
+
 bool EncoderDropIn::accepts( const PCCEncoderParameters& params ) {
-  tmc2_segmenter_params p;
-  return ctx_ != nullptr && toParams( params, p );
+  tmc2_segmenter_params            p;
+  const tmc2_color_transfer_params transfer = toColorTransferParams( params );
+  return ctx_ != nullptr && toParams( params, p ) && tmc2_color_transfer_params_check( &transfer ) == TMC2_OK;
 }
 
 #define TMC2HIP_TRY( call )             \
@@ -270,7 +295,8 @@ int EncoderDropIn::generateGeometryVideo( PCCContext& context, const PCCEncoderP
   return TMC2_OK;
 }
 
-int EncoderDropIn::generateAttributeVideo( PCCContext& context, PCCGroupOfFrames& reconstructs, const PCCEncoderParameters& ) {
+int EncoderDropIn::generateAttributeVideo( PCCContext& context, PCCGroupOfFrames& reconstructs, const PCCEncoderParameters& params ) {
+  const tmc2_color_transfer_params transfer = toColorTransferParams( params );
   auto&        frames = context.getFrames();
   const size_t W = size_t( width_ ), H = size_t( height_ );
   auto&        videoAttribute = context.getVideoAttributesMultiple()[0];
@@ -278,7 +304,7 @@ int EncoderDropIn::generateAttributeVideo( PCCContext& context, PCCGroupOfFrames
   reconstructs.setFrameCount( frames.size() );
   std::vector<uint8_t> attribute( 6 * W * H );
   for ( size_t i = 0; i < frames.size(); ++i ) {
-    TMC2HIP_TRY( tmc2_encoder_generate_attribute_images( frames_[i] ) );
+    TMC2HIP_TRY( tmc2_encoder_generate_attribute_images_ex( frames_[i], &transfer ) );
     const size_t          M = size_t( tmc2_frame_recon_count( frames_[i] ) );
     std::vector<int16_t>  xyz( 3 * M );
     std::vector<uint8_t>  rgb( 3 * M );

@@ -173,6 +173,68 @@ __global__ __launch_bounds__( 256 ) void combineColorKernel( const uint32_t* __r
   reinterpret_cast<uchar4*>( outRgb4 )[t] = combinedColor( reinterpret_cast<const uchar4*>( fwdRgb4 )[t], c );
 }
 
+// ---- S18 off the CTC point: the rules of color_transfer_rules.h over rows of `stride` results of which the first k count -----
+__device__ __forceinline__ CtColor ctColorOf( const uint8_t* __restrict__ rgb4, uint32_t i ) {
+  const uchar4 c = reinterpret_cast<const uchar4*>( rgb4 )[i];
+  return CtColor{c.x, c.y, c.z};
+}
+__device__ __forceinline__ void ctStore( uint8_t* __restrict__ rgb4, uint32_t i, const CtColor& c ) {
+  reinterpret_cast<uchar4*>( rgb4 )[i] = make_uchar4( uint8_t( c.c0 ), uint8_t( c.c1 ), uint8_t( c.c2 ), 0 );
+}
+// easy: nullptr, or launchKnnSplit's first results (only with skipAvgIfIdenticalSourcePointPresentFwd: the rows of those are not filled)
+__global__ __launch_bounds__( 256 ) void forwardColorRulesKernel( const uint32_t* __restrict__ idx, const uint32_t* __restrict__ dist, int stride,
+                                                                   const uint32_t* __restrict__ easy, const uint8_t* __restrict__ srcRgb4,
+                                                                   uint32_t m, CtRules p, uint8_t* __restrict__ fwdRgb4 ) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( t >= m ) return;
+  if ( easy && easy[t] != 0xFFFFFFFFu ) {
+    reinterpret_cast<uchar4*>( fwdRgb4 )[t] = reinterpret_cast<const uchar4*>( srcRgb4 )[easy[t]];
+    return;
+  }
+  const uint32_t* id = idx + size_t( t ) * stride;
+  const uint32_t* ds = dist + size_t( t ) * stride;
+  ctStore( fwdRgb4, t, ctForward( p, p.kFwd, [ds]( int i ) { return ds[i]; }, [id, srcRgb4]( int i ) { return ctColorOf( srcRgb4, id[i] ); } ) );
+}
+
+// source point s votes for each of its kBwd results within the geometry threshold.  FILL = false: count per target; FILL = true
+// (count: a zeroed cursor): place (dist, s * kBwd + rank) -- the number of the entry in the order the reference appends them
+template <bool FILL>
+__global__ __launch_bounds__( 256 ) void backwardVoteRulesKernel( const uint32_t* __restrict__ idx, const uint32_t* __restrict__ dist, int stride,
+                                                                   uint32_t n, int kBwd, double geoBwd, uint32_t* __restrict__ count,
+                                                                   const uint32_t* __restrict__ offset, uint2* __restrict__ entries ) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( s >= n ) return;
+  for ( int r = 0; r < kBwd; ++r ) {
+    const uint32_t d = dist[size_t( s ) * stride + r];
+    if ( !( double( d ) <= geoBwd ) ) continue;
+    const uint32_t t = idx[size_t( s ) * stride + r], slot = atomicAdd( &count[t], 1u );
+    if ( FILL ) entries[offset[t] + slot] = make_uint2( d, s * uint32_t( kBwd ) + uint32_t( r ) );
+  }
+}
+
+// One thread per target: the sort replays std::sort's moves one after the other, the shrink loop ends at the first prefix that
+// fails, and the best-colour search reads six sums of the list, not the list (color_transfer_rules.h) -- nothing here that the
+// lanes of a wavefront could share for one target, long list or not.
+__global__ __launch_bounds__( 256 ) void combineColorRulesKernel( const uint32_t* __restrict__ count, const uint32_t* __restrict__ offset,
+                                                                   uint2* __restrict__ entries, const uint8_t* __restrict__ srcRgb4,
+                                                                   const uint8_t* __restrict__ fwdRgb4, uint32_t m, CtRules p, double rTarget,
+                                                                   double rSource, uint8_t* __restrict__ outRgb4, uint32_t* __restrict__ error ) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( t >= m ) return;
+  const int     n   = int( count[t] );
+  const CtColor fwd = ctColorOf( fwdRgb4, t );
+  if ( n == 0 || p.lossless ) {
+    ctStore( outRgb4, t, fwd );
+    return;
+  }
+  uint2* e = entries + offset[t];
+  if ( !orderCandidates( e, n ) ) *error = 1;
+  const uint32_t kBwd = uint32_t( p.kBwd );
+  ctStore( outRgb4, t,
+           ctBackward( p, n, [e]( int i ) { return e[i].x; }, [e, srcRgb4, kBwd]( int i ) { return ctColorOf( srcRgb4, e[i].y / kBwd ); }, fwd,
+                       rTarget, rSource ) );
+}
+
 // ---- S20 ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__( 256 ) void attributeScatterKernel( const uint8_t* __restrict__ rgb4,
                                                                   const uint32_t* __restrict__ pointToPixel, uint32_t m,
@@ -403,9 +465,64 @@ __global__ __launch_bounds__( 256 ) void attributeGroupDilateKernel( const uint8
 
 }  // namespace
 
-// S18 on device-resident clouds: source (tree + original-order points + colours) -> target (tree + points)
+// S18 off the CTC point (the caller has checked the set against both clouds).  Device memory held: the forward rows
+// M x width( kFwd ) and the backward rows n x width( kBwd ) of (index, distance), the n x kBwd backward entries of 8 bytes, and per
+// target three words and the forward colour.
+static int transferColorsRules( tmc2_ctx* ctx, const TreeDev& srcTree, const Pt* d_srcPts, const uint8_t* d_srcRgb4, uint32_t n,
+                                const TreeDev& tgtTree, const Pt* d_tgtPts, uint32_t M, uint8_t* d_outRgb4, uint32_t* d_error,
+                                const CtRules& p ) {
+  hipStream_t      s = ctx->stream;
+  const dim3       blk( 256 );
+  const int        wf = knnWidth( p.kFwd ), wb = knnWidth( p.kBwd );
+  DevBuf<uint32_t> d_idxF, d_distF, d_easyF, d_idxB, d_distB, d_count, d_offset, d_cursor;
+  DevBuf<uint2>    d_entries;
+  DevBuf<uint8_t>  d_fwd;
+  TMC2_TRY( d_idxF.alloc( size_t( M ) * wf ) );
+  TMC2_TRY( d_distF.alloc( size_t( M ) * wf ) );
+  TMC2_TRY( d_idxB.alloc( size_t( n ) * wb ) );
+  TMC2_TRY( d_distB.alloc( size_t( n ) * wb ) );
+  TMC2_TRY( d_count.alloc( M ) );
+  TMC2_TRY( d_offset.alloc( M ) );
+  TMC2_TRY( d_cursor.alloc( M ) );
+  TMC2_TRY( d_entries.alloc( size_t( n ) * p.kBwd ) );
+  TMC2_TRY( d_fwd.alloc( size_t( M ) * 4 ) );
+  // The split form answers a query that has an identical point with one descent: forward only where that point's colour is all
+  // the rule reads (the skip flag), backward only at one result; otherwise the whole list is needed.
+  if ( p.skipFwd ) {
+    TMC2_TRY( d_easyF.alloc( M ) );
+    TMC2_TRY( launchKnnSplit( ctx, srcTree, d_tgtPts, M, wf, d_easyF.p, d_idxF.p, d_distF.p, "knn_recon_in_source", false, p.kFwd ) );
+  } else {
+    TMC2_TRY( launchKnnTree( ctx, srcTree, d_tgtPts, M, wf, d_idxF.p, d_distF.p, "knn_recon_in_source", p.kFwd ) );
+  }
+  if ( p.kBwd == 1 )
+    TMC2_TRY( launchKnnSplit( ctx, tgtTree, d_srcPts, n, 1, d_idxB.p, d_idxB.p, d_distB.p, "knn_source_in_recon" ) );
+  else
+    TMC2_TRY( launchKnnTree( ctx, tgtTree, d_srcPts, n, wb, d_idxB.p, d_distB.p, "knn_source_in_recon", p.kBwd ) );
+  StageScope stage( ctx, "transfer_colors" );
+  TMC2_TRY( fillRegions( ctx, {{d_count.p, size_t( M ) * 4, 0}, {d_cursor.p, size_t( M ) * 4, 0}, {d_error, 4, 0}} ) );
+  const dim3 grdM( ( M + 255 ) / 256 ), grdN( ( n + 255 ) / 256 );
+  hipLaunchKernelGGL( forwardColorRulesKernel, grdM, blk, 0, s, d_idxF.p, d_distF.p, wf, p.skipFwd ? d_easyF.p : (const uint32_t*)nullptr,
+                      d_srcRgb4, M, p, d_fwd.p );
+  hipLaunchKernelGGL( backwardVoteRulesKernel<false>, grdN, blk, 0, s, d_idxB.p, d_distB.p, wb, n, p.kBwd, p.geoBwd, d_count.p, d_offset.p,
+                      d_entries.p );
+  TMC2_TRY( exclusiveScanU32( ctx, d_count.p, d_offset.p, M, nullptr ) );
+  hipLaunchKernelGGL( backwardVoteRulesKernel<true>, grdN, blk, 0, s, d_idxB.p, d_distB.p, wb, n, p.kBwd, p.geoBwd, d_cursor.p, d_offset.p,
+                      d_entries.p );
+  hipLaunchKernelGGL( combineColorRulesKernel, grdM, blk, 0, s, d_count.p, d_offset.p, d_entries.p, d_srcRgb4, d_fwd.p, M, p,
+                      1.0 / double( M ), 1.0 / double( n ), d_outRgb4, d_error );
+  TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+// S18 on device-resident clouds: source (tree + original-order points + colours) -> target (tree + points).  params: nullptr or a
+// checked set; the CTC point (ctIsDefault) runs the kernels written for it, every other set the rules over its own lists.
 int transferColorsDevice( tmc2_ctx* ctx, const TreeDev& srcTree, const Pt* d_srcPts, const uint8_t* d_srcRgb4, uint32_t n,
-                          const TreeDev& tgtTree, const Pt* d_tgtPts, uint32_t M, uint8_t* d_outRgb4, uint32_t* d_error ) {
+                          const TreeDev& tgtTree, const Pt* d_tgtPts, uint32_t M, uint8_t* d_outRgb4, uint32_t* d_error,
+                          const tmc2_color_transfer_params* params = nullptr ) {
+  // (option COLOR_TRANSFER_RULES=1: the rules kernels at the CTC point too -- what pins the two texts of one rule to each other)
+  const auto forced = ctxOption( ctx, "COLOR_TRANSFER_RULES" );
+  if ( params && ( !ctIsDefault( *params ) || ( forced && ( *forced )[0] == '1' ) ) )
+    return transferColorsRules( ctx, srcTree, d_srcPts, d_srcRgb4, n, tgtTree, d_tgtPts, M, d_outRgb4, d_error, ctRules( *params ) );
   hipStream_t      s = ctx->stream;
   const dim3       blk( 256 );
   DevBuf<uint32_t> d_idx8, d_dist8, d_idx1, d_dist1, d_count, d_offset, d_cursor;
@@ -524,7 +641,27 @@ int reconstructPointCloud( tmc2_frame* f, const PbfParams* pbfParams ) {
   return TMC2_OK;
 }
 
-int generateAttributeImages( tmc2_frame* f ) {
+// the number of points reconstructPointCloud( f ) would give, from the resident canvases, with the frame left as it is
+static int reconstructionSize( tmc2_frame* f, uint32_t* M ) {
+  tmc2_ctx*      ctx   = f->ctx;
+  const uint32_t tiles = f->tileCount;
+  *M                   = 0;
+  if ( !tiles ) return TMC2_OK;
+  DevBuf<uint32_t> d_tileCount, d_tileOffset, d_small;
+  TMC2_TRY( d_tileCount.alloc( tiles ) );
+  TMC2_TRY( d_tileOffset.alloc( tiles ) );
+  TMC2_TRY( d_small.alloc( 8 ) );
+  hipLaunchKernelGGL( reconTileKernel<false>, dim3( tiles ), dim3( 256 ), 0, ctx->stream, f->d_place.p, f->d_tilePatch.p, f->d_occVideo.p,
+                      f->d_blockToPatch.p, f->d_geo.p, f->canvasW, f->canvasH, f->occPrecision, d_tileCount.p, (const uint32_t*)nullptr,
+                      (Pt*)nullptr, (uint32_t*)nullptr, PbfMapsDev() );
+  volatile uint32_t* answer = ctx->answerLine( tmc2_ctx::kAnswerRecon );
+  TMC2_TRY( exclusiveScanU32( ctx, d_tileCount.p, d_tileOffset.p, tiles, d_small.p, ScanAnswer{answer, nullptr, 0} ) );
+  TMC2_HIP( hipStreamSynchronize( ctx->stream ) );
+  *M = answer[0];
+  return TMC2_OK;
+}
+
+int generateAttributeImages( tmc2_frame* f, const tmc2_color_transfer_params* params ) {
   if ( !f->haveGeometryImages ) {
     setError( "generateAttributeImages: geometry images missing" );
     return TMC2_E_STATE;
@@ -532,6 +669,16 @@ int generateAttributeImages( tmc2_frame* f ) {
   if ( f->d_rgb.count == 0 ) {
     setError( "generateAttributeImages: the frame has no colours" );
     return TMC2_E_STATE;
+  }
+  // (refused before the frame's state changes.  A backward neighbour count above 1 is held against the size of the reconstruction
+  //  that does not exist yet: the tiles are counted first, on their own -- one launch and a scan, for such sets only)
+  if ( params ) {
+    TMC2_TRY( checkColorTransferParams( "generateAttributeImages", params, f->n, 0 ) );
+    if ( params->numNeighborsColorTransferBwd > 1 ) {
+      uint32_t size = 0;
+      TMC2_TRY( reconstructionSize( f, &size ) );
+      if ( size ) TMC2_TRY( checkColorTransferParams( "generateAttributeImages", params, f->n, size ) );
+    }
   }
   TMC2_TRY( f->ensureTree() );
   TMC2_TRY( reconstructPointCloud( f ) );
@@ -550,7 +697,7 @@ int generateAttributeImages( tmc2_frame* f ) {
   volatile uint32_t* h_err = ctx->answerLine( tmc2_ctx::kAnswerAttrError );
   // (each tree is queried with the other cloud's points: non-negative and below 2^13, like its own)
   TMC2_TRY( transferColorsDevice( ctx, f->tree.view( QueryBox::Tight ), f->d_pts.p, f->d_rgb.p, n, f->reconTree.view( QueryBox::Tight ),
-                                  f->d_recon.p, M, f->d_reconRgb.p, const_cast<uint32_t*>( h_err ) ) );
+                                  f->d_recon.p, M, f->d_reconRgb.p, const_cast<uint32_t*>( h_err ), params ) );
   // ---- S20 ----------------------------------------------------------------------------------------------
   StageScope      stage( ctx, "attribute_images" );
   DevBuf<uint8_t> d_occ;
@@ -660,14 +807,15 @@ int generateAttributeImages( tmc2_frame* f ) {
 
 extern "C" {
 
-// replaces PCCPointSet3::transferColors on two host clouds (CTC settings); rgb out = uint8[m][3]
-int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* tgtXyz,
-                          uint64_t m, uint8_t* tgtRgb ) {
+// replaces PCCPointSet3::transferColors on two host clouds; rgb out = uint8[m][3]
+int tmc2_transfer_colors_ex( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* tgtXyz, uint64_t m,
+                             const tmc2_color_transfer_params* params, uint8_t* tgtRgb ) {
   using namespace tmc2;
-  if ( !ctx || !srcXyz || !srcRgb || !tgtXyz || !tgtRgb || n < 8 || m < 1 ) {
-    setError( "transfer_colors: invalid argument (the source needs at least 8 points)" );
+  if ( !ctx || !srcXyz || !srcRgb || !tgtXyz || !tgtRgb || n < 1 || m < 1 || n > 0x3FFFFFFull || m > 0x7FFFFFF0ull ) {
+    setError( "transfer_colors: invalid argument" );
     return TMC2_E_INVALID;
   }
+  TMC2_TRY( checkColorTransferParams( "transfer_colors", params, n, m ) );
   ApiScope    scope( ctx );
   hipStream_t s = ctx->stream;
   struct Side {
@@ -693,7 +841,7 @@ int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* s
   TMC2_TRY( d_err.alloc( 1 ) );
   TMC2_HIP( hipMemcpyAsync( d_rgb.p, c4.data(), 4 * n, hipMemcpyHostToDevice, s ) );
   TMC2_TRY( transferColorsDevice( ctx, S.tree.view( QueryBox::Any ), S.pts.p, d_rgb.p, uint32_t( n ), T.tree.view( QueryBox::Any ), T.pts.p,
-                                  uint32_t( m ), d_out.p, d_err.p ) );
+                                  uint32_t( m ), d_out.p, d_err.p, params ) );
   std::vector<uint8_t> o4( 4 * m );
   uint32_t             err = 0;
   TMC2_HIP( hipMemcpyAsync( o4.data(), d_out.p, 4 * m, hipMemcpyDeviceToHost, s ) );
@@ -707,16 +855,39 @@ int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* s
   return TMC2_OK;
 }
 
+// ... at the CTC point
+int tmc2_transfer_colors( tmc2_ctx* ctx, const int16_t* srcXyz, const uint8_t* srcRgb, uint64_t n, const int16_t* tgtXyz,
+                          uint64_t m, uint8_t* tgtRgb ) {
+  if ( !ctx || !srcXyz || !srcRgb || !tgtXyz || !tgtRgb || n < 8 || m < 1 ) {
+    tmc2::setError( "transfer_colors: invalid argument (the source needs at least 8 points)" );
+    return TMC2_E_INVALID;
+  }
+  tmc2_color_transfer_params ctc;
+  tmc2::ctDefault( ctc );
+  return tmc2_transfer_colors_ex( ctx, srcXyz, srcRgb, n, tgtXyz, m, &ctc, tgtRgb );
+}
+
 int tmc2_codec_generate_point_cloud( tmc2_frame* f ) {
   if ( !f ) return TMC2_E_INVALID;
   tmc2::ApiScope scope( f->ctx );
   return tmc2::reconstructPointCloud( f );
 }
 
+int tmc2_encoder_generate_attribute_images_ex( tmc2_frame* f, const tmc2_color_transfer_params* params ) {
+  if ( !f ) return TMC2_E_INVALID;
+  if ( !params ) {
+    tmc2::setError( "generateAttributeImages: the colour-transfer parameters are NULL" );
+    return TMC2_E_INVALID;
+  }
+  tmc2::ApiScope scope( f->ctx );
+  return tmc2::generateAttributeImages( f, params );
+}
+
 int tmc2_encoder_generate_attribute_images( tmc2_frame* f ) {
   if ( !f ) return TMC2_E_INVALID;
-  tmc2::ApiScope scope( f->ctx );
-  return tmc2::generateAttributeImages( f );
+  tmc2_color_transfer_params ctc;
+  tmc2::ctDefault( ctc );
+  return tmc2_encoder_generate_attribute_images_ex( f, &ctc );
 }
 
 int64_t tmc2_frame_recon_count( tmc2_frame* f ) { return ( f && f->haveReconstruction ) ? int64_t( f->reconCount ) : 0; }

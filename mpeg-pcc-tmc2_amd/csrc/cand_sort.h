@@ -1,6 +1,12 @@
-// cand_sort.h -- libstdc++'s std::sort replayed on the device, for the candidate lists of the colour transfers.
+// cand_sort.h -- libstdc++'s std::sort replayed, for the candidate lists of the colour transfers: on the device, and by the host
+// restatement of the transfer (color_transfer_host.cpp) through a plain host compiler.
 #pragma once
+#if defined( __HIPCC__ )
 #include <hip/hip_runtime.h>
+#define TMC2_SORT_FN __host__ __device__
+#else
+#define TMC2_SORT_FN
+#endif
 
 namespace tmc2 {
 
@@ -8,16 +14,18 @@ namespace tmc2 {
 // (median-of-3 quicksort down to 16-element runs, then one insertion sort).  It is not stable, so for equal
 // distances the outcome depends on the algorithm's exact moves -- reproduced here move for move on the list that
 // is first brought into source-index order (the order in which the reference appended the candidates).
-struct CandSort {
-  uint2* a;
-  __device__ bool less( int i, int j ) const { return a[i].x < a[j].x; }
-  __device__ void swap( int i, int j ) const {
-    const uint2 t = a[i];
+// E: an entry with the distance in .x (uint2 on the device; the host restatement of the transfer sorts its own pairs).
+template <typename E>
+struct CandSortOf {
+  E* a;
+  TMC2_SORT_FN bool less( int i, int j ) const { return a[i].x < a[j].x; }
+  TMC2_SORT_FN void swap( int i, int j ) const {
+    const E t = a[i];
     a[i]          = a[j];
     a[j]          = t;
   }
-  __device__ void unguardedLinearInsert( int last ) const {
-    const uint2 val  = a[last];
+  TMC2_SORT_FN void unguardedLinearInsert( int last ) const {
+    const E val  = a[last];
     int         next = last - 1;
     while ( val.x < a[next].x ) {
       a[last] = a[next];
@@ -26,10 +34,10 @@ struct CandSort {
     }
     a[last] = val;
   }
-  __device__ void insertionSort( int first, int last ) const {
+  TMC2_SORT_FN void insertionSort( int first, int last ) const {
     for ( int i = first + 1; i < last; ++i ) {
       if ( a[i].x < a[first].x ) {
-        const uint2 val = a[i];
+        const E val = a[i];
         for ( int k = i; k > first; --k ) a[k] = a[k - 1];
         a[first] = val;
       } else {
@@ -37,7 +45,7 @@ struct CandSort {
       }
     }
   }
-  __device__ void moveMedianToFirst( int result, int x, int y, int z ) const {
+  TMC2_SORT_FN void moveMedianToFirst( int result, int x, int y, int z ) const {
     if ( less( x, y ) ) {
       if ( less( y, z ) )
         swap( result, y );
@@ -52,7 +60,7 @@ struct CandSort {
     else
       swap( result, y );
   }
-  __device__ int unguardedPartition( int first, int last, int pivot ) const {
+  TMC2_SORT_FN int unguardedPartition( int first, int last, int pivot ) const {
     for ( ;; ) {
       while ( less( first, pivot ) ) ++first;
       --last;
@@ -63,7 +71,7 @@ struct CandSort {
     }
   }
   // returns false if the depth limit was reached (libstdc++ would switch to heapsort; not reproduced)
-  __device__ bool sort( int n ) const {
+  TMC2_SORT_FN bool sort( int n ) const {
     if ( n < 2 ) return true;
     int lg = 0;
     while ( ( n >> ( lg + 1 ) ) > 0 ) ++lg;
@@ -105,5 +113,8 @@ struct CandSort {
     return ok;
   }
 };
+#if defined( __HIPCC__ )
+using CandSort = CandSortOf<uint2>;
+#endif
 
 }  // namespace tmc2

@@ -5,12 +5,10 @@
 #include <hip/hip_runtime.h>
 
 #include "cand_sort.h"
+#include "color_transfer_rules.h"  // S18 over the encoder's parameters; what follows is its CTC point and T4's constants
 
 namespace tmc2 {
 
-struct ColorSum {
-  double c0, c1, c2;
-};
 template <typename C4>
 __device__ __forceinline__ C4 roundedColor( const ColorSum& v ) {
   using S = decltype( C4().x );  // uint8_t / uint16_t: the clamp is the type's range

@@ -478,14 +478,19 @@ int launchKnnSelf( tmc2_frame* f, int k );
 int launchKnnQueries( tmc2_frame* f, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx, uint32_t* d_dist,
                       bool queriesBounded );
 int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx,
-                   uint32_t* d_dist, const char* stage );
+                   uint32_t* d_dist, const char* stage, int kNeed = 0 );
+// k = knnWidth( kNeed ), rows of k: a list length between two instantiated widths (knn.hip, dispatch)
+int knnWidth( int k );
 // the same search in two launches: the queries with an identical point in the tree first (d_easy[j]: the first result, or
 // 0xFFFFFFFF), then the compacted rest through the ordinary kernel, rows in place (knn.hip: what a caller may do with d_easy)
 int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_easy, uint32_t* d_idx,
-                    uint32_t* d_dist, const char* stage, bool uniqueTreeRows = false );
+                    uint32_t* d_dist, const char* stage, bool uniqueTreeRows = false, int kNeed = 0 );
+// color_transfer_host.cpp: TMC2_E_INVALID for a NULL set, TMC2_E_UNSUPPORTED (by name) for a value the transfer refuses or a
+// neighbour count above its cloud (n: source, m: target; 0: not known yet)
+int checkColorTransferParams( const char* who, const tmc2_color_transfer_params* q, uint64_t n, uint64_t m );
 // metrics_host.cpp: TMC2_E_INVALID for a NULL parameter set, TMC2_E_UNSUPPORTED (by name) for a value outside PCCMetricsParameters' ranges
 int checkMetricsParams( const char* who, const tmc2_metrics_params* q );
-int generateAttributeImages( tmc2_frame* f );
+int generateAttributeImages( tmc2_frame* f, const tmc2_color_transfer_params* params = nullptr );  // nullptr: the CTC point
 struct PbfParams;  // patch_border_filter.h
 // pbf != nullptr: occupancy synthesis first (patchBorderFilterDevice); occupancy and boundary types then come from its maps
 int reconstructPointCloud( tmc2_frame* f, const PbfParams* pbf = nullptr );

@@ -256,16 +256,82 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
   }
 }
 
-// nqLive / rowMap: see knnKernel
+// A tree of fewer points than the instantiated width that would serve the list (nTree < 32): the same search with a list of
+// RUN-TIME length k <= nTree -- no search asks for more results than the tree holds.  One query per lane, the list and the far-child
+// stack in private memory; the traversal is searchLevel's, far children taken when popped (knnKernel's header).  Rows of `stride`
+// words, the first k written.  Such trees are a handful of leaves: nothing here is tuned.
+__global__ __launch_bounds__( 256 ) void knnSmallTreeKernel( const Pt* __restrict__ ptsTree, const uint32_t* __restrict__ perm,
+                                                             const KdNode* __restrict__ nodes, RootBox root, const Pt* __restrict__ queries,
+                                                             uint32_t nq, int k, int stride, uint32_t* __restrict__ outIdx,
+                                                             uint32_t* __restrict__ outDist, const uint32_t* __restrict__ nqLive,
+                                                             const uint32_t* __restrict__ rowMap ) {
+  if ( nqLive ) nq = min( nq, *nqLive );
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if ( j >= nq ) return;
+  const Pt  qp   = queries[j];
+  const int q[3] = {qp.x, qp.y, qp.z};
+  uint32_t  bd[32], bi[32];
+  int       count = 0;
+  int       o[3];
+  for ( int d = 0; d < 3; ++d ) o[d] = q[d] < root.lo[d] ? root.lo[d] - q[d] : ( q[d] > root.hi[d] ? q[d] - root.hi[d] : 0 );
+  uint4    stack[kMaxStack];
+  int      sp   = 0;
+  uint32_t node = 0;
+  for ( ;; ) {
+    KdNode nd = nodes[node];
+    while ( nd.dim >= 0 ) {
+      const int  v = q[nd.dim], diff1 = v - nd.divlow, diff2 = v - nd.divhigh;
+      const bool leftNear = ( diff1 + diff2 ) < 0;
+      const int  ofar     = leftNear ? abs( diff2 ) : abs( diff1 );
+      int        f[3]     = {o[0], o[1], o[2]};
+      f[nd.dim]           = ofar;
+      if ( sp < kMaxStack ) stack[sp++] = make_uint4( leftNear ? uint32_t( nd.b ) : uint32_t( nd.a ), uint32_t( f[0] ), uint32_t( f[1] ), uint32_t( f[2] ) );
+      node = leftNear ? uint32_t( nd.a ) : uint32_t( nd.b );
+      nd   = nodes[node];
+    }
+    for ( int p = nd.a; p < nd.b; ++p ) {
+      const Pt       c  = ptsTree[p];
+      const int      ex = q[0] - c.x, ey = q[1] - c.y, ez = q[2] - c.z;
+      const uint32_t d  = uint32_t( ex * ex + ey * ey + ez * ez );
+      if ( !( d < ( count == k ? bd[k - 1] : 0xFFFFFFFFu ) ) ) continue;
+      int i = count;  // behind every entry of equal distance; the last of a full list drops out
+      for ( ; i > 0 && bd[i - 1] > d; --i )
+        if ( i < k ) bd[i] = bd[i - 1], bi[i] = bi[i - 1];
+      if ( i < k ) bd[i] = d, bi[i] = uint32_t( p );
+      if ( count < k ) ++count;
+    }
+    bool found = false;
+    while ( sp > 0 && !found ) {
+      const uint4 e = stack[--sp];
+      if ( e.y * e.y + e.z * e.z + e.w * e.w <= ( count == k ? bd[k - 1] : 0xFFFFFFFFu ) ) {
+        node = e.x, o[0] = int( e.y ), o[1] = int( e.z ), o[2] = int( e.w );
+        found = true;
+      }
+    }
+    if ( !found ) break;
+  }
+  const size_t row = ( rowMap ? size_t( rowMap[j] ) : size_t( j ) ) * size_t( stride );
+  for ( int i = 0; i < min( k, count ); ++i ) {  // (the list is full: k <= nTree, the dispatch's guard)
+    outIdx[row + i] = perm[bi[i]];
+    if ( outDist ) outDist[row + i] = bd[i];
+  }
+}
+
+// nqLive / rowMap: see knnKernel.  kNeed (0: k): the caller reads the first kNeed <= k results of every row of k -- an instantiated
+// width stands in for a list length between two of them.  The first kNeed of nanoflann's k-list ARE its kNeed-list: both visit the
+// points in one depth-first order, a wider list only prunes less, and an entry is inserted behind its equals and rejected when it
+// equals the worst of a full list -- so a point the narrow search never visits lies behind the narrow list's last entry in the wide
+// one.  No search asks for more results than the tree holds: where kNeed <= n < k (a tree of fewer than 32 points) the rows come from
+// knnSmallTreeKernel at the list length kNeed itself.
 template <bool SELF>
 int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, uint32_t* idx, uint32_t* dist,
-              const uint32_t* nqLive = nullptr, const uint32_t* rowMap = nullptr ) {
+              const uint32_t* nqLive = nullptr, const uint32_t* rowMap = nullptr, int kNeed = 0 ) {
   if ( t.depth > kMaxStack ) {
     setError( "k-d tree depth %d exceeds the traversal stack (%d)", t.depth, kMaxStack );
     return TMC2_E_UNSUPPORTED;
   }
-  if ( uint64_t( k ) > t.n ) {
-    setError( "k=%d larger than the cloud (%llu points)", k, (unsigned long long)t.n );
+  if ( kNeed < 0 || kNeed > k || uint64_t( kNeed ? kNeed : k ) > t.n ) {
+    setError( "k=%d larger than the cloud (%llu points)", kNeed ? kNeed : k, (unsigned long long)t.n );
     return TMC2_E_INVALID;
   }
   RootBox rb;
@@ -274,6 +340,16 @@ int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, 
     rb.hi[d] = t.hi[d];
   }
   const dim3 block( 256 );
+  if ( uint64_t( k ) > t.n ) {  // (kNeed <= n < k <= 32, queries from the caller)
+    if ( SELF || kNeed > 32 ) {
+      setError( "k=%d larger than the cloud (%llu points)", k, (unsigned long long)t.n );
+      return TMC2_E_INVALID;
+    }
+    hipLaunchKernelGGL( knnSmallTreeKernel, dim3( uint32_t( ( nq + 255 ) / 256 ) ), block, 0, s, t.ptsTree, t.perm, t.nodes, rb, q, uint32_t( nq ),
+                        kNeed, k, idx, dist, nqLive, rowMap );
+    TMC2_HIP( hipGetLastError() );
+    return TMC2_OK;
+  }
   const dim3 grid( chunkedGrid( uint32_t( ( nq + 255 ) / 256 ) ) );  // (knnKernel's XCD mapping)
   // the packed LDS stack needs: every offset < 2^14 (tree box and queries inside a 16383-wide window -- the caller
   // vouches for the queries with t.queriesBounded), node ids < 2^22, and at most kLdsLevels pending far children
@@ -323,10 +399,13 @@ int launchKnnQueries( tmc2_frame* f, const Pt* d_queries, uint64_t nq, int k, ui
 }
 
 int launchKnnTree( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_idx,
-                   uint32_t* d_dist, const char* stage ) {
+                   uint32_t* d_dist, const char* stage, int kNeed ) {
   StageScope span( ctx, stage );
-  return dispatch<false>( ctx->stream, tree, d_queries, nq, k, d_idx, d_dist );
+  return dispatch<false>( ctx->stream, tree, d_queries, nq, k, d_idx, d_dist, nullptr, nullptr, kNeed );
 }
+
+// the instantiated width that serves a list of k <= 32 results
+int knnWidth( int k ) { return k <= 1 ? 1 : ( k <= 4 ? 4 : ( k <= 8 ? 8 : ( k <= 16 ? 16 : 32 ) ) ); }
 
 namespace {
 // Pass 1 of launchKnnSplit.  The reference's search descends to the leaf on the query's side of every split FIRST and scans it
@@ -392,7 +471,7 @@ __global__ __launch_bounds__( 256 ) void gatherHardKernel( const uint32_t* __res
 // from the first (PCCMetrics' "all points at the minimum distance", PCCMetrics.cpp:91-96): the rows of easy queries are written
 // as [ match | 0, not 0 ].
 int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uint64_t nq, int k, uint32_t* d_easy, uint32_t* d_idx,
-                    uint32_t* d_dist, const char* stage, bool uniqueTreeRows ) {
+                    uint32_t* d_dist, const char* stage, bool uniqueTreeRows, int kNeed ) {
   hipStream_t s = ctx->stream;
   if ( nq == 0 ) return TMC2_OK;
   StageScope       span( ctx, stage );
@@ -419,7 +498,7 @@ int launchKnnSplit( tmc2_ctx* ctx, const TreeDev& tree, const Pt* d_queries, uin
     if ( r == TMC2_OK ) {
       hipLaunchKernelGGL( gatherHardKernel, grd, blk, 0, s, d_easy, d_rank.p, d_queries, uint32_t( nq ), d_hard.p, d_rowMap.p );
       // pass 2: the grid is sized for the worst case, the live count is on the device (no round trip)
-      r = dispatch<false>( s, tree, d_hard.p, nq, k, d_idx, d_dist, d_count.p, d_rowMap.p );
+      r = dispatch<false>( s, tree, d_hard.p, nq, k, d_idx, d_dist, d_count.p, d_rowMap.p, kNeed );
     }
   }
   return r;

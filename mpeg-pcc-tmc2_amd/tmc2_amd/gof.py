@@ -408,9 +408,10 @@ class GofEncoder:
         self._per_worker(frames, lambda fr: fr.encoder_generate_geometry_images(W, H, self.occ_precision))
         return W, H
 
-    def phase_b(self, frames):
-        """S17-S22 on the resident (decoded == generated) occupancy / geometry canvases."""
-        self._per_worker(frames, lambda fr: fr.encoder_generate_attribute_images())
+    def phase_b(self, frames, color_transfer=None):
+        """S17-S22 on the resident (decoded == generated) occupancy / geometry canvases.  color_transfer: None (the CTC point) or a
+        ColorTransferParams for the transfer of S18."""
+        self._per_worker(frames, lambda fr: fr.encoder_generate_attribute_images(color_transfer))
 
     def phase_c(self, frames, decoded_attribute=None, grid_size=8, threshold=64.0, i420_out=None, color_smoothing=None, pbf=None):
         """What follows the attribute images, per frame: the colour-space conversion to the I420 frames the video encoder

@@ -71,6 +71,60 @@ class MetricsParams:
                                     int(self.drop_duplicates), int(self.neighbors_proc))
 
 
+class _ColorTransferParamsStruct(C.Structure):
+    """Mirror of tmc2_color_transfer_params."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "searchRange", "losslessAttribute", "numNeighborsColorTransferFwd", "numNeighborsColorTransferBwd", "useDistWeightedAverageFwd",
+        "useDistWeightedAverageBwd", "skipAvgIfIdenticalSourcePointPresentFwd", "skipAvgIfIdenticalSourcePointPresentBwd")] + [
+        (n, C.c_double) for n in ("distOffsetFwd", "distOffsetBwd", "maxGeometryDist2Fwd", "maxGeometryDist2Bwd", "maxColorDist2Fwd",
+                                  "maxColorDist2Bwd")] + [("excludeColorOutlier", C.c_int32), ("thresholdColorOutlierDist", C.c_double)]
+
+
+@dataclasses.dataclass(frozen=True)
+class ColorTransferParams:
+    """The arguments of PCCPointSet3::transferColors in its order (tmc2_color_transfer_params).  The defaults are the CTC point, what
+    the entries without a parameter set compute; PCCEncoderParameters' own defaults differ (1 forward neighbour, no skip flags, offsets
+    0.0001, thresholds 10000)."""
+    search_range: int = 0
+    lossless_attribute: bool = False
+    num_neighbors_fwd: int = 8
+    num_neighbors_bwd: int = 1
+    use_dist_weighted_average_fwd: bool = True
+    use_dist_weighted_average_bwd: bool = True
+    skip_avg_if_identical_source_point_present_fwd: bool = True
+    skip_avg_if_identical_source_point_present_bwd: bool = True
+    dist_offset_fwd: float = 4.0
+    dist_offset_bwd: float = 4.0
+    max_geometry_dist2_fwd: float = 1000.0
+    max_geometry_dist2_bwd: float = 1000.0
+    max_color_dist2_fwd: float = 1000.0
+    max_color_dist2_bwd: float = 1000.0
+    exclude_color_outlier: bool = False
+    threshold_color_outlier_dist: float = 10.0
+
+    def struct(self):
+        v = dataclasses.astuple(self)
+        return _ColorTransferParamsStruct(*([int(x) for x in v[:8]] + [float(x) for x in v[8:14]] + [int(v[14]), float(v[15])]))
+
+
+def color_transfer_params_check(params):
+    """tmc2_color_transfer_params_check: raises Tmc2Error naming the field the transfer refuses (no device needed)."""
+    _check(load_library().tmc2_color_transfer_params_check(C.byref(params.struct())))
+
+
+def host_transfer_colors(src_xyz, src_rgb, tgt_xyz, params=None):
+    """tmc2_host_transfer_colors: PCCPointSet3::transferColors restated on the host (no device) -> the target's colours [m][3]."""
+    a = np.ascontiguousarray(src_xyz, np.int16).reshape(-1, 3)
+    b = np.ascontiguousarray(src_rgb, np.uint8).reshape(-1, 3)
+    c = np.ascontiguousarray(tgt_xyz, np.int16).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise Tmc2Error("host_transfer_colors: %d source points, %d source colours" % (len(a), len(b)))
+    out = np.zeros((len(c), 3), np.uint8)
+    st = (params or ColorTransferParams()).struct()
+    _check(load_library().tmc2_host_transfer_colors(_ptr(a), _ptr(b), len(a), _ptr(c), len(c), C.byref(st), _ptr(out)))
+    return out
+
+
 def ctc_params(iterations=10, bits3d=11, weight=(1.0, 1.0, 1.0), vox_dim=4):
     """CTC lossy settings (cfg/common/ctc-common.cfg + sequence cfg).  Per sequence: iterations 50
     (longdress), 20 (basketball_player), 10 (the others); vox_dim = voxelDimensionRefineSegmentation: 4, but 2 for loot,
@@ -355,14 +409,18 @@ class Context:
         return Frame(self, xyz, rgb)
 
     # PCCPointSet3::transferColors
-    def transfer_colors(self, src_xyz, src_rgb, tgt_xyz):
+    def transfer_colors(self, src_xyz, src_rgb, tgt_xyz, params=None):
+        """params = ColorTransferParams: tmc2_transfer_colors_ex; None: the CTC point (tmc2_transfer_colors)."""
         a = np.ascontiguousarray(src_xyz, np.int16)
         b = np.ascontiguousarray(src_rgb, np.uint8)
         c = np.ascontiguousarray(tgt_xyz, np.int16)
         if a.shape != b.shape:                                    # (the C entry takes ONE count for both: a short colour array is read past its end)
             raise Tmc2Error("transfer_colors: %d source points, %d source colours" % (len(a), len(b)))
         out = np.zeros((len(c), 3), np.uint8)
-        _check(self.L.tmc2_transfer_colors(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), len(c), _ptr(out)))
+        if params is None:
+            _check(self.L.tmc2_transfer_colors(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), len(c), _ptr(out)))
+        else:
+            _check(self.L.tmc2_transfer_colors_ex(self.h, _ptr(a), _ptr(b), len(a), _ptr(c), len(c), C.byref(params.struct()), _ptr(out)))
         return out
 
     # PCCPatchSegmenter3::convertPointsToVoxels
@@ -677,9 +735,15 @@ class Frame:
 
 
     # PCCEncoder image generation, phase B
-    def encoder_generate_attribute_images(self):
+    def encoder_generate_attribute_images(self, color_transfer=None):
+        """color_transfer = ColorTransferParams: the transfer under that set (tmc2_encoder_generate_attribute_images_ex); None: the CTC point."""
+        if color_transfer is None:
+            self._pbf = False
+            _check(self.L.tmc2_encoder_generate_attribute_images(self.h))
+            return
+        color_transfer_params_check(color_transfer)                # (a refused set leaves the frame, and what is known of it here, as it was)
         self._pbf = False
-        _check(self.L.tmc2_encoder_generate_attribute_images(self.h))
+        _check(self.L.tmc2_encoder_generate_attribute_images_ex(self.h, C.byref(color_transfer.struct())))
 
     def recon_count(self):
         """Points of the reconstructed cloud (0 before the reconstruction)."""
@@ -1242,6 +1306,10 @@ int tmc2_encoder_generate_geometry_images(tmc2_frame*, int, int, int)
 int tmc2_frame_get_geometry_images(tmc2_frame*, uint8_t*, uint8_t*, uint32_t*, uint16_t*, uint16_t*)
 int tmc2_encoder_generate_attribute_images(tmc2_frame*)
 int tmc2_transfer_colors(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, const int16_t*, uint64_t, uint8_t*)
+void tmc2_color_transfer_params_default(tmc2_color_transfer_params*)
+int tmc2_color_transfer_params_check(const tmc2_color_transfer_params*)
+int tmc2_transfer_colors_ex(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, const int16_t*, uint64_t, const tmc2_color_transfer_params*, uint8_t*)
+int tmc2_encoder_generate_attribute_images_ex(tmc2_frame*, const tmc2_color_transfer_params*)
 int64_t tmc2_frame_recon_count(tmc2_frame*)
 int tmc2_frame_get_reconstruction(tmc2_frame*, int16_t*, uint8_t*, uint32_t*)
 int tmc2_frame_get_attribute_images(tmc2_frame*, uint8_t*)
@@ -1294,6 +1362,7 @@ int tmc2_host_metrics_compute(const int16_t*, const uint8_t*, uint64_t, const in
 int tmc2_host_patch_border_filtering(const tmc2_patch*, int, int, int, int, const uint8_t*, const uint16_t*, const uint32_t*, int, int, int, int, uint8_t*, uint8_t*)
 int tmc2_host_convert_points_to_voxels(const int16_t*, uint64_t, int, int, int16_t*, uint64_t*, uint32_t*)
 int tmc2_host_refine_segmentation(const int16_t*, uint64_t, const double*, uint32_t*, int, double, int, uint32_t*)
+int tmc2_host_transfer_colors(const int16_t*, const uint8_t*, uint64_t, const int16_t*, uint64_t, const tmc2_color_transfer_params*, uint8_t*)
 int tmc2_selftest_scan(tmc2_ctx*, const uint32_t*, uint32_t*, uint64_t, uint32_t*, uint32_t*, const uint32_t*, int, uint64_t)
 int tmc2_selftest_fill(tmc2_ctx*, const uint64_t*, int)
 int tmc2_selftest_work_map(tmc2_ctx*, uint64_t, int, uint64_t, uint64_t, uint32_t*, uint32_t*)
