@@ -6,7 +6,8 @@
  * the frames meet once per pass, for the common canvas size (resizeGeometryVideo, :5546-5591).  The frames live on contexts the
  * caller made (one per slot, any device each: frame f of a sharded GOF on device f mod D); nothing here touches a GPU except
  * through include/tmc2hip.h.  bench.py times the path through this entry (--host native); integration/tmc2_encode_gof.cpp is
- * the same schedule as a program.  Built as mpeg-pcc-tmc2_amd/libtmc2gof.so (mpeg-pcc-tmc2_amd/host/Makefile).            */
+ * a client of it: a program around tmc2_gof_encode / tmc2_gof_encode_resume.  Built as mpeg-pcc-tmc2_amd/libtmc2gof.so
+ * (mpeg-pcc-tmc2_amd/host/Makefile).                                                                                     */
 #ifndef TMC2GOF_H
 #define TMC2GOF_H
 #include "tmc2hip.h"
@@ -37,7 +38,8 @@ typedef struct tmc2_gof_config {
  * the buffers then -- EXCEPT with config->guessCanvas: there a frame whose own guess fitted has copied its canvases, laid out for
  * the guessed size, before the GOF's size was known; after TMC2_E_INVALID the buffers' contents are undefined.
  * Returns TMC2_OK or the first failing status; tmc2_gof_last_error() holds the message of the calling thread's last call (of
- * whichever of its slot threads failed first).  No exception leaves the call (TMC2_E_STATE + message instead).
+ * whichever of its slot threads failed first).  No exception leaves the call (TMC2_E_STATE + message instead; one that a slot
+ * thread met fails the pass as "slot thread: <what()>", and no later step of the pass starts).
  * The slot threads are the library's (parked between passes, leased per pass: two passes of two caller threads never share one). */
 int tmc2_gof_encode( tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots, const tmc2_gof_config* config,
                      uint8_t** occupancy, uint8_t** occVideo, uint32_t** blockToPatch, uint16_t** geometryD0, uint16_t** geometryD1,
@@ -53,6 +55,10 @@ int tmc2_gof_encode_resume( tmc2_frame** frames, const int32_t* slotOf, int32_t 
                             uint16_t** geometryD1, uint8_t** attribute, int32_t capacityWidth, int32_t capacityHeight, int32_t* width,
                             int32_t* height );
 const char* tmc2_gof_last_error( void );
+/* The core a pass pins the thread of slot `slot` to (one core per slot, round-robin over the last-level caches of the process'
+ * affinity mask, SMT siblings dropped), or -1: the topology cannot be read and the slot threads stay unpinned.  For a caller that
+ * creates the context of a slot: created by a thread pinned to this core, its page-locked staging lands on the core's NUMA node. */
+int tmc2_gof_slot_core( int slot );
 
 /* ---- a GOF sharded over several processes, one per GPU (BASELINE configs 3-4: frame f of the GOF on rank f mod worldSize) -------
  * The reference runs the frames of a GOF through one tbb::parallel_for in one address space (PCCEncoder.cpp:4729-4750) and takes

@@ -1,5 +1,7 @@
 // integration/tmc2_encode_gof.cpp -- a native host front end over the C-ABI of libtmc2hip.so (no reference code, no Python):
-// the image-generation half of PccAppEncoder for one GOF, with an identity video codec.
+// the image-generation half of PccAppEncoder for one GOF, with an identity video codec.  The pass S0-S22 over the GOF is the
+// library's (libtmc2gof.so, include/tmc2gof.h: tmc2_gof_encode); this program is what stands around it -- ingest, contexts, buffers,
+// the tail, the files.
 //
 //   tmc2_encode_gof --in frame_%04d.ply --start 1051 --frames 32 --out /tmp/gof [--condition ai|ld|ra] [--devices 0-7]
 //                   [--workers 16] [--iterations 10] [--voxel 4] [--bits 10] [--precision 4] [--min-width 1280]
@@ -32,12 +34,10 @@
 #include <thread>
 #include <vector>
 
-#include <fstream>
-#include <map>
 #include <pthread.h>
 #include <sched.h>
 
-#include "tmc2hip.h"
+#include "tmc2gof.h"
 
 namespace {
 struct Options {
@@ -114,61 +114,12 @@ bool parse( int argc, char** argv, Options& o ) {
   return !o.in.empty() && o.frames > 0 && ( o.condition == "ai" || o.condition == "ld" || o.condition == "ra" );
 }
 
-// the CTC lossy settings (cfg/common/ctc-common.cfg + sequence cfg), as tmc2_amd.ctc_params
-tmc2_segmenter_params ctcParams( int iterations, int voxel, int bits3D, const double w[3] ) {
-  tmc2_segmenter_params p{};
-  p.nnNormalEstimation = 16, p.normalOrientation = 1, p.gridBasedRefineSegmentation = 1, p.maxNNCountRefineSegmentation = 1024;
-  p.iterationCountRefineSegmentation = iterations, p.voxelDimensionRefineSegmentation = voxel, p.searchRadiusRefineSegmentation = 192;
-  p.occupancyResolution = 16, p.enablePatchSplitting = 1, p.maxPatchSize = 1024, p.quantizerSizeX = 16, p.quantizerSizeY = 16;
-  p.minPointCountPerCCPatchSegmentation = 16, p.maxNNCountPatchSegmentation = 16, p.surfaceThickness = 4, p.mapCountMinus1 = 1;
-  p.minLevel = 64, p.maxAllowedDepth = 255, p.geometryBitDepth2D = 8, p.geometryBitDepth3D = bits3D;
-  p.maxAllowedDist2RawPointsDetection = 9, p.maxAllowedDist2RawPointsSelection = 1, p.lambdaRefineSegmentation = 3;
-  for ( int c = 0; c < 3; ++c ) p.weightNormal[c] = w[c];
-  return p;
-}
-
 struct Frame {
   std::vector<int16_t> xyz;
   std::vector<uint8_t> rgb;
   uint64_t             n = 0;
   tmc2_frame*          f = nullptr;
-  int32_t              height = 0;
 };
-
-// One core per slot, spread over the last-level caches (one entry per CCD on EPYC; SMT siblings dropped): the host-resident steps
-// of a frame (the orientation walk, the packers) are cache- and latency-bound, so sixteen of them should not share two L3s.
-// (What tmc2_amd/gof.py does for bench.py's workers.)  Empty when the topology cannot be read: the threads stay unpinned.
-std::vector<int> coresByCacheDomain() {
-  cpu_set_t allowed;
-  CPU_ZERO( &allowed );
-  if ( sched_getaffinity( 0, sizeof( allowed ), &allowed ) != 0 ) return {};
-  std::map<std::string, std::vector<int>> domains;
-  auto firstOf = []( const std::string& list ) { return std::atoi( list.c_str() ); };  // "0,128" / "0-7,128-135" -> 0
-  for ( int cpu = 0; cpu < CPU_SETSIZE; ++cpu ) {
-    if ( !CPU_ISSET( cpu, &allowed ) ) continue;
-    const std::string base = "/sys/devices/system/cpu/cpu" + std::to_string( cpu ) + "/";
-    std::ifstream     sib( base + "topology/thread_siblings_list" ), l3( base + "cache/index3/shared_cpu_list" );
-    std::string       s, d;
-    if ( !std::getline( sib, s ) || !std::getline( l3, d ) ) return {};
-    if ( firstOf( s ) != cpu ) continue;  // the second hardware thread of a core already listed
-    domains[d].push_back( cpu );
-  }
-  std::vector<int> order;  // round-robin over the domains
-  for ( size_t k = 0;; ++k ) {
-    bool any = false;
-    for ( auto& kv : domains )
-      if ( k < kv.second.size() ) order.push_back( kv.second[k] ), any = true;
-    if ( !any ) break;
-  }
-  return order;
-}
-void pinThisThread( const std::vector<int>& cores, int slot ) {
-  if ( cores.empty() ) return;
-  cpu_set_t one;
-  CPU_ZERO( &one );
-  CPU_SET( cores[size_t( slot ) % cores.size()], &one );
-  (void)pthread_setaffinity_np( pthread_self(), sizeof( one ), &one );
-}
 
 // run fn( frameIndex ) for every frame on `workers` threads; worker w owns context w
 template <typename Fn>
@@ -217,12 +168,17 @@ int main( int argc, char** argv ) {
   const int slots   = D * workers;
   auto      slotOf  = [&]( int i ) { return ( i % D ) * workers + ( i / D ) % workers; };
   std::vector<tmc2_ctx*> ctx( size_t( slots ), nullptr );
-  {  // a slot's context is created by a thread pinned to the slot's core: its page-locked staging lands on that core's NUMA node
-    const std::vector<int>   cores = coresByCacheDomain();
+  {  // a slot's context is created by a thread pinned to the core the pass will run the slot on: its page-locked staging lands on
+     // that core's NUMA node
     std::vector<std::thread> makers;
     for ( int s = 0; s < slots; ++s )
       makers.emplace_back( [&, s] {
-        pinThisThread( cores, s );
+        cpu_set_t one;
+        CPU_ZERO( &one );
+        if ( const int core = tmc2_gof_slot_core( s ); core >= 0 ) {
+          CPU_SET( core, &one );
+          (void)pthread_setaffinity_np( pthread_self(), sizeof( one ), &one );
+        }
         CHECK( tmc2_ctx_create( o.devices[size_t( s / workers )], &ctx[size_t( s )] ) );
       } );
     for ( auto& t : makers ) t.join();
@@ -265,76 +221,54 @@ int main( int argc, char** argv ) {
     CHECK( tmc2_frame_create( ctx[size_t( slotOf( i ) )], gof[size_t( i )].xyz.data(), gof[size_t( i )].rgb.data(), gof[size_t( i )].n,
                               &gof[size_t( i )].f ) );
 
-  std::vector<std::thread> pool;
-  const std::vector<int>   cores = coresByCacheDomain();
-  auto perFrame = [&]( auto fn ) {  // frames of one slot in order, slots in parallel
-    pool.clear();
-    for ( int sl = 0; sl < slots; ++sl )
-      pool.emplace_back( [&, sl] {
-        pinThisThread( cores, sl );
-        for ( int i = 0; i < o.frames; ++i )
-          if ( slotOf( i ) == sl ) fn( gof[size_t( i )], i );
-      } );
-    for ( auto& t : pool ) t.join();
-  };
-  const bool   chained = o.condition != "ai";
-  const size_t p       = size_t( o.precision );
-  int32_t      W = 0, H = 0;
-  std::vector<Pinned<uint8_t>>  occVideo( size_t( o.frames ) ), attribute( size_t( o.frames ) ), i420( size_t( o.frames ) );
-  std::vector<Pinned<uint16_t>> geometry( size_t( o.frames ) );
-
-  // One pass of the path S0-S22 over the GOF: everything from the k-d trees to the finished canvases in host memory.
-  auto encodeGof = [&]() {
-    for ( auto& fr : gof ) CHECK( tmc2_frame_reset( fr.f ) );
-    // S0 once per GOF on frame 0 (what a sharded run broadcasts: three doubles), then S1-S9 per frame
-    double w[3];
-    CHECK( tmc2_weight_normal( gof[0].f, o.bits + 1, 0.6, w ) );
-    const tmc2_segmenter_params params = ctcParams( o.iterations, o.voxel, o.bits + 1, w );
-    perFrame( [&]( Frame& fr, int ) {
-      CHECK( tmc2_segmenter_compute( fr.f, &params ) );
-      if ( !chained ) CHECK( tmc2_encoder_pack_flexible( fr.f, o.minW, 2, 1.0, &fr.height ) );
-    } );
-    int32_t tileW = o.minW, gofH = 0;
-    if ( chained ) {  // a sequential chain over the GOF: microseconds per frame on the host, whatever device a frame lives on
-      CHECK( tmc2_encoder_pack_flexible( gof[0].f, o.minW, 2, 1.0, &gof[0].height ) );
-      for ( int i = 1; i < o.frames; ++i )
-        CHECK( tmc2_encoder_pack_spatial_consistency( gof[size_t( i )].f, gof[size_t( i - 1 )].f, o.minW, 2, 1.0, &gof[size_t( i )].height ) );
-      if ( o.condition == "ra" ) {
-        std::vector<tmc2_frame*> fs;
-        for ( auto& fr : gof ) fs.push_back( fr.f );
-        std::vector<int32_t> widths( size_t( o.frames ) ), heights( size_t( o.frames ) );
-        CHECK( tmc2_encoder_global_patch_allocation( fs.data(), o.frames, o.minW, o.minH, widths.data(), heights.data() ) );
-        for ( int i = 0; i < o.frames; ++i ) gof[size_t( i )].height = heights[size_t( i )];
-      }
-      for ( auto& fr : gof ) {
-        int32_t pw = 0;
-        CHECK( tmc2_frame_get_packed_size( fr.f, &pw, nullptr ) );
-        tileW = std::max( tileW, pw );
-      }
+  // One pass of the path S0-S22 over the GOF -- everything from the k-d trees to the finished canvases in page-locked host memory,
+  // which every frame's GPU writes as soon as they exist -- is tmc2_gof_encode.  The buffers start at the minimum canvas; a GOF
+  // that outgrows it is refused with the size it needs and resumes, with buffers of exactly that size, where it was refused.
+  // (a real encoder codes occupancy + geometry between the geometry and the attribute images and hands the decoded frames back:
+  //  tmc2_frame_set_decoded_geometry)
+  const size_t          n = size_t( o.frames ), p = size_t( o.precision );
+  const tmc2_gof_config config{o.iterations, o.voxel, o.bits + 1, o.precision, o.minW, o.minH, o.condition == "ai" ? 0 : o.condition == "ld" ? 1 : 2, 0};
+  std::vector<tmc2_frame*> frames( n );
+  std::vector<int32_t>     slot( n );
+  for ( size_t i = 0; i < n; ++i ) frames[i] = gof[i].f, slot[i] = slotOf( int( i ) );
+  int32_t W = 0, H = 0, capacityW = 0, capacityH = 0;
+  std::vector<Pinned<uint8_t>>  occVideo( n ), attribute( n ), i420( n );
+  std::vector<Pinned<uint16_t>> geometry( n );  // (D0 then D1: one buffer per frame)
+  std::vector<uint8_t*>         occVideoAt( n ), attributeAt( n );
+  std::vector<uint16_t*>        d0At( n ), d1At( n );
+  auto hold = [&]( int32_t w, int32_t h ) {
+    const size_t area = size_t( w ) * size_t( h );
+    capacityW = w, capacityH = h;
+    for ( size_t i = 0; i < n; ++i ) {
+      occVideo[i].resize( area / ( p * p ) ), geometry[i].resize( 2 * area ), attribute[i].resize( 6 * area );
+      occVideoAt[i] = occVideo[i].p, d0At[i] = geometry[i].p, d1At[i] = geometry[i].p + area, attributeAt[i] = attribute[i].p;
     }
-    for ( auto& fr : gof ) gofH = std::max( gofH, fr.height );  // (the all-reduce(max) of a run with one process per GPU)
-    CHECK( tmc2_encoder_canvas_size( &gofH, 1, tileW, o.minW, o.minH, &W, &H ) );
-    const size_t area = size_t( W ) * H;
-    perFrame( [&]( Frame& fr, int i ) {
-      CHECK( tmc2_encoder_generate_geometry_images( fr.f, W, H, o.precision ) );
-      occVideo[size_t( i )].resize( area / ( p * p ) );
-      geometry[size_t( i )].resize( 2 * area );
-      attribute[size_t( i )].resize( 6 * area );
-      // (a real encoder codes occupancy + geometry here and hands the decoded frames back: tmc2_frame_set_decoded_geometry)
-      CHECK( tmc2_encoder_generate_attribute_images( fr.f ) );
-      // the finished canvases of THIS frame leave its GPU as soon as they exist: DMA into page-locked host memory
-      CHECK( tmc2_frame_get_geometry_images( fr.f, nullptr, occVideo[size_t( i )].p, nullptr, geometry[size_t( i )].p,
-                                             geometry[size_t( i )].p + area ) );
-      CHECK( tmc2_frame_get_attribute_images( fr.f, attribute[size_t( i )].p ) );
-    } );
+  };
+  hold( o.minW, o.minH );
+  auto gofPass = [&] {
+    auto pass = [&]( auto entry ) {
+      return entry( frames.data(), slot.data(), o.frames, slots, &config, nullptr, occVideoAt.data(), nullptr, d0At.data(), d1At.data(),
+                    attributeAt.data(), capacityW, capacityH, &W, &H );
+    };
+    int rc = pass( tmc2_gof_encode );
+    if ( rc == TMC2_E_INVALID && ( W > capacityW || H > capacityH ) ) {
+      hold( W, H );
+      rc = pass( tmc2_gof_encode_resume );
+    }
+    // (no canvas is below the minimum, so a pass that fitted its buffers filled them: the files below are written by that)
+    if ( rc != TMC2_OK || W != capacityW || H != capacityH ) {
+      std::fprintf( stderr, "tmc2_encode_gof: tmc2_gof_encode: status %d, a %d x %d canvas in buffers for %d x %d: %s\n", rc, W, H, capacityW, capacityH,
+                    tmc2_gof_last_error() );
+      std::exit( 2 );
+    }
   };
 
-  encodeGof();
+  gofPass();
   std::printf( "GOF canvas %d x %d, %d frames on %d device shard(s) x %d worker(s), condition %s\n", W, H, o.frames, D, workers,
                o.condition.c_str() );
   if ( o.repeat > 1 ) {  // throughput of the path from this (native) host: repeat the pass over the resident input
     const auto t0 = std::chrono::steady_clock::now();
-    for ( int r = 1; r < o.repeat; ++r ) encodeGof();
+    for ( int r = 1; r < o.repeat; ++r ) gofPass();
     const double dt = std::chrono::duration<double>( std::chrono::steady_clock::now() - t0 ).count();
     std::printf( "{\"driver\": \"tmc2_encode_gof\", \"frames_per_s\": %.2f, \"ms_per_gof\": %.2f, \"frames\": %d, \"passes\": %d, "
                  "\"device_shards\": %d, \"workers_per_shard\": %d, \"condition\": \"%s\", \"canvas\": [%d, %d]}\n",
@@ -345,8 +279,8 @@ int main( int argc, char** argv ) {
   const size_t area = size_t( W ) * H, frame420 = area * 3 / 2;
   std::vector<std::string> checksums( size_t( o.frames ) );
   std::vector<uint8_t>     digests( size_t( o.frames ) * 16 );
-  if ( o.tail )
-    perFrame( [&]( Frame& fr, int i ) {
+  if ( o.tail ) {  // per frame, the frames of one slot in order (they share a context), slots side by side
+    auto tail = [&]( Frame& fr, int i ) {
       i420[size_t( i )].resize( 2 * frame420 );
       CHECK( tmc2_encoder_attribute_to_yuv420( fr.f, 4, i420[size_t( i )].p ) );
       // (attribute video codec here) -- identity: the frames come straight back
@@ -370,7 +304,15 @@ int main( int argc, char** argv ) {
       char hex[33];
       for ( int k = 0; k < 16; ++k ) std::snprintf( hex + 2 * k, 3, "%02x", digest[k] );
       checksums[size_t( i )] = hex;
-    } );
+    };
+    std::vector<std::thread> pool;
+    for ( int sl = 0; sl < slots; ++sl )
+      pool.emplace_back( [&, sl] {
+        for ( int i = 0; i < o.frames; ++i )
+          if ( slotOf( i ) == sl ) tail( gof[size_t( i )], i );
+      } );
+    for ( auto& t : pool ) t.join();
+  }
 
   auto writeAll = [&]( const std::string& name, auto&& writer ) {
     FILE* fp = std::fopen( name.c_str(), "wb" );

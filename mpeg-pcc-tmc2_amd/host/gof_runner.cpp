@@ -2,10 +2,15 @@
 // (include/tmc2gof.h).  No device code and no HIP call here: threads, the call sequence of INTEGRATION.md section 4, one rendezvous.
 #include <algorithm>
 #include <atomic>
+#include <chrono>
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -19,13 +24,6 @@
 #include <sched.h>
 #include <sys/stat.h>
 #include <unistd.h>
-
-#include <condition_variable>
-#include <deque>
-#include <functional>
-
-#include <chrono>
-#include <exception>
 
 #include "tmc2gof.h"
 
@@ -71,6 +69,7 @@ std::vector<int> coresOf( const cpu_set_t& allowed ) {
   }
   return order;
 }
+int coreOfSlot( const std::vector<int>& cores, int slot ) { return cores.empty() || slot < 0 ? -1 : cores[size_t( slot ) % cores.size()]; }
 
 // the CTC lossy settings (cfg/common/ctc-common.cfg + the sequence's), as tmc2_amd.lib.ctc_params
 tmc2_segmenter_params ctcParams( const tmc2_gof_config& c, const double w[3] ) {
@@ -86,6 +85,44 @@ tmc2_segmenter_params ctcParams( const tmc2_gof_config& c, const double w[3] ) {
   return p;
 }
 
+// What a pass knows of its own failure: the first failing status and the message that goes with it, from whichever thread.
+struct Pass {
+  std::atomic<int> status{TMC2_OK};
+  std::mutex       lock;
+  std::string      message;
+  bool             failed() const { return status.load() != TMC2_OK; }
+  void             fail( int rc, const std::string& why ) {
+    int expected = TMC2_OK;
+    if ( status.compare_exchange_strong( expected, rc ) ) {
+      std::lock_guard<std::mutex> g( lock );
+      message = why;
+    }
+  }
+  void failCall( int rc, const char* call ) { fail( rc, std::string( call ) + ": " + tmc2_last_error() ); }  // (the failing thread's own message)
+  // an exception a slot thread caught: the status always, the text if there is memory for it
+  void caught( const char* what ) noexcept {
+    try {
+      fail( TMC2_E_STATE, std::string( "slot thread: " ) + what );
+    } catch ( const std::exception& ) {
+      int expected = TMC2_OK;
+      status.compare_exchange_strong( expected, TMC2_E_STATE );
+    }
+  }
+  int done() {  // on the calling thread: the pass' status, its message for tmc2_gof_last_error()
+    std::lock_guard<std::mutex> g( lock );
+    t_err = message;
+    return status.load();
+  }
+};
+#define GOF_TRY( call )                               \
+  do {                                                \
+    const int rc_ = ( call );                         \
+    if ( rc_ != TMC2_OK ) {                           \
+      s.pass.failCall( rc_, #call );                  \
+      return;                                         \
+    }                                                 \
+  } while ( 0 )
+
 // The slot threads of the passes: parked between passes instead of being born and joined twice per pass (32 births per 180 ms GOF
 // with sixteen slots).  A pass LEASES as many as it has slots -- two passes of two caller threads never share a thread -- and hands
 // them back when its phase is over; the set only grows.  Never destroyed (a thread parked in a condition variable whose owner's
@@ -95,7 +132,6 @@ class SlotThreads {
     std::mutex              lock;
     std::condition_variable wake;
     std::function<void()>   job;
-    bool                    busy = false;
     int                     pinned = -1;
     std::thread             thread;
   };
@@ -119,8 +155,9 @@ class SlotThreads {
     static SlotThreads* pool = new SlotThreads();  // (leaked on purpose: see above)
     return *pool;
   }
-  // fn( slot ) on `slots` threads side by side, slot s pinned to cores[s % cores.size()]; returns when all are done
-  void run( int slots, const std::vector<int>& cores, const std::function<void( int )>& fn ) {
+  // fn( slot ) on `slots` threads side by side, slot s pinned to cores[s % cores.size()]; returns when all are done.  Nothing may
+  // unwind a parked thread: what fn throws fails the pass (Pass::caught) before the slot signals that it is done.
+  void run( int slots, const std::vector<int>& cores, Pass& pass, const std::function<void( int )>& fn ) {
     std::vector<Worker*> mine;
     {
       std::lock_guard<std::mutex> g( lock_ );
@@ -141,7 +178,7 @@ class SlotThreads {
     int                     left = slots;
     for ( int sl = 0; sl < slots; ++sl ) {
       Worker*   w    = mine[size_t( sl )];
-      const int core = cores.empty() ? -1 : cores[size_t( sl ) % cores.size()];
+      const int core = coreOfSlot( cores, sl );
       std::lock_guard<std::mutex> g( w->lock );
       w->job = [&, w, sl, core] {
         if ( core >= 0 && w->pinned != core ) {
@@ -153,7 +190,10 @@ class SlotThreads {
         }
         try {
           fn( sl );
-        } catch ( ... ) {  // (fn reports through the pass; nothing may unwind a parked thread)
+        } catch ( const std::exception& e ) {
+          pass.caught( e.what() );
+        } catch ( ... ) {
+          pass.caught( "unknown exception" );
         }
         std::lock_guard<std::mutex> d( doneLock );
         if ( --left == 0 ) doneCv.notify_one();
@@ -168,35 +208,10 @@ class SlotThreads {
     for ( Worker* w : mine ) idle_.push_back( w );
   }
 };
-
-struct Pass {
-  std::atomic<int> status{TMC2_OK};
-  std::mutex       lock;
-  std::string      message;
-  void             fail( int rc, const char* what, const char* detail = nullptr ) {
-    int expected = TMC2_OK;
-    if ( status.compare_exchange_strong( expected, rc ) ) {
-      std::lock_guard<std::mutex> g( lock );
-      message = std::string( what ) + ": " + ( detail ? detail : tmc2_last_error() );  // (the failing thread's own message)
-    }
-  }
-  int done() {  // on the calling thread: the pass' status, its message for tmc2_gof_last_error()
-    std::lock_guard<std::mutex> g( lock );
-    t_err = message;
-    return status.load();
-  }
-};
-#define GOF_TRY( call )                               \
-  do {                                                \
-    const int rc_ = ( call );                         \
-    if ( rc_ != TMC2_OK ) {                           \
-      pass.fail( rc_, #call );                        \
-      return;                                         \
-    }                                                 \
-  } while ( 0 )
 }  // namespace
 
 extern "C" const char* tmc2_gof_last_error( void ) { return t_err.c_str(); }
+extern "C" int         tmc2_gof_slot_core( int slot ) { return coreOfSlot( coresByCacheDomain(), slot ); }
 
 
 // ---- the ranks of a sharded GOF (one process per GPU): RCCL, loaded at run time --------------------------------------------
@@ -307,15 +322,6 @@ class Watchdog {
   }
   ~Watchdog() { (void)finish(); }
 };
-#define COMM_TRY( call, what )                                                                              \
-  do {                                                                                                      \
-    const int rc_ = ( call );                                                                               \
-    if ( rc_ != 0 ) {                                                                                       \
-      t_err = std::string( what ) + ": " + ( comm->rccl.GetErrorString ? comm->rccl.GetErrorString( rc_ ) : "?" ); \
-      breakComm( comm );                                                                                    \
-      return TMC2_E_HIP;                                                                                    \
-    }                                                                                                       \
-  } while ( 0 )
 #define HIP_TRY( call, what )                              \
   do {                                                     \
     const int rc_ = ( call );                              \
@@ -324,16 +330,66 @@ class Watchdog {
       return rc_;                                          \
     }                                                      \
   } while ( 0 )
+int ncclFailed( tmc2_gof_comm* comm, int rc, const char* what ) {  // a failed RCCL call: its text, the communicator aborted
+  t_err = std::string( what ) + ": " + ( comm->rccl.GetErrorString ? comm->rccl.GetErrorString( rc ) : "?" );
+  breakComm( comm );
+  return TMC2_E_HIP;
+}
 int refuseBroken( tmc2_gof_comm* comm ) {
   if ( !comm->broken ) return TMC2_OK;
   t_err = "tmc2_gof_comm: the communicator was aborted after a collective failed or timed out; make a new one";
   return TMC2_E_STATE;
 }
-template <typename F>
-int underWatchdog( tmc2_gof_comm* comm, const char* what, F&& body ) {
+
+// ncclGroupStart .. ncclGroupEnd around the calls handed to then(): once the group is open it is ALWAYS closed (an open group is the
+// thread's, and would swallow the calls of the next communicator made on it); the first error inside is the group's, and no call
+// is enqueued after it.
+class Group {
+  const Rccl& rccl_;
+  int         first_;
+  bool        open_;
+
+ public:
+  explicit Group( const Rccl& rccl ) : rccl_( rccl ), first_( rccl.GroupStart() ), open_( first_ == 0 ) {}
+  template <typename Call>
+  void then( Call&& call ) {
+    if ( first_ == 0 ) first_ = call();
+  }
+  int end() {  // -> the first error of the group, 0 if none
+    if ( open_ ) {
+      open_        = false;
+      const int rc = rccl_.GroupEnd();
+      if ( first_ == 0 ) first_ = rc;
+    }
+    return first_;
+  }
+  ~Group() { (void)end(); }
+};
+
+// ONE collective, the whole dance: a broken communicator is refused; under the watchdog the words to send go up, the collective is
+// issued, and the wait behind it is a download of the answer or (nothing to bring back) a synchronisation.  Every rank ALWAYS
+// issues the collective -- one whose upload failed still takes part, with whatever the buffer holds, and reports its own failure
+// LAST, so that nobody waits for it; the stage behind the collective carries the failure.  issue( stream ) -> RCCL's status.
+struct Copy {
+  void*  host   = nullptr;
+  void*  device = nullptr;
+  size_t bytes  = 0;  // 0: no copy
+};
+template <typename Issue>
+int collective( tmc2_gof_comm* comm, const char* what, Copy up, Issue&& issue, Copy down ) {
   if ( const int rc = refuseBroken( comm ) ) return rc;
-  Watchdog  dog( comm );
-  const int rc = body();
+  Watchdog    dog( comm );
+  std::string upError;
+  const int   upRc = up.bytes ? tmc2_ctx_upload( comm->ctx, up.device, up.host, up.bytes ) : TMC2_OK;
+  if ( upRc != TMC2_OK ) upError = std::string( what ) + ": upload: " + tmc2_last_error();
+  int rc = TMC2_OK;
+  if ( const int nccl = issue( tmc2_ctx_stream( comm->ctx ) ) ) {
+    rc = ncclFailed( comm, nccl, what );
+  } else {
+    rc = down.bytes ? tmc2_ctx_download( comm->ctx, down.host, down.device, down.bytes ) : tmc2_ctx_synchronize( comm->ctx );
+    if ( rc != TMC2_OK ) t_err = std::string( what ) + ": " + tmc2_last_error();
+    if ( upRc != TMC2_OK ) t_err = upError, rc = upRc;
+  }
   if ( dog.finish() ) {
     t_err = std::string( what ) + ": no answer from the other ranks within " + std::to_string( int( comm->timeoutSeconds ) ) +
             " s (TMC2_GOF_COLLECTIVE_TIMEOUT): the communicator was aborted";
@@ -341,50 +397,47 @@ int underWatchdog( tmc2_gof_comm* comm, const char* what, F&& body ) {
   }
   return rc;
 }
-// the wait behind a collective.  host == nullptr: only the synchronisation
-int waitFor( tmc2_gof_comm* comm, void* host, const void* device, size_t bytes, const char* what ) {
-  const int rc = host ? tmc2_ctx_download( comm->ctx, host, device, bytes ) : tmc2_ctx_synchronize( comm->ctx );
-  if ( rc != TMC2_OK ) t_err = std::string( what ) + ": " + tmc2_last_error();
-  return rc;
-}
-
-// One small collective on device words: every rank ALWAYS issues it -- a rank whose upload failed still takes part (with whatever
-// the buffer holds) and reports its own failure afterwards, so that nobody waits for it; the stage behind it carries the failure.
-// 24 bytes from rank 0 to everybody (the axis weights of frame 0: PCCEncoder::calculateWeightNormal runs on the first frame only)
-int commBroadcastBody( tmc2_gof_comm* comm, void* host, size_t count, int type, size_t width, const char* what ) {
-  void*             st = tmc2_ctx_stream( comm->ctx );
-  const int         up = tmc2_ctx_upload( comm->ctx, comm->dSmall, host, count * width );
-  const std::string upError = up != TMC2_OK ? std::string( what ) + ": upload: " + tmc2_last_error() : std::string();
-  COMM_TRY( comm->rccl.Broadcast( comm->dSmall, comm->dSmall, count, type, 0, comm->comm, st ), what );
-  const int rc = waitFor( comm, host, comm->dSmall, count * width, what );
-  if ( up != TMC2_OK ) {
-    t_err = upError;
-    return up;
-  }
-  return rc;
-}
+// `count` words of `width` bytes from rank 0 to everybody (the axis weights of frame 0: PCCEncoder::calculateWeightNormal runs on
+// the first frame only; the canvas of a chained GOF)
 int commBroadcast( tmc2_gof_comm* comm, void* host, size_t count, int type, size_t width, const char* what ) {
-  return underWatchdog( comm, what, [&] { return commBroadcastBody( comm, host, count, type, width, what ); } );
+  const Copy words{host, comm->dSmall, count * width};
+  return collective( comm, what, words, [&]( void* st ) { return comm->rccl.Broadcast( comm->dSmall, comm->dSmall, count, type, 0, comm->comm, st ); }, words );
 }
-int commBroadcastWeights( tmc2_gof_comm* comm, double w[3] ) { return commBroadcast( comm, w, 3, kNcclFloat64, 8, "ncclBroadcast( weights )" ); }
-// max over the ranks of `count` int32 words (count <= 16)
-int commMaxBody( tmc2_gof_comm* comm, int32_t* words, size_t count, const char* what ) {
-  void*             st = tmc2_ctx_stream( comm->ctx );
-  const int         up = tmc2_ctx_upload( comm->ctx, comm->dSmall, words, 4 * count );
-  const std::string upError = up != TMC2_OK ? std::string( what ) + ": upload: " + tmc2_last_error() : std::string();
-  COMM_TRY( comm->rccl.AllReduce( comm->dSmall, comm->dSmall, count, kNcclInt32, kNcclMax, comm->comm, st ), what );
-  const int rc = waitFor( comm, words, comm->dSmall, 4 * count, what );
-  if ( up != TMC2_OK ) {
-    t_err = upError;
-    return up;
-  }
-  return rc;
+// max over the ranks of `count` int32 words (count <= 16): the canvas height of the GOF is the max of what the ranks' frames packed
+// into (resizeGeometryVideo, PCCEncoder.cpp:5546-5591)
+int commMax( tmc2_gof_comm* comm, int32_t* host, size_t count, const char* what ) {
+  const Copy words{host, comm->dSmall, 4 * count};
+  return collective( comm, what, words, [&]( void* st ) { return comm->rccl.AllReduce( comm->dSmall, comm->dSmall, count, kNcclInt32, kNcclMax, comm->comm, st ); }, words );
 }
-int commMax( tmc2_gof_comm* comm, int32_t* words, size_t count, const char* what ) {
-  return underWatchdog( comm, what, [&] { return commMaxBody( comm, words, count, what ); } );
+// every rank's block of `mine` bytes (hostBlocks[0 .. mine)) to rank 0 (hostBlocks[mine * (r + 1) ..)): one grouped send / receive
+// (an upload that failed lets a stale block travel; its pass number gives it away)
+int commBlocksToRoot( tmc2_gof_comm* comm, size_t mine, const char* what ) {
+  uint8_t*   host = comm->hostBlocks.data();
+  uint8_t*   dev  = static_cast<uint8_t*>( comm->dBlocks );
+  const bool root = comm->rank == 0;
+  const auto exchange = [&]( void* st ) {
+    Group group( comm->rccl );
+    for ( int r = 0; root && r < comm->world; ++r )
+      group.then( [&] { return comm->rccl.Recv( dev + mine * size_t( r + 1 ), mine, kNcclUint8, r, comm->comm, st ); } );
+    group.then( [&] { return comm->rccl.Send( dev, mine, kNcclUint8, 0, comm->comm, st ); } );
+    return group.end();
+  };
+  return collective( comm, what, {host, dev, mine}, exchange, root ? Copy{host + mine, dev + mine, mine * size_t( comm->world )} : Copy{} );
 }
-// the canvas height of the GOF: max over the ranks of what their frames packed into (resizeGeometryVideo, PCCEncoder.cpp:5546-5591)
-int commMaxHeight( tmc2_gof_comm* comm, int32_t* h ) { return commMax( comm, h, 1, "ncclAllReduce( height, max )" ); }
+// rank 0's block for rank r (hostBlocks[mine * r ..), r = 0 .. world-1) to rank r (hostBlocks[0 .. mine)): the way back
+int commBlocksFromRoot( tmc2_gof_comm* comm, size_t mine, const char* what ) {
+  uint8_t*   host = comm->hostBlocks.data();
+  uint8_t*   dev  = static_cast<uint8_t*>( comm->dBlocks );
+  const bool root = comm->rank == 0;
+  const auto exchange = [&]( void* st ) {
+    Group group( comm->rccl );
+    for ( int r = 0; root && r < comm->world; ++r )
+      group.then( [&] { return comm->rccl.Send( dev + mine * size_t( r + 1 ), mine, kNcclUint8, r, comm->comm, st ); } );
+    group.then( [&] { return comm->rccl.Recv( dev, mine, kNcclUint8, 0, comm->comm, st ); } );
+    return group.end();
+  };
+  return collective( comm, what, root ? Copy{host, dev + mine, mine * size_t( comm->world )} : Copy{}, exchange, {host, dev, mine} );
+}
 
 int ensureBlocks( tmc2_gof_comm* comm, size_t need ) {
   if ( need <= comm->blocksBytes ) return TMC2_OK;
@@ -394,119 +447,153 @@ int ensureBlocks( tmc2_gof_comm* comm, size_t need ) {
   comm->blocksBytes = need;
   return TMC2_OK;
 }
-// every rank's block of `mine` bytes (hostBlocks[0 .. mine)) to rank 0 (hostBlocks[mine * (r + 1) ..)): one grouped send / receive
-int commBlocksToRootBody( tmc2_gof_comm* comm, size_t mine, const char* what ) {
-  void*     st  = tmc2_ctx_stream( comm->ctx );
-  uint8_t*  dev = static_cast<uint8_t*>( comm->dBlocks );
-  const int up  = tmc2_ctx_upload( comm->ctx, dev, comm->hostBlocks.data(), mine );  // (failed: a stale block travels; its pass number gives it away)
-  const std::string upError = up != TMC2_OK ? std::string( what ) + ": upload: " + tmc2_last_error() : std::string();
-  COMM_TRY( comm->rccl.GroupStart(), "ncclGroupStart" );
-  if ( comm->rank == 0 )
-    for ( int r = 0; r < comm->world; ++r ) COMM_TRY( comm->rccl.Recv( dev + mine * size_t( r + 1 ), mine, kNcclUint8, r, comm->comm, st ), what );
-  COMM_TRY( comm->rccl.Send( dev, mine, kNcclUint8, 0, comm->comm, st ), what );
-  COMM_TRY( comm->rccl.GroupEnd(), "ncclGroupEnd" );
-  const int rc = comm->rank == 0 ? waitFor( comm, comm->hostBlocks.data() + mine, dev + mine, mine * size_t( comm->world ), what )
-                                 : waitFor( comm, nullptr, nullptr, 0, what );
-  if ( up != TMC2_OK ) {
-    t_err = upError;
-    return up;
-  }
-  return rc;
-}
-int commBlocksToRoot( tmc2_gof_comm* comm, size_t mine, const char* what ) {
-  return underWatchdog( comm, what, [&] { return commBlocksToRootBody( comm, mine, what ); } );
-}
-// rank 0's block for rank r (hostBlocks[mine * r ..), r = 0 .. world-1) to rank r (hostBlocks[0 .. mine)): the way back
-int commBlocksFromRootBody( tmc2_gof_comm* comm, size_t mine, const char* what ) {
-  void*     st  = tmc2_ctx_stream( comm->ctx );
-  uint8_t*  dev = static_cast<uint8_t*>( comm->dBlocks );
-  int       up  = TMC2_OK;
-  std::string upError;
-  if ( comm->rank == 0 ) {
-    up = tmc2_ctx_upload( comm->ctx, dev + mine, comm->hostBlocks.data(), mine * size_t( comm->world ) );
-    if ( up != TMC2_OK ) upError = std::string( what ) + ": upload: " + tmc2_last_error();
-  }
-  COMM_TRY( comm->rccl.GroupStart(), "ncclGroupStart" );
-  if ( comm->rank == 0 )
-    for ( int r = 0; r < comm->world; ++r ) COMM_TRY( comm->rccl.Send( dev + mine * size_t( r + 1 ), mine, kNcclUint8, r, comm->comm, st ), what );
-  COMM_TRY( comm->rccl.Recv( dev, mine, kNcclUint8, 0, comm->comm, st ), what );
-  COMM_TRY( comm->rccl.GroupEnd(), "ncclGroupEnd" );
-  const int rc = waitFor( comm, comm->hostBlocks.data(), dev, mine, what );
-  if ( up != TMC2_OK ) {
-    t_err = upError;
-    return up;
-  }
-  return rc;
-}
-
-int commBlocksFromRoot( tmc2_gof_comm* comm, size_t mine, const char* what ) {
-  return underWatchdog( comm, what, [&] { return commBlocksFromRootBody( comm, mine, what ); } );
-}
 
 constexpr size_t roundUp( size_t n, size_t to ) { return ( n + to - 1 ) / to * to; }
 
+// One frame's block on the wire: a header of int64 words, `slots` records, with the packed lists one int32 per record slot (the
+// patch each was matched to), a pool of block occupancy.  Three blocks travel, told apart by the header word that carries the
+// pass number (a block of another pass, or of impossible sizes, is not read):
+//   the final gather     [count, PASS]                                 records
+//   records to rank 0    [count, pool bytes, PASS, 0]                  records, pool
+//   packed lists back    [count, pool bytes, tile (W << 32 | H), PASS] records, matches, pool
+struct Block {
+  enum Kind { kGather = 1, kToRoot = 2, kFromRoot = 3 };  // (= the header word of the pass number)
+  Kind   kind;
+  size_t slots, pool;  // record slots; pool bytes, a multiple of 64
+  size_t recordsAt() const { return kind == kGather ? 16 : 32; }
+  size_t matchesAt() const { return recordsAt() + slots * sizeof( tmc2_patch ); }
+  size_t poolAt() const { return matchesAt() + ( kind == kFromRoot ? 4 * slots : 0 ); }
+  size_t bytes() const { return poolAt() + pool; }
+  // count < 0: a frame this rank cannot deliver (no records are looked at)
+  void write( uint8_t* at, int64_t pass, int64_t count, const tmc2_patch* records, const int32_t* matches = nullptr,
+              const uint8_t* poolBytes = nullptr, size_t poolSize = 0, int64_t tile = 0 ) const {
+    int64_t header[4] = {count, int64_t( poolSize ), tile, 0};
+    header[kind]      = pass;
+    memcpy( at, header, recordsAt() );
+    const size_t n = count > 0 ? size_t( count ) : 0;
+    if ( n ) memcpy( at + recordsAt(), records, n * sizeof( tmc2_patch ) );
+    if ( n && matches ) memcpy( at + matchesAt(), matches, n * 4 );
+    if ( poolSize ) memcpy( at + poolAt(), poolBytes, poolSize );
+  }
+  struct View {  // (bytes, not typed pointers: a block need not be aligned for its records)
+    size_t         count = 0, poolSize = 0;
+    int64_t        tile = 0;
+    const uint8_t *records = nullptr, *matches = nullptr, *pool = nullptr;
+    void recordsTo( tmc2_patch* to ) const { if ( count ) memcpy( to, records, count * sizeof( tmc2_patch ) ); }
+  };
+  bool read( const uint8_t* at, int64_t pass, View& v ) const {  // -> false: not a block of this pass, or of impossible sizes
+    int64_t header[4] = {0, 0, 0, 0};
+    memcpy( header, at, recordsAt() );
+    const int64_t poolSize = kind == kGather ? 0 : header[1];
+    if ( header[kind] != pass || header[0] < 0 || header[0] > int64_t( slots ) || poolSize < 0 || poolSize > int64_t( pool ) ) return false;
+    v.count = size_t( header[0] ), v.poolSize = size_t( poolSize ), v.tile = header[2];
+    v.records = at + recordsAt(), v.matches = at + matchesAt(), v.pool = at + poolAt();
+    return true;
+  }
+};
+
+constexpr int32_t kFailedWord = 0x7FFFFFF0;
+
+// One pass over the frames this process holds, and what its steps share.  comm == nullptr: the frames are the whole GOF -- a world
+// of one rank whose meetings are no-ops.  Otherwise they are this rank's share (frame f of the GOF on rank f mod world): the weights
+// come from rank 0, the canvas is the maximum over the ranks, the packed records of every frame end on rank 0.
+// resume: the frames are segmented and packed already (a pass that ended with "the GOF needs a larger canvas than the buffers hold"):
+// the pass starts at the canvas size, from what the packers left in the frames.
+struct GofPass {
+  tmc2_gof_comm*         comm;
+  tmc2_frame**           frames;
+  const int32_t*         slotOf;
+  int32_t                count, slots;
+  const tmc2_gof_config* config;
+  uint8_t **             occupancy, **occVideo;
+  uint32_t**             blockToPatch;
+  uint16_t **            geometryD0, **geometryD1;
+  uint8_t**              attribute;
+  int32_t                capacityWidth, capacityHeight;
+  int32_t *              width, *height;
+  int32_t                recordSlots;
+  tmc2_patch*            gathered;
+  int64_t*               gatheredCounts;
+  bool                   resume;
+  // what the steps leave for each other
+  Pass                 pass;
+  bool                 chained = false, guess = false, recordsChain = false;
+  std::vector<int>     cores;
+  double               weights[3] = {0, 0, 0};
+  std::vector<int32_t> heights, guessW, guessH;
+  int32_t              W = 0, H = 0;
+};
+
+// the frames of one slot in order, slots side by side; a pass that has failed starts no further frame
+template <typename Fn>
+void perSlot( GofPass& s, Fn fn ) {
+  SlotThreads::instance().run( s.slots, s.cores, s.pass, [&]( int sl ) {
+    for ( int i = 0; i < s.count; ++i )
+      if ( s.slotOf[i] == sl && !s.pass.failed() ) fn( i );
+  } );
+}
+
+// THE RULE of the sharded pass: a rank that fails locally goes on through every collective of the pass, with a value that says so
+// -- nobody is ever left waiting for a rank that has returned.  Here once: the ranks meet in an all-reduce( max ) of `count` words
+// whose word 0 carries whether one of them failed (kFailedWord: above every height and size).  -> this rank's own failure with its
+// own message, else the collective's, else that another rank failed `phrase`.  Without a communicator: this rank's own failure.
+int meet( GofPass& s, int32_t* words, size_t count, const char* what, const char* phrase ) {
+  if ( !s.comm ) return s.pass.done();
+  if ( s.pass.failed() ) words[0] = kFailedWord;
+  const int rc = commMax( s.comm, words, count, what );
+  if ( s.pass.failed() ) return s.pass.done();
+  if ( rc != TMC2_OK ) return rc;
+  if ( words[0] != kFailedWord ) return TMC2_OK;
+  t_err = std::string( "tmc2_gof_encode_sharded: another rank's frames " ) + phrase + " (its own call says why)";
+  return TMC2_E_STATE;
+}
+
 // The final gather: the packed patch records of every frame (the side information the bitstream carries: ~ 100 bytes a patch) to
-// rank 0 -- one grouped send / receive per pass.  Block of a frame: int64 count, int64 pass number, then recordSlots records in
-// list order.
-int commGatherRecords( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, int32_t recordSlots, tmc2_patch* gathered,
-                       int64_t* gatheredCounts, int failed ) {
-  const size_t frameBytes = 16 + size_t( recordSlots ) * sizeof( tmc2_patch ), mine = frameBytes * size_t( count );
-  const size_t need       = mine * ( comm->rank == 0 ? size_t( comm->world ) + 1 : 1 );
-  int         localStatus = failed;
-  std::string localError  = failed != TMC2_OK ? t_err : std::string();
-  if ( const int rc = ensureBlocks( comm, need ); rc != TMC2_OK && localStatus == TMC2_OK ) localStatus = rc, localError = t_err;
+// rank 0, in list order -- one grouped send / receive per pass.
+int commGatherRecords( GofPass& s ) {
+  tmc2_gof_comm* comm = s.comm;
+  const Block    block{Block::kGather, size_t( s.recordSlots ), 0};
+  const size_t   mine = block.bytes() * size_t( s.count ), need = mine * ( comm->rank == 0 ? size_t( comm->world ) + 1 : 1 );
+  if ( const int rc = ensureBlocks( comm, need ) ) s.pass.fail( rc, t_err );
   comm->hostBlocks.assign( need, 0 );
-  std::vector<tmc2_patch> list;
+  std::vector<tmc2_patch> byIndex, list;
   std::vector<int32_t>    order;
   // (A rank that cannot fill its block -- its pass failed after the rendezvous, or a frame has more patches than the block holds --
   //  STILL takes part in the exchange, with a negative count in the block: the other ranks must not be left waiting in a receive.)
-  for ( int i = 0; i < count; ++i ) {
-    uint8_t* at  = comm->hostBlocks.data() + frameBytes * size_t( i );
-    int64_t  n64 = -1;
-    if ( localStatus == TMC2_OK ) {
-      const int n = tmc2_frame_patch_count( frames[i] );
-      if ( n < 0 || n > recordSlots ) {
-        localStatus = TMC2_E_INVALID;
-        localError  = "tmc2_gof_encode_sharded: a frame with " + std::to_string( n ) + " patches, the gather holds " + std::to_string( recordSlots );
+  for ( int i = 0; i < s.count; ++i ) {
+    int n = -1;
+    if ( !s.pass.failed() ) {
+      n = tmc2_frame_patch_count( s.frames[i] );
+      if ( n < 0 || n > s.recordSlots ) {
+        s.pass.fail( TMC2_E_INVALID, "tmc2_gof_encode_sharded: a frame with " + std::to_string( n ) + " patches, the gather holds " + std::to_string( s.recordSlots ) );
       } else {
-        list.resize( size_t( n ) ), order.resize( size_t( n ) );
-        int rc = tmc2_frame_get_patches( frames[i], list.data(), nullptr, nullptr, nullptr );
-        if ( rc == TMC2_OK ) rc = tmc2_frame_get_patch_order( frames[i], order.data() );
-        if ( rc != TMC2_OK ) {
-          localStatus = rc, localError = std::string( "tmc2_frame_get_patches: " ) + tmc2_last_error();
-        } else {
-          n64 = n;
-          for ( int k = 0; k < n; ++k ) memcpy( at + 16 + size_t( k ) * sizeof( tmc2_patch ), &list[size_t( order[size_t( k )] )], sizeof( tmc2_patch ) );
-        }
+        byIndex.resize( size_t( n ) ), list.resize( size_t( n ) ), order.resize( size_t( n ) );
+        int rc = tmc2_frame_get_patches( s.frames[i], byIndex.data(), nullptr, nullptr, nullptr );
+        if ( rc == TMC2_OK ) rc = tmc2_frame_get_patch_order( s.frames[i], order.data() );
+        if ( rc != TMC2_OK ) s.pass.failCall( rc, "tmc2_frame_get_patches" );
+        for ( int k = 0; k < n && rc == TMC2_OK; ++k ) list[size_t( k )] = byIndex[size_t( order[size_t( k )] )];
       }
     }
-    memcpy( at, &n64, 8 );
-    memcpy( at + 8, &comm->passes, 8 );
+    block.write( comm->hostBlocks.data() + block.bytes() * size_t( i ), comm->passes, s.pass.failed() ? -1 : n, list.data() );
   }
   if ( comm->blocksBytes < need ) {  // (no device buffer: this rank cannot take part at all -- the others must not wait for it)
     breakComm( comm );
-    t_err = localError;
-    return localStatus;
+    return s.pass.done();
   }
   const int rc = commBlocksToRoot( comm, mine, "ncclSend / ncclRecv( records )" );
-  if ( localStatus != TMC2_OK ) {
-    t_err = localError;
-    return localStatus;
-  }
+  if ( s.pass.failed() ) return s.pass.done();
   if ( rc != TMC2_OK || comm->rank != 0 ) return rc;
   for ( int r = 0; r < comm->world; ++r )
-    for ( int i = 0; i < count; ++i ) {
-      const uint8_t* at = comm->hostBlocks.data() + mine * size_t( r + 1 ) + frameBytes * size_t( i );
-      int64_t        n = 0, pass = 0;
-      memcpy( &n, at, 8 ), memcpy( &pass, at + 8, 8 );
-      if ( n < 0 || n > recordSlots || pass != comm->passes ) {
+    for ( int i = 0; i < s.count; ++i ) {
+      Block::View  v;
+      const size_t slot = size_t( r ) * size_t( s.count ) + size_t( i );
+      if ( !block.read( comm->hostBlocks.data() + mine * size_t( r + 1 ) + block.bytes() * size_t( i ), comm->passes, v ) ) {
         t_err = "tmc2_gof_encode_sharded: rank " + std::to_string( r ) + " could not deliver the records of its frame " + std::to_string( i ) +
                 " (its own call says why)";
         return TMC2_E_STATE;
       }
-      if ( gatheredCounts ) gatheredCounts[size_t( r ) * size_t( count ) + size_t( i )] = n;
-      if ( gathered )
-        memcpy( gathered + ( size_t( r ) * size_t( count ) + size_t( i ) ) * size_t( recordSlots ), at + 16, size_t( n ) * sizeof( tmc2_patch ) );
+      if ( s.gatheredCounts ) s.gatheredCounts[slot] = int64_t( v.count );
+      if ( s.gathered ) v.recordsTo( s.gathered + slot * size_t( s.recordSlots ) );
     }
   return TMC2_OK;
 }
@@ -518,7 +605,6 @@ int commGatherRecords( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, 
 // frame), rank 0 runs PCCEncoder::placeSegments over them (tmc2_host_place_segments: no device), and every rank gets the packed
 // lists of ITS frames back (a 32-byte header broadcast with the canvas and the block size, one grouped send / receive) and
 // installs them (tmc2_frame_set_packing).  Rank 0 is left with every frame's records in list order: no gather at the end.
-constexpr int32_t kFailedWord = 0x7FFFFFF0;
 struct ChainResult {
   int32_t W = 0, H = 0;
   // per frame of this rank: the packed list, matches, pool, tile size
@@ -530,62 +616,48 @@ struct ChainResult {
   };
   std::vector<Frame> frames;
 };
-int chainOverRanks( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, const tmc2_gof_config& c, int32_t recordSlots,
-                    tmc2_patch* gathered, int64_t* gatheredCounts, int failed, ChainResult& out ) {
-  const int world = comm->world;
-  int         localStatus = failed;
-  std::string localError  = failed != TMC2_OK ? t_err : std::string();
-  auto        localFail   = [&]( int rc, const std::string& why ) {
-    if ( localStatus == TMC2_OK ) localStatus = rc, localError = why;
-  };
+int chainOverRanks( GofPass& s, ChainResult& out ) {
+  tmc2_gof_comm*         comm  = s.comm;
+  const tmc2_gof_config& c     = *s.config;
+  const int              world = comm->world, count = s.count;
+  const size_t           held  = comm->rank == 0 ? size_t( world ) + 1 : 1;  // blocks of `mine` bytes this rank's buffers hold
   // (1) what this rank's frames hold; the largest frame of the GOF sizes everybody's blocks
   std::vector<std::vector<tmc2_patch>> recs( static_cast<size_t>( count ) );
   std::vector<std::vector<uint8_t>>    pools( static_cast<size_t>( count ) );
   int32_t sizes[3] = {0, 0, 0};  // failed?, most patches of a frame, largest pool of a frame
-  for ( int i = 0; i < count && localStatus == TMC2_OK; ++i ) {
-    const int n = tmc2_frame_patch_count( frames[i] );
+  for ( int i = 0; i < count && !s.pass.failed(); ++i ) {
+    const int n = tmc2_frame_patch_count( s.frames[i] );
     int64_t   depth = 0, occ = 0;
-    if ( n < 0 || tmc2_frame_patch_pool_sizes( frames[i], &depth, &occ ) != TMC2_OK || occ < 0 || occ > 0x3FFFFFFF ) {
-      localFail( TMC2_E_STATE, std::string( "tmc2_frame_patch_pool_sizes: " ) + tmc2_last_error() );
+    if ( n < 0 || tmc2_frame_patch_pool_sizes( s.frames[i], &depth, &occ ) != TMC2_OK || occ < 0 || occ > 0x3FFFFFFF ) {
+      s.pass.failCall( TMC2_E_STATE, "tmc2_frame_patch_pool_sizes" );
       break;
     }
     recs[size_t( i )].resize( size_t( n ) ), pools[size_t( i )].resize( size_t( occ ) );
-    if ( const int rc = tmc2_frame_get_patches( frames[i], recs[size_t( i )].data(), nullptr, nullptr, pools[size_t( i )].data() ) ) {
-      localFail( rc, std::string( "tmc2_frame_get_patches: " ) + tmc2_last_error() );
+    if ( const int rc = tmc2_frame_get_patches( s.frames[i], recs[size_t( i )].data(), nullptr, nullptr, pools[size_t( i )].data() ) ) {
+      s.pass.failCall( rc, "tmc2_frame_get_patches" );
       break;
     }
     sizes[1] = std::max( sizes[1], int32_t( n ) ), sizes[2] = std::max( sizes[2], int32_t( occ ) );
   }
-  if ( localStatus != TMC2_OK ) sizes[0] = kFailedWord;
-  {
-    const int rc = commMax( comm, sizes, 3, "ncclAllReduce( records of the largest frame, max )" );
-    if ( rc != TMC2_OK ) return localStatus != TMC2_OK ? ( t_err = localError, localStatus ) : rc;
-  }
-  if ( sizes[0] != 0 ) {  // (every rank leaves here, together)
-    if ( localStatus != TMC2_OK ) return t_err = localError, localStatus;
-    t_err = "tmc2_gof_encode_sharded: another rank's frames failed before the packing chain (its own call says why)";
-    return TMC2_E_STATE;
-  }
-  if ( sizes[1] > recordSlots ) {
-    t_err = "tmc2_gof_encode_sharded: a frame with " + std::to_string( sizes[1] ) + " patches, the records hold " + std::to_string( recordSlots );
+  // (every rank leaves here, together)
+  if ( const int rc = meet( s, sizes, 3, "ncclAllReduce( records of the largest frame, max )", "failed before the packing chain" ) ) return rc;
+  if ( sizes[1] > s.recordSlots ) {
+    t_err = "tmc2_gof_encode_sharded: a frame with " + std::to_string( sizes[1] ) + " patches, the records hold " + std::to_string( s.recordSlots );
     return TMC2_E_INVALID;
   }
-  const size_t slotsN = size_t( std::max( sizes[1], 1 ) ), poolN = roundUp( size_t( sizes[2] ), 64 );
-  const size_t inFrame = 32 + slotsN * sizeof( tmc2_patch ) + poolN, inMine = inFrame * size_t( count );
+  const size_t slotsN = size_t( std::max( sizes[1], 1 ) );
+  const Block  in{Block::kToRoot, slotsN, roundUp( size_t( sizes[2] ), 64 )};
+  const size_t inMine = in.bytes() * size_t( count );
   // (2) records + pools -> rank 0
-  int rc = ensureBlocks( comm, inMine * ( comm->rank == 0 ? size_t( world ) + 1 : 1 ) );
+  int rc = ensureBlocks( comm, inMine * held );
   if ( rc != TMC2_OK ) {  // (cannot take part: the others must not wait)
     breakComm( comm );
     return rc;
   }
-  comm->hostBlocks.assign( inMine * ( comm->rank == 0 ? size_t( world ) + 1 : 1 ), 0 );
-  for ( int i = 0; i < count; ++i ) {
-    uint8_t*      at = comm->hostBlocks.data() + inFrame * size_t( i );
-    const int64_t hd[4] = {int64_t( recs[size_t( i )].size() ), int64_t( pools[size_t( i )].size() ), comm->passes, 0};
-    memcpy( at, hd, 32 );
-    memcpy( at + 32, recs[size_t( i )].data(), recs[size_t( i )].size() * sizeof( tmc2_patch ) );
-    memcpy( at + 32 + slotsN * sizeof( tmc2_patch ), pools[size_t( i )].data(), pools[size_t( i )].size() );
-  }
+  comm->hostBlocks.assign( inMine * held, 0 );
+  for ( int i = 0; i < count; ++i )
+    in.write( comm->hostBlocks.data() + in.bytes() * size_t( i ), comm->passes, int64_t( recs[size_t( i )].size() ), recs[size_t( i )].data(), nullptr,
+              pools[size_t( i )].data(), pools[size_t( i )].size() );
   rc = commBlocksToRoot( comm, inMine, "ncclSend / ncclRecv( records for the packing chain )" );
   if ( rc != TMC2_OK ) return rc;
   // (3) rank 0: PCCEncoder::placeSegments over the GOF in frame order (frame f = slot f / world of rank f mod world)
@@ -600,27 +672,23 @@ int chainOverRanks( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, con
     std::vector<int64_t> inBase;
     counts.resize( size_t( gofFrames ) ), inBase.resize( size_t( gofFrames ) ), outBase.resize( size_t( gofFrames ) + 1 );
     widths.resize( size_t( gofFrames ) ), heights.resize( size_t( gofFrames ) );
-    int64_t maxU0 = 1, maxV0 = 1;
-    bool    ok    = true;
+    bool ok = true;
     for ( int f = 0; f < gofFrames && ok; ++f ) {
-      const uint8_t* at = comm->hostBlocks.data() + inMine * size_t( f % world + 1 ) + inFrame * size_t( f / world );
-      int64_t        hd[4];
-      memcpy( hd, at, 32 );
-      if ( hd[0] < 0 || hd[0] > int64_t( slotsN ) || hd[1] < 0 || hd[1] > int64_t( poolN ) || hd[2] != comm->passes ) {
-        ok = false;
-        break;
-      }
-      counts[size_t( f )] = int32_t( hd[0] ), inBase[size_t( f )] = int64_t( occIn.size() );
-      const tmc2_patch* p = reinterpret_cast<const tmc2_patch*>( at + 32 );
-      all.insert( all.end(), p, p + hd[0] );
-      occIn.insert( occIn.end(), at + 32 + slotsN * sizeof( tmc2_patch ), at + 32 + slotsN * sizeof( tmc2_patch ) + hd[1] );
-      for ( int64_t k = 0; k < hd[0]; ++k ) maxU0 = std::max<int64_t>( maxU0, p[k].sizeU0 ), maxV0 = std::max<int64_t>( maxV0, p[k].sizeV0 );
+      Block::View v;
+      ok = in.read( comm->hostBlocks.data() + inMine * size_t( f % world + 1 ) + in.bytes() * size_t( f / world ), comm->passes, v );
+      if ( !ok ) break;
+      counts[size_t( f )] = int32_t( v.count ), inBase[size_t( f )] = int64_t( occIn.size() );
+      all.resize( all.size() + v.count );
+      v.recordsTo( all.data() + all.size() - v.count );
+      occIn.insert( occIn.end(), v.pool, v.pool + v.poolSize );
     }
     if ( !ok ) {
       header[0] = kFailedWord;
-      localFail( TMC2_E_STATE, "tmc2_gof_encode_sharded: a rank delivered a block of another pass or of impossible sizes" );
+      s.pass.fail( TMC2_E_STATE, "tmc2_gof_encode_sharded: a rank delivered a block of another pass or of impossible sizes" );
     } else {
       // (random access: a tracked patch grows to the box of its track's union -- never beyond the largest box of the GOF in either direction)
+      int64_t maxU0 = 1, maxV0 = 1;
+      for ( const tmc2_patch& p : all ) maxU0 = std::max<int64_t>( maxU0, p.sizeU0 ), maxV0 = std::max<int64_t>( maxV0, p.sizeV0 );
       const int64_t cap = c.packing == 2 ? int64_t( all.size() ) * maxU0 * maxV0 : int64_t( occIn.size() );
       occOut.assign( size_t( std::max<int64_t>( cap, 1 ) ), 0 ), matches.assign( std::max<size_t>( all.size(), 1 ), -1 );
       const int prc = tmc2_host_place_segments( gofFrames, counts.data(), all.data(), occIn.data(), inBase.data(), c.packing, c.minimumImageWidth,
@@ -633,7 +701,7 @@ int chainOverRanks( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, con
       const int crc = prc != TMC2_OK ? prc : tmc2_encoder_canvas_size( &tileH, 1, tileW, c.minimumImageWidth, c.minimumImageHeight, &W, &H );
       if ( crc != TMC2_OK ) {
         header[0] = kFailedWord;
-        localFail( crc, std::string( prc != TMC2_OK ? "tmc2_host_place_segments: " : "tmc2_encoder_canvas_size: " ) + tmc2_last_error() );
+        s.pass.failCall( crc, prc != TMC2_OK ? "tmc2_host_place_segments" : "tmc2_encoder_canvas_size" );
       } else {
         int64_t largest = 0;
         for ( int f = 0; f < gofFrames; ++f ) largest = std::max( largest, outBase[size_t( f ) + 1] - outBase[size_t( f )] );
@@ -644,14 +712,14 @@ int chainOverRanks( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, con
   rc = commBroadcast( comm, header, 8, kNcclInt32, 4, "ncclBroadcast( canvas of the GOF )" );
   if ( rc != TMC2_OK ) return rc;
   if ( header[0] != 0 ) {
-    if ( localStatus != TMC2_OK ) return t_err = localError, localStatus;
+    if ( s.pass.failed() ) return s.pass.done();
     t_err = "tmc2_gof_encode_sharded: the packing chain failed on rank 0 (its own call says why)";
     return TMC2_E_STATE;
   }
   // (4) the packed lists back to the ranks that hold the frames
-  const size_t outPool = roundUp( size_t( header[3] ), 64 ), outFrame = 32 + slotsN * ( sizeof( tmc2_patch ) + 4 ) + outPool;
-  const size_t outMine = outFrame * size_t( count );
-  rc = ensureBlocks( comm, outMine * ( comm->rank == 0 ? size_t( world ) + 1 : 1 ) );
+  const Block  back{Block::kFromRoot, slotsN, roundUp( size_t( header[3] ), 64 )};
+  const size_t outMine = back.bytes() * size_t( count );
+  rc = ensureBlocks( comm, outMine * held );
   if ( rc != TMC2_OK ) {
     breakComm( comm );
     return rc;
@@ -660,17 +728,12 @@ int chainOverRanks( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, con
   if ( comm->rank == 0 ) {
     size_t first = 0;
     for ( int f = 0; f < gofFrames; ++f ) {
-      uint8_t*      at = comm->hostBlocks.data() + outMine * size_t( f % world ) + outFrame * size_t( f / world );
-      const size_t  n  = size_t( counts[size_t( f )] );
-      const int64_t hd[4] = {int64_t( n ), outBase[size_t( f ) + 1] - outBase[size_t( f )],
-                             ( int64_t( widths[size_t( f )] ) << 32 ) | uint32_t( heights[size_t( f )] ), comm->passes};
-      memcpy( at, hd, 32 );
-      memcpy( at + 32, all.data() + first, n * sizeof( tmc2_patch ) );
-      memcpy( at + 32 + slotsN * sizeof( tmc2_patch ), matches.data() + first, n * 4 );
-      memcpy( at + 32 + slotsN * ( sizeof( tmc2_patch ) + 4 ), occOut.data() + outBase[size_t( f )], size_t( hd[1] ) );
-      const size_t slot = size_t( f % world ) * size_t( count ) + size_t( f / world );
-      if ( gatheredCounts ) gatheredCounts[slot] = int64_t( n );
-      if ( gathered ) memcpy( gathered + slot * size_t( recordSlots ), all.data() + first, n * sizeof( tmc2_patch ) );
+      const size_t n = size_t( counts[size_t( f )] ), slot = size_t( f % world ) * size_t( count ) + size_t( f / world );
+      back.write( comm->hostBlocks.data() + outMine * size_t( f % world ) + back.bytes() * size_t( f / world ), comm->passes, int64_t( n ),
+                  all.data() + first, matches.data() + first, occOut.data() + outBase[size_t( f )], size_t( outBase[size_t( f ) + 1] - outBase[size_t( f )] ),
+                  ( int64_t( widths[size_t( f )] ) << 32 ) | uint32_t( heights[size_t( f )] ) );
+      if ( s.gatheredCounts ) s.gatheredCounts[slot] = int64_t( n );
+      if ( s.gathered && n ) memcpy( s.gathered + slot * size_t( s.recordSlots ), all.data() + first, n * sizeof( tmc2_patch ) );
       first += n;
     }
   }
@@ -679,19 +742,16 @@ int chainOverRanks( tmc2_gof_comm* comm, tmc2_frame** frames, int32_t count, con
   out.W = header[1], out.H = header[2];
   out.frames.resize( size_t( count ) );
   for ( int i = 0; i < count; ++i ) {
-    const uint8_t* at = comm->hostBlocks.data() + outFrame * size_t( i );
-    int64_t        hd[4];
-    memcpy( hd, at, 32 );
-    if ( hd[0] < 0 || hd[0] > int64_t( slotsN ) || hd[1] < 0 || hd[1] > int64_t( outPool ) || hd[3] != comm->passes ) {
+    Block::View v;
+    if ( !back.read( comm->hostBlocks.data() + back.bytes() * size_t( i ), comm->passes, v ) ) {
       t_err = "tmc2_gof_encode_sharded: the packed list of frame " + std::to_string( i ) + " did not arrive";
       return TMC2_E_STATE;
     }
     ChainResult::Frame& fr = out.frames[size_t( i )];
-    fr.list.resize( size_t( hd[0] ) ), fr.matches.resize( size_t( hd[0] ) ), fr.occupancy.resize( size_t( hd[1] ) );
-    memcpy( fr.list.data(), at + 32, size_t( hd[0] ) * sizeof( tmc2_patch ) );
-    memcpy( fr.matches.data(), at + 32 + slotsN * sizeof( tmc2_patch ), size_t( hd[0] ) * 4 );
-    memcpy( fr.occupancy.data(), at + 32 + slotsN * ( sizeof( tmc2_patch ) + 4 ), size_t( hd[1] ) );
-    fr.packedW = int32_t( hd[2] >> 32 ), fr.packedH = int32_t( hd[2] & 0xFFFFFFFF );
+    fr.list.resize( v.count ), fr.matches.resize( v.count ), fr.occupancy.assign( v.pool, v.pool + v.poolSize );
+    v.recordsTo( fr.list.data() );
+    if ( v.count ) memcpy( fr.matches.data(), v.matches, v.count * 4 );
+    fr.packedW = int32_t( v.tile >> 32 ), fr.packedH = int32_t( v.tile & 0xFFFFFFFF );
   }
   return TMC2_OK;
 }
@@ -761,7 +821,7 @@ extern "C" int tmc2_gof_comm_create( int rank, int worldSize, tmc2_ctx* ctx, con
     if ( const int rc = defaultRendezvous( worldSize, path ) ) return rc;
   NcclId id{};
   if ( rank == 0 ) {
-    COMM_TRY( comm->rccl.GetUniqueId( &id ), "ncclGetUniqueId" );
+    if ( const int rc = comm->rccl.GetUniqueId( &id ) ) return ncclFailed( comm, rc, "ncclGetUniqueId" );
     if ( worldSize > 1 ) {
       const std::string tmp = path + ".tmp." + std::to_string( long( getpid() ) );
       (void)unlink( path.c_str() ), (void)unlink( tmp.c_str() );
@@ -799,11 +859,11 @@ extern "C" int tmc2_gof_comm_create( int rank, int worldSize, tmc2_ctx* ctx, con
       std::this_thread::sleep_for( std::chrono::milliseconds( 5 ) );
     }
   }
-  COMM_TRY( comm->rccl.CommInitRank( &comm->comm, worldSize, id, rank ), "ncclCommInitRank" );
+  if ( const int rc = comm->rccl.CommInitRank( &comm->comm, worldSize, id, rank ) ) return ncclFailed( comm, rc, "ncclCommInitRank" );
   HIP_TRY( tmc2_ctx_device_alloc( ctx, 64, &comm->dSmall ), "tmc2_ctx_device_alloc" );
   int32_t probe = 100 + rank;  // pre-flight: one collective through the new communicator, checked
   {
-    const int rc = commMaxHeight( comm, &probe );
+    const int rc = commMax( comm, &probe, 1, "ncclAllReduce( height, max )" );
     if ( rank == 0 && worldSize > 1 ) unlink( path.c_str() );  // (every rank has read it -- or will never: the all-reduce is over)
     if ( rc != TMC2_OK ) return rc;
   }
@@ -824,279 +884,248 @@ extern "C" void tmc2_gof_comm_destroy( tmc2_gof_comm* comm ) {
   delete comm;
 }
 
+// ---- the steps of a pass, in the order encodeGof() takes them.  A step returns TMC2_OK to go on, anything else to leave the
+// pass with -- and where there are ranks every rank leaves at the same step (meet(), the weights, the chain's header).
 namespace {
-// One pass over the frames this process holds.  comm == nullptr: they are the whole GOF.  Otherwise they are this rank's share
-// (frame f of the GOF on rank f mod world): the weights come from rank 0, the canvas height is the maximum over the ranks, the
-// packed records of every frame end on rank 0.  THE RULE of the sharded pass: a rank that fails locally goes on through every
-// collective of the pass, with a value that says so -- nobody is ever left waiting for a rank that has returned.
-// resume: the frames are segmented and packed already (a pass that ended with "the GOF needs a larger canvas than the buffers hold"):
-// the pass starts at the canvas size, from what the packers left in the frames.
-int encodeGof( tmc2_gof_comm* comm, tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots, const tmc2_gof_config* config,
-               uint8_t** occupancy, uint8_t** occVideo, uint32_t** blockToPatch, uint16_t** geometryD0, uint16_t** geometryD1,
-               uint8_t** attribute, int32_t capacityWidth, int32_t capacityHeight, int32_t* width, int32_t* height,
-               int32_t recordSlots, tmc2_patch* gathered, int64_t* gatheredCounts, bool resume ) {
-  t_err.clear();
-  if ( !frames || !slotOf || !config || count <= 0 || slots <= 0 || !width || !height ) {
+int checkArguments( GofPass& s ) {
+  if ( !s.frames || !s.slotOf || !s.config || s.count <= 0 || s.slots <= 0 || !s.width || !s.height ) {
     t_err = "tmc2_gof_encode: invalid argument";
     return TMC2_E_INVALID;
   }
-  for ( int i = 0; i < count; ++i )
-    if ( !frames[i] || slotOf[i] < 0 || slotOf[i] >= slots ) {
-      t_err = "tmc2_gof_encode: frame " + std::to_string( i ) + " is null or on a slot outside [0, " + std::to_string( slots ) + ")";
+  for ( int i = 0; i < s.count; ++i )
+    if ( !s.frames[i] || s.slotOf[i] < 0 || s.slotOf[i] >= s.slots ) {
+      t_err = "tmc2_gof_encode: frame " + std::to_string( i ) + " is null or on a slot outside [0, " + std::to_string( s.slots ) + ")";
       return TMC2_E_INVALID;
     }
-  const tmc2_gof_config& c = *config;
+  const tmc2_gof_config& c = *s.config;
   if ( c.packing < 0 || c.packing > 2 ) {
     t_err = "tmc2_gof_encode: packing " + std::to_string( c.packing ) + " (0 all-intra, 1 low-delay, 2 random-access)";
     return TMC2_E_INVALID;
   }
-  if ( comm ) {
-    if ( const int rc = refuseBroken( comm ) ) return rc;
-    ++comm->passes;
+  if ( s.comm ) {
+    if ( const int rc = refuseBroken( s.comm ) ) return rc;
+    ++s.comm->passes;
   }
   // several ranks under a chained condition: the chain runs on rank 0 over the records (TMC2_GOF_RECORDS_CHAIN=1 forces that route
   // for a communicator of one rank too: the GPU tier runs it that way on a one-GPU box)
-  const bool chained = c.packing != 0, guess = !chained && c.guessCanvas != 0;
-  const bool recordsChain = comm && chained && ( comm->world > 1 || ( getenv( "TMC2_GOF_RECORDS_CHAIN" ) && atoi( getenv( "TMC2_GOF_RECORDS_CHAIN" ) ) != 0 ) );
-  const std::vector<int> cores = coresByCacheDomain();
-  Pass                   pass;
-  auto perSlot = [&]( auto fn ) {  // the frames of one slot in order, slots side by side
-    SlotThreads::instance().run( slots, cores, [&]( int sl ) {
-      for ( int i = 0; i < count; ++i )
-        if ( slotOf[i] == sl && pass.status.load() == TMC2_OK ) fn( i );
-    } );
-  };
-  for ( int i = 0; i < count && pass.status.load() == TMC2_OK && !resume; ++i ) {
-    const int rc = tmc2_frame_reset( frames[i] );
-    if ( rc != TMC2_OK ) pass.fail( rc, "tmc2_frame_reset" );
-  }
-  if ( !comm && pass.status.load() != TMC2_OK ) return pass.done();
-  double w[3] = {0, 0, 0};
-  if ( ( !comm || comm->rank == 0 ) && pass.status.load() == TMC2_OK && !resume ) {
-    const int rc = tmc2_weight_normal( frames[0], c.geometryBitDepth3D, 0.6, w );  // S0: frame 0 of the GOF only (rank 0's first)
-    if ( rc != TMC2_OK ) {
-      pass.fail( rc, "tmc2_weight_normal" );
-      if ( !comm ) return pass.done();
-    }
-  }
-  if ( comm && !resume ) {
-    // (no axis weight is negative: from a negative one the other ranks learn that rank 0 has no pass to offer)
-    if ( comm->rank == 0 && pass.status.load() != TMC2_OK ) w[0] = w[1] = w[2] = -1.0;
-    const int rc = commBroadcastWeights( comm, w );
-    if ( rc != TMC2_OK ) pass.fail( rc, "tmc2_gof_encode_sharded", t_err.c_str() );
-    if ( w[0] < 0.0 ) {  // (the same on every rank: all leave here)
-      if ( pass.status.load() != TMC2_OK ) return pass.done();
-      t_err = "tmc2_gof_encode_sharded: rank 0 could not start the pass (its own call says why)";
-      return TMC2_E_STATE;
-    }
-    if ( comm->broken ) return pass.done();
-  }
-  const tmc2_segmenter_params params = ctcParams( c, w );
-  std::vector<int32_t>        heights( static_cast<size_t>( count ), 0 ), guessW( static_cast<size_t>( count ), 0 ),
-      guessH( static_cast<size_t>( count ), 0 );
-  const bool anyOut = occupancy || occVideo || blockToPatch || geometryD0 || geometryD1 || attribute;  // (none: nothing leaves the device)
-  if ( !anyOut ) capacityWidth = capacityHeight = INT32_MAX;
-  // what follows the packing of one frame, on a canvas of W x H: S12-S22 and the copies of its finished canvases
-  auto images = [&]( int i, int32_t W, int32_t H ) {
-    if ( W > capacityWidth || H > capacityHeight ) return;  // (refused after the rendezvous, with the size the GOF needs)
-    GOF_TRY( tmc2_encoder_generate_geometry_images( frames[i], W, H, c.occupancyPrecision ) );
-    GOF_TRY( tmc2_encoder_generate_attribute_images( frames[i] ) );
-    auto at = []( auto** arr, int k ) { return arr ? arr[k] : nullptr; };
-    if ( occupancy || occVideo || blockToPatch || geometryD0 || geometryD1 )
-      GOF_TRY( tmc2_frame_get_geometry_images( frames[i], at( occupancy, i ), at( occVideo, i ), at( blockToPatch, i ), at( geometryD0, i ),
-                                               at( geometryD1, i ) ) );
-    if ( attribute && attribute[i] ) GOF_TRY( tmc2_frame_get_attribute_images( frames[i], attribute[i] ) );
-  };
-  // All-intra with guessCanvas: a frame does not wait for the others.  It goes through its whole chain on the canvas ITS OWN packed height gives
-  // (with the CTC sequences: the minimum canvas, for every frame); the rendezvous then only compares, and a frame whose guess
-  // was short rasterises again on the common canvas (same bytes as the two-phase order: the images depend on the final size only).
-  if ( pass.status.load() == TMC2_OK && !resume )
-    perSlot( [&]( int i ) {
-      GOF_TRY( tmc2_segmenter_compute( frames[i], &params ) );
-      if ( chained ) return;
-      GOF_TRY( tmc2_encoder_pack_flexible( frames[i], c.minimumImageWidth, 2, 1.0, &heights[size_t( i )] ) );
-      if ( !guess ) return;
-      GOF_TRY( tmc2_encoder_canvas_size( &heights[size_t( i )], 1, c.minimumImageWidth, c.minimumImageWidth, c.minimumImageHeight,
-                                         &guessW[size_t( i )], &guessH[size_t( i )] ) );
-      images( i, guessW[size_t( i )], guessH[size_t( i )] );
-    } );
-  int32_t W = 0, H = 0;
-  if ( resume ) {
-    // ---- the canvas of a GOF whose frames are packed: the tiles the packers left (tmc2_frame_get_packed_size) ---------------
-    int32_t words[3] = {0, c.minimumImageWidth, 0};  // failed?, widest tile, tallest tile
-    for ( int i = 0; i < count; ++i ) {
-      int32_t   pw = 0, ph = 0;
-      const int rc = tmc2_frame_get_packed_size( frames[i], &pw, &ph );
-      if ( rc != TMC2_OK ) pass.fail( rc, "tmc2_frame_get_packed_size" );
-      else if ( pw <= 0 ) pass.fail( TMC2_E_STATE, "tmc2_gof_encode_resume", "a frame is not packed (the pass to resume must have ended with 'the GOF needs a larger canvas')" );
-      words[1] = std::max( words[1], pw ), words[2] = std::max( words[2], ph );
-    }
-    if ( c.packing == 2 ) words[2] = std::max( words[2], c.minimumImageHeight );
-    if ( pass.status.load() != TMC2_OK ) words[0] = kFailedWord;
-    if ( comm ) {
-      const int rc = commMax( comm, words, 3, "ncclAllReduce( tile of the GOF, max )" );
-      if ( pass.status.load() != TMC2_OK ) return pass.done();
-      if ( rc != TMC2_OK ) return rc;
-      if ( words[0] != 0 ) {
-        t_err = "tmc2_gof_encode_sharded_resume: another rank's frames are not packed (its own call says why)";
-        return TMC2_E_STATE;
-      }
-    } else if ( pass.status.load() != TMC2_OK ) {
-      return pass.done();
-    }
-    const int rc = tmc2_encoder_canvas_size( &words[2], 1, words[1], c.minimumImageWidth, c.minimumImageHeight, &W, &H );
-    if ( rc != TMC2_OK ) {
-      pass.fail( rc, "tmc2_encoder_canvas_size" );
-      return pass.done();
-    }
-  } else if ( recordsChain ) {
-    // ---- the rendezvous of a sharded chained GOF: records to rank 0, the chain there, the packed lists back ------------------
-    ChainResult chain;
-    const int   rc = chainOverRanks( comm, frames, count, c, recordSlots, gathered, gatheredCounts, pass.done(), chain );
-    if ( rc != TMC2_OK ) return rc;  // (every rank leaves at the same place: chainOverRanks)
-    W = chain.W, H = chain.H;
-    // (installed before the buffers are looked at: a pass that ends with "the GOF needs a larger canvas" leaves its frames packed)
-    perSlot( [&]( int i ) {
-      const ChainResult::Frame& fr = chain.frames[size_t( i )];
-      GOF_TRY( tmc2_frame_set_packing( frames[i], fr.list.data(), int( fr.list.size() ), fr.matches.data(), fr.occupancy.data(),
-                                       int64_t( fr.occupancy.size() ), fr.packedW, fr.packedH ) );
-    } );
-  } else {
-    // (several ranks: a rank whose frames failed still goes to the rendezvous -- with a height no canvas has -- so that every rank
-    //  leaves the pass at the same place instead of waiting in a collective for one that has returned)
-    if ( pass.status.load() != TMC2_OK ) {
-      if ( comm ) {
-        const int   rc  = pass.done();
-        const auto  why = t_err;
-        int32_t     h   = kFailedWord;
-        (void)commMaxHeight( comm, &h );
-        t_err = why;
-        return rc;
-      }
-      return pass.done();
-    }
-    // ---- the rendezvous: the packing chain (if any) and the common canvas size -----------------------------------------------
-    int32_t tileW = c.minimumImageWidth, gofH = 0;
-    if ( chained ) {
-      auto once = [&]( int rc, const char* what ) {
-        if ( rc != TMC2_OK ) pass.fail( rc, what );
-        return rc == TMC2_OK;
-      };
-      bool ok = once( tmc2_encoder_pack_flexible( frames[0], c.minimumImageWidth, 2, 1.0, &heights[0] ), "tmc2_encoder_pack_flexible" );
-      for ( int i = 1; i < count && ok; ++i )
-        ok = once( tmc2_encoder_pack_spatial_consistency( frames[i], frames[i - 1], c.minimumImageWidth, 2, 1.0, &heights[size_t( i )] ),
-                   "tmc2_encoder_pack_spatial_consistency" );
-      if ( ok && c.packing == 2 ) {
-        std::vector<int32_t> widths( static_cast<size_t>( count ), 0 );
-        ok = once( tmc2_encoder_global_patch_allocation( frames, count, c.minimumImageWidth, c.minimumImageHeight, widths.data(), heights.data() ),
-                   "tmc2_encoder_global_patch_allocation" );
-        for ( int i = 0; i < count && ok; ++i ) {
-          tileW                = std::max( tileW, widths[size_t( i )] );
-          heights[size_t( i )] = std::max( heights[size_t( i )], c.minimumImageHeight );
-        }
-      } else {
-        for ( int i = 0; i < count && ok; ++i ) {
-          int32_t pw = 0;
-          ok         = once( tmc2_frame_get_packed_size( frames[i], &pw, nullptr ), "tmc2_frame_get_packed_size" );
-          tileW      = std::max( tileW, pw );
-        }
-      }
-    }
-    for ( int i = 0; i < count; ++i ) gofH = std::max( gofH, heights[size_t( i )] );
-    if ( comm ) {  // the one number the ranks of an all-intra GOF share
-      if ( pass.status.load() != TMC2_OK ) gofH = kFailedWord;
-      const int rc = commMaxHeight( comm, &gofH );
-      if ( pass.status.load() != TMC2_OK ) return pass.done();
-      if ( rc != TMC2_OK ) return rc;
-      if ( gofH == kFailedWord ) {
-        t_err = "tmc2_gof_encode_sharded: another rank's frames failed before the rendezvous (its own call says why)";
-        return TMC2_E_STATE;
-      }
-    } else if ( pass.status.load() != TMC2_OK ) {
-      return pass.done();
-    }
-    const int rc = tmc2_encoder_canvas_size( &gofH, 1, tileW, c.minimumImageWidth, c.minimumImageHeight, &W, &H );
-    if ( rc != TMC2_OK ) {  // (a function of the GOF's numbers: the same on every rank)
-      pass.fail( rc, "tmc2_encoder_canvas_size" );
-      return pass.done();
-    }
-  }
-  *width = W, *height = H;
-  if ( pass.status.load() != TMC2_OK && !comm ) return pass.done();
-  if ( W > capacityWidth || H > capacityHeight ) {  // (the same on every rank: W and H are the GOF's)
-    char msg[160];
-    std::snprintf( msg, sizeof( msg ), "tmc2_gof_encode: the GOF needs a %d x %d canvas, the buffers hold %d x %d", W, H, capacityWidth, capacityHeight );
-    t_err = msg;
-    return TMC2_E_INVALID;
-  }
-  // ---- from here the frames are independent: images, attribute images, copies, each on its slot -----------------------------
-  perSlot( [&]( int i ) {
-    if ( guess && !resume && guessW[size_t( i )] == W && guessH[size_t( i )] == H ) return;  // (already there)
-    images( i, W, H );
-  } );
-  if ( !comm ) return pass.done();
-  const int failed = pass.done();  // (a pass that failed after the rendezvous still takes part in the exchange)
-  if ( !recordsChain || resume ) return commGatherRecords( comm, frames, count, recordSlots, gathered, gatheredCounts, failed );
-  // the chained GOF left every record on rank 0 already; what the ranks still owe each other is whether the pass held
-  const std::string why = t_err;
-  int32_t           bad = failed != TMC2_OK ? 1 : 0;
-  const int         rc  = commMax( comm, &bad, 1, "ncclAllReduce( status of the pass, max )" );
-  if ( failed != TMC2_OK ) return t_err = why, failed;
-  if ( rc != TMC2_OK ) return rc;
-  if ( bad != 0 ) {
-    t_err = "tmc2_gof_encode_sharded: another rank's frames failed after the rendezvous (its own call says why)";
+  const char* forced = getenv( "TMC2_GOF_RECORDS_CHAIN" );
+  s.chained = c.packing != 0, s.guess = !s.chained && c.guessCanvas != 0;
+  s.recordsChain = s.comm && s.chained && ( s.comm->world > 1 || ( forced && atoi( forced ) != 0 ) );
+  s.cores = coresByCacheDomain();
+  s.heights.assign( size_t( s.count ), 0 ), s.guessW.assign( size_t( s.count ), 0 ), s.guessH.assign( size_t( s.count ), 0 );
+  const bool anyOut = s.occupancy || s.occVideo || s.blockToPatch || s.geometryD0 || s.geometryD1 || s.attribute;
+  if ( !anyOut ) s.capacityWidth = s.capacityHeight = INT32_MAX;  // (nothing leaves the device: no capacity to respect)
+  return TMC2_OK;
+}
+
+// every frame reset, S0 on frame 0 of the GOF (rank 0's first), its weights to every rank
+int resetAndWeights( GofPass& s ) {
+  if ( s.resume ) return TMC2_OK;
+  for ( int i = 0; i < s.count && !s.pass.failed(); ++i )
+    if ( const int rc = tmc2_frame_reset( s.frames[i] ) ) s.pass.failCall( rc, "tmc2_frame_reset" );
+  const bool root = !s.comm || s.comm->rank == 0;
+  if ( root && !s.pass.failed() )
+    if ( const int rc = tmc2_weight_normal( s.frames[0], s.config->geometryBitDepth3D, 0.6, s.weights ) ) s.pass.failCall( rc, "tmc2_weight_normal" );
+  if ( !s.comm ) return s.pass.done();
+  // (no axis weight is negative: from a negative one the other ranks learn that rank 0 has no pass to offer)
+  if ( root && s.pass.failed() ) s.weights[0] = s.weights[1] = s.weights[2] = -1.0;
+  if ( const int rc = commBroadcast( s.comm, s.weights, 3, kNcclFloat64, 8, "ncclBroadcast( weights )" ) ) s.pass.fail( rc, "tmc2_gof_encode_sharded: " + t_err );
+  if ( s.weights[0] < 0.0 ) {  // (the same on every rank: all leave here)
+    if ( s.pass.failed() ) return s.pass.done();
+    t_err = "tmc2_gof_encode_sharded: rank 0 could not start the pass (its own call says why)";
     return TMC2_E_STATE;
   }
+  return s.comm->broken ? s.pass.done() : TMC2_OK;
+}
+
+// what follows the packing of one frame, on a canvas of W x H: S12-S22 and the copies of its finished canvases
+void images( GofPass& s, int i, int32_t W, int32_t H ) {
+  if ( W > s.capacityWidth || H > s.capacityHeight ) return;  // (refused after the rendezvous, with the size the GOF needs)
+  tmc2_frame* f = s.frames[i];
+  GOF_TRY( tmc2_encoder_generate_geometry_images( f, W, H, s.config->occupancyPrecision ) );
+  GOF_TRY( tmc2_encoder_generate_attribute_images( f ) );
+  auto at = []( auto** arr, int k ) { return arr ? arr[k] : nullptr; };
+  if ( s.occupancy || s.occVideo || s.blockToPatch || s.geometryD0 || s.geometryD1 )
+    GOF_TRY( tmc2_frame_get_geometry_images( f, at( s.occupancy, i ), at( s.occVideo, i ), at( s.blockToPatch, i ), at( s.geometryD0, i ),
+                                             at( s.geometryD1, i ) ) );
+  if ( s.attribute && s.attribute[i] ) GOF_TRY( tmc2_frame_get_attribute_images( f, s.attribute[i] ) );
+}
+
+// S1-S9 per frame and, all-intra, the frame's own packing.  With guessCanvas a frame does not wait for the others: it goes through
+// its whole chain on the canvas ITS OWN packed height gives (with the CTC sequences: the minimum canvas, for every frame); the
+// rendezvous then only compares, and a frame whose guess was short rasterises again on the common canvas (same bytes as the
+// two-phase order: the images depend on the final size only).
+void segmentAndPack( GofPass& s ) {
+  if ( s.resume || s.pass.failed() ) return;
+  const tmc2_gof_config&      c      = *s.config;
+  const tmc2_segmenter_params params = ctcParams( c, s.weights );
+  perSlot( s, [&]( int i ) {
+    int32_t& h = s.heights[size_t( i )];
+    GOF_TRY( tmc2_segmenter_compute( s.frames[i], &params ) );
+    if ( s.chained ) return;
+    GOF_TRY( tmc2_encoder_pack_flexible( s.frames[i], c.minimumImageWidth, 2, 1.0, &h ) );
+    if ( !s.guess ) return;
+    GOF_TRY( tmc2_encoder_canvas_size( &h, 1, c.minimumImageWidth, c.minimumImageWidth, c.minimumImageHeight, &s.guessW[size_t( i )], &s.guessH[size_t( i )] ) );
+    images( s, i, s.guessW[size_t( i )], s.guessH[size_t( i )] );
+  } );
+}
+
+// the canvas of a GOF from its widest and tallest tile (a function of the GOF's numbers: the same on every rank)
+int canvasOf( GofPass& s, int32_t tileW, int32_t tileH ) {
+  const tmc2_gof_config& c = *s.config;
+  if ( const int rc = tmc2_encoder_canvas_size( &tileH, 1, tileW, c.minimumImageWidth, c.minimumImageHeight, &s.W, &s.H ) ) s.pass.failCall( rc, "tmc2_encoder_canvas_size" );
+  return s.pass.done();
+}
+
+// route 1, resume: the frames are packed -- the tiles the packers left (tmc2_frame_get_packed_size)
+int canvasFromTiles( GofPass& s ) {
+  const tmc2_gof_config& c = *s.config;
+  int32_t words[3] = {0, c.minimumImageWidth, 0};  // failed?, widest tile, tallest tile
+  for ( int i = 0; i < s.count; ++i ) {
+    int32_t   pw = 0, ph = 0;
+    const int rc = tmc2_frame_get_packed_size( s.frames[i], &pw, &ph );
+    if ( rc != TMC2_OK ) s.pass.failCall( rc, "tmc2_frame_get_packed_size" );
+    else if ( pw <= 0 ) s.pass.fail( TMC2_E_STATE, "tmc2_gof_encode_resume: a frame is not packed (the pass to resume must have ended with 'the GOF needs a larger canvas')" );
+    words[1] = std::max( words[1], pw ), words[2] = std::max( words[2], ph );
+  }
+  if ( c.packing == 2 ) words[2] = std::max( words[2], c.minimumImageHeight );
+  if ( const int rc = meet( s, words, 3, "ncclAllReduce( tile of the GOF, max )", "are not packed" ) ) return rc;
+  return canvasOf( s, words[1], words[2] );
+}
+
+// route 2, several ranks under a chained condition: records to rank 0, the chain there, the packed lists back
+int canvasThroughChain( GofPass& s ) {
+  ChainResult chain;
+  if ( const int rc = chainOverRanks( s, chain ) ) return rc;  // (every rank leaves at the same place: chainOverRanks)
+  s.W = chain.W, s.H = chain.H;
+  // (installed before the buffers are looked at: a pass that ends with "the GOF needs a larger canvas" leaves its frames packed)
+  perSlot( s, [&]( int i ) {
+    const ChainResult::Frame& fr = chain.frames[size_t( i )];
+    GOF_TRY( tmc2_frame_set_packing( s.frames[i], fr.list.data(), int( fr.list.size() ), fr.matches.data(), fr.occupancy.data(),
+                                     int64_t( fr.occupancy.size() ), fr.packedW, fr.packedH ) );
+  } );
   return TMC2_OK;
+}
+
+// the packing chain over frames that all live here, in frame order on the calling thread -> the widest tile
+int32_t chainHere( GofPass& s ) {
+  const tmc2_gof_config& c = *s.config;
+  int32_t                tileW = c.minimumImageWidth;
+  auto once = [&]( int rc, const char* what ) {
+    if ( rc != TMC2_OK ) s.pass.failCall( rc, what );
+    return rc == TMC2_OK;
+  };
+  bool ok = once( tmc2_encoder_pack_flexible( s.frames[0], c.minimumImageWidth, 2, 1.0, &s.heights[0] ), "tmc2_encoder_pack_flexible" );
+  for ( int i = 1; i < s.count && ok; ++i )
+    ok = once( tmc2_encoder_pack_spatial_consistency( s.frames[i], s.frames[i - 1], c.minimumImageWidth, 2, 1.0, &s.heights[size_t( i )] ),
+               "tmc2_encoder_pack_spatial_consistency" );
+  if ( ok && c.packing == 2 ) {
+    std::vector<int32_t> widths( static_cast<size_t>( s.count ), 0 );
+    ok = once( tmc2_encoder_global_patch_allocation( s.frames, s.count, c.minimumImageWidth, c.minimumImageHeight, widths.data(), s.heights.data() ),
+               "tmc2_encoder_global_patch_allocation" );
+    for ( int i = 0; i < s.count && ok; ++i ) {
+      tileW                  = std::max( tileW, widths[size_t( i )] );
+      s.heights[size_t( i )] = std::max( s.heights[size_t( i )], c.minimumImageHeight );
+    }
+  } else {
+    for ( int i = 0; i < s.count && ok; ++i ) {
+      int32_t pw = 0;
+      ok         = once( tmc2_frame_get_packed_size( s.frames[i], &pw, nullptr ), "tmc2_frame_get_packed_size" );
+      tileW      = std::max( tileW, pw );
+    }
+  }
+  return tileW;
+}
+
+// route 3: the heights the packers gave (all-intra: per frame, above; chained: the chain over the frames here), and -- the one
+// number the ranks of an all-intra GOF share -- their maximum over the ranks
+int canvasFromHeights( GofPass& s ) {
+  const int32_t tileW = s.chained && !s.pass.failed() ? chainHere( s ) : s.config->minimumImageWidth;
+  int32_t       gofH  = 0;
+  for ( int i = 0; i < s.count; ++i ) gofH = std::max( gofH, s.heights[size_t( i )] );
+  if ( const int rc = meet( s, &gofH, 1, "ncclAllReduce( height, max )", "failed before the rendezvous" ) ) return rc;
+  return canvasOf( s, tileW, gofH );
+}
+
+int refuseACanvasBeyondTheBuffers( GofPass& s ) {  // (the same on every rank: W and H are the GOF's)
+  *s.width = s.W, *s.height = s.H;
+  if ( s.W <= s.capacityWidth && s.H <= s.capacityHeight ) return TMC2_OK;
+  char msg[160];
+  std::snprintf( msg, sizeof( msg ), "tmc2_gof_encode: the GOF needs a %d x %d canvas, the buffers hold %d x %d", s.W, s.H, s.capacityWidth, s.capacityHeight );
+  t_err = msg;
+  return TMC2_E_INVALID;
+}
+
+// from here the frames are independent: images, attribute images, copies, each on its slot
+void imagesAndCopies( GofPass& s ) {
+  perSlot( s, [&]( int i ) {
+    if ( s.guess && !s.resume && s.guessW[size_t( i )] == s.W && s.guessH[size_t( i )] == s.H ) return;  // (already there)
+    images( s, i, s.W, s.H );
+  } );
+}
+
+// (a pass that failed after the rendezvous still takes part in the exchange.)  A chained GOF left every record on rank 0 already;
+// what its ranks still owe each other is whether the pass held.
+int closePass( GofPass& s ) {
+  if ( s.comm && ( !s.recordsChain || s.resume ) ) return commGatherRecords( s );
+  int32_t bad = 0;
+  return meet( s, &bad, 1, "ncclAllReduce( status of the pass, max )", "failed after the rendezvous" );
+}
+
+int encodeGof( GofPass& s ) {
+  t_err.clear();
+  if ( const int rc = checkArguments( s ) ) return rc;
+  if ( const int rc = resetAndWeights( s ) ) return rc;
+  segmentAndPack( s );
+  if ( const int rc = s.resume ? canvasFromTiles( s ) : s.recordsChain ? canvasThroughChain( s ) : canvasFromHeights( s ) ) return rc;
+  if ( const int rc = refuseACanvasBeyondTheBuffers( s ) ) return rc;
+  imagesAndCopies( s );
+  return closePass( s );
+}
+
+// (nothing may leave through the C boundary but a status: what the CALLING thread throws -- a std::bad_alloc, a std::system_error
+//  of the thread pool -- is caught here; what a slot thread throws fails the pass where it is caught, SlotThreads::run)
+int guarded( GofPass& s ) {
+  try {
+    return encodeGof( s );
+  } catch ( const std::exception& e ) {
+    t_err = std::string( "tmc2_gof_encode: " ) + e.what();
+  } catch ( ... ) {
+    t_err = "tmc2_gof_encode: unknown exception";
+  }
+  return TMC2_E_STATE;
 }
 }  // namespace
 
-// (nothing may leave through the C boundary but a status: a std::bad_alloc / std::system_error of the thread pool included)
-template <typename F>
-static int guarded( F&& f ) {
-  try {
-    return f();
-  } catch ( const std::exception& e ) {
-    t_err = std::string( "tmc2_gof_encode: " ) + e.what();
-    return TMC2_E_STATE;
-  } catch ( ... ) {
-    t_err = "tmc2_gof_encode: unknown exception";
-    return TMC2_E_STATE;
-  }
+// the entries: one pass each, told apart by the communicator (none: the frames are the whole GOF) and by where the pass starts
+static int run( tmc2_gof_comm* comm, bool resume, tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots,
+                const tmc2_gof_config* config, uint8_t** occupancy, uint8_t** occVideo, uint32_t** blockToPatch, uint16_t** geometryD0,
+                uint16_t** geometryD1, uint8_t** attribute, int32_t capacityWidth, int32_t capacityHeight, int32_t* width, int32_t* height,
+                int32_t recordSlots = 0, tmc2_patch* gathered = nullptr, int64_t* gatheredCounts = nullptr ) {
+  GofPass s{comm,      frames,        slotOf,         count, slots,  config,      occupancy, occVideo,       blockToPatch, geometryD0, geometryD1,
+            attribute, capacityWidth, capacityHeight, width, height, recordSlots, gathered,  gatheredCounts, resume};
+  return guarded( s );
+}
+static int shardedArguments( tmc2_gof_comm* comm, int32_t recordSlots ) {  // -> what the sharded entries refuse before the pass
+  if ( comm && recordSlots > 0 ) return TMC2_OK;
+  t_err = "tmc2_gof_encode_sharded: invalid argument";
+  return TMC2_E_INVALID;
 }
 
 extern "C" int tmc2_gof_encode( tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots, const tmc2_gof_config* config,
                                 uint8_t** occupancy, uint8_t** occVideo, uint32_t** blockToPatch, uint16_t** geometryD0,
                                 uint16_t** geometryD1, uint8_t** attribute, int32_t capacityWidth, int32_t capacityHeight,
                                 int32_t* width, int32_t* height ) {
-  return guarded( [&] {
-    return encodeGof( nullptr, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
-                      capacityWidth, capacityHeight, width, height, 0, nullptr, nullptr, false );
-  } );
+  return run( nullptr, false, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
+              capacityWidth, capacityHeight, width, height );
 }
 
 extern "C" int tmc2_gof_encode_resume( tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots, const tmc2_gof_config* config,
                                        uint8_t** occupancy, uint8_t** occVideo, uint32_t** blockToPatch, uint16_t** geometryD0,
                                        uint16_t** geometryD1, uint8_t** attribute, int32_t capacityWidth, int32_t capacityHeight,
                                        int32_t* width, int32_t* height ) {
-  return guarded( [&] {
-    return encodeGof( nullptr, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
-                      capacityWidth, capacityHeight, width, height, 0, nullptr, nullptr, true );
-  } );
-}
-
-static int sharded( bool resume, tmc2_gof_comm* comm, tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots,
-                    const tmc2_gof_config* config, uint8_t** occupancy, uint8_t** occVideo, uint32_t** blockToPatch, uint16_t** geometryD0,
-                    uint16_t** geometryD1, uint8_t** attribute, int32_t capacityWidth, int32_t capacityHeight, int32_t* width, int32_t* height,
-                    int32_t recordSlots, tmc2_patch* gathered, int64_t* gatheredCounts ) {
-  if ( !comm || recordSlots <= 0 ) {
-    t_err = "tmc2_gof_encode_sharded: invalid argument";
-    return TMC2_E_INVALID;
-  }
-  return guarded( [&] {
-    return encodeGof( comm, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
-                      capacityWidth, capacityHeight, width, height, recordSlots, gathered, gatheredCounts, resume );
-  } );
+  return run( nullptr, true, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
+              capacityWidth, capacityHeight, width, height );
 }
 
 extern "C" int tmc2_gof_encode_sharded( tmc2_gof_comm* comm, tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots,
@@ -1104,8 +1133,9 @@ extern "C" int tmc2_gof_encode_sharded( tmc2_gof_comm* comm, tmc2_frame** frames
                                         uint16_t** geometryD0, uint16_t** geometryD1, uint8_t** attribute, int32_t capacityWidth,
                                         int32_t capacityHeight, int32_t* width, int32_t* height, int32_t recordSlots, tmc2_patch* gathered,
                                         int64_t* gatheredCounts ) {
-  return sharded( false, comm, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
-                  capacityWidth, capacityHeight, width, height, recordSlots, gathered, gatheredCounts );
+  if ( const int rc = shardedArguments( comm, recordSlots ) ) return rc;
+  return run( comm, false, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
+              capacityWidth, capacityHeight, width, height, recordSlots, gathered, gatheredCounts );
 }
 
 extern "C" int tmc2_gof_encode_sharded_resume( tmc2_gof_comm* comm, tmc2_frame** frames, const int32_t* slotOf, int32_t count, int32_t slots,
@@ -1113,6 +1143,7 @@ extern "C" int tmc2_gof_encode_sharded_resume( tmc2_gof_comm* comm, tmc2_frame**
                                                uint32_t** blockToPatch, uint16_t** geometryD0, uint16_t** geometryD1, uint8_t** attribute,
                                                int32_t capacityWidth, int32_t capacityHeight, int32_t* width, int32_t* height,
                                                int32_t recordSlots, tmc2_patch* gathered, int64_t* gatheredCounts ) {
-  return sharded( true, comm, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
-                  capacityWidth, capacityHeight, width, height, recordSlots, gathered, gatheredCounts );
+  if ( const int rc = shardedArguments( comm, recordSlots ) ) return rc;
+  return run( comm, true, frames, slotOf, count, slots, config, occupancy, occVideo, blockToPatch, geometryD0, geometryD1, attribute,
+              capacityWidth, capacityHeight, width, height, recordSlots, gathered, gatheredCounts );
 }

@@ -30,6 +30,7 @@ TMC2GOF = """
 int tmc2_gof_encode(tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*)
 int tmc2_gof_encode_resume(tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*)
 const char* tmc2_gof_last_error(void)
+int tmc2_gof_slot_core(int)
 int tmc2_gof_comm_create(int, int, tmc2_ctx*, const char*, tmc2_gof_comm**)
 void tmc2_gof_comm_destroy(tmc2_gof_comm*)
 int tmc2_gof_encode_sharded(tmc2_gof_comm*, tmc2_frame**, const int32_t*, int32_t, int32_t, const tmc2_gof_config*, uint8_t**, uint8_t**, uint32_t**, uint16_t**, uint16_t**, uint8_t**, int32_t, int32_t, int32_t*, int32_t*, int32_t, tmc2_patch*, int64_t*)

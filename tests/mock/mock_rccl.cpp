@@ -134,6 +134,8 @@ int ncclGroupEnd() {
 int ncclSend( const void* buf, size_t count, int type, int peer, void* comm, void* ) {
   Comm* c = static_cast<Comm*>( comm );
   log( c, "send " + std::to_string( count * width( type ) ) + " to " + std::to_string( peer ) );
+  if ( const char* failing = getenv( "MOCK_RCCL_SEND_FAIL" ) )  // (MOCK_RCCL_SEND_FAIL=<rank>: that rank's sends are refused when they are enqueued)
+    if ( atoi( failing ) == c->rank ) return 3;
   c->pending.push_back( {true, const_cast<void*>( buf ), count * width( type ), peer} );
   return c->grouped ? 0 : flush( c );
 }
@@ -143,5 +145,5 @@ int ncclRecv( void* buf, size_t count, int type, int peer, void* comm, void* ) {
   c->pending.push_back( {false, buf, count * width( type ), peer} );
   return c->grouped ? 0 : flush( c );
 }
-const char* ncclGetErrorString( int rc ) { return rc == 1 ? "mock: peer never arrived" : rc == 4 ? "mock: unexpected arguments" : "mock error"; }
+const char* ncclGetErrorString( int rc ) { return rc == 1 ? "mock: peer never arrived" : rc == 4 ? "mock: unexpected arguments" : rc == 3 ? "mock: send refused" : "mock error"; }
 }

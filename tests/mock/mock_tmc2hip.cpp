@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -13,7 +14,7 @@
 #include "tmc2hip.h"
 
 struct tmc2_frame {
-  int32_t id, packedHeight, packedWidth, failAt;  // failAt: the call code that fails on this frame (0: none)
+  int32_t id, packedHeight, packedWidth, failAt;  // failAt: the call code that fails on this frame (0: none; -code: that call throws std::bad_alloc)
   int32_t canvasW, canvasH;
 };
 
@@ -32,6 +33,7 @@ int note( int call, tmc2_frame* f, int a = 0, int b = 0 ) {
     std::lock_guard<std::mutex> g( g_lock );
     g_log.push_back( {call, f ? f->id : -1, a, b, uint64_t( std::hash<std::thread::id>()( std::this_thread::get_id() ) )} );
   }
+  if ( f && f->failAt == -call ) throw std::bad_alloc();
   if ( f && f->failAt == call ) {
     char msg[96];
     std::snprintf( msg, sizeof( msg ), "mock failure of call %d on frame %d", call, f->id );

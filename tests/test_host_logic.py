@@ -34,7 +34,7 @@ def test_native_gof_host_exports_its_header_and_refuses_bad_arguments():
     hdr = open(os.path.join(ROOT, "include", "tmc2gof.h")).read()
     names = sorted(set(re.findall(r"\b(tmc2_gof_[a-z0-9_]+)\s*\(", hdr)))
     assert names == ["tmc2_gof_comm_create", "tmc2_gof_comm_destroy", "tmc2_gof_encode", "tmc2_gof_encode_resume", "tmc2_gof_encode_sharded",
-                     "tmc2_gof_encode_sharded_resume", "tmc2_gof_last_error"]
+                     "tmc2_gof_encode_sharded_resume", "tmc2_gof_last_error", "tmc2_gof_slot_core"]
     G = native_gof.load_library()
     assert not [n for n in names if not hasattr(G, n)]
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
@@ -48,6 +48,19 @@ def test_native_gof_host_exports_its_header_and_refuses_bad_arguments():
     assert G.tmc2_gof_encode(handles, slot, 1, 1, C.byref(cfg), none, none, none, none, none, none, 1280, 1280, C.byref(W), C.byref(H)) == invalid
     handles, slot = (C.c_void_p * 1)(1), (C.c_int32 * 1)(3)   # slot out of range: refused before the handle is touched
     assert G.tmc2_gof_encode(handles, slot, 1, 2, C.byref(cfg), none, none, none, none, none, none, 1280, 1280, C.byref(W), C.byref(H)) == invalid
+
+
+def test_native_gof_host_names_the_core_of_a_slot():
+    """tmc2_gof_slot_core: the core a pass pins a slot's thread to -- one of the CPUs this process may run on, or -1 where the cache
+    topology cannot be read -- and the same answer every time (the list is kept)."""
+    from tmc2_amd import native_gof
+    G = native_gof.load_library()
+    allowed = os.sched_getaffinity(0)
+    first = [G.tmc2_gof_slot_core(s) for s in range(40)]
+    assert all(c == -1 or c in allowed for c in first), (first, sorted(allowed))
+    assert len({c == -1 for c in first}) == 1                                     # (readable for every slot or for none)
+    assert [G.tmc2_gof_slot_core(s) for s in range(40)] == first
+    assert G.tmc2_gof_slot_core(-1) == -1
 
 
 def test_every_declared_symbol_is_bound_and_documented():
@@ -564,8 +577,8 @@ def test_every_bench_configuration_has_its_reference_fixture():
 
 def test_native_front_end_builds_and_fails_loudly_without_a_gpu(tmp_path):
     """integration/tmc2_encode_gof.cpp (a C++ host front end over the C-ABI, the whole GOF path) compiles against
-    include/tmc2hip.h alone and, on a machine without an MI355X, stops with the library's "no device" error instead of
-    computing anything on the CPU."""
+    include/tmc2hip.h and include/tmc2gof.h -- its pass is libtmc2gof.so's -- and, on a machine without an MI355X, stops with
+    the library's "no device" error instead of computing anything on the CPU."""
     import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -202,6 +202,41 @@ def test_a_failing_call_ends_the_pass_with_its_status_and_message(runner, call, 
         assert not [e for e in log if e[0] >= GEOMETRY]
 
 
+def test_a_throwing_slot_job_fails_the_pass(runner):
+    """An exception out of a slot job (here std::bad_alloc out of a frame's segmentation: a negative call code) is not swallowed: the
+    pass fails with TMC2_E_STATE and "slot thread: <what()>" before the slot counts as done, no later phase starts, and -- nothing
+    having unwound a parked thread -- the next pass runs clean on the same threads."""
+    rc, _, log, _, _ = run(runner, [100] * 8, 4, 0, fail=(3, -SEGMENT))
+    msg = runner[1].tmc2_gof_last_error().decode()
+    assert rc == -5 and "slot thread" in msg and "bad_alloc" in msg, (rc, msg)     # TMC2_E_STATE
+    assert (SEGMENT, 3) in [e[:2] for e in log] and not [e for e in log if e[0] >= GEOMETRY]
+    threw = {e[4] for e in log if e[0] == SEGMENT}
+    rc, size, log, occ, _ = run(runner, [100] * 8, 4, 0)
+    assert rc == 0 and size == (MIN_W, MIN_H), runner[1].tmc2_gof_last_error()
+    for f in range(8):
+        assert per_frame(log, f) == [RESET, SEGMENT, PACK_FLEXIBLE, GEOMETRY, ATTRIBUTE, GET_GEOMETRY, GET_ATTRIBUTE]
+    clean = {e[4] for e in log if e[0] == SEGMENT}
+    assert len(clean) == 4 and threw <= clean
+
+
+@pytest.mark.parametrize("sanitizer", [None, "thread", "address,undefined"])
+def test_the_runner_as_a_program_plain_and_under_the_host_sanitizers(tmp_path, sanitizer):
+    """tests/helpers/gof_runner_check.cpp: the runner and the recorder linked into one program with its own main -- the three packing
+    conditions, a failing and a throwing call, two callers at once -- built plain, with ThreadSanitizer and with AddressSanitizer +
+    UBSan, and run as a process of its own: exit status 0 and nothing on stderr.  (Nothing is preloaded, nothing here runs in python.)"""
+    exe = str(tmp_path / "gof_runner_check")
+    build = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] +
+                           (["-fsanitize=" + sanitizer, "-fno-omit-frame-pointer", "-fno-sanitize-recover=all"] if sanitizer else []) +
+                           [os.path.join(ROOT, "tests", "helpers", "gof_runner_check.cpp"), os.path.join(ROOT, "tests", "mock", "mock_tmc2hip.cpp"),
+                            os.path.join(ROOT, "mpeg-pcc-tmc2_amd", "host", "gof_runner.cpp"), "-o", exe, "-pthread", "-ldl"],
+                           capture_output=True, text=True)
+    if sanitizer and build.returncode != 0 and ("cannot find" in build.stderr or "sanitizer" in build.stderr.lower()):
+        pytest.skip("no runtime for -fsanitize=%s here: %s" % (sanitizer, build.stderr.strip()[-300:]))
+    assert build.returncode == 0, build.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stdout, r.stderr)
+
+
 # ---- the sharded mode: one process per rank, RCCL replaced by a recorder that moves the bytes through files -------------------------
 class _Patch(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("index", "viewId", "normalAxis", "tangentAxis", "bitangentAxis", "projectionMode", "u1", "v1", "d1",
@@ -437,6 +472,20 @@ def test_a_rank_that_never_arrives_ends_the_wait_after_the_timeout(sharded_libs)
     assert x["rc"] == -5 and "no answer from the other ranks" in x["err"] and "aborted" in x["err"], x
     assert "abort" in x["rccl"]
     assert x["again"][0] == -5 and "make a new one" in x["again"][1], x["again"]
+
+
+def test_a_failed_enqueue_inside_a_group_closes_the_group(sharded_libs):
+    """Rank 1's ncclSend of the final gather is refused when it is enqueued (MOCK_RCCL_SEND_FAIL): the group it stands in is still
+    closed -- an open group is the thread's and would swallow the calls of the next communicator made on it -- then the communicator
+    is aborted and the call returns the enqueue's own error.  Nobody hangs: rank 0, whose receive is never answered, returns by the
+    watchdog."""
+    res = _run_world(sharded_libs, 2, 2, [64] * 4, env={"MOCK_RCCL_SEND_FAIL": "1", "TMC2_GOF_COLLECTIVE_TIMEOUT": "1.5"})
+    x = res[1]
+    assert x["rc"] != 0 and "mock: send refused" in x["err"], x
+    calls = [c.split()[0] for c in x["rccl"]]
+    after = calls[calls.index("send") + 1:]
+    assert "group" in after and "abort" in after[after.index("group"):], x["rccl"]
+    assert res[0]["rc"] == -5 and "no answer from the other ranks" in res[0]["err"], res[0]
 
 
 def _plant_stale(path):
