@@ -450,7 +450,10 @@ int tmc2_codec_color_point_cloud( tmc2_frame* f, const uint16_t* attribute );
 /* replaces: PCCCodec::smoothPointCloudPostprocess (PCCCodec.cpp:54-148, gridSmoothing branch: addGridCentroid :982,
  * gridFiltering :1002, smoothPointCloudGrid :1067).  Boundary points that the trilinear blend of the cell centroids
  * pulls further than the threshold are moved there; their boundary type becomes 3.  Runs
- * tmc2_codec_identify_boundary_points first if that has not happened.                                                */
+ * tmc2_codec_identify_boundary_points first if that has not happened.  gridSize: an even size of 2 .. 64; any other is refused
+ * (TMC2_E_UNSUPPORTED, the message names gridSize) before anything is allocated or launched, and the frame stays as it was --
+ * with an odd size the 2x2x2 cells of a point next to the upper faces are not all inside the grid, and the reference writes
+ * outside its cellIndex (PCCCodec.cpp:99-106).  A cell of more than 65535 points or a coordinate sum beyond 2^24 is refused too.  */
 int tmc2_codec_smooth_point_cloud_postprocess( tmc2_frame* f, int gridSize, double thresholdSmoothing );
 /* replaces: PCCPointSet3::transferColors16bitBP (PccLibCommon/source/PCCPointSet.cpp:1126-1470) with filterType 1 and the
  * arguments of PCCEncoder.cpp:657-672 / PCCDecoder.cpp:416-431: source = the cloud before smoothing with its 16-bit

@@ -14,7 +14,10 @@
 namespace tmc2 {
 
 struct CellGrid {
-  int gridSize, half, w, disth, th;  // w cells a side, th = gridSize * w; any gridSize (T3 takes 2..64): divisions, not shifts
+  // w cells a side, th = gridSize * w.  Any EVEN gridSize (T3 takes the even sizes of 2..64): divisions, not shifts.  Even, because
+  // only then is half the cell's middle and do the 2x2x2 cells of every point inside the faces lie in the grid; with an odd size a
+  // point at th - half - 1 has lowerCell == w - 1 and names cell w
+  int gridSize, half, w, disth, th;
   // too close to a face: such a point marks nothing and is not filtered
   TMC2_HD bool outside( int x, int y, int z ) const {
     return x < disth || y < disth || z < disth || th <= x + disth || th <= y + disth || th <= z + disth;

@@ -11,7 +11,7 @@ __global__ __launch_bounds__( 256 ) void markCellsKernel( const Pt* __restrict__
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if ( i >= M || btype[i] != 1 ) return;
   const Pt p = pts[i];
-  if ( g.outside( p.x, p.y, p.z ) ) return;  // (inside the faces: the eight cells lie in the grid)
+  if ( g.outside( p.x, p.y, p.z ) ) return;  // (inside the faces and gridSize even: the eight cells lie in the grid)
   const int qx = g.lowerCell( p.x ), qy = g.lowerCell( p.y ), qz = g.lowerCell( p.z );
   for ( int k = 0; k < 8; ++k ) {
     const uint32_t key = g.key( qx + ( k & 1 ), qy + ( ( k >> 1 ) & 1 ), qz + ( k >> 2 ) );

@@ -332,11 +332,14 @@ int colorPointCloud( tmc2_frame* f, const uint16_t* attribute ) {
 
 int smoothPointCloudGrid( tmc2_frame* f, int gridSize, double thresholdSmoothing ) {
   TMC2_TRY( needReconstruction( f, "smoothPointCloudPostprocess" ) );
-  if ( !f->haveBoundaryTypes || f->haveSmoothed ) TMC2_TRY( identifyBoundaryPoints( f ) );  // (a previous run left 3s behind)
-  if ( gridSize < 2 || gridSize > 64 ) {
-    setError( "smoothPointCloudPostprocess: gridSize %d unsupported", gridSize );
+  // (refused before anything is allocated or launched: the frame stays as it was.  An odd size leaves half = gridSize / 2 short of
+  //  the cell's middle: a point at th - half - 1 is inside the faces, sits in the upper half of the last cell and names cell w --
+  //  the next row, or past the w^3 cells of the grid; the reference writes outside its cellIndex there, PCCCodec.cpp:99-106)
+  if ( gridSize < 2 || gridSize > 64 || gridSize % 2 ) {
+    setError( "smoothPointCloudPostprocess: gridSize %d unsupported (even sizes 2..64)", gridSize );
     return TMC2_E_UNSUPPORTED;
   }
+  if ( !f->haveBoundaryTypes || f->haveSmoothed ) TMC2_TRY( identifyBoundaryPoints( f ) );  // (a previous run left 3s behind)
   tmc2_ctx*      ctx = f->ctx;
   hipStream_t    s   = ctx->stream;
   const uint32_t M   = uint32_t( f->reconCount );
@@ -369,6 +372,7 @@ int smoothPointCloudGrid( tmc2_frame* f, int gridSize, double thresholdSmoothing
   TMC2_HIP( hipStreamSynchronize( s ) );
   TMC2_HIP( hipGetLastError() );
   if ( err ) {
+    f->haveBoundaryTypes = false;  // (the filter ran and left 3s behind: the next stage that needs the types identifies them again)
     setError( "smoothPointCloudPostprocess: a grid cell holds more than 65535 points or a coordinate sum beyond 2^24 (the "
               "reference's uint16 count / float sum leave their exact range there)" );
     return TMC2_E_UNSUPPORTED;

@@ -78,6 +78,9 @@ int orc_color_point_cloud( const uint32_t* pointToPixel, int64_t M, const uint16
 // T3.  xyz in/out, btype in/out (moved points become 3); partition = patch index (list position) of every point.
 int orc_smooth_point_cloud_grid( int16_t* xyz, uint16_t* btype, const uint32_t* partition, int64_t M, int gridSize,
                                  double thresholdSmoothing ) {
+  // an odd size is not restated: gridSize / 2 is short of the cell's middle, a boundary point at th - gridSize / 2 - 1 names cell w
+  // and the reference writes outside cellIndex (:99-106); -1, nothing touched
+  if ( gridSize < 2 || gridSize % 2 ) return -1;
   if ( M == 0 ) return 0;
   int maxSize = 0;
   {

@@ -398,7 +398,9 @@ class Oracle:
         xyz = np.array(_i16(xyz), copy=True)
         bt = np.array(btype, dtype=np.uint16, copy=True)
         part = np.ascontiguousarray(partition, dtype=np.uint32)
-        self.L.orc_smooth_point_cloud_grid(_p(xyz), _p(bt), _p(part), C.c_int64(len(xyz)), int(grid_size), C.c_double(threshold))
+        rc = self.L.orc_smooth_point_cloud_grid(_p(xyz), _p(bt), _p(part), C.c_int64(len(xyz)), int(grid_size), C.c_double(threshold))
+        if rc != 0:
+            raise ValueError("orc_smooth_point_cloud_grid: gridSize %d refused (even sizes only), rc %d" % (grid_size, rc))
         return xyz, bt
 
     def transfer_colors16_bp(self, src_xyz, src_c16, tgt_xyz, tgt_btype):

@@ -79,8 +79,8 @@ def test_gpu_whole_path_on_degenerate_gofs(oracle, seed):
 
 @pytest.mark.parametrize("seed", range(20))
 def test_gpu_tail_on_random_clouds(gpu_ctx, oracle, seed):
-    """The tail's kernels cannot be fed an arbitrary cloud through the C-ABI (they work on a frame's reconstruction); the
-    colour conversion can: white noise and block images of odd sizes."""
+    """The tail's kernels work on a frame's reconstruction: arbitrary input reaches them as hand-built decoder frames
+    (tests/test_gpu_decoder_frames.py).  The colour conversion takes any image: white noise and block images of odd sizes."""
     rng = np.random.default_rng(17000 + seed)
     H, W = 2 * int(rng.integers(8, 200)), 2 * int(rng.integers(8, 200))
     rgb = rng.integers(0, 256, (3, H, W), dtype=np.uint8)

@@ -220,14 +220,34 @@ def test_gpu_tail_grid_sizes_and_thresholds(gpu_ctx, oracle, tail_phases, grid, 
     assert threshold < 1e9 or int((o_c["boundary"] == 3).sum()) == 0
 
 
-def test_gpu_tail_refuses_grid_sizes_outside_2_to_64(gpu_ctx, oracle):
+def test_gpu_tail_refuses_grid_sizes_outside_2_to_64(gpu_ctx, oracle, tail_phases):
+    """Sizes outside 2..64 and the odd ones inside it (with an odd size the eight cells of a point next to the upper faces are not
+    all in the grid) are refused by name before anything runs: after every refusal the same frame still gives the oracle's tail at
+    8 / 64.0.  The oracle refuses an odd size too."""
     xyz, rgb = pc.cloud("tiny")
+    o_a, o_b, dec = tail_phases
+    o_c = oracle.phase_c(o_a, o_b, [dec], 4, 8, 64.0)[0]
     fr = _encoded_frame(gpu_ctx, oracle, xyz, rgb)
     fr.codec_identify_boundary_points()
     fr.codec_color_point_cloud(None)
-    for grid in (1, 65, 0, -8):
-        with pytest.raises(T.Tmc2Error):
+    before = fr.get_post_reconstruction(rgb=False)
+    for grid in (1, 65, 0, -8, 3, 5, 63):
+        with pytest.raises(T.Tmc2Error) as e:
             fr.codec_smooth_point_cloud_postprocess(grid, 64.0)
+        assert "error -4:" in str(e.value) and "gridSize" in str(e.value), grid    # TMC2_E_UNSUPPORTED, by name
+        after = fr.get_post_reconstruction(rgb=False)                # (the refused call left the frame as it was)
+        for k in ("xyz", "colors16", "boundary"):
+            assert np.array_equal(after[k], before[k]), (grid, k)
+        fr.codec_post_reconstruct(None, 8, 64.0)
+        post = fr.get_post_reconstruction()
+        for k in ("xyz", "colors16", "rgb", "boundary"):
+            assert np.array_equal(post[k], o_c[k]), (grid, k)
+        fr.codec_identify_boundary_points()                          # back to the state before the tail for the next refusal
+        fr.codec_color_point_cloud(None)
+        before = fr.get_post_reconstruction(rgb=False)
+    for grid in (3, 5, 63):
+        with pytest.raises(ValueError):
+            oracle.smooth_point_cloud_grid(o_b[0]["recon_xyz"], o_c["boundary_before"], o_c["partition"], grid, 64.0)
 
 
 @pytest.mark.parametrize("name", SMALL_K_CLOUDS)
