@@ -638,7 +638,7 @@ int buildKdTreePlaced( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n, const int16_t
     ctx->stageAddHostMs( ( std::string( stage ) + "_host" ).c_str(), std::chrono::duration<double, std::milli>( t1 - t0 ).count() );
   }
   gate.release();
-  TMC2_TRY( tree.ptsTree.alloc( n ) );
+  TMC2_TRY( tree.ptsTree.alloc( n + 1 ) );  // (one spare Pt: the k-NN kernels load the points in pairs, knn.hip loadLeafPairs)
   TMC2_TRY( tree.perm.alloc( n ) );
   TMC2_TRY( tree.nodes.alloc( host.nodes.size() ) );
   TMC2_HIP( hipMemcpyAsync( tree.ptsTree.p, hp, n * sizeof( Pt ), hipMemcpyHostToDevice, s ) );

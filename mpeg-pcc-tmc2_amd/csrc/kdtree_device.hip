@@ -1322,7 +1322,7 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DeviceTree&
   const uint32_t tiles   = ( n + kScanTile - 1 ) / kScanTile;
   const size_t   maxSegs = 2 * ( size_t( n ) / ( kLeafMax + 1 ) + 1 ) + 2;
   const size_t   maxNode = 2 * size_t( n ) + 2;  // (every split takes exactly two ids: hugeSegmentsKernel, pieceKernel, lvDecideKernel)
-  TMC2_TRY( tree.ptsTree.alloc( n ) );
+  TMC2_TRY( tree.ptsTree.alloc( size_t( n ) + 1 ) );  // (one spare Pt: the k-NN kernels load the points in pairs, knn.hip loadLeafPairs)
   TMC2_TRY( tree.perm.alloc( n ) );
   TMC2_TRY( tree.nodes.alloc( maxNode ) );
   DevBuf<uint32_t>   d_work, d_small;

@@ -10,9 +10,14 @@
 //
 // Design (MI355X-first, integer/HBM path -- no MFMA):
 //   * one query per lane; queries are issued in TREE order, so the 64 lanes of a wavefront are spatial
-//     neighbours, walk almost the same node sequence and hit the same leaves: node records (16 B,
-//     one dwordx4 load) and leaf points (8 B each) are wave-uniform or near-uniform loads served by
-//     L1/L2; the only HBM streams are the query points (8 B/pt) and the result rows (4k B/pt).
+//     neighbours, walk almost the same node sequence and hit the same leaves: node records (16 B) and
+//     leaf points (8 B each) are wave-uniform or near-uniform loads served by L1/L2; the only HBM
+//     streams are the query points (8 B/pt) and the result rows (4k B/pt).
+//   * a query's life is a chain of DEPENDENT loads (the next node's address comes out of this node's record), so
+//     what counts is the number of round trips: a node record is one global_load_dwordx4 and one wait per tree
+//     level (loadNode), a leaf's points come two per global_load_dwordx4, three such loads issued ahead of one
+//     wait (loadLeafPairs: a 10-point leaf is two round trips, not ten).  The code object is checked for both:
+//     profiles/knn_batched_loads.txt.
 //   * the k-best list lives in VGPRs (fully unrolled insertion = the reference's "insert after equal
 //     distances, reject when equal to the current worst" rule); the far-child stack lives in scratch.
 //   * the recursion of searchLevel is unrolled into near-descend / far-stack form.  A far child is
@@ -48,6 +53,35 @@ constexpr uint32_t kInf       = 0x7FFFFFFFu;
 struct RootBox {
   int lo[3], hi[3];
 };
+
+// A node record in ONE 16-byte load, decoded from registers.  (Read field by field -- or as a vector the optimiser is free to take
+// apart again -- the record came in pieces: `dim` for the loop test first, the rest behind it: two dependent round trips per tree
+// level.  The empty asm statement consumes the four words as one register tuple right behind the load, so it stays one load.)
+typedef uint32_t NodeWords __attribute__( ( ext_vector_type( 4 ) ) );
+__device__ __forceinline__ KdNode loadNode( const KdNode* __restrict__ nodes, uint32_t at ) {
+  NodeWords w = *reinterpret_cast<const NodeWords*>( nodes + at );
+  asm volatile( "" : "+v"( w ) );
+  KdNode nd;
+  nd.a       = int32_t( w.x );
+  nd.b       = int32_t( w.y );
+  nd.divlow  = int16_t( w.z & 0xFFFFu );
+  nd.divhigh = int16_t( w.z >> 16 );
+  nd.dim     = int32_t( w.w );
+  return nd;
+}
+
+// A leaf's points, two per 16-byte load, a batch of kLeafPairs loads issued back to back ahead of one wait.  A pair starts at an
+// even tree position; a leaf of kLeafMax = 10 points spans 5 or 6 pairs (6 where it starts at an odd position): two batches of
+// three, and however many a longer leaf takes.  (One batch of six costs 12 more VGPRs -- k = 16: 82 instead of 70, 5 waves per
+// SIMD instead of 7 -- and was no faster alone and slower with 16 frames in flight: profiles/knn_batched_loads.txt.)  The last
+// pair of an odd-sized cloud reaches one point past the end: the tree-order point arrays are allocated with one spare Pt
+// (buildKdTreeDevice, buildKdTreePlaced), and what lies outside [a, b) is never looked at.
+constexpr int kLeafPairs = 3;
+__device__ __forceinline__ void loadLeafPairs( uint4 ( &pr )[kLeafPairs], const Pt* __restrict__ ptsTree, int p0, int end ) {
+#pragma unroll
+  for ( int i = 0; i < kLeafPairs; ++i )
+    if ( p0 + 2 * i < end ) pr[i] = *reinterpret_cast<const uint4*>( ptsTree + p0 + 2 * i );
+}
 
 template <int K>
 __device__ __forceinline__ void knnInsert( uint32_t ( &bd )[K], uint32_t ( &bi )[K], uint32_t dist, uint32_t index ) {
@@ -128,11 +162,11 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
     uint32_t centre = j;
     if ( !SELF ) {
       uint32_t at = 0;
-      KdNode   nd = nodes[0];
+      KdNode   nd = loadNode( nodes, 0 );
       while ( nd.dim >= 0 ) {
         const int v = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
         at          = ( ( v - nd.divlow ) + ( v - nd.divhigh ) ) < 0 ? uint32_t( nd.a ) : uint32_t( nd.b );
-        nd          = nodes[at];
+        nd          = loadNode( nodes, at );
       }
       centre = uint32_t( nd.a + nd.b ) >> 1;
     }
@@ -150,7 +184,7 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
   int      sp    = 0;
   uint32_t node = 0;
   for ( ;; ) {
-    KdNode nd = nodes[node];
+    KdNode nd = loadNode( nodes, node );
     while ( nd.dim >= 0 ) {
       const int  v        = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
       const int  ocur     = nd.dim == 0 ? o0 : ( nd.dim == 1 ? o1 : o2 );
@@ -177,29 +211,29 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
         ++sp;
       }
       node = nearC;
-      nd   = nodes[node];
+      nd   = loadNode( nodes, node );
     }
-    // The leaf's points, two per 16-byte load (a pair starts at an even tree position; what lies outside [a, b) is skipped).
-    // The list keeps TREE POSITIONS: the original indices are looked up once at the end, all lanes in step, instead of one
-    // scattered 4-byte load per insertion.  (A candidate beyond cap cannot stay in the list and is never the reason another
-    // one is rejected: it is skipped.)
-    for ( int p = nd.a & ~1; p < nd.b; p += 2 ) {
-      uint4 two;
-      if ( uint32_t( p ) + 1u < nTree ) {
-        two = *reinterpret_cast<const uint4*>( ptsTree + p );
-      } else {
-        const uint2 one = *reinterpret_cast<const uint2*>( ptsTree + p );
-        two             = make_uint4( one.x, one.y, 0u, 0u );
-      }
-      if ( p >= nd.a ) {
-        const int      ex = qx - int( int16_t( two.x & 0xFFFFu ) ), ey = qy - int( int16_t( two.x >> 16 ) ), ez = qz - int( int16_t( two.y & 0xFFFFu ) );
-        const uint32_t dist = uint32_t( ex * ex + ey * ey + ez * ez );
-        if ( dist < bd[K - 1] && dist <= cap ) knnInsert<K>( bd, bi, dist, uint32_t( p ) );
-      }
-      if ( p + 1 < nd.b ) {
-        const int      ex = qx - int( int16_t( two.z & 0xFFFFu ) ), ey = qy - int( int16_t( two.z >> 16 ) ), ez = qz - int( int16_t( two.w & 0xFFFFu ) );
-        const uint32_t dist = uint32_t( ex * ex + ey * ey + ez * ez );
-        if ( dist < bd[K - 1] && dist <= cap ) knnInsert<K>( bd, bi, dist, uint32_t( p + 1 ) );
+    // The leaf's points: the pair loads of a batch first (loadLeafPairs), then its candidates in ascending tree position (what
+    // lies outside [a, b) is skipped).  The list keeps TREE POSITIONS: the original indices are looked up once at the end, all
+    // lanes in step, instead of one scattered 4-byte load per insertion.  (A candidate beyond cap cannot stay in the list and
+    // is never the reason another one is rejected: it is skipped.)
+    for ( int p0 = nd.a & ~1; p0 < nd.b; p0 += 2 * kLeafPairs ) {
+      uint4 pr[kLeafPairs];
+      loadLeafPairs( pr, ptsTree, p0, nd.b );
+#pragma unroll
+      for ( int i = 0; i < kLeafPairs; ++i ) {
+        const int   p   = p0 + 2 * i;
+        const uint4 two = pr[i];
+        if ( p >= nd.a && p < nd.b ) {
+          const int      ex = qx - int( int16_t( two.x & 0xFFFFu ) ), ey = qy - int( int16_t( two.x >> 16 ) ), ez = qz - int( int16_t( two.y & 0xFFFFu ) );
+          const uint32_t dist = uint32_t( ex * ex + ey * ey + ez * ez );
+          if ( dist < bd[K - 1] && dist <= cap ) knnInsert<K>( bd, bi, dist, uint32_t( p ) );
+        }
+        if ( p + 1 < nd.b ) {
+          const int      ex = qx - int( int16_t( two.z & 0xFFFFu ) ), ey = qy - int( int16_t( two.z >> 16 ) ), ez = qz - int( int16_t( two.w & 0xFFFFu ) );
+          const uint32_t dist = uint32_t( ex * ex + ey * ey + ez * ez );
+          if ( dist < bd[K - 1] && dist <= cap ) knnInsert<K>( bd, bi, dist, uint32_t( p + 1 ) );
+        }
       }
     }
     // The first descent runs with an unbounded list and therefore leaves one pending far child per tree level.  As soon as
@@ -422,15 +456,24 @@ __global__ __launch_bounds__( 256 ) void easyQueryKernel( const Pt* __restrict__
   if ( j >= nq ) return;
   const Pt  qp = queries[j];
   const int qx = qp.x, qy = qp.y, qz = qp.z;
-  KdNode    nd = nodes[0];
+  KdNode    nd = loadNode( nodes, 0 );
   while ( nd.dim >= 0 ) {
     const int v = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
-    nd          = nodes[( ( v - nd.divlow ) + ( v - nd.divhigh ) ) < 0 ? uint32_t( nd.a ) : uint32_t( nd.b )];
+    nd          = loadNode( nodes, ( ( v - nd.divlow ) + ( v - nd.divhigh ) ) < 0 ? uint32_t( nd.a ) : uint32_t( nd.b ) );
   }
-  uint32_t found = kHardQuery;
-  for ( int p = nd.b - 1; p >= nd.a; --p ) {  // (backwards: the FIRST identical point is what is left in `found`)
-    const Pt c = ptsTree[p];
-    if ( c.x == qp.x && c.y == qp.y && c.z == qp.z ) found = uint32_t( p );
+  // the leaf in batches of pair loads (loadLeafPairs); the FIRST identical point is the one kept
+  const uint32_t qxy = uint32_t( uint16_t( qp.x ) ) | ( uint32_t( uint16_t( qp.y ) ) << 16 ), qzz = uint32_t( uint16_t( qp.z ) );
+  uint32_t       found = kHardQuery;
+  for ( int p0 = nd.a & ~1; p0 < nd.b; p0 += 2 * kLeafPairs ) {
+    uint4 pr[kLeafPairs];
+    loadLeafPairs( pr, ptsTree, p0, nd.b );
+#pragma unroll
+    for ( int i = 0; i < kLeafPairs; ++i ) {
+      const int   p   = p0 + 2 * i;
+      const uint4 two = pr[i];
+      if ( p >= nd.a && p < nd.b && found == kHardQuery && two.x == qxy && ( two.y & 0xFFFFu ) == qzz ) found = uint32_t( p );
+      if ( p + 1 < nd.b && found == kHardQuery && two.z == qxy && ( two.w & 0xFFFFu ) == qzz ) found = uint32_t( p + 1 );
+    }
   }
   easyIdx[j] = found == kHardQuery ? kHardQuery : perm[found];
   if ( easyDist && found != kHardQuery ) easyDist[j] = 0u;
