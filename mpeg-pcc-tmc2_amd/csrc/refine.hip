@@ -352,7 +352,7 @@ template <int CAP, int WAVES>
 __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void neighbourhoodKernel(
     const Pt* __restrict__ centre, const uint32_t* __restrict__ count, Grid g, uint32_t V,
     const int* __restrict__ rows, int nRows, int maxNN, double lambda, int idBits, int devRange, uint32_t devStride,
-    uint32_t rowCapacity, uint32_t* __restrict__ rowLen, uint32_t* __restrict__ devLen, double* __restrict__ weight,
+    uint32_t rowCapacity, uint32_t* __restrict__ rowLen, double* __restrict__ weight,
     uint32_t* __restrict__ adjOff, uint32_t* __restrict__ adj, uint32_t* __restrict__ dev, uint32_t* __restrict__ rowCursor,
     uint32_t* __restrict__ overflow, const uint2* __restrict__ bits /* occupancy bitmap + ranks of the keys */,
     const uint2* __restrict__ voxelOfRank /* record of the voxel that owns the rank-th occupied key (rankRecord) */,
@@ -594,7 +594,6 @@ __global__ __launch_bounds__( 64 * WAVES, ldsWavesPerSimd( CAP, WAVES ) ) void n
     nDev = devStride;
   }
   for ( uint32_t i = nDev + lane; i < devStride; i += 64 ) drow[i] = kDevPad;
-  if ( lane == 0 ) devLen[v] = nDev;
 }
 
 
@@ -741,7 +740,9 @@ __device__ __forceinline__ int argOfPacked( uint32_t s0, uint32_t s1, uint32_t s
 //                  mark" (-> v is appended to the work list, exactly once) and "first to activate" (-> v is walked, once).
 //   work list:     kSubLists sub-lists with their counters 128 bytes apart (a reservation on ONE word costs 11 ns and they
 //                  queue up: tools/gpu/atomic_rate.hip; spread over cache lines they are free).  The voxels active at
-//                  sweep start carry kWorkActive; for the others sweepKernel reads the activated bit.
+//                  sweep start carry kWorkActive; for the others sweepKernel reads the activated bit.  A hop makes ONE
+//                  reservation for all it was the first to mark and does not wait for the answer: the group's next hop
+//                  stores them (ListAppend).
 //   LDS ring:      head / tail only grow and never pass ringCap: a position is handed out once per sweep (what does not fit
 //                  spills); a slot holds kNoVoxel until its giver stores, so a taker that won the slot waits for that store.
 //                  `pending` = voxels given and not yet hopped on: a group retires when it finds nothing and pending == 0.
@@ -759,8 +760,6 @@ struct Closure {
   const uint8_t*  ppi;
   const uint4*    rec;
   const uint32_t* dev;
-  const uint32_t* devLen;
-  uint32_t        stride;
   uint32_t*       state;
   uint32_t*       list;   // this workgroup's sub-list
   uint32_t*       count;  // ... and its counter
@@ -805,51 +804,103 @@ __device__ __forceinline__ uint32_t closureTake( const Closure& c ) {
   return x;
 }
 
-// One hop of the 32-lane group on voxel x; returns the activated voxel the group keeps (kNoVoxel: none).
-__device__ __forceinline__ uint32_t closureHop( const Closure& c, uint32_t x, uint32_t lane, int half ) {
+// The voxels a hop was the first to mark, on their way to the work list: the reservation's answer is asked for at the end of
+// the hop and not waited for there -- the next hop (or the group, before it goes to the ring) stores them.
+template <int CHUNKS>
+struct ListAppend {
+  uint32_t total;      // voxels to append (uniform over the 32-lane group; 0: nothing held)
+  uint32_t at;         // (lane 0) the reservation's answer
+  uint32_t v[CHUNKS];  // this lane's voxel of each chunk, kNoVoxel where it has none
+};
+
+template <int CHUNKS>
+__device__ __forceinline__ void closureFlush( const Closure& c, ListAppend<CHUNKS>& held, uint32_t lane, int half ) {
+  if ( !held.total ) return;
   const uint32_t below = ( 1u << lane ) - 1u;
-  const uint4    r     = c.rec[x];
-  const uint8_t  a     = uint8_t( argOfPacked( r.x, r.y, r.z ) );
-  // (rows are padded with kDevPad to `stride` entries; a row of 32 is one load that waits for nothing, a row of 128 is
-  // walked as far as its length says)
-  const uint32_t len  = c.stride == 32 ? 32u : c.devLen[x];
-  uint32_t       keep = kNoVoxel;
-  // (round 6: a row of 128 is up to four chunks of 32 -- their entries, then edge / ppi of all of them, then all the returning
-  //  atomics are issued together: three dependent round trips per hop whatever the row's length, not three per chunk.  The
-  //  voxels of a row are distinct, so an atomic's answer does not depend on the other chunks'.)
-  constexpr int kChunks = 4;  // (devStride <= 128)
-  uint32_t      vAll[kChunks];
-  bool          candAll[kChunks], firstAll[kChunks], freshAll[kChunks];
+  uint32_t       at    = __shfl( held.at, 0, 32 );
 #pragma unroll
-  for ( int k = 0; k < kChunks; ++k ) vAll[k] = uint32_t( 32 * k ) < len ? c.dev[size_t( x ) * c.stride + 32 * k + lane] : kDevPad;
-#pragma unroll
-  for ( int k = 0; k < kChunks; ++k ) candAll[k] = vAll[k] != kDevPad && c.edge[vAll[k]] == NO_EDGE && c.ppi[vAll[k]] != a;
-#pragma unroll
-  for ( int k = 0; k < kChunks; ++k ) {
-    firstAll[k] = freshAll[k] = false;
-    if ( candAll[k] ) {
-      const uint32_t v   = vAll[k];
-      const uint32_t sh  = ( v & 15u ) * 2u;
-      const uint32_t old = atomicOr( &c.state[v >> 4], ( v > x ? 3u : 1u ) << sh ) >> sh;
-      firstAll[k]        = !( old & 1u );
-      freshAll[k]        = v > x && !( old & 2u );  // (v is a NO_EDGE voxel: only a mark activates it)
-    }
+  for ( int k = 0; k < CHUNKS; ++k ) {  // (chunk after chunk, lane after lane: the sub-list stays a dense [0, count))
+    const bool     mine = held.v[k] != kNoVoxel;
+    const uint32_t m    = uint32_t( __ballot( mine ) >> ( 32 * half ) );
+    if ( mine ) c.list[at + __popc( m & below )] = held.v[k];
+    at += uint32_t( __popc( m ) );
   }
+  held.total = 0;
+}
+
+// One hop of the 32-lane group on voxel x; returns the activated voxel the group keeps (kNoVoxel: none).  CHUNKS = stride / 32.
+// Three dependent round trips to memory, whatever the row's length (checked in the code object: profiles/refine_sweep_loads.txt):
+//   1. S[x] and the whole padded DEV row (rows are padded with kDevPad to `stride` entries, so nothing has to know the row's
+//      length first; the entries of a row are dense from its start),
+//   2. edge / ppi of every entry (a pad entry reads x's own: no load hangs on another load's answer),
+//   3. every candidate's returning atomicOr, all issued before the first answer is looked at.  The voxels of a row are
+//      distinct, so an atomic's answer does not depend on the other chunks'.
+// The work-list reservation (a fourth returning atomic) is not on that chain: ONE per hop, asked for at the end, its answer
+// used by closureFlush -- behind the next hop's second batch of loads, by when it has long arrived (answers come back in the
+// order of issue, so the wait for the first batch has covered it) and where the stores' acknowledgements ride with that batch.
+template <int CHUNKS>
+__device__ __forceinline__ uint32_t closureHop( const Closure& c, uint32_t x, uint32_t lane, int half, ListAppend<CHUNKS>& held ) {
+  static_assert( CHUNKS == 1 || CHUNKS == 4, "a DEV row is 32 or 128 entries" );
+  const uint32_t  below = ( 1u << lane ) - 1u;
+  uint32_t        keep  = kNoVoxel;
+  const uint32_t* row   = c.dev + size_t( x ) * ( 32u * CHUNKS ) + lane;
+  uint4           r     = c.rec[x];
+  uint32_t        vAll[CHUNKS];
 #pragma unroll
-  for ( int ch = 0; ch < kChunks; ++ch ) {
-    if ( uint32_t( 32 * ch ) >= len ) continue;  // (uniform over the 32-lane group)
+  for ( int k = 0; k < CHUNKS; ++k ) vAll[k] = row[32 * k];
+  // (the empty asm statements consume a batch's registers together: the one wait of the batch sits here, and the optimiser
+  //  can neither take the batch apart nor move a later load's wait in between -- as knn.hip's loadNode)
+  if constexpr ( CHUNKS == 1 )
+    asm volatile( "" : "+v"( r.x ), "+v"( r.y ), "+v"( r.z ), "+v"( vAll[0] ) );
+  else
+    asm volatile( "" : "+v"( r.x ), "+v"( r.y ), "+v"( r.z ), "+v"( vAll[0] ), "+v"( vAll[1] ), "+v"( vAll[2] ), "+v"( vAll[3] ) );
+  const uint32_t a = uint32_t( argOfPacked( r.x, r.y, r.z ) );
+  uint32_t       eAll[CHUNKS], pAll[CHUNKS];
+#pragma unroll
+  for ( int k = 0; k < CHUNKS; ++k ) {
+    const uint32_t at = vAll[k] != kDevPad ? vAll[k] : x;
+    eAll[k] = c.edge[at], pAll[k] = c.ppi[at];
+  }
+  closureFlush( c, held, lane, half );  // (the previous hop's first marks)
+  if constexpr ( CHUNKS == 1 )
+    asm volatile( "" : "+v"( eAll[0] ), "+v"( pAll[0] ) );
+  else
+    asm volatile( "" : "+v"( eAll[0] ), "+v"( pAll[0] ), "+v"( eAll[1] ), "+v"( pAll[1] ), "+v"( eAll[2] ), "+v"( pAll[2] ), "+v"( eAll[3] ), "+v"( pAll[3] ) );
+  bool     candAll[CHUNKS], firstAll[CHUNKS], freshAll[CHUNKS];
+  uint32_t oldAll[CHUNKS];
+#pragma unroll
+  for ( int k = 0; k < CHUNKS; ++k ) {
+    const uint32_t v = vAll[k];
+    candAll[k]       = ( v != kDevPad ) & ( eAll[k] == uint32_t( NO_EDGE ) ) & ( pAll[k] != a );
+    oldAll[k]        = 0;
+    if ( candAll[k] ) oldAll[k] = atomicOr( &c.state[v >> 4], ( v > x ? 3u : 1u ) << ( ( v & 15u ) * 2u ) );
+  }
+  if constexpr ( CHUNKS == 1 )
+    asm volatile( "" : "+v"( oldAll[0] ) );
+  else
+    asm volatile( "" : "+v"( oldAll[0] ), "+v"( oldAll[1] ), "+v"( oldAll[2] ), "+v"( oldAll[3] ) );
+  uint32_t total = 0;
+#pragma unroll
+  for ( int k = 0; k < CHUNKS; ++k ) {
+    const uint32_t v   = vAll[k];
+    const uint32_t old = oldAll[k] >> ( ( v & 15u ) * 2u );
+    firstAll[k]        = candAll[k] && !( old & 1u );
+    freshAll[k]        = candAll[k] && v > x && !( old & 2u );  // (v is a NO_EDGE voxel: only a mark activates it)
+    held.v[k]          = firstAll[k] ? v : kNoVoxel;
+    total += uint32_t( __popc( uint32_t( __ballot( firstAll[k] ) >> ( 32 * half ) ) ) );
+  }
+  held.total = total;
+  // (nobody waits for this here.  The counter is addressed through an offset of zero that the optimiser cannot see into: an
+  //  atomic on an address it knows to be the same in both 32-lane groups is merged into one per wavefront, whose answer it
+  //  then has to wait for on the spot to hand it out)
+  uint32_t same = 0;
+  asm volatile( "" : "+v"( same ) );
+  if ( total && lane == 0 ) held.at = atomicAdd( c.count + same, total );
+#pragma unroll
+  for ( int ch = 0; ch < CHUNKS; ++ch ) {
     const uint32_t v     = vAll[ch];
-    const bool     first = firstAll[ch];
     bool           fresh = freshAll[ch];
-    const uint32_t mFirst = uint32_t( __ballot( first ) >> ( 32 * half ) );
     uint32_t       mFresh = uint32_t( __ballot( fresh ) >> ( 32 * half ) );
-    if ( mFirst ) {
-      const int leader = __ffs( int( mFirst ) ) - 1;
-      uint32_t  at     = 0;
-      if ( int( lane ) == leader ) at = atomicAdd( c.count, uint32_t( __popc( mFirst ) ) );
-      at = __shfl( at, leader, 32 );
-      if ( first ) c.list[at + __popc( mFirst & below )] = v;
-    }
     if ( !mFresh ) continue;
     const int leader = __ffs( int( mFresh ) ) - 1;
     if ( keep == kNoVoxel ) {  // the first one stays with the group (it is pending like the others)
@@ -898,10 +949,43 @@ __device__ __forceinline__ uint32_t closureHop( const Closure& c, uint32_t x, ui
   return keep;
 }
 
+// The walk of a 32-lane group: take a voxel, hop, hop on from the voxel the hop kept.  Returns the group's hops.  What a hop was
+// the first to mark travels in `held` to the next hop; a group with nothing to hop on stores it before it looks at the ring, so
+// a group that retires holds nothing.
+template <int CHUNKS>
+__device__ __forceinline__ uint32_t closureWalk( const Closure& c, uint32_t lane, int half ) {
+  ListAppend<CHUNKS> held;
+  held.total = 0, held.at = 0;
+#pragma unroll
+  for ( int k = 0; k < CHUNKS; ++k ) held.v[k] = kNoVoxel;
+  uint32_t hops = 0, x = kNoVoxel;
+  while ( true ) {
+    if ( x == kNoVoxel ) {
+      closureFlush( c, held, lane, half );
+      const uint32_t pending = reinterpret_cast<volatile uint32_t*>( c.wg )[kPending];  // (read BEFORE the attempt)
+      if ( lane == 0 ) x = closureTake( c );
+      x = __shfl( x, 0, 32 );
+      if ( x == kNoVoxel ) {
+        if ( pending == 0 ) break;  // nothing in the ring, nobody hopping: nothing can turn up any more
+        __builtin_amdgcn_s_sleep( 2 );  // (longer naps -- 4 x, 16 x -- measured: nothing, profiles/r06_knobs_in_flight.txt)
+        continue;
+      }
+    }
+    const uint32_t next = closureHop( c, x, lane, half, held );
+    ++hops;
+    if ( lane == 0 ) atomicSub( &c.wg[kPending], 1u );
+    x = next;
+  }
+  return hops;
+}
+
+// (CHUNKS = devStride / 32 is the kernel's template parameter, not an argument it branches on: with both strides' walks in one
+//  code object, one behind the other, the second began every hop with a wait for whatever the first might have left in flight)
+template <int CHUNKS>
 __global__ __launch_bounds__( 1024 ) void closureKernel( const uint8_t* __restrict__ edge, const uint8_t* __restrict__ ppi,
                                                           const uint4* __restrict__ recCur, uint4* __restrict__ recNxt,
-                                                          const uint32_t* __restrict__ dev, const uint32_t* __restrict__ devLen,
-                                                          uint32_t stride, uint32_t V, uint32_t run, uint32_t* __restrict__ state,
+                                                          const uint32_t* __restrict__ dev,
+                                                          uint32_t V, uint32_t run, uint32_t* __restrict__ state,
                                                           uint32_t* __restrict__ stateNext, uint32_t stateWords,
                                                           uint32_t* __restrict__ lists, uint32_t listCap,
                                                           uint32_t* __restrict__ counts, uint32_t* __restrict__ countsNext,
@@ -934,7 +1018,7 @@ __global__ __launch_bounds__( 1024 ) void closureKernel( const uint8_t* __restri
   }
   __syncthreads();
   Closure c;
-  c.edge = edge, c.ppi = ppi, c.rec = recCur, c.dev = dev, c.devLen = devLen, c.stride = stride, c.state = state;
+  c.edge = edge, c.ppi = ppi, c.rec = recCur, c.dev = dev, c.state = state;
   c.list = lists + size_t( sub ) * listCap, c.count = &counts[sub * 32], c.spill = spill, c.spillCap = listCap, c.ctl = ctl;
   c.ring = ring, c.ringCap = ringCap, c.wg = wg;
   const uint32_t lane = threadIdx.x & 31;
@@ -942,23 +1026,7 @@ __global__ __launch_bounds__( 1024 ) void closureKernel( const uint8_t* __restri
   // (test hook: timing[0] = max ticks from kernel start to the walk, [1] = max ticks in the walk, [2] = most hops of a
   //  group, [3] += hops, [4] += workgroups that spilled)
   const unsigned long long t0   = timing ? wall_clock64() : 0ull;
-  uint32_t                 hops = 0, x = kNoVoxel;
-  while ( true ) {
-    if ( x == kNoVoxel ) {
-      const uint32_t pending = reinterpret_cast<volatile uint32_t*>( wg )[kPending];  // (read BEFORE the attempt)
-      if ( lane == 0 ) x = closureTake( c );
-      x = __shfl( x, 0, 32 );
-      if ( x == kNoVoxel ) {
-        if ( pending == 0 ) break;  // nothing in the ring, nobody hopping: nothing can turn up any more
-        __builtin_amdgcn_s_sleep( 2 );  // (longer naps -- 4 x, 16 x -- measured: nothing, profiles/r06_knobs_in_flight.txt)
-        continue;
-      }
-    }
-    const uint32_t next = closureHop( c, x, lane, half );
-    ++hops;
-    if ( lane == 0 ) atomicSub( &wg[kPending], 1u );
-    x = next;
-  }
+  const uint32_t           hops = closureWalk<CHUNKS>( c, lane, half );
   if ( timing && lane == 0 ) {
     atomicMax( &timing[0], t0 - tStart );
     atomicMax( &timing[1], wall_clock64() - t0 );
@@ -995,36 +1063,51 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
   __syncthreads();
   const int      sub    = threadIdx.x & 15;
   const uint32_t groups = gridDim.x * 16, count = pre[kSubLists];
-  for ( uint32_t idx = blockIdx.x * 16 + ( threadIdx.x >> 4 ); idx < count; idx += groups ) {  // (uniform over the 16 lanes)
+  // entry idx of the sub-lists taken as one (idx < count)
+  const auto listEntry = [&]( uint32_t idx ) {
     uint32_t sl = 0;  // the last sub-list that starts at or before idx
 #pragma unroll
     for ( int step = kSubLists / 2; step > 0; step >>= 1 )
       if ( pre[sl + step] <= idx ) sl += step;
-    const uint32_t raw = lists[size_t( sl ) * listCap + ( idx - pre[sl] )], v = raw & ~kWorkActive;
+    return lists[size_t( sl ) * listCap + ( idx - pre[sl] )];
+  };
+  uint32_t idx = blockIdx.x * 16 + ( threadIdx.x >> 4 );
+  uint32_t raw = idx < count ? listEntry( idx ) : 0u;
+  asm volatile( "" : "+v"( raw ) );  // (waited for here, so that the loop's top waits for nothing: not for the stores and adds of the voxel before)
+  for ( ; idx < count; idx += groups ) {  // (uniform over the 16 lanes)
+    const uint32_t v = raw & ~kWorkActive;
+    // Everything that is indexed by v alone in ONE batch of loads, whether the decisions below need it or not, and the group's
+    // next list entry with it: a voxel costs list entry -> this batch -> pointList -> normals + partition -> radj -> atomics and
+    // nothing in between.  (A voxel is on the list exactly once, so what the batch reads is this group's own or frozen for the
+    // launch; pointStart has V + 1 entries.  The empty asm statement consumes the batch's registers together: one wait, here.)
+    uint32_t st = state[v >> 4], e0w = edge[v], p0 = ppi[v];
+    uint4    s  = recCur[v], h = hist[v];
+    uint32_t last = lastRescore[v], begin = pointStart[v], end = pointStart[v + 1], rb = roff[v], rl = rlen[v];
+    double   w  = weight[v];
+    uint32_t rawNext = idx + groups < count ? listEntry( idx + groups ) : 0u;
+    asm volatile( "" : "+v"( st ), "+v"( e0w ), "+v"( p0 ), "+v"( s.x ), "+v"( s.y ), "+v"( s.z ), "+v"( s.w ), "+v"( h.x ), "+v"( h.y ), "+v"( h.z ),
+                  "+v"( last ), "+v"( begin ), "+v"( end ), "+v"( rb ), "+v"( rl ), "+v"( w ), "+v"( rawNext ) );
+    const uint32_t rawNow = raw;
+    raw                   = rawNext;
     // active at sweep start (flagged by closureKernel), or activated by the closure
-    const uint32_t entry = v | ( ( raw & kWorkActive ) || ( ( state[v >> 4] >> ( ( v & 15u ) * 2u + 1u ) ) & 1u ) ? kWorkActive : 0u );
-    const uint8_t  e0 = edge[v];
-    bool           p  = false;
-    uint32_t       b[6];
-    uint4          s  = make_uint4( 0, 0, 0, 0 );
-    if ( entry & kWorkActive ) {
-      s = recCur[v];
+    const bool    active = ( rawNow & kWorkActive ) || ( ( st >> ( ( v & 15u ) * 2u + 1u ) ) & 1u );
+    const uint8_t e0     = uint8_t( e0w );
+    bool          p      = false;
+    uint32_t      b[6];
+    if ( active ) {
       unpackHist( s, b );
       p = true;
       if ( ( e0 != NO_EDGE ? e0 : uint8_t( INDIRECT_EDGE ) ) != M_DIRECT_EDGE ) {
         int nz, a;
         classify( b, nz, a );
-        if ( nz == 1 && b[ppi[v]] > 0 ) p = false;
+        if ( nz == 1 && b[p0] > 0 ) p = false;
       }
     }
     if ( !p ) {  // marked (every voxel of the list that was NO_EDGE at sweep start is) and not re-scored: INDIRECT from now on
       if ( sub == 0 && e0 == NO_EDGE ) edge[v] = INDIRECT_EDGE;
       continue;
     }
-    uint4 h = hist[v];
-    if ( s.w > lastRescore[v] ) {
-      const double   w     = weight[v];
-      const uint32_t begin = pointStart[v], end = pointStart[v + 1];
+    if ( s.w > last ) {
       uint32_t       h0 = 0, h1 = 0, h2 = 0, moved = 0;
       for ( uint32_t q = begin + sub; q < end; q += 16 ) {
         const uint32_t j  = pointList[q];
@@ -1058,7 +1141,7 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
         // borrows between the halves cancel in the final sums whatever the order of the adds
         const uint32_t d0 = h0 - h.x, d1 = h1 - h.y, d2 = h2 - h.z;
         if ( d0 | d1 | d2 ) {
-          const uint32_t rb = roff[v], re = rb + rlen[v];
+          const uint32_t re = rb + rl;
           // (round 6: the first two words in ONE 64-bit add.  A word's difference is the true integer T = dHi * 65536 + dLo modulo
           //  2^32, and with fields below 2^15 -- pairedPush: maxNN + 255 < 32 768 -- |T| < 2^31, so T is d as an int32; adding
           //  T0 + T1 * 2^32 as a SIGNED 64-bit number to x + y * 2^32 is exact integer arithmetic on the pair: every true word stays
@@ -1120,7 +1203,7 @@ struct RefineJob {
   uint64_t         capacity = 0;
   uint32_t         res[5] = {0, 0, 0, 0, 0};  // the neighbourhood pass' answer: row entries written, overflow flag, reverse row entries, room asked for, kept hits out of room
   uint32_t         hitRegionCap = 0;
-  DevBuf<uint32_t> d_key, d_flag, d_vid, d_small, d_count, d_rowLen, d_devLen, d_adjOff, d_hist, d_activeBuf, d_pointStart,
+  DevBuf<uint32_t> d_key, d_flag, d_vid, d_small, d_count, d_rowLen, d_adjOff, d_hist, d_activeBuf, d_pointStart,
       d_pointList, d_cursor, d_lastRescore, d_flags, d_gbits, d_adj, d_dev, d_lastKey, d_roffG, d_rlenG, d_radjG,
       d_voxelOfRank, d_hitBuf, d_hitCtl, d_hitOff, d_hitLen, d_rowCtl;
   std::vector<uint32_t> rowCtlHost;  // the forward rows' region cursors, fetched with the pass' answer (their sum: the row entries)
@@ -1175,7 +1258,7 @@ void RefineJob::launchNeighbourhood() {
 #define TMC2_NEIGHBOURHOOD( CAP, WAVES )                                                                                       \
   hipLaunchKernelGGL( ( neighbourhoodKernel<CAP, WAVES> ), dim3( ( V + WAVES - 1 ) / WAVES ), dim3( 64 * WAVES ), 0, s, d_centre.p,      \
                       d_count.p, g, V, d_rows, nRows, maxNNCount, lambda, idBits, devRange, devStride,                      \
-                      rowRegionCap, d_rowLen.p, d_devLen.p, d_weight.p, d_adjOff.p, d_adj.p, d_dev.p, d_rowCtl.p,            \
+                      rowRegionCap, d_rowLen.p, d_weight.p, d_adjOff.p, d_adj.p, d_dev.p, d_rowCtl.p,            \
                       d_small.p + 2, bits, reinterpret_cast<const uint2*>( d_voxelOfRank.p ), d_lastKey.p, savedHits );      \
   hipLaunchKernelGGL( ( reverseRowsKernel<CAP, WAVES> ), dim3( ( V + WAVES - 1 ) / WAVES ), dim3( 64 * WAVES ), 0, s, d_centre.p, reinterpret_cast<const uint2*>( d_voxelOfRank.p ), \
                       bits, g, V, d_rows, nRows, idBits, d_lastKey.p, rowRegionCap, d_roffG.p, d_rlenG.p, d_radjG.p,          \
@@ -1280,7 +1363,6 @@ int RefineJob::geometry( tmc2_frame* f ) {
   V = answer[0];
   TMC2_TRY( d_count.alloc( size_t( V ) + 1 ) );  // (+1: scanned into the point-list offsets)
   TMC2_TRY( d_rowLen.alloc( V ) );
-  TMC2_TRY( d_devLen.alloc( V ) );
   TMC2_TRY( d_adjOff.alloc( V + 1 ) );
   TMC2_TRY( d_hist.alloc( size_t( V ) * 4 ) );
   TMC2_TRY( d_centre.alloc( V ) );
@@ -1451,7 +1533,8 @@ int RefineJob::finish() {
   const dim3     grdClosure( ( V + run - 1 ) / run );
   const uint32_t ringCap    = run + ( ringEnv ? uint32_t( std::min( 8192, std::max( 1, atoi( ringEnv->c_str() ) ) ) ) : 1024u );
   const size_t   closureLds = 4 * ( size_t( run ) + ringCap );
-  if ( closureLds > 48 * 1024 ) TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( closureKernel ), closureLds, ctx->device ) );
+  const auto closure = devStride == 32 ? closureKernel<1> : closureKernel<4>;  // (chunks of 32 in a DEV row)
+  if ( closureLds > 48 * 1024 ) TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( closure ), closureLds, ctx->device ) );
   // (test hook TMC2_REFINE_SWEEP_BLOCKS: the sweep kernel's grid)
   const auto  sweepGridEnv = ctxOption( ctx, "REFINE_SWEEP_BLOCKS" );
   const dim3  grdSweep( uint32_t( std::min<size_t>( ( size_t( V ) + 15 ) / 16, sweepGridEnv ? size_t( std::max( 1, atoi( sweepGridEnv->c_str() ) ) ) : size_t( refineOverlap( ctx ) ? 8 : 2 ) * ctx->cuCount ) ) );
@@ -1487,8 +1570,8 @@ int RefineJob::finish() {
   for ( int iter = 0; iter < iterationCount; ++iter ) {
     const int cur    = iter & 1, nxt = cur ^ 1;
     uint4 *   recCur = d_rec.p + size_t( cur ) * V, *recNxt = d_rec.p + size_t( nxt ) * V;
-    hipLaunchKernelGGL( closureKernel, grdClosure, dim3( closureThreads ), closureLds, s, d_edge, d_ppi, recCur, recNxt, d_dev.p, d_devLen.p,
-                        devStride, V, run, state[cur], state[nxt], uint32_t( W2 ), d_lists.p, V, counts[cur], counts[nxt], spill,
+    hipLaunchKernelGGL( closure, grdClosure, dim3( closureThreads ), closureLds, s, d_edge, d_ppi, recCur, recNxt, d_dev.p,
+                        V, run, state[cur], state[nxt], uint32_t( W2 ), d_lists.p, V, counts[cur], counts[nxt], spill,
                         ctl, ringCap, wantTiming ? d_timing.p + 8 * size_t( iter ) : nullptr );
     if ( debugSweeps ) {
       const hipError_t e = hipStreamSynchronize( s );
