@@ -514,7 +514,7 @@ struct OrientCrossEdge {
 // the contracted graph in compact form (device contraction, orient_contract.hip): clusters numbered by first member, per
 // ordered pair of clusters the one light cross edge that can be accepted + the strong one-way edges
 struct OrientCompactEdge {
-  uint32_t u, v, c2, pad;  // start / end vertex (original indices: the tie order of the reference's queue), cluster of v
+  uint32_t u, v, c2, pv;  // start / end vertex (original indices: the tie order of the reference's queue), cluster and parity of v
   double   d;              // n_u . n_v on the original normals, negated if the parities of u and v differ
 };
 struct OrientClusterRec {
@@ -528,9 +528,10 @@ struct OrientCompact {
   const OrientCompactEdge* edges;
 };
 bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign, uint32_t* component, std::vector<uint32_t>& seeds,
-                         std::vector<uint32_t>& seedClusters );
+                         std::vector<uint32_t>& seedClusters, std::vector<uint8_t>& anchored );
 void resolveSeedSignsCompact( const OrientCompact& g, int kNN, const std::vector<uint32_t>& seeds, const std::vector<uint32_t>& seedClusters,
-                              const uint32_t* component, const uint32_t* who, const double* normals, const int16_t* xyz0, int8_t* clusterSign );
+                              const uint32_t* component, const std::vector<uint8_t>& anchored, const uint32_t* who, const double* normals,
+                              const int16_t* xyz0, int8_t* clusterSign );
 int gatherSeedTables( tmc2_frame* f, const uint32_t* d_cid, const uint8_t* d_parity, const std::vector<uint32_t>& seeds,
                       std::vector<uint32_t>& who, std::vector<double>& normals );
 int orientSpanningTreeSigns( const int16_t* xyz, size_t n, const uint32_t* knn, int k, const double* normals,

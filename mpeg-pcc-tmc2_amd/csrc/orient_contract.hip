@@ -77,7 +77,7 @@ __global__ __launch_bounds__( 256 ) void initWordsKernel( const uint32_t* __rest
   const uint32_t i  = perm ? perm[at] : at;
   const uint32_t vj = knn[size_t( i ) * K + j];
   const double   dj = edgeDotOf( normals, i, vj );
-  const bool     strong = fabs( dj ) >= tau;
+  const bool     strong = fabs( dj ) >= tau && dj != 0.0;  // (a dot product of exactly zero relates no two signs: orient_host.cpp, isStrong)
   const bool     cand   = ( ( mutual[i] >> j ) & 1u ) && strong;
   {
     const uint32_t bits = ballot16( cand, lane ), sb = ballot16( strong, lane ), nb = ballot16( dj < 0.0, lane );
@@ -386,7 +386,7 @@ __global__ __launch_bounds__( 256 ) void scatterCompactKernel( const uint32_t* _
       const uint32_t v = knn[size_t( u ) * K + j];
       const double   d = edgeDotOf( normals, u, v );
       const uint32_t pos = pos0 + __popc( m & ( ( 1u << j ) - 1u ) );
-      if ( pos < edgeCap ) edges[pos] = OrientCompactEdge{u, v, cid[v], 0u, ( ( parity[u] ^ parity[v] ) & 1 ) ? -d : d};
+      if ( pos < edgeCap ) edges[pos] = OrientCompactEdge{u, v, cid[v], uint32_t( parity[v] ), ( ( parity[u] ^ parity[v] ) & 1 ) ? -d : d};
     }
   }
   __syncthreads();

@@ -19,6 +19,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 #include "internal.h"
 
@@ -137,6 +138,11 @@ struct VertexHeap {
 
 inline double dot( const double* a, const double* b ) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// An edge whose dot product is exactly zero (a zero normal, two exactly orthogonal ones) is never strong, whatever the threshold:
+// the reference's test "n_u(now) . n_v < 0" is false for it whichever way u points, so it relates no two signs -- its end simply
+// keeps the sign it came with.  (orient_contract.hip, initWordsKernel, classifies the same way.)
+inline bool isStrong( double d, double tau ) { return std::fabs( d ) >= tau && d != 0.0; }
+
 }  // namespace
 
 // Spanning-tree growth proper.  edgeDot[u][j] = n_u . n_knn[u][j] on the ORIGINAL normals (fp64, evaluated as dot()
@@ -194,7 +200,7 @@ static bool growSigns( const int16_t* xyz, size_t n, const uint32_t* knn, int k,
       for ( int j = 0; j < k; ++j ) {
         const uint32_t v      = row[j];
         const double   d      = sc * dr[j];
-        const bool     strong = std::fabs( d ) >= tau;
+        const bool     strong = isStrong( d, tau );
         const int32_t  pv     = st[v];  // an earlier edge of this row may have changed it (cached by now)
         if ( pv == kVisited ) {
           if ( strong && phase[v] == epoch && ( d < 0.0 ) != ( sign[v] < 0 ) && v != cur ) return false;
@@ -266,6 +272,10 @@ static bool growSigns( const int16_t* xyz, size_t n, const uint32_t* knn, int k,
 // growSigns() with clusters for vertices: strong cross edges (one-way ones) are absorbed breadth-first and checked,
 // light ones go through the heap, whose key is still the reference's (weight, start vertex, end vertex) -- one pending
 // entry per unvisited cluster: the best edge into any of its vertices is the one the per-vertex heap would pop first.
+// Edges of weight exactly zero.  Such an edge is light at every threshold (isStrong) and the last the heap gives out; when it is
+// the one that reaches a cluster, the end vertex keeps the sign it came with (sign[u] * 0 is never < 0), whatever sign[u] is.  The
+// cluster's sign is then ABSOLUTE, not relative to the seed, and so is everything the growth reaches from it: such clusters are
+// marked `anchored` and take no part in the seed's flip below.
 // Seeds.  The reference orients the first point of every connected component by a rule that reads the normals of its
 // already oriented neighbours (orientSeedSign below).  Everything else in the component is oriented RELATIVE to its
 // seed, so the walk gives every seed +1 provisionally, numbers the components in the order it opens them
@@ -282,7 +292,7 @@ namespace {
 struct ClusterHeap {  // indexed 4-ary max-heap, one pending entry per cluster; key = the reference's (|d|, start, end)
   struct Entry {
     double   d;
-    uint32_t v, s, c, pad;
+    uint32_t v, s, c, flags;  // (flags: bit 0 = parity of v, bit 1 = the start cluster is anchored)
   };
   std::vector<Entry>   heap;
   std::vector<int32_t> st;  // slot of the cluster's entry, kAbsent, kVisited
@@ -321,8 +331,8 @@ struct ClusterHeap {  // indexed 4-ary max-heap, one pending entry per cluster; 
     }
     place( i, e );
   }
-  void offer( uint32_t c, double d, uint32_t v, uint32_t start ) {
-    const Entry   cand{d, v, start, c, 0};
+  void offer( uint32_t c, double d, uint32_t v, uint32_t start, uint32_t flags ) {  // (flags ride along: no part of the key)
+    const Entry   cand{d, v, start, c, flags};
     const int32_t pos = st[c];
     if ( pos == kAbsent ) {
       heap.push_back( cand );
@@ -361,8 +371,9 @@ struct ClusterHeap {  // indexed 4-ary max-heap, one pending entry per cluster; 
 // clusterSign[c]: the sign of cluster c's root-relative frame; component[c]: the component it
 // belongs to; seeds / seedClusters: the first point and the cluster of every component, in the order they were opened
 bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign, uint32_t* component, std::vector<uint32_t>& seeds,
-                         std::vector<uint32_t>& seedClusters ) {
+                         std::vector<uint32_t>& seedClusters, std::vector<uint8_t>& anchored ) {
   const uint32_t        C = g.clusters;
+  anchored.assign( C, 0 );
   ClusterHeap           heap( C );
   std::vector<uint32_t> phase( C, 0 ), queue;
   for ( uint32_t c = 0; c < C; ++c ) clusterSign[c] = 1;
@@ -380,7 +391,7 @@ bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign
         const OrientCompactEdge& x      = g.edges[e];
         const uint32_t           c2     = x.c2;
         const double             d      = sc * x.d;  // = sign[u] n_u.n_v (-1)^parity[v]
-        const bool               strong = std::fabs( x.d ) >= tau;
+        const bool               strong = isStrong( x.d, tau );
         const int32_t            pv     = heap.st[c2];
         if ( pv == kVisited ) {
           if ( strong && phase[c2] == epoch && ( d < 0.0 ) != ( clusterSign[c2] < 0 ) ) return false;
@@ -388,10 +399,11 @@ bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign
           if ( pv >= 0 ) heap.remove( size_t( pv ) );
           heap.st[c2]     = kVisited;
           clusterSign[c2] = d < 0.0 ? -1 : 1;
+          anchored[c2]    = anchored[c];
           phase[c2]       = epoch;
           queue.push_back( c2 );
         } else {
-          heap.offer( c2, d, x.v, x.u );
+          heap.offer( c2, d, x.v, x.u, ( x.pv & 1u ) | ( anchored[c] ? 2u : 0u ) );
         }
       }
     }
@@ -410,7 +422,13 @@ bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign
     if ( !absorb( c ) ) return false;
     while ( !heap.heap.empty() ) {
       const ClusterHeap::Entry e = heap.popMax();
-      clusterSign[e.c]           = e.d < 0.0 ? -1 : 1;
+      if ( e.d == 0.0 ) {  // (+-0: the end vertex stays as it is -- its cluster's frame follows from its parity alone)
+        clusterSign[e.c] = int8_t( ( e.flags & 1u ) ? -1 : 1 );
+        anchored[e.c]    = 1;
+      } else {
+        clusterSign[e.c] = e.d < 0.0 ? -1 : 1;
+        anchored[e.c]    = uint8_t( ( e.flags >> 1 ) & 1u );
+      }
       if ( !absorb( e.c ) ) return false;
     }
   }
@@ -422,7 +440,8 @@ bool orientCompactSigns( const OrientCompact& g, double tau, int8_t* clusterSign
 // Seed rule after the compact walk.  who: [seeds][kNN + 1][3] = (point, cluster, parity) of the point before the seed in index
 // order and of its kNN neighbours; normals: [seeds][kNN + 2][3] = seed, point before, neighbours (gatherSeedTables).
 void resolveSeedSignsCompact( const OrientCompact& g, int kNN, const std::vector<uint32_t>& seeds, const std::vector<uint32_t>& seedClusters,
-                              const uint32_t* component, const uint32_t* who, const double* normals, const int16_t* xyz0, int8_t* clusterSign ) {
+                              const uint32_t* component, const std::vector<uint8_t>& anchored, const uint32_t* who, const double* normals,
+                              const int16_t* xyz0, int8_t* clusterSign ) {
   std::vector<int8_t> compSign( seeds.size(), 1 );
   for ( size_t k = 0; k < seeds.size(); ++k ) {
     const uint32_t  i   = seeds[k];
@@ -432,7 +451,7 @@ void resolveSeedSignsCompact( const OrientCompact& g, int kNN, const std::vector
     const auto signThen = [&]( int t ) -> int {
       const uint32_t c = w[3 * t + 1];
       if ( component[c] >= k ) return 0;
-      const int sc = int( clusterSign[c] ) * int( compSign[component[c]] );
+      const int sc = int( clusterSign[c] ) * ( anchored[c] ? 1 : int( compSign[component[c]] ) );
       return ( w[3 * t + 2] & 1 ) ? -sc : sc;
     };
     double acc[3]   = {0.0, 0.0, 0.0};
@@ -465,7 +484,7 @@ void resolveSeedSignsCompact( const OrientCompact& g, int kNN, const std::vector
   }
   (void)seedClusters;
   for ( uint32_t c = 0; c < g.clusters; ++c )
-    if ( compSign[component[c]] < 0 ) clusterSign[c] = int8_t( -clusterSign[c] );
+    if ( !anchored[c] && compSign[component[c]] < 0 ) clusterSign[c] = int8_t( -clusterSign[c] );
 }
 
 // host-side contraction (the device path does the same in orient_contract.hip): union-find with parity over the
@@ -499,7 +518,7 @@ static bool contractOnHost( size_t n, const uint32_t* knn, int k, const double* 
     for ( int j = 0; j < k; ++j ) {
       const uint32_t v = knn[u * k + j];
       const double   d = edgeDot[u * k + j];
-      if ( v >= u || std::fabs( d ) < tau ) continue;  // every mutual edge is seen from both ends: the larger acts
+      if ( v >= u || !isStrong( d, tau ) ) continue;  // every mutual edge is seen from both ends: the larger acts
       bool mutual = false;
       for ( int t = 0; t < k; ++t ) mutual |= knn[size_t( v ) * k + t] == u;
       if ( !mutual ) continue;
@@ -525,7 +544,7 @@ static bool contractOnHost( size_t n, const uint32_t* knn, int k, const double* 
     for ( int j = 0; j < k; ++j ) {
       const uint32_t v = knn[u * k + j];
       const double   d = edgeDot[u * k + j];
-      if ( std::fabs( d ) >= tau && root[v] == root[u] && ( uint8_t( parity[u] ^ parity[v] ) != ( d < 0.0 ? 1 : 0 ) ) ) return false;
+      if ( isStrong( d, tau ) && root[v] == root[u] && ( uint8_t( parity[u] ^ parity[v] ) != ( d < 0.0 ? 1 : 0 ) ) ) return false;
     }
   off.assign( n + 1, 0 );
   for ( size_t u = 0; u < n; ++u )
@@ -573,7 +592,7 @@ static void compactOnHost( size_t n, const std::vector<uint32_t>& root, const st
     std::vector<OrientCompactEdge> all;
     for ( uint32_t e = off[r]; e < off[r + 1]; ++e ) {
       const OrientCrossEdge& x = edges[e];
-      all.push_back( OrientCompactEdge{x.u, x.v, out.cid[x.v], 0u, ( ( parity[x.u] ^ parity[x.v] ) & 1 ) ? -x.d : x.d} );
+      all.push_back( OrientCompactEdge{x.u, x.v, out.cid[x.v], uint32_t( parity[x.v] ), ( ( parity[x.u] ^ parity[x.v] ) & 1 ) ? -x.d : x.d} );
     }
     std::stable_sort( all.begin(), all.end(), []( const OrientCompactEdge& a, const OrientCompactEdge& b ) { return a.c2 < b.c2; } );
     std::vector<OrientCompactEdge>& keep = per[out.cid[r]];
@@ -581,13 +600,13 @@ static void compactOnHost( size_t n, const std::vector<uint32_t>& root, const st
       size_t j    = i;
       double best = -1.0;
       while ( j < all.size() && all[j].c2 == all[i].c2 ) {
-        if ( std::fabs( all[j].d ) < tau ) best = std::max( best, std::fabs( all[j].d ) );
+        if ( !isStrong( all[j].d, tau ) ) best = std::max( best, std::fabs( all[j].d ) );
         ++j;
       }
       bool strongSeen[2] = {false, false};
       for ( size_t t = i; t < j; ++t ) {
         const double w = std::fabs( all[t].d );
-        if ( w >= tau ) {
+        if ( isStrong( all[t].d, tau ) ) {
           const int cls = all[t].d < 0.0 ? 1 : 0;
           if ( !strongSeen[cls] ) keep.push_back( all[t] );
           strongSeen[cls] = true;
@@ -661,8 +680,9 @@ int orientSpanningTreeSigns( const int16_t* xyz, size_t n, const uint32_t* knn, 
       const OrientCompact   g = hc.view();
       std::vector<int8_t>   clusterSign( g.clusters + 1 );
       std::vector<uint32_t> component( g.clusters + 1 ), seeds, seedClusters;
+      std::vector<uint8_t>  anchored;
       const auto tg0 = std::chrono::steady_clock::now();
-      const bool okw = orientCompactSigns( g, first, clusterSign.data(), component.data(), seeds, seedClusters );
+      const bool okw = orientCompactSigns( g, first, clusterSign.data(), component.data(), seeds, seedClusters, anchored );
       if ( ctxOption( ctx, "ORIENT_TIMING" ) )
         fprintf( stderr, "  the growth over the compact graph alone: %.2f ms (%u clusters, %u edges)\n",
                  std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - tg0 ).count(), g.clusters, g.rec[g.clusters].off );
@@ -681,7 +701,7 @@ int orientSpanningTreeSigns( const int16_t* xyz, size_t n, const uint32_t* knn, 
             for ( int c = 0; c < 3; ++c ) nrm[( sd * size_t( k + 2 ) + size_t( j ) ) * 3 + c] = normals[3 * size_t( v ) + c];
           }
         }
-        resolveSeedSignsCompact( g, k, seeds, seedClusters, component.data(), who.data(), nrm.data(), xyz, clusterSign.data() );
+        resolveSeedSignsCompact( g, k, seeds, seedClusters, component.data(), anchored, who.data(), nrm.data(), xyz, clusterSign.data() );
         for ( size_t i = 0; i < n; ++i ) sign[i] = int8_t( ( parity[i] & 1 ) ? -clusterSign[hc.cid[i]] : clusterSign[hc.cid[i]] );
       }
       if ( ctxOption( ctx, "ORIENT_TIMING" ) )
@@ -695,7 +715,8 @@ int orientSpanningTreeSigns( const int16_t* xyz, size_t n, const uint32_t* knn, 
     ++growths;
     if ( growSigns( xyz, n, knn, k, normals, edgeDot, sign, scratch, tau ) ) return growths;
   }
-  growSigns( xyz, n, knn, k, normals, edgeDot, sign, scratch, 4.0 );  // no edge is "strong"
+  // the plain growth: no edge is "strong" -- at NO finite threshold (|n_u . n_v| passes 4 as soon as a caller's normals are longer than 2)
+  growSigns( xyz, n, knn, k, normals, edgeDot, sign, scratch, std::numeric_limits<double>::infinity() );
   return growths + 1;
 }
 
@@ -760,11 +781,12 @@ int orientNormalsHost( tmc2_frame* f, const std::function<int()>* beforeHostWalk
       const uint32_t        C           = g.clusters;
       int8_t*               clusterSign = reinterpret_cast<int8_t*>( ctx->hostC.get<uint32_t>( 4 + ( n + 4 ) / 4 + 4 ) + 4 );  // (behind the counters)
       std::vector<uint32_t> seeds, seedClusters, component( C );
+      std::vector<uint8_t>  anchored;
       bool                  ok;
       {
         HostGate   gate( ctx );
         const auto t0 = std::chrono::steady_clock::now();
-        ok            = orientCompactSigns( g, tau, clusterSign, component.data(), seeds, seedClusters );
+        ok            = orientCompactSigns( g, tau, clusterSign, component.data(), seeds, seedClusters, anchored );
         const auto t1 = std::chrono::steady_clock::now();
         ctx->stageAddHostMs( "orient_normals_host", std::chrono::duration<double, std::milli>( t1 - t0 ).count() );
       }
@@ -773,7 +795,7 @@ int orientNormalsHost( tmc2_frame* f, const std::function<int()>* beforeHostWalk
         std::vector<uint32_t> who;
         std::vector<double>   seedNormals;
         TMC2_TRY( gatherSeedTables( f, d_root.p, d_parity.p, seeds, who, seedNormals ) );
-        resolveSeedSignsCompact( g, f->k, seeds, seedClusters, component.data(), who.data(), seedNormals.data(), f->h_xyz.data(), clusterSign );
+        resolveSeedSignsCompact( g, f->k, seeds, seedClusters, component.data(), anchored, who.data(), seedNormals.data(), f->h_xyz.data(), clusterSign );
         TMC2_TRY( d_clusterSign.alloc( std::max<uint32_t>( C, 1u ) ) );
         TMC2_HIP( hipMemcpyAsync( d_clusterSign.p, clusterSign, C, hipMemcpyHostToDevice, s ) );
         TMC2_TRY( launchClusterSigns( f, d_root.p, d_parity.p, d_clusterSign.p, d_sign.p ) );
