@@ -108,6 +108,24 @@ struct BuildArgs {
 
 __device__ __forceinline__ int coordOf( const Pt p, int d ) { return d == 0 ? p.x : ( d == 1 ? p.y : p.z ); }
 
+// What a thread fetches together is loaded into registers AHEAD of the branches that consume it and pinned there (lvPin): left
+// alone, the compiler sinks every load into the exec-masked block of its first use, behind that block's own s_waitcnt vmcnt(0),
+// and takes a 16-byte load apart into the words that are used -- a chain of round trips where the source reads like a batch.
+typedef uint32_t LvW2 __attribute__( ( ext_vector_type( 2 ) ) );
+typedef uint32_t LvW4 __attribute__( ( ext_vector_type( 4 ) ) );
+__device__ __forceinline__ void lvPin( uint32_t& a ) { asm volatile( "" : "+v"( a ) ); }
+__device__ __forceinline__ void lvPin( LvW2& a ) { asm volatile( "" : "+v"( a ) ); }
+__device__ __forceinline__ void lvPin( LvW4& a ) { asm volatile( "" : "+v"( a ) ); }
+template <typename T, typename... Rest>
+__device__ __forceinline__ void lvPin( T& a, Rest&... rest ) {  // (one asm per value: the waits the compiler puts before them collapse into the first)
+  lvPin( a );
+  lvPin( rest... );
+}
+// a point as its two words (x | y << 16, z | w << 16): one 8-byte load that stays one
+__device__ __forceinline__ int32_t lvCoord( LvW2 p, int d ) {
+  return d == 0 ? int32_t( int16_t( p.x & 0xFFFFu ) ) : ( d == 1 ? int32_t( int16_t( p.x >> 16 ) ) : int32_t( int16_t( p.y & 0xFFFFu ) ) );
+}
+
 struct SplitRule {
   int     dim;
   int32_t cut;
@@ -172,10 +190,14 @@ __device__ __forceinline__ uint32_t blockClassLists( const Pt* pts, uint32_t cou
     const uint32_t i0 = base + 4u * threadIdx.x;
     bool           ge[4];
     uint32_t       cGE = 0, cIn = 0;
+    LvW2           pw[4];  // (the four loads ahead of one wait)
+#pragma unroll
+    for ( int j = 0; j < 4; ++j ) pw[j] = *reinterpret_cast<const LvW2*>( pts + ( i0 + j < count ? i0 + j : 0u ) );
+    lvPin( pw[0], pw[1], pw[2], pw[3] );
 #pragma unroll
     for ( int j = 0; j < 4; ++j ) {
       const bool    in = i0 + j < count;
-      const int32_t x  = coordOf( pts[in ? i0 + j : 0u], dim );
+      const int32_t x  = lvCoord( pw[j], dim );
       ge[j]            = in && x >= c;
       cGE += uint32_t( ge[j] ), cIn += uint32_t( in );
     }
@@ -213,9 +235,9 @@ __device__ __forceinline__ uint32_t blockSweep( Pt* pts, uint32_t* id, uint32_t 
   const uint32_t nGE = blockClassLists( pts, count, dim, c, listGE, listLT, waveCnt ), nL = count - nGE;
   __syncthreads();
   for ( uint32_t t = threadIdx.x; t < min( nGE, nL ); t += blockDim.x ) {
-    const uint32_t x = listGE[t];
+    uint32_t x = listGE[t], y = listLT[nL - 1u - t];  // (both entries together: t < nL)
+    lvPin( x, y );
     if ( x >= nL ) break;  // (ascending: nothing misplaced from here on)
-    const uint32_t y  = listLT[nL - 1u - t];
     const Pt       px = pts[x], py = pts[y];
     const uint32_t ix = id[x], iy = id[y];
     pts[x] = py, pts[y] = px, id[x] = iy, id[y] = ix;
@@ -301,9 +323,18 @@ __global__ __launch_bounds__( 64 * kHugeWaves ) void hugeSegmentsKernel( BuildAr
         if ( lane == 0 )
           for ( int k = 0; k < 12; ++k ) red[wave][k] = r[k];
         __syncthreads();
+        // the wavefronts' partial ranges, one of the twelve numbers per thread.  (Thread 0 folding all 16 x 12 was unrolled
+        // into 192 LDS reads in flight at once: the kernel sat at its 128-VGPR cap with 596 bytes of private memory per lane
+        // and spilled inside the sweeps' loops; now 101 VGPRs and none.)
+        if ( threadIdx.x < 12 ) {
+          int32_t v = red[0][threadIdx.x];
+          for ( int w = 1; w < kHugeWaves; ++w ) v = ( threadIdx.x % 6 ) < 3 ? min( v, red[w][threadIdx.x] ) : max( v, red[w][threadIdx.x] );
+          red[0][threadIdx.x] = v;
+        }
+        __syncthreads();
         if ( threadIdx.x == 0 ) {
-          for ( int w = 0; w < kHugeWaves; ++w )
-            for ( int k = 0; k < 12; ++k ) r[k] = ( k % 6 ) < 3 ? min( r[k], red[w][k] ) : max( r[k], red[w][k] );
+#pragma unroll
+          for ( int k = 0; k < 12; ++k ) r[k] = red[0][k];
           const uint32_t id0 = atomicAdd( a.nodeCount, 2u );
           KdNode         nd;
           nd.a = int32_t( id0 ), nd.b = int32_t( id0 + 1 ), nd.divlow = int16_t( r[3 + rule.dim] ), nd.divhigh = int16_t( r[6 + rule.dim] ),
@@ -460,18 +491,41 @@ __device__ __forceinline__ void ldsMax( int32_t* slot, int32_t v ) {
 //     that thread of the last pass.
 // Launches per level: flags, swaps, flags, swaps + landing, decide (tiny).  Swap for swap nanoflann's planeSplit
 // (nanoflann.hpp:1154-1181), as everything in this file.
-struct LvSeg {
-  uint32_t begin, end;     // range in tree order
-  uint32_t cutInfo;        // cut (16 bits) | cutDim << 16 | splits << 24
-  uint32_t edge1;          // first position not of the first sweep's left class (stored by the first swap pass)
-  uint32_t slot;           // the children's segments at the next level: slot, slot + 1
-  uint32_t childNode;      // ... and their node ids: childNode, childNode + 1
-  uint32_t node, parent;   // own node id; parent's node id (kNone for the root)
-  int16_t  lo[3], hi[3];   // loose box handed down by the parent (root: unused, its box is its range)
-  uint8_t  side, pdim;     // which child of the parent we are, and the parent's cut dimension
+// The chains as the code object has them (what a thread waits for in a row; loads of one step are issued together, ahead of
+// the branches that use them, at clamped addresses where a position is retired or lies beyond n -- lvPin above):
+//   * lvFlagKernel, per tile, a thread on its 8 consecutive positions: the 8 seg words (two 16-byte loads) -> the cut word of
+//     the 8 records (second sweep: cut word and edge1, one 8-byte load each) together with the 8 points (four 16-byte loads).
+//     loc goes out as two 16-byte stores.  The second sweep's reset of the children's ranges: cutInfo and slot together,
+//     then a 16- and an 8-byte store per child.  (Was: seg, record, point one after the other for each of the 8 positions.)
+//   * lvSwapTwoKernel, per position: seg -> { record rows 0, 1, 2, P[i], loc2[i], perm[i] } -> { loc2[edge1], loc2[end] } ->
+//     list -> { P[j], perm[j] }; the thread on a segment's first position builds both children in registers from the rows it
+//     holds and stores rows 0 .. 2 of each whole; lvReport reads its six words ahead of one wait and then issues the
+//     atomics it still needs with no wait between them.
+//   * lvSwapOneKernel and lvDecideKernel read their records field by field as before: the batched forms (SwapOne: 5 trips
+//     instead of 8, also with a thread's two positions sharing every trip; Decide: the record's rows and the six range words
+//     in two batches) measured no faster, alone or with 16 frames in flight -- the first swap pass is bound by its scattered
+//     swaps, not by its chain.  Fetching P[i] / loc[i] / perm[i] before seg[i] is known (a trip less, but for retired positions
+//     too) measured no better either.  profiles/kdtree_level_loads.txt has the figures.
+// The record is read and written in ROWS of 16 bytes (lvRow / lvStoreRow): row 0 is what every position of a sweep needs, row 1
+// what the landing pass adds, row 2 the box a segment's first position hands down; the tight range (atomics) follows and is
+// only ever touched word by word.  80 bytes, 16-byte aligned: a row is one global_load_dwordx4.
+struct alignas( 16 ) LvSeg {
+  uint32_t begin, end;     // [ 0] range in tree order
+  uint32_t cutInfo;        //      cut (16 bits) | cutDim << 16 | splits << 24
+  uint32_t edge1;          //      first position not of the first sweep's left class (stored by the first swap pass)
+  uint32_t slot;           // [16] the children's segments at the next level: slot, slot + 1
+  uint32_t childNode;      //      ... and their node ids: childNode, childNode + 1
+  uint32_t node, parent;   //      own node id; parent's node id (kNone for the root)
+  int16_t  lo[3], hi[3];   // [32] loose box handed down by the parent (root: unused, its box is its range)
+  uint8_t  side, pdim;     //      which child of the parent we are, and the parent's cut dimension
   uint16_t unused;
-  int32_t  mn[3], mx[3];   // tight range of the points (atomics)
+  int32_t  mn[3], mx[3];   // [48] tight range of the points (atomics)
+  uint32_t pad[2];
 };
+static_assert( sizeof( LvSeg ) == 80 && offsetof( LvSeg, slot ) == 16 && offsetof( LvSeg, lo ) == 32 && offsetof( LvSeg, mn ) == 48, "LvSeg rows" );
+
+__device__ __forceinline__ LvW4 lvRow( const LvSeg* q, int row ) { return reinterpret_cast<const LvW4*>( q )[row]; }
+__device__ __forceinline__ void lvStoreRow( LvSeg* q, int row, LvW4 w ) { reinterpret_cast<LvW4*>( q )[row] = w; }
 
 constexpr int kLandBlock = 256;  // the landing pass: one record of the children's ranges per workgroup (measured: 1 024-thread workgroups quarter the records the decide pass folds -- 14 -> 7 us -- and cost the landing pass itself 18 -> 32 us)
 constexpr int kLandRounds = 2;  // ... of consecutive rounds of kLandBlock positions: their records are merged where they name the same segment
@@ -482,16 +536,29 @@ struct LvPartial {
 };
 
 __device__ __forceinline__ void lvReport( LvSeg* child, int mnx, int mny, int mnz, int mxx, int mxy, int mxz ) {
-  if ( mnx < loadStaleOk( &child->mn[0] ) ) atomicMin( &child->mn[0], mnx );
-  if ( mny < loadStaleOk( &child->mn[1] ) ) atomicMin( &child->mn[1], mny );
-  if ( mnz < loadStaleOk( &child->mn[2] ) ) atomicMin( &child->mn[2], mnz );
-  if ( mxx > loadStaleOk( &child->mx[0] ) ) atomicMax( &child->mx[0], mxx );
-  if ( mxy > loadStaleOk( &child->mx[1] ) ) atomicMax( &child->mx[1], mxy );
-  if ( mxz > loadStaleOk( &child->mx[2] ) ) atomicMax( &child->mx[2], mxz );
+  // the six (possibly stale) words ahead of one wait, then the atomics that are still needed, none of them waited for
+  uint32_t s0 = uint32_t( loadStaleOk( &child->mn[0] ) ), s1 = uint32_t( loadStaleOk( &child->mn[1] ) ), s2 = uint32_t( loadStaleOk( &child->mn[2] ) );
+  uint32_t s3 = uint32_t( loadStaleOk( &child->mx[0] ) ), s4 = uint32_t( loadStaleOk( &child->mx[1] ) ), s5 = uint32_t( loadStaleOk( &child->mx[2] ) );
+  lvPin( s0, s1, s2, s3, s4, s5 );
+  if ( mnx < int32_t( s0 ) ) atomicMin( &child->mn[0], mnx );
+  if ( mny < int32_t( s1 ) ) atomicMin( &child->mn[1], mny );
+  if ( mnz < int32_t( s2 ) ) atomicMin( &child->mn[2], mnz );
+  if ( mxx > int32_t( s3 ) ) atomicMax( &child->mx[0], mxx );
+  if ( mxy > int32_t( s4 ) ) atomicMax( &child->mx[1], mxy );
+  if ( mxz > int32_t( s5 ) ) atomicMax( &child->mx[2], mxz );
 }
 
 __device__ __forceinline__ uint32_t lvPrefix( const uint32_t* __restrict__ loc, const uint32_t* sums, uint32_t tiles, uint32_t i, uint32_t n ) {
   return i < n ? loc[i] + sums[i / kScanTile] : sums[tiles];
+}
+// The prefix sums at two positions (the ends of a sweep), both look-ups issued together.  A segment may end at n, where the
+// prefix is the grand total: the address is clamped and what it returns is not used.
+__device__ __forceinline__ void lvPrefix2( const uint32_t* __restrict__ loc, const uint32_t* sums, uint32_t tiles, uint32_t i0, uint32_t i1, uint32_t n,
+                                           uint32_t& r0, uint32_t& r1 ) {
+  uint32_t l0 = loc[min( i0, n - 1u )], l1 = loc[min( i1, n - 1u )];
+  lvPin( l0, l1 );
+  r0 = i0 < n ? l0 + sums[i0 / kScanTile] : sums[tiles];
+  r1 = i1 < n ? l1 + sums[i1 / kScanTile] : sums[tiles];
 }
 
 // The position of the element of global rank G among the elements that are NOT of the sweep's class, known to lie in
@@ -699,42 +766,71 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
   uint32_t*      tile  = FIRST ? a.tile1 : a.tile2;
   if ( !FIRST ) {  // the children's ranges start empty (the landing pass gathers them)
     for ( uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x ) {
-      const LvSeg* q = cur + s;
-      if ( !( q->cutInfo >> 24 ) ) continue;
-      for ( int c = 0; c < 2; ++c )
-        for ( int d = 0; d < 3; ++d ) next[q->slot + c].mn[d] = 0x7FFFFFFF, next[q->slot + c].mx[d] = int32_t( 0x80000000 );
+      const LvSeg* q  = cur + s;
+      uint32_t     ci = q->cutInfo, slot = q->slot;  // (one batch; the stores below cannot make the compiler read them again)
+      lvPin( ci, slot );
+      if ( !( ci >> 24 ) ) continue;
+      for ( int c = 0; c < 2; ++c ) {  // (the words of LvSeg::mn / mx: a row and a half)
+        uint32_t* w = reinterpret_cast<uint32_t*>( next[slot + c].mn );
+        *reinterpret_cast<LvW4*>( w )     = LvW4{0x7FFFFFFFu, 0x7FFFFFFFu, 0x7FFFFFFFu, 0x80000000u};
+        *reinterpret_cast<LvW2*>( w + 4 ) = LvW2{0x80000000u, 0x80000000u};
+      }
     }
   }
+  // A thread owns 8 consecutive positions (32 bytes of seg and loc, 64 of P, all 16-byte aligned: the arrays start on 32-byte
+  // boundaries and are padded to whole groups).  Two round trips per tile: the 8 segment ids; then, together, the cut word(s)
+  // of the 8 records and the 8 points.  Positions at or beyond n and retired positions read record 0 / point 0 instead (always
+  // there) and what comes back is not used.
   for ( uint32_t t = blockIdx.x; t < tiles; t += gridDim.x ) {
     const uint32_t base = t * kScanTile + threadIdx.x * 8;
-    uint32_t       v[8], run = 0;
+    uint32_t       run = 0, flags = 0, liveAt = 0;  // (bit k: position base + k carries the class flag / lies in a segment)
+    LvW4           sA = LvW4{kNone, kNone, kNone, kNone}, sB = sA;
+    if ( base < n ) sA = *reinterpret_cast<const LvW4*>( a.seg + base );
+    if ( base + 4 < n ) sB = *reinterpret_cast<const LvW4*>( a.seg + base + 4 );
+    lvPin( sA, sB );
+    uint32_t sg[8] = {sA.x, sA.y, sA.z, sA.w, sB.x, sB.y, sB.z, sB.w};
+    uint32_t ci[8], e1[8];
+    LvW4     pp[4];
 #pragma unroll
     for ( int k = 0; k < 8; ++k ) {
-      const uint32_t i = base + k;
-      uint32_t       f = 0;
-      if ( i < n ) {
-        const uint32_t s = a.seg[i];
-        if ( s != kNone ) {
-          const LvSeg*   q  = cur + s;
-          const uint32_t ci = q->cutInfo;
-          if ( ci >> 24 ) {
-            const int32_t c = int32_t( int16_t( ci & 0xFFFFu ) ), x = coordOf( a.P[i], int( ( ci >> 16 ) & 0xFFu ) );
-            f               = FIRST ? uint32_t( x >= c ) : uint32_t( i >= q->edge1 && x > c );
-          }
-        }
+      if ( base + k >= n ) sg[k] = kNone;  // (the padding of a group that n cuts holds whatever the pool left there)
+      liveAt |= uint32_t( sg[k] != kNone ) << k;
+      const LvSeg* q = cur + ( sg[k] != kNone ? sg[k] : 0u );
+      if ( FIRST ) {
+        ci[k] = q->cutInfo, e1[k] = 0;
+      } else {
+        const LvW2 w = *reinterpret_cast<const LvW2*>( &q->cutInfo );  // cutInfo, edge1
+        ci[k] = w.x, e1[k] = w.y;
       }
-      v[k] = f;
+    }
+#pragma unroll
+    for ( int m = 0; m < 4; ++m ) pp[m] = *reinterpret_cast<const LvW4*>( a.P + ( base + 2 * m < n ? base + 2 * m : 0u ) );  // (P has a spare element past n)
+#pragma unroll
+    for ( int k = 0; k < 8; ++k ) lvPin( ci[k] ), lvPin( e1[k] );
+    lvPin( pp[0], pp[1], pp[2], pp[3] );
+#pragma unroll
+    for ( int k = 0; k < 8; ++k ) {
+      const uint32_t i  = base + k;
+      const uint32_t lw = ( k & 1 ) ? pp[k / 2].z : pp[k / 2].x, hw = ( k & 1 ) ? pp[k / 2].w : pp[k / 2].y;  // x | y << 16, z | w << 16
+      const int      dim = int( ( ci[k] >> 16 ) & 0xFFu );
+      const int32_t  c = int32_t( int16_t( ci[k] & 0xFFFFu ) );
+      const int32_t  x = dim == 0 ? int32_t( int16_t( lw & 0xFFFFu ) ) : ( dim == 1 ? int32_t( int16_t( lw >> 16 ) ) : int32_t( int16_t( hw & 0xFFFFu ) ) );
+      const bool     live = ( ( liveAt >> k ) & 1u ) != 0 && ( ci[k] >> 24 ) != 0;
+      const uint32_t f    = live ? ( FIRST ? uint32_t( x >= c ) : uint32_t( i >= e1[k] && x > c ) ) : 0u;
+      flags |= f << k;
       run += f;
     }
     uint32_t offset = blockExclusive<kWaves>( run, waveTot );
+    uint32_t at[8];
 #pragma unroll
     for ( int k = 0; k < 8; ++k ) {
-      if ( base + k < n ) {
-        loc[base + k] = offset;
-        if ( !v[k] ) a.list[size_t( t ) * kScanTile + ( threadIdx.x * 8 + k - offset )] = uint16_t( threadIdx.x * 8 + k );
-      }
-      offset += v[k];
+      at[k] = offset;
+      const uint32_t f = ( flags >> k ) & 1u;
+      if ( base + k < n && !f ) a.list[size_t( t ) * kScanTile + ( threadIdx.x * 8 + k - offset )] = uint16_t( threadIdx.x * 8 + k );
+      offset += f;
     }
+    if ( base < n ) *reinterpret_cast<LvW4*>( loc + base ) = LvW4{at[0], at[1], at[2], at[3]};            // (into the padding where n cuts
+    if ( base + 4 < n ) *reinterpret_cast<LvW4*>( loc + base + 4 ) = LvW4{at[4], at[5], at[6], at[7]};    //  the group: never read)
     if ( threadIdx.x == kBlock - 1 ) tile[t] = offset;  // (the RAW total: the swap passes scan the totals themselves, in LDS)
     __syncthreads();
   }
@@ -817,62 +913,71 @@ __global__ __launch_bounds__( kLandBlock ) void lvSwapTwoKernel( BuildArgs a, ui
     bool           moved = false;
     uint32_t       s = kNone, slot = 0;
     if ( i < n ) {
-      s           = a.seg[i];
+      // the chain of a position: seg -> { record rows 0, 1, 2, P[i], loc2[i], perm[i] } -> { loc2[edge1], loc2[end] } -> list ->
+      // { P[j], perm[j] }.  Row 2 (the loose box) is only used by the thread on the segment's first position; which one that is
+      // comes with row 0, so everybody asks for it in the same batch (the lanes of a segment ask for the same 16 bytes).
+      s = a.seg[i];
+      LvW2     pw;
+      uint32_t li, u;
       uint32_t to = kNone;
       if ( s != kNone ) {
-        LvSeg*         q  = cur + s;
-        const uint32_t ci = q->cutInfo;
+        LvSeg* q  = cur + s;
+        LvW4   r0 = lvRow( q, 0 ), r1 = lvRow( q, 1 ), r2 = lvRow( q, 2 );
+        pw = *reinterpret_cast<const LvW2*>( a.P + i ), li = a.loc2[i], u = a.perm[i];
+        lvPin( r0, r1, r2, pw, li, u );
+        const uint32_t ci = r0.z;
         if ( ci >> 24 ) {
-          const uint32_t b = q->begin, e = q->end, e1 = q->edge1;
-          slot               = q->slot;
+          const uint32_t b = r0.x, e = r0.y, e1 = r0.w;
+          slot               = r1.x;
           const int      dim = int( ( ci >> 16 ) & 0xFFu );
           const int32_t  cut = int32_t( int16_t( ci & 0xFFFFu ) );
-          Pt             pi  = a.P[i];
-          const uint32_t li  = a.loc2[i];
-          const uint32_t rb = lvPrefix( a.loc2, lvSums, tiles, e1, n ), re = lvPrefix( a.loc2, lvSums, tiles, e, n );
+          uint32_t       rb, re;
+          lvPrefix2( a.loc2, lvSums, tiles, e1, e, n, rb, re );
           const uint32_t e2   = e1 + ( ( e - e1 ) - ( re - rb ) );
           const uint32_t cnt  = e - b, half = cnt / 2, lim1 = e1 - b, lim2 = e2 - b;
           const uint32_t idx  = lim1 > half ? lim1 : ( lim2 < half ? lim2 : half );
           const uint32_t mid  = b + idx;
           if ( i == b ) {  // the children (their ranges are being gathered by everybody: not touched here) and the node record
-            KdNode nd;
-            nd.a = int32_t( q->childNode ), nd.b = int32_t( q->childNode + 1u ), nd.divlow = nd.divhigh = 0, nd.dim = dim;
-            a.nodes[q->node] = nd;
-            for ( int c = 0; c < 2; ++c ) {
-              LvSeg* ch = next + slot + c;
-              ch->begin = c ? mid : b, ch->end = c ? e : mid, ch->cutInfo = 0, ch->edge1 = 0, ch->slot = 0, ch->childNode = 0;
-              ch->node = q->childNode + c, ch->parent = q->node, ch->side = uint8_t( c ), ch->pdim = uint8_t( dim ), ch->unused = 0;
-              for ( int d = 0; d < 3; ++d ) ch->lo[d] = q->lo[d], ch->hi[d] = q->hi[d];
-              if ( c == 0 ) {
-                if ( dim == 0 ) ch->hi[0] = int16_t( cut );
-                if ( dim == 1 ) ch->hi[1] = int16_t( cut );
-                if ( dim == 2 ) ch->hi[2] = int16_t( cut );
-              } else {
-                if ( dim == 0 ) ch->lo[0] = int16_t( cut );
-                if ( dim == 1 ) ch->lo[1] = int16_t( cut );
-                if ( dim == 2 ) ch->lo[2] = int16_t( cut );
-              }
-            }
+            const uint32_t childNode = r1.y, node = r1.z;
+            KdNode         nd;
+            nd.a = int32_t( childNode ), nd.b = int32_t( childNode + 1u ), nd.divlow = nd.divhigh = 0, nd.dim = dim;
+            a.nodes[node] = nd;
+            // both children built in registers from the parent's rows and stored as whole rows 0 .. 2: the left one takes the cut
+            // as hi[dim], the right one as lo[dim] (row 2 = lo[0] lo[1] | lo[2] hi[0] | hi[1] hi[2] | side, pdim, unused)
+            const uint32_t c16 = uint32_t( cut ) & 0xFFFFu;
+            LvW4           left = r2, right = r2;
+            if ( dim == 0 ) left.y = ( r2.y & 0x0000FFFFu ) | ( c16 << 16 ), right.x = ( r2.x & 0xFFFF0000u ) | c16;
+            if ( dim == 1 ) left.z = ( r2.z & 0xFFFF0000u ) | c16, right.x = ( r2.x & 0x0000FFFFu ) | ( c16 << 16 );
+            if ( dim == 2 ) left.z = ( r2.z & 0x0000FFFFu ) | ( c16 << 16 ), right.y = ( r2.y & 0xFFFF0000u ) | c16;
+            left.w = uint32_t( dim ) << 8, right.w = 1u | ( uint32_t( dim ) << 8 );
+            LvSeg* ch = next + slot;
+            lvStoreRow( ch, 0, LvW4{b, mid, 0u, 0u} );
+            lvStoreRow( ch, 1, LvW4{0u, 0u, childNode, node} );
+            lvStoreRow( ch, 2, left );
+            lvStoreRow( ch + 1, 0, LvW4{mid, e, 0u, 0u} );
+            lvStoreRow( ch + 1, 1, LvW4{0u, 0u, childNode + 1u, node} );
+            lvStoreRow( ch + 1, 2, right );
           }
-          const int32_t x = coordOf( pi, dim );
+          const int32_t x = lvCoord( pw, dim );
           to              = slot + ( i >= mid ? 1u : 0u );
           key             = to;
           if ( i >= e1 && i < e2 && x > cut ) {  // misplaced on the left of the second sweep: swap; what moves away lands right of mid
             const uint32_t r  = li + lvSums[i / kScanTile] - rb;
             const uint32_t j  = lvPartner( a.list, lvSums, e2, e, ( e - re ) - 1u - r );
-            const Pt       pj = a.P[j];
-            a.P[i]            = pj;
-            a.P[j]            = pi;
-            const uint32_t u  = a.perm[i];
-            a.perm[i]         = a.perm[j];
-            a.perm[j]         = u;
-            moved             = true;
-            A2 = pk2( pi.x, pi.y ), B2 = A2, C2 = pk2( pi.z, ~int( pi.z ) );
-            pi = pj;
+            LvW2           pj = *reinterpret_cast<const LvW2*>( a.P + j );
+            uint32_t       uj = a.perm[j];
+            lvPin( pj, uj );
+            *reinterpret_cast<LvW2*>( a.P + i ) = pj;
+            *reinterpret_cast<LvW2*>( a.P + j ) = pw;
+            a.perm[i]                            = uj;
+            a.perm[j]                            = u;
+            moved                                = true;
+            A2 = pw.x, B2 = A2, C2 = pk2( lvCoord( pw, 2 ), ~lvCoord( pw, 2 ) );
+            pw = pj;
           }
           // (misplaced on the right of the second sweep: the partner swaps and reports what lands here -- this lane keeps the
           //  run of its child together and adds nothing; if the swap has happened already it sees the element that landed)
-          if ( !( i >= e2 && x <= cut ) ) A = pk2( pi.x, pi.y ), B = A, C = pk2( pi.z, ~int( pi.z ) );
+          if ( !( i >= e2 && x <= cut ) ) A = pw.x, B = A, C = pk2( lvCoord( pw, 2 ), ~lvCoord( pw, 2 ) );
         }
         a.seg[i] = to;
       }
@@ -1339,14 +1444,17 @@ int buildKdTreeDevice( tmc2_ctx* ctx, const Pt* d_pts, uint64_t n64, DeviceTree&
   // third cross-check next to the host builder and the oracle) left the library in round 6.
   const auto     hugeEnv = ctxOption( ctx, "KD_HUGEMAX" );
   const uint32_t hugeMax = std::min<uint32_t>( kHugeLimit, std::max<uint32_t>( kPieceMax, hugeEnv ? uint32_t( atoi( hugeEnv->c_str() ) ) : 16384u ) );
-  TMC2_TRY( d_work.alloc( 3 * size_t( n ) + 2 * ( size_t( tiles ) + 1 ) ) );  // seg, loc1, loc2, tile totals x 2
+  // seg, loc1, loc2, tile totals x 2.  The flag passes read seg and write loc1 / loc2 in groups of 8 positions as 16-byte
+  // accesses: each array starts on a 32-byte boundary and is padded to whole groups (what the padding holds is never used).
+  const size_t nPad = ( size_t( n ) + 7 ) & ~size_t( 7 );
+  TMC2_TRY( d_work.alloc( 3 * nPad + 2 * ( size_t( tiles ) + 1 ) ) );
   TMC2_TRY( d_segs.alloc( 2 * maxSegs ) );
   TMC2_TRY( d_small.alloc( kMaxLevels + 16 ) );  // [0..64] segments per level, then node count, levels, barrier, root box
   static_assert( kMaxLevels + 16 <= 128, "lvRootKernel clears the counters with one workgroup of 128" );
   BuildArgs a;
   a.pts = d_pts, a.n = n, a.tiles = tiles, a.P = tree.ptsTree.p, a.perm = tree.perm.p;
-  a.seg = d_work.p, a.loc1 = d_work.p + n, a.loc2 = d_work.p + 2 * size_t( n );
-  a.tile1 = d_work.p + 3 * size_t( n ), a.tile2 = a.tile1 + tiles + 1;
+  a.seg = d_work.p, a.loc1 = d_work.p + nPad, a.loc2 = d_work.p + 2 * nPad;
+  a.tile1 = d_work.p + 3 * nPad, a.tile2 = a.tile1 + tiles + 1;
   a.segA = d_segs.p, a.segB = d_segs.p + maxSegs, a.nodes = tree.nodes.p;
   a.counts    = d_small.p;
   a.nodeCount = d_small.p + kMaxLevels + 1;
