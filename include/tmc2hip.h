@@ -119,9 +119,19 @@ void        tmc2_set_host_parallelism( int maxConcurrentHostSteps );
  * unsets an option.  None of them ever changes a result.  Options may be set from any thread while frames of the context are
  * in flight (a mutex guards the table; a stage reads an option when it starts).  tmc2_ctx_get_option returns a pointer to a COPY
  * held in one string reserved for it per calling thread, valid until that thread's next tmc2_ctx_get_option call -- never a
- * pointer into the table; NULL if the option is unset.                                                                  */
+ * pointer into the table; NULL if the option is unset.
+ * "POOL_POISON" (for tests; unset by default): a byte 0 .. 255, decimal or 0x.. -- anything else is refused with TMC2_E_INVALID, by
+ * tmc2_ctx_set_option and, for a TMC2_POOL_POISON of the environment, by tmc2_ctx_create.  While it is set, every block the
+ * context's pool hands out (a recycled block, a piece of reserved memory, a fresh allocation) is filled with that byte over its
+ * whole size class, on the context's stream, and the fill is waited for: slow, and a stage that reads a word it has not written
+ * computes from the poison instead of from what the block's last owner left.  It changes no result -- that is what it tests.
+ * Memory that does not come from the pool is not filled: tmc2_ctx_device_alloc, a buffer allocated with no context entered,
+ * page-locked host staging; nor is a buffer that keeps its block from one call to the next.  "POOL_POISON_STAGE" = a stage name
+ * (tmc2_ctx_stage_name) narrows the fill to the blocks acquired while a stage of that name is open (set both between stages).
+ * tmc2_option_check: what tmc2_ctx_set_option would answer for this key and value, without a context (host only).       */
 int         tmc2_ctx_set_option( tmc2_ctx* ctx, const char* key, const char* value );
 const char* tmc2_ctx_get_option( tmc2_ctx* ctx, const char* key );
+int         tmc2_option_check( const char* key, const char* value );
 /* Reserve, at context creation time, the device memory the frames of a sequence will need (upper bounds of the sequence: points
  * per frame, voxelDimensionRefineSegmentation, geometry3dCoordinatesBitdepth + 1, the largest canvas).  The reference sizes its
  * containers per frame as it goes (std::vector growth inside PCCPatchSegmenter3::compute / PCCEncoder::generateGeometryVideo); here
@@ -705,6 +715,12 @@ int tmc2_selftest_marked_cells( tmc2_ctx* ctx, const int16_t* d_xyz4, const uint
  * op 8: blockExclusive over workgroups of param (1, 2, 4, 16) wavefronts: d_out[i] = the sum of the workgroup's values before
  *   thread i, d_aux[i] = the workgroup's total.  (uint32 for op 6 .. 8; d_aux may be NULL for op 0 .. 5 and 7.)               */
 int tmc2_selftest_wave( tmc2_ctx* ctx, int op, int param, const void* d_in, void* d_out, uint32_t* d_aux, uint64_t n );
+/* pool probe: a buffer of `bytes` (1 .. 2^30) from the context's pool, as every stage gets its temporaries, downloaded over its whole
+ * size class to hostOut (HOST memory of *classBytes bytes: the next power of two, at least 256; hostOut NULL: only *classBytes is
+ * reported) and released -- on purpose a reader of memory it has not written.  Under option POOL_POISON every byte is the poison
+ * byte; without it the content is unspecified.  This entry waits.  pool poisoned: the blocks the pool has filled so far.          */
+int tmc2_selftest_pool_probe( tmc2_ctx* ctx, uint64_t bytes, uint8_t* hostOut, uint64_t* classBytes );
+int tmc2_selftest_pool_poisoned( tmc2_ctx* ctx, uint64_t* blocks );
 
 #ifdef __cplusplus
 }

@@ -99,7 +99,7 @@ ApiScope::ApiScope( tmc2_ctx* ctx ) : prev( g_tlsCtx ) {
 }
 ApiScope::~ApiScope() { g_tlsCtx = prev; }
 
-int DevicePool::acquire( size_t bytes, void** out, size_t* got ) {
+int DevicePool::take( size_t bytes, void** out, size_t* got ) {
   if ( bytes > ( size_t( 1 ) << 40 ) ) {  // 1 TiB: beyond any device; also what a wrapped n * sizeof( T ) looks like
     setError( "device allocation of %zu bytes refused", bytes );
     return TMC2_E_INVALID;
@@ -140,6 +140,50 @@ int DevicePool::acquire( size_t bytes, void** out, size_t* got ) {
   *out = p;
   *got = cls;
   return TMC2_OK;
+}
+int DevicePool::poisonBlock( void* p, size_t cls ) {
+  {
+    std::lock_guard<std::mutex> g( lock );
+    const int byte = poison.load( std::memory_order_relaxed );
+    if ( byte < 0 ) return TMC2_OK;  // (unset since the caller looked)
+    if ( !poisonStage.empty() && std::find( openStages.begin(), openStages.end(), poisonStage ) == openStages.end() ) return TMC2_OK;
+    ++poisonedBlocks;
+    TMC2_HIP( hipMemsetAsync( p, byte, cls, stream ) );
+  }
+  TMC2_HIP( hipStreamSynchronize( stream ) );
+  return TMC2_OK;
+}
+void DevicePool::setPoison( int byte ) {
+  std::lock_guard<std::mutex> g( lock );
+  openStages.clear();  // (a stage that is open now is not seen by POOL_POISON_STAGE: set the option between stages)
+  poison.store( byte, std::memory_order_relaxed );
+}
+void DevicePool::setPoisonStage( const char* name ) {
+  std::lock_guard<std::mutex> g( lock );
+  poisonStage = name ? name : "";
+}
+void DevicePool::stageOpened( const char* name ) {
+  std::lock_guard<std::mutex> g( lock );
+  openStages.push_back( name );
+}
+void DevicePool::stageClosed( const std::string& name ) {
+  std::lock_guard<std::mutex> g( lock );
+  const auto it = std::find( openStages.rbegin(), openStages.rend(), name );
+  if ( it != openStages.rend() ) openStages.erase( std::next( it ).base() );
+}
+int parsePoolPoison( const char* value ) {
+  if ( !value ) return -1;
+  const bool  hex    = value[0] == '0' && ( value[1] == 'x' || value[1] == 'X' );
+  const char* digits = hex ? value + 2 : value;
+  int         v      = 0;
+  if ( !*digits ) return -1;
+  for ( const char* c = digits; *c; ++c ) {
+    const int d = *c >= '0' && *c <= '9' ? *c - '0' : hex && *c >= 'a' && *c <= 'f' ? *c - 'a' + 10 : hex && *c >= 'A' && *c <= 'F' ? *c - 'A' + 10 : -1;
+    if ( d < 0 ) return -1;
+    v = v * ( hex ? 16 : 10 ) + d;
+    if ( v > 255 ) return -1;
+  }
+  return v;
 }
 int DevicePool::reserve( size_t bytes ) {
   bytes = ( bytes + 255 ) & ~size_t( 255 );
@@ -186,6 +230,7 @@ int tmc2_ctx::stageBegin( const char* name ) {
     id = int( stages.size() ) - 1;
   }
   stages[id].calls++;
+  if ( pool.poison.load( std::memory_order_relaxed ) >= 0 ) pool.stageOpened( name );  // (POOL_POISON_STAGE)
   if ( !timing ) return id;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if ( freeEvents.size() >= 2 ) {
@@ -202,6 +247,7 @@ int tmc2_ctx::stageBegin( const char* name ) {
   return id;
 }
 void tmc2_ctx::stageEnd( int id ) {
+  if ( id >= 0 && pool.poison.load( std::memory_order_relaxed ) >= 0 ) pool.stageClosed( stages[id].name );
   if ( id < 0 || !timing || stages[id].pending.empty() ) return;
   (void)hipEventRecord( stages[id].pending.back().second, stream );
 }
@@ -272,10 +318,36 @@ int tmc2_ctx_create( int device, tmc2_ctx** out ) {
     return TMC2_E_HIP;
   }
   memset( c->mailbox, 0, tmc2_ctx::kMailboxWords * 4 );
+  c->pool.stream = c->stream;
+  // the options that are kept in parsed form (tmc2_ctx_set_option), from the environment's defaults
+  for ( const char* key : {"POOL_POISON", "POOL_POISON_STAGE"} ) {
+    const auto it = c->options.find( key );
+    if ( it == c->options.end() ) continue;
+    const std::string value = it->second;
+    c->options.erase( it );
+    if ( tmc2_ctx_set_option( c, key, value.c_str() ) != TMC2_OK ) {
+      tmc2_ctx_destroy( c );
+      return TMC2_E_INVALID;
+    }
+  }
   *out = c;
   return TMC2_OK;
 }
 
+/* What tmc2_ctx_set_option accepts for an option, without a context (host only): the options whose value is parsed when it is set
+   (POOL_POISON) refuse what does not parse; every other key takes any value. */
+int tmc2_option_check( const char* key, const char* value ) {
+  if ( !key || !*key ) {
+    tmc2::setError( "tmc2_option_check: invalid argument" );
+    return TMC2_E_INVALID;
+  }
+  if ( strncmp( key, "TMC2_", 5 ) == 0 ) key += 5;
+  if ( value && strcmp( key, "POOL_POISON" ) == 0 && tmc2::parsePoolPoison( value ) < 0 ) {
+    tmc2::setError( "option POOL_POISON: a byte 0 .. 255, decimal or 0x.., expected, not \"%s\"", value );
+    return TMC2_E_INVALID;
+  }
+  return TMC2_OK;
+}
 /* Per-context options: no process-global state, no environment look-ups at run time.  key: the knob's name without the
    TMC2_ prefix ("REFINE_OVERLAP", "KDTREE_HOST", "UF_CHECK", "KD_DECIDE", ...: the names DESIGN.md lists); value NULL unsets it. */
 int tmc2_ctx_set_option( tmc2_ctx* ctx, const char* key, const char* value ) {
@@ -284,6 +356,10 @@ int tmc2_ctx_set_option( tmc2_ctx* ctx, const char* key, const char* value ) {
     return TMC2_E_INVALID;
   }
   const std::string k = strncmp( key, "TMC2_", 5 ) == 0 ? key + 5 : key;
+  TMC2_TRY( tmc2_option_check( k.c_str(), value ) );
+  // the two options that the pool reads on every acquire are kept there in parsed form, not looked up in the table
+  if ( k == "POOL_POISON" ) ctx->pool.setPoison( value ? tmc2::parsePoolPoison( value ) : -1 );
+  if ( k == "POOL_POISON_STAGE" ) ctx->pool.setPoisonStage( value );
   std::lock_guard<std::mutex> g( ctx->optionsLock );  // (the context's worker thread may be reading: stage code looks options up)
   if ( value )
     ctx->options[k] = value;

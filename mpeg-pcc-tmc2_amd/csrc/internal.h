@@ -59,10 +59,34 @@ struct DevicePool {
     while ( c < bytes ) c <<= 1;
     return c;
   }
-  int  acquire( size_t bytes, void** out, size_t* got );
+  int  acquire( size_t bytes, void** out, size_t* got ) {
+    TMC2_TRY( take( bytes, out, got ) );
+    if ( poison.load( std::memory_order_relaxed ) >= 0 ) return poisonBlock( *out, *got );  // option POOL_POISON: tests only
+    return TMC2_OK;
+  }
   void recycle( void* p, size_t cls );
   void drain();
+  // Option POOL_POISON (tests; unset: -1): every block acquire hands out -- a free-list hit, a slab piece, a fresh hipMalloc -- is
+  // filled with this byte over its whole size class, on the context's stream (the one stream of the context: after the previous
+  // owner's queued work, before the new owner's), and the fill is waited for.  A stage that reads a word none of its kernels
+  // wrote then computes from the poison, not from what the last owner happened to leave.  POOL_POISON_STAGE: only the blocks
+  // acquired while a stage of that name is open (openStages: kept by stageBegin / stageEnd while the option is set).
+  std::atomic<int>                           poison{-1};
+  hipStream_t                                stream = nullptr;  // the context's stream (tmc2_ctx_create)
+  std::string                                poisonStage;       // guarded by lock, like the three below
+  std::vector<std::string>                   openStages;
+  uint64_t                                   poisonedBlocks = 0;
+  void setPoison( int byte );  // -1: off
+  void setPoisonStage( const char* name );  // nullptr: any stage, and between stages
+  void stageOpened( const char* name );
+  void stageClosed( const std::string& name );
+
+ private:
+  int take( size_t bytes, void** out, size_t* got );
+  int poisonBlock( void* p, size_t cls );
 };
+// the byte of a POOL_POISON value: decimal or 0x.., 0 .. 255, nothing around it; -1 for anything else
+int parsePoolPoison( const char* value );
 DevicePool* currentPool();  // pool of the context the calling thread entered (see ApiScope), or nullptr
 
 // Owning device buffer; memory comes from the current context's pool.

@@ -3,7 +3,7 @@
 // (scan.hip), the XCD work mapping (internal.h), UnionFind<false / true> (union_find.h), CandSort (cand_sort.h), the marked
 // cells of a boundary-cell grid (cell_grid.h, cell_grid.hip; this one waits for its count, as the stages do) and the cross-lane
 // idioms of wave.h.  The entries take DEVICE pointers and queue on the context's stream without synchronising: a test queues many
-// calls, then reads back.
+// calls, then reads back.  (tmc2_selftest_pool_probe reads a block of the context's pool as it is handed out: option POOL_POISON.)
 // Nothing of the product path calls into this file.  (S7's own kernels on a caller's neighbour table: tmc2_selftest_components,
 // patches.hip -- the kernels are local to that file.)
 #include <algorithm>
@@ -332,6 +332,39 @@ int tmc2_selftest_wave( tmc2_ctx* ctx, int op, int param, const void* d_in, void
     if ( param == 16 ) hipLaunchKernelGGL( waveBlockScanKernel<16>, dim3( blocks ), dim3( 1024 ), 0, s, in, out, d_aux );
   }
   TMC2_HIP( hipGetLastError() );
+  return TMC2_OK;
+}
+
+// A block of the context's pool as acquire hands it out, read without having been written -- on purpose: under option POOL_POISON
+// every byte of the size class is the poison byte; without it the content is whatever the last owner or the driver left.
+// hostOut null: only the size class is reported.  This one waits: the block goes back to the pool when it returns.
+int tmc2_selftest_pool_probe( tmc2_ctx* ctx, uint64_t bytes, uint8_t* hostOut, uint64_t* classBytes ) {
+  using namespace tmc2;
+  if ( !ctx || !classBytes || bytes == 0 || bytes > ( uint64_t( 1 ) << 30 ) ) {
+    setError( "selftest_pool_probe: invalid argument (null pointer, no byte or more than 2^30)" );
+    return TMC2_E_INVALID;
+  }
+  *classBytes = DevicePool::sizeClass( size_t( bytes ) );
+  if ( !hostOut ) return TMC2_OK;
+  ApiScope        scope( ctx );
+  DevBuf<uint8_t> block;
+  TMC2_TRY( block.alloc( size_t( bytes ) ) );
+  if ( block.bytes() != *classBytes ) {
+    setError( "selftest_pool_probe: a block of %zu bytes for the class of %llu", block.bytes(), static_cast<unsigned long long>( *classBytes ) );
+    return TMC2_E_HIP;
+  }
+  TMC2_HIP( hipMemcpyAsync( hostOut, block.p, block.bytes(), hipMemcpyDeviceToHost, ctx->stream ) );
+  TMC2_HIP( hipStreamSynchronize( ctx->stream ) );
+  return TMC2_OK;
+}
+// how many blocks the context's pool has filled with the poison byte so far
+int tmc2_selftest_pool_poisoned( tmc2_ctx* ctx, uint64_t* blocks ) {
+  if ( !ctx || !blocks ) {
+    tmc2::setError( "selftest_pool_poisoned: invalid argument" );
+    return TMC2_E_INVALID;
+  }
+  std::lock_guard<std::mutex> g( ctx->pool.lock );
+  *blocks = ctx->pool.poisonedBlocks;
   return TMC2_OK;
 }
 

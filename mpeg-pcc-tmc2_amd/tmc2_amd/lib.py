@@ -377,6 +377,20 @@ class Context:
         """one idiom of csrc/wave.h per call (include/tmc2hip.h: the op codes)"""
         _check(self.L.tmc2_selftest_wave(self.h, int(op), int(param), d_in, d_out, d_aux, int(n)))
 
+    def selftest_pool_probe(self, nbytes):
+        """the whole size class of a pool block of nbytes as the pool hands it out, unwritten (option POOL_POISON); this one waits"""
+        cls = C.c_uint64(0)
+        _check(self.L.tmc2_selftest_pool_probe(self.h, int(nbytes), None, C.byref(cls)))
+        out = np.empty(cls.value, np.uint8)
+        _check(self.L.tmc2_selftest_pool_probe(self.h, int(nbytes), _ptr(out), C.byref(cls)))
+        return out
+
+    def selftest_pool_poisoned(self):
+        """blocks this context's pool has filled with the poison byte so far"""
+        blocks = C.c_uint64(0)
+        _check(self.L.tmc2_selftest_pool_poisoned(self.h, C.byref(blocks)))
+        return blocks.value
+
     def stream(self):
         return self.L.tmc2_ctx_stream(self.h)
 
@@ -1232,6 +1246,11 @@ def selftest_std_sort(pairs, offsets):
     return out
 
 
+def option_check(key, value):
+    """tmc2_option_check: raises Tmc2Error where Context.set_option would refuse this value for this option (host only)."""
+    _check(load_library().tmc2_option_check(key.encode(), None if value is None else str(value).encode()))
+
+
 # ---- the prototypes of include/tmc2hip.h (declare, above) ---------------------------------------------
 TMC2HIP = """
 int tmc2_ctx_create(int, tmc2_ctx**)
@@ -1248,6 +1267,7 @@ int tmc2_ctx_set_host_gate(tmc2_ctx*, tmc2_host_gate*)
 void tmc2_set_host_parallelism(int)
 int tmc2_ctx_set_option(tmc2_ctx*, const char*, const char*)
 const char* tmc2_ctx_get_option(tmc2_ctx*, const char*)
+int tmc2_option_check(const char*, const char*)
 int tmc2_ctx_reserve(tmc2_ctx*, uint64_t, int, int, int, int)
 int tmc2_ctx_pool_stats(tmc2_ctx*, uint64_t*, uint64_t*, double*, uint64_t*)
 int tmc2_ctx_device_alloc(tmc2_ctx*, size_t, void**)
@@ -1372,4 +1392,6 @@ int tmc2_selftest_cand_sort(tmc2_ctx*, uint32_t*, const uint32_t*, uint64_t, uin
 int tmc2_selftest_std_sort(uint32_t*, const uint32_t*, uint64_t)
 int tmc2_selftest_marked_cells(tmc2_ctx*, const int16_t*, const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint32_t*, const uint32_t*, uint64_t, uint32_t*)
 int tmc2_selftest_wave(tmc2_ctx*, int, int, const void*, void*, uint32_t*, uint64_t)
+int tmc2_selftest_pool_probe(tmc2_ctx*, uint64_t, uint8_t*, uint64_t*)
+int tmc2_selftest_pool_poisoned(tmc2_ctx*, uint64_t*)
 """.strip().split("\n")

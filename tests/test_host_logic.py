@@ -146,6 +146,23 @@ def test_struct_mirrors_match_the_headers():
         assert dt.fields[n] == (np.dtype(t), getattr(T.Patch, n).offset), n
 
 
+def test_pool_poison_option_values():
+    """POOL_POISON takes a byte, decimal or 0x..; tmc2_option_check is tmc2_ctx_set_option's own check without a context (a context
+    needs a device: the set / get round trip on one is tests/test_gpu_pool_poison.py::test_gpu_probe_unset_option_fills_nothing)"""
+    from tmc2_amd import lib
+    for good in ("0", "255", "0x5A", "90", "0xff", "0X00", 7):
+        lib.option_check("POOL_POISON", good)
+        lib.option_check("TMC2_POOL_POISON", good)
+    for bad in ("256", "-1", "zz", "", "0x", "0x100", " 5", "5 ", "1e2", "0x5G", "+3", "99999999999999999999"):
+        with pytest.raises(T.Tmc2Error, match=r"error -3: option POOL_POISON"):          # TMC2_E_INVALID
+            lib.option_check("POOL_POISON", bad)
+    lib.option_check("POOL_POISON", None)                    # unsetting is always accepted
+    lib.option_check("KD_HUGEMAX", "zz")                     # the options read where they are used keep taking any text
+    lib.option_check("POOL_POISON_STAGE", "kdtree_build")
+    with pytest.raises(T.Tmc2Error, match="error -3"):
+        lib.option_check("", "1")
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():
