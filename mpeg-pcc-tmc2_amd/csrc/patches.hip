@@ -57,6 +57,47 @@ __device__ __forceinline__ void lazyAtomicMax( int32_t* a, int v ) {
   if ( v > loadStaleOk( a ) ) atomicMax( a, v );
 }
 
+// What a point's step needs is fetched TOGETHER, ahead of the branches that consume it, and pinned (kdtree_device.hip: lvPin; knn.hip:
+// loadNode): left alone, the compiler sinks every load into the exec-masked block of its first use, behind that block's own
+// s_waitcnt vmcnt(0), and a wave of a per-point pass lives as long as its slowest lane's chain of round trips.  The empty asm
+// statements consume a batch's registers one after the other with no load between them: the batch's wait sits at the first.
+// A value that was not loaded (its predicate failed) is pinned as the constant it was given.  Every batch keeps the predicate of the
+// serial form on what it turns into an address: an index a batch reads early is one the serial form read too, or one valid by
+// construction (i < n, an entry of a k-NN row).
+typedef uint32_t Words4 __attribute__( ( ext_vector_type( 4 ) ) );
+typedef uint32_t Words2 __attribute__( ( ext_vector_type( 2 ) ) );
+__device__ __forceinline__ void pin( uint32_t& a ) { asm volatile( "" : "+v"( a ) ); }
+__device__ __forceinline__ void pin( int32_t& a ) { asm volatile( "" : "+v"( a ) ); }
+__device__ __forceinline__ void pin( Words2& a ) { asm volatile( "" : "+v"( a ) ); }
+__device__ __forceinline__ void pin( Words4& a ) { asm volatile( "" : "+v"( a ) ); }
+template <typename T, typename... Rest>
+__device__ __forceinline__ void pin( T& a, Rest&... rest ) {
+  pin( a );
+  pin( rest... );
+}
+template <int N>
+__device__ __forceinline__ void pinAll( uint32_t ( &a )[N] ) {
+#pragma unroll
+  for ( int k = 0; k < N; ++k ) pin( a[k] );
+}
+// a whole 16-entry k-NN row in four 16-byte loads (not yet waited for: pin r[0..3] with the rest of the batch)
+__device__ __forceinline__ void loadRow16( const uint32_t* __restrict__ knn, uint32_t u, Words4 ( &r )[4] ) {
+  const Words4* row = reinterpret_cast<const Words4*>( knn + size_t( u ) * 16 );
+#pragma unroll
+  for ( int t = 0; t < 4; ++t ) r[t] = row[t];
+}
+__device__ __forceinline__ void rowEntries( const Words4 ( &r )[4], uint32_t ( &v )[16] ) {
+#pragma unroll
+  for ( int t = 0; t < 4; ++t ) v[4 * t] = r[t].x, v[4 * t + 1] = r[t].y, v[4 * t + 2] = r[t].z, v[4 * t + 3] = r[t].w;
+}
+// the point's own coordinates in one 8-byte load
+__device__ __forceinline__ Pt ptOf( const Words2 w ) {
+  Pt q;
+  q.x = int16_t( w.x & 0xFFFFu ), q.y = int16_t( w.x >> 16 ), q.z = int16_t( w.y & 0xFFFFu ), q.w = int16_t( w.y >> 16 );
+  return q;
+}
+__device__ __forceinline__ Words2 loadPt( const Pt* __restrict__ pts, uint32_t i ) { return reinterpret_cast<const Words2*>( pts )[i]; }
+
 // ---- S7 ---------------------------------------------------------------------------------------------
 // Connected components of the reference = "smallest eligible seed that reaches v" over the DIRECTED k-NN graph
 // restricted to raw points of one plane.  Pushing labels along edges needs as many dependent steps as
@@ -133,22 +174,34 @@ __global__ __launch_bounds__( 256 ) void ccInitKernel( const uint32_t* __restric
                                                         uint32_t* __restrict__ ccCount ) {
   const uint32_t i = roundPoint<LIST>( list, count, perm, chunked, n );
   if ( i >= n ) return;
-  lab[i]        = kNoLabel;
-  ccCount[i]    = 0;
-  uint32_t best = i;
-  if ( raw[i] ) {
-    uint32_t      bestPrio = ufPriority( i ), m = mutual[i];
-    const uint8_t pi       = partition[i];
-    while ( m ) {
-      const int j = __ffs( int( m ) ) - 1;
-      m &= m - 1;
-      const uint32_t v = knn[size_t( i ) * K + j];
-      if ( ufPriority( v ) < bestPrio && raw[v] && partition[v] == pi ) {
-        best     = v;
-        bestPrio = ufPriority( v );
-      }
-    }
+  static_assert( K == 16, "the row is read as four 16-byte loads" );
+  lab[i]     = kNoLabel;
+  ccCount[i] = 0;
+  // trip 1: everything indexed by the point alone, the whole row included
+  Words4 r[4];
+  loadRow16( knn, i, r );
+  uint32_t rawI = raw[i], m = mutual[i], pi = partition[i];
+  pin( r[0], r[1], r[2], r[3], rawI, m, pi );
+  uint32_t v[K];
+  rowEntries( r, v );
+  if ( !rawI ) m = 0;
+  // trip 2: raw and plane of the masked (mutual) neighbours -- row entries: valid indices whatever the point's own state
+  uint32_t rawV[K], partV[K];
+#pragma unroll
+  for ( int j = 0; j < K; ++j ) {
+    rawV[j] = 0, partV[j] = 0;
+    if ( ( m >> j ) & 1u ) rawV[j] = raw[v[j]], partV[j] = partition[v[j]];
   }
+  pinAll( rawV );
+  pinAll( partV );
+  // the choice: ascending j, strict <, as the serial loop over the set bits made it
+  uint32_t best = i, bestPrio = ufPriority( i );
+#pragma unroll
+  for ( int j = 0; j < K; ++j )
+    if ( ( ( m >> j ) & 1u ) && ufPriority( v[j] ) < bestPrio && rawV[j] && partV[j] == pi ) {
+      best     = v[j];
+      bestPrio = ufPriority( v[j] );
+    }
   parent[i] = best;
 }
 
@@ -242,25 +295,62 @@ __global__ __launch_bounds__( 256 ) void ccRelaxKernel( const uint32_t* __restri
                                                          uint32_t* __restrict__ lab, uint32_t* __restrict__ changed, uint32_t token,
                                                          bool agent ) {
   const uint32_t u = roundPoint<LIST>( list, count, perm, chunked, n );
-  if ( u >= n || !raw[u] ) return;
-  uint32_t m = ~uint32_t( mutual[u] ) & ( ( 1u << K ) - 1u );
-  if ( !m ) return;
-  const uint32_t ru = parent[u];
-  const uint32_t lu = loadStaleOk( &lab[ru], agent );
-  if ( lu == kNoLabel ) return;
-  const uint8_t   pu  = partition[u];
-  const uint32_t* row = knn + size_t( u ) * K;
-  bool            any = false;
-  while ( m ) {
-    const int j = __ffs( int( m ) ) - 1;
-    m &= m - 1;
-    const uint32_t v = row[j];
-    if ( v == u || !raw[v] || partition[v] != pu ) continue;
-    const uint32_t rv = parent[v];
-    if ( rv != ru && loadStaleOk( &lab[rv], agent ) > lu &&
-         atomicMin( &lab[rv], lu ) > lu )
-      any = true;
+  static_assert( K == 16, "the row is read as four 16-byte loads" );
+  if ( u >= n ) return;
+  // trip 1: everything indexed by the point alone (parent[u] of a point that is not raw is stale: it goes nowhere, below)
+  Words4 r[4];
+  loadRow16( knn, u, r );
+  uint32_t rawU = raw[u], mu = mutual[u], ru = parent[u], pu = partition[u];
+  pin( r[0], r[1], r[2], r[3], rawU, mu, ru, pu );
+  uint32_t m = ~mu & ( ( 1u << K ) - 1u );
+  if ( !rawU || !m ) return;
+  uint32_t v[K];
+  rowEntries( r, v );
+  // trip 2: the point's label, and raw and plane of every one-way neighbour (row entries: valid indices)
+  uint32_t lu = loadStaleOk( &lab[ru], agent );
+  uint32_t rawV[K], partV[K];
+#pragma unroll
+  for ( int j = 0; j < K; ++j ) {
+    rawV[j] = 0, partV[j] = 0;
+    if ( ( m >> j ) & 1u ) rawV[j] = raw[v[j]], partV[j] = partition[v[j]];
   }
+  pin( lu );
+  pinAll( rawV );
+  pinAll( partV );
+  if ( lu == kNoLabel ) return;
+  uint32_t elig = 0;
+#pragma unroll
+  for ( int j = 0; j < K; ++j )
+    elig |= uint32_t( ( v[j] != u ) & ( rawV[j] != 0 ) & ( partV[j] == pu ) ) << j;  // (the predicates of the serial loop)
+  elig &= m;
+  if ( !elig ) return;
+  // trip 3: the flat root of the eligible neighbours (raw points of this round: written by ccFlattenSeedKernel)
+  uint32_t rv[K];
+#pragma unroll
+  for ( int j = 0; j < K; ++j ) {
+    rv[j] = ru;
+    if ( ( elig >> j ) & 1u ) rv[j] = parent[v[j]];
+  }
+  pinAll( rv );
+  // trip 4: their labels
+  uint32_t lv[K];
+#pragma unroll
+  for ( int j = 0; j < K; ++j ) {
+    lv[j] = 0;
+    if ( rv[j] != ru ) lv[j] = loadStaleOk( &lab[rv[j]], agent );
+  }
+  pinAll( lv );
+  // the pushes: every one issued before an answer is looked at (atomicMin and the token do not depend on the order)
+#pragma unroll
+  for ( int j = 0; j < K; ++j ) {
+    const uint32_t seen = lv[j];
+    lv[j]               = 0;
+    if ( rv[j] != ru && seen > lu ) lv[j] = atomicMin( &lab[rv[j]], lu );
+  }
+  pinAll( lv );
+  bool any = false;
+#pragma unroll
+  for ( int j = 0; j < K; ++j ) any |= lv[j] > lu;
   if ( any ) *changed = token;  // (which sweep changed something last: nothing to clear between sweeps)
 }
 
@@ -433,13 +523,20 @@ __global__ __launch_bounds__( 256 ) void patchTrimBboxKernel( const Pt* __restri
   __shared__ PatchAgg<6> agg;
   aggInit<6, 3>( agg );
   const uint32_t i = roundPoint<LIST>( list, count, n );
-  int32_t        p = i < n ? pointPatch[i] : -1;
+  int32_t        p = -1;
+  Words2         qw = {0u, 0u};
+  if ( i < n ) p = pointPatch[i], qw = loadPt( pts, i );  // trip 1
+  pin( p, qw );
   if ( p >= 0 ) {
-    const Pt q = pts[i];
+    const Pt q = ptOf( qw );
     if ( splitting ) {
-      const int view = patchView[p] % 3;
+      // trip 2: the patch's view with both words of its window anchor (one 8-byte load: 2 p is even, the array starts a pool block)
+      int32_t vw = patchView[p];
+      Words2  mn = reinterpret_cast<const Words2*>( minUv )[p];
+      pin( vw, mn );
+      const int view = vw % 3;
       const int axT = view == 0 ? 2 : ( view == 1 ? 2 : 0 ), axB = view == 0 ? 1 : ( view == 1 ? 0 : 1 );
-      if ( !( coordOf( q, axT ) - minUv[2 * p] < maxPatchSize && coordOf( q, axB ) - minUv[2 * p + 1] < maxPatchSize ) ) {
+      if ( !( coordOf( q, axT ) - int32_t( mn.x ) < maxPatchSize && coordOf( q, axB ) - int32_t( mn.y ) < maxPatchSize ) ) {
         pointPatch[i] = -1;  // trimmed: stays raw for a later round
         p             = -1;
       }
@@ -641,6 +738,37 @@ __global__ __launch_bounds__( 256 ) void patchResampleTileKernel( const PatchDev
 }
 
 // ---- S9 -------------------------------------------------------------------------------------------------
+// B probes of the voxel bitmap in one trip: offsets[o .. o + B) (FULL: all below nOffsets; else those beyond it repeat the last
+// and count as no hit), d2 of the first hit in index order or kFar.  o is uniform: the offsets are one scalar load and what they
+// add to a bit index is scalar arithmetic.  A cell outside the grid reads the word of `home` -- the point's own cell, clamped into
+// the grid: an address the walk has read -- and counts as no hit.
+constexpr int kProbeBatch = 8;
+template <int B, bool FULL>
+__device__ __forceinline__ uint32_t probeBatch( const uint32_t* __restrict__ bitmap, int bitmapBits, const int* __restrict__ offsets, int o,
+                                                int nOffsets, const Pt q, size_t home ) {
+  const uint32_t size = 1u << bitmapBits;
+  int            packed[B];
+#pragma unroll
+  for ( int k = 0; k < B; ++k ) packed[k] = offsets[FULL ? o + k : min( o + k, nOffsets - 1 )];
+  uint32_t word[B], hitBit[B];
+#pragma unroll
+  for ( int k = 0; k < B; ++k ) {
+    const int dx = ( packed[k] & 0xFF ) - 128, dy = ( ( packed[k] >> 8 ) & 0xFF ) - 128, dz = ( ( packed[k] >> 16 ) & 0xFF ) - 128;
+    const long long step = (long long)dx + ( (long long)dy << bitmapBits ) + ( (long long)dz << ( 2 * bitmapBits ) );
+    const bool inside = uint32_t( q.x + dx ) < size && uint32_t( q.y + dy ) < size && uint32_t( q.z + dz ) < size &&
+                        uint32_t( q.x ) < size && uint32_t( q.y ) < size && uint32_t( q.z ) < size && ( FULL || o + k < nOffsets );
+    const size_t bit = inside ? size_t( (long long)home + step ) : home;
+    hitBit[k]        = inside ? 1u << ( bit & 31 ) : 0u;
+    word[k]          = bitmap[bit >> 5];
+  }
+  pinAll( word );
+  uint32_t best = kFar;
+#pragma unroll
+  for ( int k = B - 1; k >= 0; --k )
+    if ( word[k] & hitBit[k] ) best = uint32_t( packed[k] >> 24 );
+  return best;
+}
+
 // dist2 of every point still raw to the resampled cloud, exact up to the probe radius, kFar beyond it.  A point that has come
 // within thrSelection is raw no longer and never will be again (the bitmap only gains bits), and its dist is not read again: later
 // rounds probe the points of the list alone.  keep[j] = the j-th point of the pass stays raw (the next list: rawListScatterKernel).
@@ -654,19 +782,19 @@ __global__ __launch_bounds__( 256 ) void rawDistanceKernel( const Pt* __restrict
   if ( j >= count ) return;
   const uint32_t i    = LIST ? list[j] : j;
   const Pt       q    = pts[i];
-  const int      size = 1 << bitmapBits;
-  uint32_t       best = kFar;
-  for ( int o = 0; o < nOffsets; ++o ) {
-    const int packed = offsets[o];
-    const int dx = ( packed & 0xFF ) - 128, dy = ( ( packed >> 8 ) & 0xFF ) - 128, dz = ( ( packed >> 16 ) & 0xFF ) - 128;
-    const int x = q.x + dx, y = q.y + dy, z = q.z + dz;
-    if ( x < 0 || y < 0 || z < 0 || x >= size || y >= size || z >= size ) continue;
-    const size_t bit = size_t( x ) + ( size_t( y ) << bitmapBits ) + ( size_t( z ) << ( 2 * bitmapBits ) );
-    if ( bitmap[bit >> 5] & ( 1u << ( bit & 31 ) ) ) {
-      best = uint32_t( packed >> 24 );  // offsets are sorted by d2 and carry it in the top byte
-      break;
-    }
-  }
+  // The first trip is the single probe of offset 0 (the point's own voxel): most points of round 1 have just been resampled and
+  // end there -- a batch of speculative reads of a 128 MiB bitmap for each of them would be new HBM traffic.
+  const int    top  = ( 1 << bitmapBits ) - 1;
+  const size_t home = size_t( min( max( int( q.x ), 0 ), top ) ) + ( size_t( min( max( int( q.y ), 0 ), top ) ) << bitmapBits ) +
+                      ( size_t( min( max( int( q.z ), 0 ), top ) ) << ( 2 * bitmapBits ) );
+  uint32_t best = probeBatch<1, true>( bitmap, bitmapBits, offsets, 0, nOffsets, q, home );
+  // Lanes still searching: kProbeBatch offsets in one uniform load, their bitmap words issued together, the hit of lowest index
+  // wins -- offsets are sorted by d2 and carry it in the top byte, so this is the hit the probe-by-probe walk stopped at.  The
+  // last, partial batch starts at an index every lane knows (a lane's own loop counter differs from lane to lane behind the loop).
+  const int tail = 1 + ( nOffsets - 1 ) / kProbeBatch * kProbeBatch;
+  for ( int o = 1; best == kFar && o < tail; o += kProbeBatch )
+    best = probeBatch<kProbeBatch, true>( bitmap, bitmapBits, offsets, o, nOffsets, q, home );
+  if ( best == kFar && tail < nOffsets ) best = probeBatch<kProbeBatch, false>( bitmap, bitmapBits, offsets, tail, nOffsets, q, home );
   const bool isRaw = best > thrSelection;
   dist[i]          = best;
   raw[i]           = isRaw ? 1 : 0;
