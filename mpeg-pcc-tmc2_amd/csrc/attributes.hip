@@ -334,119 +334,310 @@ __global__ __launch_bounds__( 256 ) void pushPullBlurKernel( const uint8_t* __re
   if ( i < W * H ) pushPullBlurPixel( i, src, dst, occ, W, H );
 }
 
-// One level of the way up in ONE launch: the fill from the coarser level and all `iters` blur passes, a 96 x 96 tile of one
-// plane per workgroup, in LDS.  The tile is loaded with a margin of `iters` pixels (clipped to the image): a blur pass reads
-// the 8 neighbours, so what a pass computes next to a cut edge of the region is wrong one pixel further in per pass -- and
-// after `iters` passes has just not reached the tile.  Coordinates clamp at the region's edges, which are the image's edges
-// wherever the clamp is the reference's.  Occupied pixels never change; only unoccupied pixels of the tile are written, and no
-// workgroup reads a pixel another one writes (unoccupied pixels are computed from the coarser level, not loaded).
-constexpr int kPushPullTile = 96, kPushPullSpan = 128, kPushPullMaxIters = ( kPushPullSpan - kPushPullTile ) / 2;
-__global__ __launch_bounds__( 1024 ) void pushPullFillBlurKernel( uint8_t* __restrict__ img, const uint8_t* __restrict__ occ, int W,
-                                                                   int H, const uint8_t* __restrict__ mip, int w, int h, int iters,
-                                                                   int tilesX ) {
-  __shared__ uint8_t sOcc[kPushPullSpan * kPushPullSpan];
-  __shared__ uint8_t sBuf[2][kPushPullSpan * kPushPullSpan];
-  const int      X0 = ( blockIdx.x % tilesX ) * kPushPullTile, Y0 = ( blockIdx.x / tilesX ) * kPushPullTile;
-  const int      RX0 = max( X0 - iters, 0 ), RY0 = max( Y0 - iters, 0 );
-  const int      RW = min( X0 + kPushPullTile + iters, W ) - RX0, RH = min( Y0 + kPushPullTile + iters, H ) - RY0;
-  uint8_t*       plane = img + size_t( blockIdx.y ) * W * H;
-  const uint8_t* m     = mip + size_t( blockIdx.y ) * w * h;
-  for ( int i = threadIdx.x; i < kPushPullSpan * RH; i += 1024 ) {
-    const int rx = i & ( kPushPullSpan - 1 ), ry = i >> 7;
-    if ( rx >= RW ) continue;
-    const int     X = RX0 + rx, Y = RY0 + ry;
-    const size_t  g = size_t( Y ) * W + X;
-    const uint8_t o = occ[g];
-    uint8_t       v;
-    if ( o ) {
-      v = plane[g];
-    } else {  // pushPullFillPixel, this plane
-      const int  x = X >> 1, y = Y >> 1, dx = ( X & 1 ) ? 1 : -1, dy = ( Y & 1 ) ? 1 : -1;
-      const bool hx = dx < 0 ? x > 0 : x < w - 1, hy = dy < 0 ? y > 0 : y < h - 1;
-      const int  c  = m[size_t( y ) * w + x];
-      const int  vx = hx ? m[size_t( y ) * w + x + dx] : 0;
-      const int  vy = hy ? m[size_t( y + dy ) * w + x] : 0;
-      const int  vd = ( hx && hy ) ? m[size_t( y + dy ) * w + x + dx] : 0;
-      v             = uint8_t( mean4w( c, 144, vx, hx ? 48 : 0, vy, hy ? 48 : 0, vd, ( hx && hy ) ? 16 : 0 ) );
+// ---- S21, packed: a lane works on FOUR horizontally adjacent pixels, one aligned 32-bit LDS word ---------------------------
+// Rows lie in LDS with a pitch that is a whole number of words; byte j of word wx of a row is pixel 4 wx + j.  Next to each image
+// word lies a mask word, 0xFF in the bytes of the occupied pixels (and of the bytes beyond the row's last pixel): those never
+// change.  The eight-neighbour sum is the 3 x 3 box sum less the centre.  The box sum is taken vertically first -- the three rows'
+// bytes of a column added in 16-bit fields, pixels 0 and 2 of the word in one register, 1 and 3 in another, the column left of the
+// word and the one right of it in a third -- and then horizontally by shifting fields (a sum is at most 9 x 255 + 4).
+struct PushPullEdge {  // per lane: where the row's first and last pixel sit, if in this word (the reference's clamp, by selects)
+  bool     first;      // pixel 0 of the word is the row's first: its left neighbour is itself
+  bool     last3;      // pixel 3 of the word is the row's last: its right neighbour is itself
+  uint32_t after;      // the byte after the row's last pixel, if that is pixel 0, 1 or 2 of this word: it repeats the pixel before it
+};
+__device__ __forceinline__ PushPullEdge pushPullEdge( int wx, int w ) {
+  const bool last = wx == ( ( w - 1 ) >> 2 );
+  const int  b    = ( w - 1 ) & 3;
+  return PushPullEdge{wx == 0, last && b == 3, last && b < 3 ? 0xFF00u << ( 8 * b ) : 0u};
+}
+struct PushPullRow {
+  uint32_t lo, hi, e;  // the bytes of the pixels 0, 2 (lo) and 1, 3 (hi) of a word, and of its neighbours left (low half) and right
+};
+// l, c, r: the words left of, at and right of the position
+__device__ __forceinline__ PushPullRow pushPullRowTerms( uint32_t l, uint32_t c, uint32_t r, const PushPullEdge& E ) {
+  constexpr uint32_t kF = 0x00FF00FFu;
+  const uint32_t     cp = ( c & ~E.after ) | ( ( c << 8 ) & E.after );
+  const uint32_t     lb = E.first ? c & 0xFFu : l >> 24, rb = E.last3 ? c >> 24 : r & 0xFFu;
+  return PushPullRow{cp & kF, ( cp >> 8 ) & kF, lb | ( rb << 16 )};
+}
+// One blur pass over the rows y0 .. y1 - 1 of word column wx: src -> dst (both with a readable word before the first and after the
+// last), `rows` rows of `pitch` words.  Walks down with the terms of two rows in registers, R rows at a time: the reads of the R
+// rows below -- three words and a mask word each -- are issued together, then R words are computed and written.  Row indices
+// clamp at 0 and rows - 1 (offsets are carried, not multiplied).
+template <int R>
+__device__ __forceinline__ void pushPullBlurStrip( const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
+                                                   const uint32_t* __restrict__ occ, int pitch, int rows, int wx, int y0, int y1,
+                                                   const PushPullEdge& E ) {
+  constexpr uint32_t kF = 0x00FF00FFu;
+  const int          oLast = ( rows - 1 ) * pitch + wx;
+  int                o = y0 * pitch + wx;
+  const uint32_t*    s = src + max( o - pitch, wx );
+  PushPullRow        up = pushPullRowTerms( s[-1], s[0], s[1], E );
+  s                     = src + o;
+  uint32_t    cw  = s[0];
+  PushPullRow mid = pushPullRowTerms( s[-1], cw, s[1], E );
+  for ( int y = y0; y < y1; y += R ) {
+    uint32_t l[R], c[R], r[R], m[R];
+    int      at[R];
+#pragma unroll
+    for ( int k = 0; k < R; ++k ) {
+      at[k]               = min( o + k * pitch, oLast );
+      const uint32_t* n   = src + min( o + ( k + 1 ) * pitch, oLast );
+      l[k] = n[-1], c[k] = n[0], r[k] = n[1], m[k] = occ[at[k]];
     }
-    sOcc[i]    = o;
-    sBuf[0][i] = v;
-    sBuf[1][i] = v;
-  }
-  __syncthreads();
-  int cur = 0;
-  for ( int it = 0; it < iters; ++it ) {
-    const uint8_t* src = sBuf[cur];
-    uint8_t*       dst = sBuf[cur ^ 1];
-    for ( int i = threadIdx.x; i < kPushPullSpan * RH; i += 1024 ) {
-      const int rx = i & ( kPushPullSpan - 1 ), ry = i >> 7;
-      if ( rx >= RW || sOcc[i] ) continue;
-      const int l = rx > 0 ? -1 : 0, r = rx < RW - 1 ? 1 : 0;
-      const int u = ry > 0 ? -kPushPullSpan : 0, d = ry < RH - 1 ? kPushPullSpan : 0;
-      const int sum = src[i + u + l] + src[i + u + r] + src[i + d + l] + src[i + d + r] + src[i + l] + src[i + r] + src[i + u] +
-                      src[i + d];
-      dst[i] = uint8_t( ( sum + 4 ) >> 3 );
+#pragma unroll
+    // The mask words are used only under `y + k < y1`.  Left alone, the compiler moves each ds_read of a mask into the exec-masked
+    // block of its store, behind a wait of its own (seen in the gfx950 assembly: R - 1 further LDS round trips per batch); the empty
+    // statement keeps the R reads with the other reads of the batch (kdtree_device.hip's lvPin).  Not timed without it: the passes
+    // are bound by their VALU work either way (profiles/attribute_padding.txt, section 3); without it the result is the same.
+    for ( int k = 0; k < R; ++k ) asm volatile( "" : "+v"( m[k] ) );
+#pragma unroll
+    for ( int k = 0; k < R; ++k ) {
+      const PushPullRow dn  = pushPullRowTerms( l[k], c[k], r[k], E );
+      const uint32_t    vlo = up.lo + mid.lo + dn.lo, vhi = up.hi + mid.hi + dn.hi, ve = up.e + mid.e + dn.e, t = vlo + vhi;
+      // t = columns (0 + 1, 2 + 3); with columns (-1, 1) the sums around the pixels 0, 2, with columns (2, 4) those around 1, 3
+      const uint32_t slo = t + ( ( vhi << 16 ) | ( ve & 0xFFFFu ) ), shi = t + ( ( vlo >> 16 ) | ( ve & 0xFFFF0000u ) );
+      const uint32_t lo = ( ( slo - mid.lo + 0x00040004u ) >> 3 ) & kF, hi = ( ( shi - mid.hi + 0x00040004u ) >> 3 ) & kF;
+      if ( y + k < y1 ) dst[at[k]] = ( cw & m[k] ) | ( ( lo | ( hi << 8 ) ) & ~m[k] );
+      up = mid, mid = dn, cw = c[k];
     }
-    __syncthreads();
-    cur ^= 1;
-  }
-  const uint8_t* res = sBuf[cur];
-  for ( int i = threadIdx.x; i < kPushPullSpan * RH; i += 1024 ) {
-    const int rx = i & ( kPushPullSpan - 1 ), ry = i >> 7;
-    const int X = RX0 + rx, Y = RY0 + ry;
-    if ( rx >= RW || sOcc[i] || X < X0 || X >= X0 + kPushPullTile || Y < Y0 || Y >= Y0 + kPushPullTile ) continue;
-    plane[size_t( Y ) * W + X] = res[i];
+    o += R * pitch;
   }
 }
 
-// The coarse end of the pyramid in ONE workgroup: the levels of at most kPushPullSmall pixels -- their mip maps on the way
-// down, and on the way up the fill, the ping-pong partner's copy and the 4, 5, ... blur iterations of every level.  That is
-// ~ 60 of the ~ 100 launches of the padding, each over a few hundred to a few thousand pixels; between the steps a
-// workgroup barrier does what a kernel boundary did (the images are tiny: L1 / L2 resident, one CU).
+// pushPullFillPixel's value for pixel (X, Y) from the coarser level m (w x h, rows `pitch` bytes apart).  mean4w's weights are 144,
+// 48, 48, 16, or 0 for a neighbour beyond the edge.  With the coordinate of such a neighbour clamped instead -- it then repeats a
+// pixel that is there -- the full form gives the same integer quotient: (144 + 48) v + (48 + 16) vy over 256 is 3 v + vy over 4, the
+// form with the x neighbour missing, likewise in y, and 256 v over 256 is v.  So: four loads that never leave the level, one shift.
+__device__ __forceinline__ uint32_t pushPullFillValue( const uint8_t* m, int pitch, int w, int h, int X, int Y ) {
+  const int      x = X >> 1, y = Y >> 1;
+  const int      xn = ( X & 1 ) ? min( x + 1, w - 1 ) : max( x - 1, 0 ), yn = ( Y & 1 ) ? min( y + 1, h - 1 ) : max( y - 1, 0 );
+  const uint8_t *r0 = m + size_t( y ) * pitch, *r1 = m + size_t( yn ) * pitch;
+  return ( 9u * r0[x] + 3u * r0[xn] + 3u * r1[x] + r1[xn] ) >> 4;
+}
+
+// four bytes from any address (the rows and planes of the images are not word aligned)
+__device__ __forceinline__ uint32_t pushPullLoad4( const uint8_t* p ) {
+  uint32_t v;
+  __builtin_memcpy( &v, p, 4 );
+  return v;
+}
+
+// One level of the way up in ONE launch: the fill from the coarser level and all `iters` blur passes, a 96 x 96 tile of one
+// plane per workgroup, in LDS.  The tile is loaded with a margin of `iters` pixels (clipped to the image): a blur pass reads
+// the 8 neighbours, so pass k (of iters, from 0) is computed on the tile grown by iters - 1 - k pixels only -- what the later
+// passes can still carry into the tile -- and reads nothing but what the pass before computed or the load put there.  Coordinates
+// clamp at the region's edges, which a pass reaches only where they are the image's edges.  Occupied pixels never change; only
+// unoccupied pixels of the tile are written, and no workgroup USES a pixel another one writes: unoccupied pixels are computed
+// from the coarser level.  (The word load of four pixels does fetch the bytes of unoccupied pixels, which the tile that owns
+// them may be storing at that moment; the byte mask drops them before anything is computed, so whatever they hold -- the clear
+// of d_attr, or the other tile's result -- reaches nothing.)  A tile without an unoccupied pixel is left after the load.
+constexpr int kPushPullTile = 96, kPushPullSpan = 128, kPushPullMaxIters = ( kPushPullSpan - kPushPullTile ) / 2;
+constexpr int kPushPullPitch = kPushPullSpan / 4, kPushPullWords = kPushPullPitch * kPushPullSpan;
+// 512 threads: a lane per word column and sixteen strips of rows (256 and 1 024 measured slower, profiles/attribute_padding.txt)
+constexpr int kPushPullThreads = 512, kPushPullStrips = kPushPullThreads / kPushPullPitch;
+static_assert( kPushPullThreads % kPushPullPitch == 0 && kPushPullThreads <= 1024, "whole strips of word columns" );
+__global__ __launch_bounds__( kPushPullThreads ) void pushPullFillBlurKernel( uint8_t* __restrict__ img, const uint8_t* __restrict__ occ,
+                                                                               int W, int H, const uint8_t* __restrict__ mip, int w, int h,
+                                                                               int iters, int tilesX ) {
+  __shared__ uint32_t sOcc[kPushPullWords];
+  __shared__ uint32_t sBuf[2 * kPushPullWords + 2];  // (a word before the first buffer and one after the second: the strips' l and r)
+  const int      X0 = ( blockIdx.x % tilesX ) * kPushPullTile, Y0 = ( blockIdx.x / tilesX ) * kPushPullTile;
+  const int      RX0 = max( X0 - iters, 0 ), RY0 = max( Y0 - iters, 0 );
+  const int      RW = min( X0 + kPushPullTile + iters, W ) - RX0, RH = min( Y0 + kPushPullTile + iters, H ) - RY0;
+  const int      CX0 = X0 - RX0, CX1 = min( X0 + kPushPullTile, W ) - RX0, CY0 = Y0 - RY0, CY1 = min( Y0 + kPushPullTile, H ) - RY0;
+  uint8_t*       plane = img + size_t( blockIdx.y ) * W * H;
+  const uint8_t* m     = mip + size_t( blockIdx.y ) * w * h;
+  const int      wx = threadIdx.x & ( kPushPullPitch - 1 ), strip = threadIdx.x / kPushPullPitch;
+  // The load: a lane keeps its word column.  A word wholly inside the region takes four loads that depend on nothing but the
+  // position -- its occupancies, its pixels and the two rows of four coarse pixels its fills can touch (pushPullFillValue), each as one
+  // unaligned 32-bit load -- so the rows of a lane are in flight together; the word that holds the region's last pixels, and every
+  // word over a coarse level narrower than four pixels, goes pixel by pixel.
+  const int      rx0 = 4 * wx, XW = RX0 + rx0, mb = w >= 4 ? min( max( ( XW >> 1 ) - 1, 0 ), w - 4 ) : 0;
+  const uint32_t coreX = ( rx0 >= CX0 && rx0 < CX1 ? 0xFFu : 0u ) | ( rx0 + 1 >= CX0 && rx0 + 1 < CX1 ? 0xFF00u : 0u ) |
+                         ( rx0 + 2 >= CX0 && rx0 + 2 < CX1 ? 0xFF0000u : 0u ) | ( rx0 + 3 >= CX0 && rx0 + 3 < CX1 ? 0xFF000000u : 0u );
+  int            hole  = 0;  // an unoccupied pixel of the tile seen by this lane
+  if ( rx0 + 3 < RW && w >= 4 ) {
+#pragma unroll 4
+    for ( int ry = strip; ry < RH; ry += kPushPullStrips ) {
+      const int      Y = RY0 + ry, y = Y >> 1, yn = ( Y & 1 ) ? min( y + 1, h - 1 ) : max( y - 1, 0 );
+      const size_t   g  = size_t( Y ) * W + XW;
+      const uint32_t o4 = pushPullLoad4( occ + g ), p4 = pushPullLoad4( plane + g );
+      const uint32_t r0 = pushPullLoad4( m + size_t( y ) * w + mb ), r1 = pushPullLoad4( m + size_t( yn ) * w + mb );
+      const uint32_t nz = ( ( ( o4 & 0x7F7F7F7Fu ) + 0x7F7F7F7Fu ) | o4 ) & 0x80808080u, msk = ( nz >> 7 ) * 0xFFu;
+      uint32_t       fill = 0;
+#pragma unroll
+      for ( int j = 0; j < 4; ++j ) {
+        const int      X = XW + j, x = X >> 1, xn = ( X & 1 ) ? min( x + 1, w - 1 ) : max( x - 1, 0 ), sx = 8 * ( x - mb ), sn = 8 * ( xn - mb );
+        fill |= ( ( 9u * ( ( r0 >> sx ) & 0xFFu ) + 3u * ( ( r0 >> sn ) & 0xFFu ) + 3u * ( ( r1 >> sx ) & 0xFFu ) + ( ( r1 >> sn ) & 0xFFu ) ) >> 4 ) << ( 8 * j );
+      }
+      const uint32_t pix = ( p4 & msk ) | ( fill & ~msk );
+      const int      i   = ry * kPushPullPitch + wx;
+      hole |= int( ( ~msk & coreX ) != 0 && ry >= CY0 && ry < CY1 );
+      sOcc[i] = msk, sBuf[1 + i] = pix, sBuf[1 + kPushPullWords + i] = pix;
+    }
+  } else {
+    for ( int ry = strip; ry < RH; ry += kPushPullStrips ) {
+      const int Y = RY0 + ry, i = ry * kPushPullPitch + wx;
+      uint32_t  pix = 0, msk = 0;
+#pragma unroll
+      for ( int j = 0; j < 4; ++j ) {
+        const int rx = rx0 + j, X = RX0 + rx;
+        uint32_t  v = 0, o = 0xFFu;  // beyond the region: a constant
+        if ( rx < RW ) {
+          const size_t g = size_t( Y ) * W + X;
+          o              = occ[g] ? 0xFFu : 0u;
+          v              = o ? uint32_t( plane[g] ) : pushPullFillValue( m, w, w, h, X, Y );
+          hole |= int( !o && rx >= CX0 && rx < CX1 && ry >= CY0 && ry < CY1 );
+        }
+        pix |= v << ( 8 * j ), msk |= o << ( 8 * j );
+      }
+      sOcc[i] = msk, sBuf[1 + i] = pix, sBuf[1 + kPushPullWords + i] = pix;
+    }
+  }
+  if ( !__syncthreads_or( hole ) ) return;
+  const PushPullEdge edge = pushPullEdge( wx, RW );
+  int            cur = 0;
+  for ( int it = 0; it < iters; ++it ) {
+    const int g  = iters - 1 - it;
+    const int xa = max( X0 - g, 0 ) - RX0, xb = min( X0 + kPushPullTile + g, W ) - RX0;
+    const int ya = max( Y0 - g, 0 ) - RY0, yb = min( Y0 + kPushPullTile + g, H ) - RY0;
+    const int per = ( yb - ya + kPushPullStrips - 1 ) / kPushPullStrips, y0 = ya + strip * per, y1 = min( y0 + per, yb );
+    if ( wx >= ( xa >> 2 ) && wx <= ( ( xb - 1 ) >> 2 ) && y0 < y1 )
+      pushPullBlurStrip<4>( sBuf + 1 + cur * kPushPullWords, sBuf + 1 + ( cur ^ 1 ) * kPushPullWords, sOcc, kPushPullPitch, RH, wx, y0, y1,
+                            edge );
+    __syncthreads();
+    cur ^= 1;
+  }
+  const uint32_t* res = sBuf + 1 + cur * kPushPullWords;
+  for ( int i = kPushPullPitch * CY0 + threadIdx.x; i < kPushPullPitch * CY1; i += kPushPullThreads ) {
+    const int      cx = i & ( kPushPullPitch - 1 ), ry = i / kPushPullPitch;
+    const uint32_t v = res[i], o = sOcc[i];
+#pragma unroll
+    for ( int j = 0; j < 4; ++j ) {
+      const int rx = 4 * cx + j;
+      if ( rx >= CX0 && rx < CX1 && !( ( o >> ( 8 * j ) ) & 0xFFu ) ) plane[size_t( RY0 + ry ) * W + RX0 + rx] = uint8_t( v >> ( 8 * j ) );
+    }
+  }
+}
+
+// The coarse end of the pyramid in ONE workgroup per plane, in LDS: the levels from the first of at most kPushPullSmall pixels down
+// -- their mip maps on the way down, and on the way up the fill and the 4, 5, ... blur iterations of every level.  Level `first`
+// (made by the launch before) is read from global memory once; every step after that works on LDS, a workgroup barrier between
+// two steps; only the final image of level `first` goes back, into the buffer of the level the host's parity rule names (nothing
+// outside this kernel reads the coarser levels or their occupancies).  Every level keeps its image, its ping-pong partner and its
+// mask in words (pushPullBlurStrip); the fill writes both partners, which is the copy the separate launches made.
 constexpr int kPushPullSmall  = 160 * 160;
 constexpr int kPushPullLevels = 16;
 struct PushPullLevels {
-  int      count;                   // levels of the pyramid, 0 = the canvas
-  int      first;                   // the first (finest) level handled here: every level >= first has at most kPushPullSmall pixels
-  int      w[kPushPullLevels], h[kPushPullLevels];
-  uint8_t *img[kPushPullLevels], *tmp[kPushPullLevels], *occ[kPushPullLevels];
+  int            count;  // levels of the pyramid, 0 = the canvas
+  int            first;  // the first (finest) level handled here
+  int            w[kPushPullLevels], h[kPushPullLevels];
+  const uint8_t *img, *occ;  // level `first`: six planes, one occupancy
+  uint8_t*       out;        // level `first` after its blur passes: six planes
 };
+// words of LDS a level takes: a word in front, image, partner, a word behind, mask
+__host__ __device__ inline int pushPullLevelWords( int w, int h ) { return 3 * ( ( w + 3 ) >> 2 ) * h + 2; }
 __global__ __launch_bounds__( 1024 ) void pushPullCoarseLevelsKernel( PushPullLevels L ) {
-  // The six planes (2 maps x 3 channels) never read each other: one workgroup per plane, six CUs instead of one for the ~ 60
-  // dependent steps (0.79 -> ~ 0.15 ms).  The occupancy of the coarse levels is common to the planes: every workgroup derives
-  // it for itself (the same bytes from six writers).
-  const int p0 = int( blockIdx.x ), p1 = p0 + 1;
-  // down: mip maps of the levels first + 1 .. count - 1 (level `first` itself was produced by the launch before)
+  extern __shared__ uint32_t sPyr[];
+  // The six planes (2 maps x 3 channels) never read each other: one workgroup per plane.  The occupancy of the coarse levels is
+  // common to the planes: every workgroup derives it for itself.
+  const int plane = int( blockIdx.x ), tid = int( threadIdx.x );
+  int       w = L.w[L.first], h = L.h[L.first], pw = ( w + 3 ) >> 2, n = pw * h, base = 0;
+  {
+    const uint8_t* src = L.img + size_t( plane ) * w * h;
+    uint32_t *     img = sPyr + base + 1, *occ = sPyr + base + 2 + 2 * n;
+    for ( int i = tid; i < n; i += 1024 ) {
+      const int wx = i % pw, y = i / pw;
+      uint32_t  pix = 0, msk = 0;
+#pragma unroll
+      for ( int j = 0; j < 4; ++j ) {
+        const int x = 4 * wx + j;
+        uint32_t  v = 0, o = 0xFFu;
+        if ( x < w ) {
+          const size_t g = size_t( y ) * w + x;
+          o = L.occ[g] ? 0xFFu : 0u, v = src[g];
+        }
+        pix |= v << ( 8 * j ), msk |= o << ( 8 * j );
+      }
+      img[i] = pix, occ[i] = msk;
+    }
+  }
+  __syncthreads();
+  // down: mip maps of the levels first + 1 .. count - 1 (pushPullMipPixel; mean4w with weights of 255 or 0 is the sum of the
+  // occupied pixels over their number)
   for ( int l = L.first + 1; l < L.count; ++l ) {
-    const int cnt = L.w[l] * L.h[l];
-    for ( int i = threadIdx.x; i < cnt; i += blockDim.x )
-      pushPullMipPixel( i, L.img[l - 1], L.occ[l - 1], L.w[l - 1], L.h[l - 1], L.img[l], L.occ[l], L.w[l], L.h[l], p0, p1 );
+    const int      W = w, H = h, fp = 4 * pw;
+    const uint8_t *fimg = reinterpret_cast<const uint8_t*>( sPyr + base + 1 ), *focc = reinterpret_cast<const uint8_t*>( sPyr + base + 2 + 2 * n );
+    base += 3 * n + 2;
+    w = L.w[l], h = L.h[l], pw = ( w + 3 ) >> 2, n = pw * h;
+    uint32_t *img = sPyr + base + 1, *occ = sPyr + base + 2 + 2 * n;
+    for ( int i = tid; i < n; i += 1024 ) {
+      const int wx = i % pw, y = i / pw, Y = 2 * y;
+      uint32_t  pix = 0, msk = 0;
+#pragma unroll
+      for ( int j = 0; j < 4; ++j ) {
+        const int x = 4 * wx + j, X = 2 * x;
+        uint32_t  v = 0, o = 0xFFu;
+        if ( x < w ) {
+          const bool i2 = X + 1 < W, i3 = Y + 1 < H;
+          const int  a = Y * fp + X;
+          const bool o1 = focc[a], o2 = i2 && focc[a + 1], o3 = i3 && focc[a + fp], o4 = i2 && i3 && focc[a + fp + 1];
+          const int  cnt = int( o1 ) + int( o2 ) + int( o3 ) + int( o4 );
+          const int  sum = ( o1 ? fimg[a] : 0 ) + ( o2 ? fimg[a + 1] : 0 ) + ( o3 ? fimg[a + fp] : 0 ) + ( o4 ? fimg[a + fp + 1] : 0 );
+          o              = cnt ? 0xFFu : 0u;
+          v              = cnt == 3 ? uint32_t( sum ) / 3u : uint32_t( sum ) >> ( cnt >> 1 );
+        }
+        pix |= v << ( 8 * j ), msk |= o << ( 8 * j );
+      }
+      img[i] = pix, occ[i] = msk;
+    }
     __syncthreads();
   }
   // up: fill level l - 1 from level l, then iters blur passes between the level's two buffers (host loop of
-  // generateAttributeImages, same order, same buffers)
-  int iters = 4;
+  // generateAttributeImages, same order); an odd count leaves the level's image in the partner
+  int iters = 4, inTmp = 0;
   for ( int l = L.count - 1; l > L.first; --l ) {
-    const int fw = L.w[l - 1], fh = L.h[l - 1], cnt = fw * fh;
-    uint8_t * img = L.img[l - 1], *tmp = L.tmp[l - 1];
-    const uint8_t* occ = L.occ[l - 1];
-    for ( int i = threadIdx.x; i < cnt; i += blockDim.x ) pushPullFillPixel( i, img, occ, fw, fh, L.img[l], L.w[l], L.h[l], p0, p1 );
+    const int      cw = w, ch = h, cp = 4 * pw;
+    const uint8_t* m = reinterpret_cast<const uint8_t*>( sPyr + base + 1 + ( inTmp ? n : 0 ) );
+    w = L.w[l - 1], h = L.h[l - 1], pw = ( w + 3 ) >> 2, n = pw * h;
+    base -= 3 * n + 2;
+    uint32_t *      img = sPyr + base + 1, *tmp = img + n;
+    const uint32_t* occ = sPyr + base + 2 + 2 * n;
+    for ( int i = tid; i < n; i += 1024 ) {
+      const int      wx = i % pw, y = i / pw;
+      const uint32_t msk = occ[i];
+      uint32_t       pix = img[i];
+#pragma unroll
+      for ( int j = 0; j < 4; ++j )
+        if ( !( ( msk >> ( 8 * j ) ) & 0xFFu ) ) pix = ( pix & ~( 0xFFu << ( 8 * j ) ) ) | ( pushPullFillValue( m, cp, cw, ch, 4 * wx + j, y ) << ( 8 * j ) );
+      img[i] = pix, tmp[i] = pix;
+    }
     __syncthreads();
-    for ( int i = threadIdx.x; i < cnt; i += blockDim.x ) tmp[size_t( p0 ) * cnt + i] = img[size_t( p0 ) * cnt + i];
-    __syncthreads();
-    uint8_t *src = img, *dst = tmp;
+    // strips of `per` rows, as many as give every lane one while the rows last
+    const int per = ( h + max( 1024 / pw, 1 ) - 1 ) / max( 1024 / pw, 1 ), strips = ( h + per - 1 ) / per;
     for ( int it = 0; it < iters; ++it ) {
-      for ( int i = threadIdx.x; i < cnt; i += blockDim.x ) pushPullBlurPixel( i, src, dst, occ, fw, fh, p0, p1 );
+      const uint32_t* src = ( it & 1 ) ? tmp : img;
+      uint32_t*       dst = ( it & 1 ) ? img : tmp;
+      for ( int i = tid; i < pw * strips; i += 1024 ) {
+        const int wx = i % pw, y0 = ( i / pw ) * per;
+        pushPullBlurStrip<2>( src, dst, occ, pw, h, wx, y0, min( y0 + per, h ), pushPullEdge( wx, w ) );
+      }
       __syncthreads();
-      uint8_t* t = src;
-      src        = dst;
-      dst        = t;
     }
-    if ( src != img ) {  // odd iteration count: the result sits in the partner buffer -- the level's image from now on
-      L.img[l - 1] = src;
-      L.tmp[l - 1] = img;
-    }
+    inTmp = iters & 1;
     iters = min( iters + 1, 16 );
+  }
+  {
+    const uint32_t* res = sPyr + base + 1 + ( inTmp ? n : 0 );
+    uint8_t*        out = L.out + size_t( plane ) * w * h;
+    for ( int i = tid; i < n; i += 1024 ) {
+      const int      wx = i % pw, y = i / pw;
+      const uint32_t v = res[i];
+#pragma unroll
+      for ( int j = 0; j < 4; ++j )
+        if ( 4 * wx + j < w ) out[size_t( y ) * w + 4 * wx + j] = uint8_t( v >> ( 8 * j ) );
+    }
   }
 }
 
@@ -738,12 +929,16 @@ int generateAttributeImages( tmc2_frame* f, const tmc2_color_transfer_params* pa
       lv[l].occ = p, p += ( a + 15 ) & ~size_t( 15 );
     }
   }
-  // the coarse end of the pyramid (levels of at most kPushPullSmall pixels) goes through ONE launch
-  size_t firstSmall = lv.size();
+  // the coarse end of the pyramid (levels of at most kPushPullSmall pixels) goes through ONE launch, in LDS: from the first
+  // level that is small and fits with everything below it (by the rows' word pitch a narrow level takes up to 8 bytes for 5 pixels)
+  size_t                firstSmall = lv.size(), coarseLds = 0;
+  constexpr size_t      kCoarseLdsMax = 160 * 1024 - 64;  // (allowLargeLds)
+  std::vector<size_t>   ldsFrom( lv.size() + 1, 0 );      // bytes of LDS of the levels l .. count - 1
+  for ( size_t l = lv.size(); l-- > 1; ) ldsFrom[l] = ldsFrom[l + 1] + sizeof( uint32_t ) * size_t( pushPullLevelWords( lv[l].w, lv[l].h ) );
   if ( lv.size() <= size_t( kPushPullLevels ) )
     for ( size_t l = 1; l < lv.size(); ++l )
-      if ( lv[l].w * lv[l].h <= kPushPullSmall ) {
-        firstSmall = l;
+      if ( lv[l].w * lv[l].h <= kPushPullSmall && ldsFrom[l] <= kCoarseLdsMax ) {
+        firstSmall = l, coarseLds = ldsFrom[l];
         break;
       }
   for ( size_t l = 1; l < lv.size() && l <= firstSmall; ++l ) {
@@ -755,12 +950,16 @@ int generateAttributeImages( tmc2_frame* f, const tmc2_color_transfer_params* pa
   if ( firstSmall + 1 < lv.size() ) {
     PushPullLevels L;
     L.count = int( lv.size() ), L.first = int( firstSmall );
-    for ( size_t l = 0; l < lv.size(); ++l ) L.w[l] = lv[l].w, L.h[l] = lv[l].h, L.img[l] = lv[l].img, L.tmp[l] = lv[l].tmp, L.occ[l] = lv[l].occ;
-    hipLaunchKernelGGL( pushPullCoarseLevelsKernel, dim3( 6 ), dim3( 1024 ), 0, s, L );
-    for ( size_t l = lv.size() - 1; l > firstSmall; --l ) {  // (what the kernel did to the buffers of the levels it filled)
+    for ( size_t l = 0; l < lv.size(); ++l ) L.w[l] = lv[l].w, L.h[l] = lv[l].h;
+    L.img = lv[firstSmall].img, L.occ = lv[firstSmall].occ;
+    for ( size_t l = lv.size() - 1; l > firstSmall; --l ) {  // (an odd iteration count leaves a level's image in its partner buffer)
       if ( iters & 1 ) std::swap( lv[l - 1].img, lv[l - 1].tmp );
       iters = std::min( iters + 1, 16 );
     }
+    L.out = lv[firstSmall].img;  // (of the levels the kernel fills, only this one is read again: by the fill of level first - 1)
+    if ( coarseLds > 48 * 1024 )
+      TMC2_TRY( allowLargeLds( reinterpret_cast<const void*>( pushPullCoarseLevelsKernel ), coarseLds, ctx->device ) );
+    hipLaunchKernelGGL( pushPullCoarseLevelsKernel, dim3( 6 ), dim3( 1024 ), coarseLds, s, L );
   }
   for ( size_t l = std::min( firstSmall, lv.size() - 1 ); l >= 1; --l ) {
     Level&    fine = lv[l - 1];
@@ -768,7 +967,7 @@ int generateAttributeImages( tmc2_frame* f, const tmc2_color_transfer_params* pa
     const dim3 grd( ( cnt + 255 ) / 256 );
     if ( iters <= kPushPullMaxIters ) {  // fill + every blur pass of the level: one launch, tiles in LDS
       const int tilesX = ( fine.w + kPushPullTile - 1 ) / kPushPullTile, tilesY = ( fine.h + kPushPullTile - 1 ) / kPushPullTile;
-      hipLaunchKernelGGL( pushPullFillBlurKernel, dim3( tilesX * tilesY, 6 ), dim3( 1024 ), 0, s, fine.img, fine.occ, fine.w, fine.h,
+      hipLaunchKernelGGL( pushPullFillBlurKernel, dim3( tilesX * tilesY, 6 ), dim3( kPushPullThreads ), 0, s, fine.img, fine.occ, fine.w, fine.h,
                           lv[l].img, lv[l].w, lv[l].h, iters, tilesX );
       iters = std::min( iters + 1, 16 );
       continue;
