@@ -24,6 +24,7 @@
 
 #include "color_transfer.h"
 #include "internal.h"
+#include "loads.h"
 #include "wave.h"
 #include "patch_border_filter.h"
 
@@ -387,10 +388,10 @@ __device__ __forceinline__ void pushPullBlurStrip( const uint32_t* __restrict__ 
     }
 #pragma unroll
     // The mask words are used only under `y + k < y1`.  Left alone, the compiler moves each ds_read of a mask into the exec-masked
-    // block of its store, behind a wait of its own (seen in the gfx950 assembly: R - 1 further LDS round trips per batch); the empty
-    // statement keeps the R reads with the other reads of the batch (kdtree_device.hip's lvPin).  Not timed without it: the passes
-    // are bound by their VALU work either way (profiles/attribute_padding.txt, section 3); without it the result is the same.
-    for ( int k = 0; k < R; ++k ) asm volatile( "" : "+v"( m[k] ) );
+    // block of its store, behind a wait of its own (seen in the gfx950 assembly: R - 1 further LDS round trips per batch); the pin
+    // keeps the R reads with the other reads of the batch (loads.h).  Not timed without it: the passes are bound by their VALU
+    // work either way (profiles/attribute_padding.txt, section 3); without it the result is the same.
+    for ( int k = 0; k < R; ++k ) pin( m[k] );
 #pragma unroll
     for ( int k = 0; k < R; ++k ) {
       const PushPullRow dn  = pushPullRowTerms( l[k], c[k], r[k], E );

@@ -36,6 +36,7 @@
 #include <cstring>
 
 #include "internal.h"
+#include "loads.h"
 #include "wave.h"
 
 namespace tmc2 {
@@ -106,26 +107,6 @@ struct BuildArgs {
   volatile uint32_t* hostDepth;  // pieceKernel's last workgroup: finishDepth
 };
 
-__device__ __forceinline__ int coordOf( const Pt p, int d ) { return d == 0 ? p.x : ( d == 1 ? p.y : p.z ); }
-
-// What a thread fetches together is loaded into registers AHEAD of the branches that consume it and pinned there (lvPin): left
-// alone, the compiler sinks every load into the exec-masked block of its first use, behind that block's own s_waitcnt vmcnt(0),
-// and takes a 16-byte load apart into the words that are used -- a chain of round trips where the source reads like a batch.
-typedef uint32_t LvW2 __attribute__( ( ext_vector_type( 2 ) ) );
-typedef uint32_t LvW4 __attribute__( ( ext_vector_type( 4 ) ) );
-__device__ __forceinline__ void lvPin( uint32_t& a ) { asm volatile( "" : "+v"( a ) ); }
-__device__ __forceinline__ void lvPin( LvW2& a ) { asm volatile( "" : "+v"( a ) ); }
-__device__ __forceinline__ void lvPin( LvW4& a ) { asm volatile( "" : "+v"( a ) ); }
-template <typename T, typename... Rest>
-__device__ __forceinline__ void lvPin( T& a, Rest&... rest ) {  // (one asm per value: the waits the compiler puts before them collapse into the first)
-  lvPin( a );
-  lvPin( rest... );
-}
-// a point as its two words (x | y << 16, z | w << 16): one 8-byte load that stays one
-__device__ __forceinline__ int32_t lvCoord( LvW2 p, int d ) {
-  return d == 0 ? int32_t( int16_t( p.x & 0xFFFFu ) ) : ( d == 1 ? int32_t( int16_t( p.x >> 16 ) ) : int32_t( int16_t( p.y & 0xFFFFu ) ) );
-}
-
 struct SplitRule {
   int     dim;
   int32_t cut;
@@ -190,14 +171,14 @@ __device__ __forceinline__ uint32_t blockClassLists( const Pt* pts, uint32_t cou
     const uint32_t i0 = base + 4u * threadIdx.x;
     bool           ge[4];
     uint32_t       cGE = 0, cIn = 0;
-    LvW2           pw[4];  // (the four loads ahead of one wait)
+    Words2           pw[4];  // (the four loads ahead of one wait)
 #pragma unroll
-    for ( int j = 0; j < 4; ++j ) pw[j] = *reinterpret_cast<const LvW2*>( pts + ( i0 + j < count ? i0 + j : 0u ) );
-    lvPin( pw[0], pw[1], pw[2], pw[3] );
+    for ( int j = 0; j < 4; ++j ) pw[j] = *reinterpret_cast<const Words2*>( pts + ( i0 + j < count ? i0 + j : 0u ) );
+    pin( pw[0], pw[1], pw[2], pw[3] );
 #pragma unroll
     for ( int j = 0; j < 4; ++j ) {
       const bool    in = i0 + j < count;
-      const int32_t x  = lvCoord( pw[j], dim );
+      const int32_t x  = ptCoord( pw[j], dim );
       ge[j]            = in && x >= c;
       cGE += uint32_t( ge[j] ), cIn += uint32_t( in );
     }
@@ -236,7 +217,7 @@ __device__ __forceinline__ uint32_t blockSweep( Pt* pts, uint32_t* id, uint32_t 
   __syncthreads();
   for ( uint32_t t = threadIdx.x; t < min( nGE, nL ); t += blockDim.x ) {
     uint32_t x = listGE[t], y = listLT[nL - 1u - t];  // (both entries together: t < nL)
-    lvPin( x, y );
+    pin( x, y );
     if ( x >= nL ) break;  // (ascending: nothing misplaced from here on)
     const Pt       px = pts[x], py = pts[y];
     const uint32_t ix = id[x], iy = id[y];
@@ -492,7 +473,7 @@ __device__ __forceinline__ void ldsMax( int32_t* slot, int32_t v ) {
 // Launches per level: flags, swaps, flags, swaps + landing, decide (tiny).  Swap for swap nanoflann's planeSplit
 // (nanoflann.hpp:1154-1181), as everything in this file.
 // The chains as the code object has them (what a thread waits for in a row; loads of one step are issued together, ahead of
-// the branches that use them, at clamped addresses where a position is retired or lies beyond n -- lvPin above):
+// the branches that use them, at clamped addresses where a position is retired or lies beyond n -- loads.h):
 //   * lvFlagKernel, per tile, a thread on its 8 consecutive positions: the 8 seg words (two 16-byte loads) -> the cut word of
 //     the 8 records (second sweep: cut word and edge1, one 8-byte load each) together with the 8 points (four 16-byte loads).
 //     loc goes out as two 16-byte stores.  The second sweep's reset of the children's ranges: cutInfo and slot together,
@@ -524,8 +505,8 @@ struct alignas( 16 ) LvSeg {
 };
 static_assert( sizeof( LvSeg ) == 80 && offsetof( LvSeg, slot ) == 16 && offsetof( LvSeg, lo ) == 32 && offsetof( LvSeg, mn ) == 48, "LvSeg rows" );
 
-__device__ __forceinline__ LvW4 lvRow( const LvSeg* q, int row ) { return reinterpret_cast<const LvW4*>( q )[row]; }
-__device__ __forceinline__ void lvStoreRow( LvSeg* q, int row, LvW4 w ) { reinterpret_cast<LvW4*>( q )[row] = w; }
+__device__ __forceinline__ Words4 lvRow( const LvSeg* q, int row ) { return reinterpret_cast<const Words4*>( q )[row]; }
+__device__ __forceinline__ void lvStoreRow( LvSeg* q, int row, Words4 w ) { reinterpret_cast<Words4*>( q )[row] = w; }
 
 constexpr int kLandBlock = 256;  // the landing pass: one record of the children's ranges per workgroup (measured: 1 024-thread workgroups quarter the records the decide pass folds -- 14 -> 7 us -- and cost the landing pass itself 18 -> 32 us)
 constexpr int kLandRounds = 2;  // ... of consecutive rounds of kLandBlock positions: their records are merged where they name the same segment
@@ -539,7 +520,7 @@ __device__ __forceinline__ void lvReport( LvSeg* child, int mnx, int mny, int mn
   // the six (possibly stale) words ahead of one wait, then the atomics that are still needed, none of them waited for
   uint32_t s0 = uint32_t( loadStaleOk( &child->mn[0] ) ), s1 = uint32_t( loadStaleOk( &child->mn[1] ) ), s2 = uint32_t( loadStaleOk( &child->mn[2] ) );
   uint32_t s3 = uint32_t( loadStaleOk( &child->mx[0] ) ), s4 = uint32_t( loadStaleOk( &child->mx[1] ) ), s5 = uint32_t( loadStaleOk( &child->mx[2] ) );
-  lvPin( s0, s1, s2, s3, s4, s5 );
+  pin( s0, s1, s2, s3, s4, s5 );
   if ( mnx < int32_t( s0 ) ) atomicMin( &child->mn[0], mnx );
   if ( mny < int32_t( s1 ) ) atomicMin( &child->mn[1], mny );
   if ( mnz < int32_t( s2 ) ) atomicMin( &child->mn[2], mnz );
@@ -556,7 +537,7 @@ __device__ __forceinline__ uint32_t lvPrefix( const uint32_t* __restrict__ loc, 
 __device__ __forceinline__ void lvPrefix2( const uint32_t* __restrict__ loc, const uint32_t* sums, uint32_t tiles, uint32_t i0, uint32_t i1, uint32_t n,
                                            uint32_t& r0, uint32_t& r1 ) {
   uint32_t l0 = loc[min( i0, n - 1u )], l1 = loc[min( i1, n - 1u )];
-  lvPin( l0, l1 );
+  pin( l0, l1 );
   r0 = i0 < n ? l0 + sums[i0 / kScanTile] : sums[tiles];
   r1 = i1 < n ? l1 + sums[i1 / kScanTile] : sums[tiles];
 }
@@ -768,12 +749,12 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
     for ( uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < count; s += gridDim.x * blockDim.x ) {
       const LvSeg* q  = cur + s;
       uint32_t     ci = q->cutInfo, slot = q->slot;  // (one batch; the stores below cannot make the compiler read them again)
-      lvPin( ci, slot );
+      pin( ci, slot );
       if ( !( ci >> 24 ) ) continue;
       for ( int c = 0; c < 2; ++c ) {  // (the words of LvSeg::mn / mx: a row and a half)
         uint32_t* w = reinterpret_cast<uint32_t*>( next[slot + c].mn );
-        *reinterpret_cast<LvW4*>( w )     = LvW4{0x7FFFFFFFu, 0x7FFFFFFFu, 0x7FFFFFFFu, 0x80000000u};
-        *reinterpret_cast<LvW2*>( w + 4 ) = LvW2{0x80000000u, 0x80000000u};
+        *reinterpret_cast<Words4*>( w )     = Words4{0x7FFFFFFFu, 0x7FFFFFFFu, 0x7FFFFFFFu, 0x80000000u};
+        *reinterpret_cast<Words2*>( w + 4 ) = Words2{0x80000000u, 0x80000000u};
       }
     }
   }
@@ -784,13 +765,13 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
   for ( uint32_t t = blockIdx.x; t < tiles; t += gridDim.x ) {
     const uint32_t base = t * kScanTile + threadIdx.x * 8;
     uint32_t       run = 0, flags = 0, liveAt = 0;  // (bit k: position base + k carries the class flag / lies in a segment)
-    LvW4           sA = LvW4{kNone, kNone, kNone, kNone}, sB = sA;
-    if ( base < n ) sA = *reinterpret_cast<const LvW4*>( a.seg + base );
-    if ( base + 4 < n ) sB = *reinterpret_cast<const LvW4*>( a.seg + base + 4 );
-    lvPin( sA, sB );
+    Words4           sA = Words4{kNone, kNone, kNone, kNone}, sB = sA;
+    if ( base < n ) sA = *reinterpret_cast<const Words4*>( a.seg + base );
+    if ( base + 4 < n ) sB = *reinterpret_cast<const Words4*>( a.seg + base + 4 );
+    pin( sA, sB );
     uint32_t sg[8] = {sA.x, sA.y, sA.z, sA.w, sB.x, sB.y, sB.z, sB.w};
     uint32_t ci[8], e1[8];
-    LvW4     pp[4];
+    Words4     pp[4];
 #pragma unroll
     for ( int k = 0; k < 8; ++k ) {
       if ( base + k >= n ) sg[k] = kNone;  // (the padding of a group that n cuts holds whatever the pool left there)
@@ -799,15 +780,15 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
       if ( FIRST ) {
         ci[k] = q->cutInfo, e1[k] = 0;
       } else {
-        const LvW2 w = *reinterpret_cast<const LvW2*>( &q->cutInfo );  // cutInfo, edge1
+        const Words2 w = *reinterpret_cast<const Words2*>( &q->cutInfo );  // cutInfo, edge1
         ci[k] = w.x, e1[k] = w.y;
       }
     }
 #pragma unroll
-    for ( int m = 0; m < 4; ++m ) pp[m] = *reinterpret_cast<const LvW4*>( a.P + ( base + 2 * m < n ? base + 2 * m : 0u ) );  // (P has a spare element past n)
+    for ( int m = 0; m < 4; ++m ) pp[m] = *reinterpret_cast<const Words4*>( a.P + ( base + 2 * m < n ? base + 2 * m : 0u ) );  // (P has a spare element past n)
 #pragma unroll
-    for ( int k = 0; k < 8; ++k ) lvPin( ci[k] ), lvPin( e1[k] );
-    lvPin( pp[0], pp[1], pp[2], pp[3] );
+    for ( int k = 0; k < 8; ++k ) pin( ci[k] ), pin( e1[k] );
+    pin( pp[0], pp[1], pp[2], pp[3] );
 #pragma unroll
     for ( int k = 0; k < 8; ++k ) {
       const uint32_t i  = base + k;
@@ -829,8 +810,8 @@ __global__ __launch_bounds__( kBlock ) void lvFlagKernel( BuildArgs a, uint32_t 
       if ( base + k < n && !f ) a.list[size_t( t ) * kScanTile + ( threadIdx.x * 8 + k - offset )] = uint16_t( threadIdx.x * 8 + k );
       offset += f;
     }
-    if ( base < n ) *reinterpret_cast<LvW4*>( loc + base ) = LvW4{at[0], at[1], at[2], at[3]};            // (into the padding where n cuts
-    if ( base + 4 < n ) *reinterpret_cast<LvW4*>( loc + base + 4 ) = LvW4{at[4], at[5], at[6], at[7]};    //  the group: never read)
+    if ( base < n ) *reinterpret_cast<Words4*>( loc + base ) = Words4{at[0], at[1], at[2], at[3]};            // (into the padding where n cuts
+    if ( base + 4 < n ) *reinterpret_cast<Words4*>( loc + base + 4 ) = Words4{at[4], at[5], at[6], at[7]};    //  the group: never read)
     if ( threadIdx.x == kBlock - 1 ) tile[t] = offset;  // (the RAW total: the swap passes scan the totals themselves, in LDS)
     __syncthreads();
   }
@@ -917,14 +898,14 @@ __global__ __launch_bounds__( kLandBlock ) void lvSwapTwoKernel( BuildArgs a, ui
       // { P[j], perm[j] }.  Row 2 (the loose box) is only used by the thread on the segment's first position; which one that is
       // comes with row 0, so everybody asks for it in the same batch (the lanes of a segment ask for the same 16 bytes).
       s = a.seg[i];
-      LvW2     pw;
+      Words2     pw;
       uint32_t li, u;
       uint32_t to = kNone;
       if ( s != kNone ) {
         LvSeg* q  = cur + s;
-        LvW4   r0 = lvRow( q, 0 ), r1 = lvRow( q, 1 ), r2 = lvRow( q, 2 );
-        pw = *reinterpret_cast<const LvW2*>( a.P + i ), li = a.loc2[i], u = a.perm[i];
-        lvPin( r0, r1, r2, pw, li, u );
+        Words4   r0 = lvRow( q, 0 ), r1 = lvRow( q, 1 ), r2 = lvRow( q, 2 );
+        pw = *reinterpret_cast<const Words2*>( a.P + i ), li = a.loc2[i], u = a.perm[i];
+        pin( r0, r1, r2, pw, li, u );
         const uint32_t ci = r0.z;
         if ( ci >> 24 ) {
           const uint32_t b = r0.x, e = r0.y, e1 = r0.w;
@@ -945,39 +926,39 @@ __global__ __launch_bounds__( kLandBlock ) void lvSwapTwoKernel( BuildArgs a, ui
             // both children built in registers from the parent's rows and stored as whole rows 0 .. 2: the left one takes the cut
             // as hi[dim], the right one as lo[dim] (row 2 = lo[0] lo[1] | lo[2] hi[0] | hi[1] hi[2] | side, pdim, unused)
             const uint32_t c16 = uint32_t( cut ) & 0xFFFFu;
-            LvW4           left = r2, right = r2;
+            Words4           left = r2, right = r2;
             if ( dim == 0 ) left.y = ( r2.y & 0x0000FFFFu ) | ( c16 << 16 ), right.x = ( r2.x & 0xFFFF0000u ) | c16;
             if ( dim == 1 ) left.z = ( r2.z & 0xFFFF0000u ) | c16, right.x = ( r2.x & 0x0000FFFFu ) | ( c16 << 16 );
             if ( dim == 2 ) left.z = ( r2.z & 0x0000FFFFu ) | ( c16 << 16 ), right.y = ( r2.y & 0xFFFF0000u ) | c16;
             left.w = uint32_t( dim ) << 8, right.w = 1u | ( uint32_t( dim ) << 8 );
             LvSeg* ch = next + slot;
-            lvStoreRow( ch, 0, LvW4{b, mid, 0u, 0u} );
-            lvStoreRow( ch, 1, LvW4{0u, 0u, childNode, node} );
+            lvStoreRow( ch, 0, Words4{b, mid, 0u, 0u} );
+            lvStoreRow( ch, 1, Words4{0u, 0u, childNode, node} );
             lvStoreRow( ch, 2, left );
-            lvStoreRow( ch + 1, 0, LvW4{mid, e, 0u, 0u} );
-            lvStoreRow( ch + 1, 1, LvW4{0u, 0u, childNode + 1u, node} );
+            lvStoreRow( ch + 1, 0, Words4{mid, e, 0u, 0u} );
+            lvStoreRow( ch + 1, 1, Words4{0u, 0u, childNode + 1u, node} );
             lvStoreRow( ch + 1, 2, right );
           }
-          const int32_t x = lvCoord( pw, dim );
+          const int32_t x = ptCoord( pw, dim );
           to              = slot + ( i >= mid ? 1u : 0u );
           key             = to;
           if ( i >= e1 && i < e2 && x > cut ) {  // misplaced on the left of the second sweep: swap; what moves away lands right of mid
             const uint32_t r  = li + lvSums[i / kScanTile] - rb;
             const uint32_t j  = lvPartner( a.list, lvSums, e2, e, ( e - re ) - 1u - r );
-            LvW2           pj = *reinterpret_cast<const LvW2*>( a.P + j );
+            Words2           pj = *reinterpret_cast<const Words2*>( a.P + j );
             uint32_t       uj = a.perm[j];
-            lvPin( pj, uj );
-            *reinterpret_cast<LvW2*>( a.P + i ) = pj;
-            *reinterpret_cast<LvW2*>( a.P + j ) = pw;
+            pin( pj, uj );
+            *reinterpret_cast<Words2*>( a.P + i ) = pj;
+            *reinterpret_cast<Words2*>( a.P + j ) = pw;
             a.perm[i]                            = uj;
             a.perm[j]                            = u;
             moved                                = true;
-            A2 = pw.x, B2 = A2, C2 = pk2( lvCoord( pw, 2 ), ~lvCoord( pw, 2 ) );
+            A2 = pw.x, B2 = A2, C2 = pk2( ptCoord( pw, 2 ), ~ptCoord( pw, 2 ) );
             pw = pj;
           }
           // (misplaced on the right of the second sweep: the partner swaps and reports what lands here -- this lane keeps the
           //  run of its child together and adds nothing; if the swap has happened already it sees the element that landed)
-          if ( !( i >= e2 && x <= cut ) ) A = pw.x, B = A, C = pk2( lvCoord( pw, 2 ), ~lvCoord( pw, 2 ) );
+          if ( !( i >= e2 && x <= cut ) ) A = pw.x, B = A, C = pk2( ptCoord( pw, 2 ), ~ptCoord( pw, 2 ) );
         }
         a.seg[i] = to;
       }

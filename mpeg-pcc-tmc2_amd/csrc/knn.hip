@@ -40,6 +40,8 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "kd_walk.h"
+#include "loads.h"
 
 namespace tmc2 {
 
@@ -50,17 +52,11 @@ constexpr int      kLdsLevels = 40;  // deepest tree the packed-stack kernel tak
 constexpr int      kLdsTop    = 8;   // stack slots kept in LDS (the top of the stack)
 constexpr uint32_t kInf       = 0x7FFFFFFFu;
 
-struct RootBox {
-  int lo[3], hi[3];
-};
-
-// A node record in ONE 16-byte load, decoded from registers.  (Read field by field -- or as a vector the optimiser is free to take
-// apart again -- the record came in pieces: `dim` for the loop test first, the rest behind it: two dependent round trips per tree
-// level.  The empty asm statement consumes the four words as one register tuple right behind the load, so it stays one load.)
-typedef uint32_t NodeWords __attribute__( ( ext_vector_type( 4 ) ) );
+// A node record in ONE 16-byte load, decoded from registers (loads.h).  Read field by field the record came in pieces: `dim` for the
+// loop test first, the rest behind it -- two dependent round trips per tree level.
 __device__ __forceinline__ KdNode loadNode( const KdNode* __restrict__ nodes, uint32_t at ) {
-  NodeWords w = *reinterpret_cast<const NodeWords*>( nodes + at );
-  asm volatile( "" : "+v"( w ) );
+  Words4 w = *reinterpret_cast<const Words4*>( nodes + at );
+  pin( w );
   KdNode nd;
   nd.a       = int32_t( w.x );
   nd.b       = int32_t( w.y );
@@ -108,7 +104,7 @@ __device__ __forceinline__ void knnInsert( uint32_t ( &bd )[K], uint32_t ( &bi )
 constexpr uint32_t kHardQuery = 0xFFFFFFFFu;
 template <int K, bool SELF, bool LDS>
 __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTree, const uint32_t* __restrict__ perm,
-                                                     const KdNode* __restrict__ nodes, RootBox root,
+                                                     const KdNode* __restrict__ nodes, KdBox root,
                                                      const Pt* __restrict__ queries, uint32_t nq,
                                                      uint32_t* __restrict__ outIdx, uint32_t* __restrict__ outDist,
                                                      uint32_t nTree, int nodeBits,
@@ -137,15 +133,7 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
     bd[i] = kInf;
     bi[i] = 0;
   }
-  // offset of the query to the root box, per dimension (nanoflann computeInitialDistances); the per-dimension
-  // distances are the squares of these offsets all the way down
-  int o0 = 0, o1 = 0, o2 = 0;
-  if ( qx < root.lo[0] ) o0 = root.lo[0] - qx;
-  if ( qx > root.hi[0] ) o0 = qx - root.hi[0];
-  if ( qy < root.lo[1] ) o1 = root.lo[1] - qy;
-  if ( qy > root.hi[1] ) o1 = qy - root.hi[1];
-  if ( qz < root.lo[2] ) o2 = root.lo[2] - qz;
-  if ( qz > root.hi[2] ) o2 = qz - root.hi[2];
+  KdOffsets o = kdInitialOffsets( root, qx, qy, qz );  // (the walk and its offsets: kd_walk.h)
 
   // An upper bound of the K-th distance BEFORE the traversal: K real points next to the query in tree order (the query's own
   // neighbours for SELF; the points around the leaf a stack-less descent ends in otherwise) -- their largest distance bounds
@@ -161,13 +149,8 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
   } else {
     uint32_t centre = j;
     if ( !SELF ) {
-      uint32_t at = 0;
-      KdNode   nd = loadNode( nodes, 0 );
-      while ( nd.dim >= 0 ) {
-        const int v = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
-        at          = ( ( v - nd.divlow ) + ( v - nd.divhigh ) ) < 0 ? uint32_t( nd.a ) : uint32_t( nd.b );
-        nd          = loadNode( nodes, at );
-      }
+      KdNode nd = loadNode( nodes, 0 );
+      while ( nd.dim >= 0 ) nd = loadNode( nodes, kdNearChild( nd, qx, qy, qz ) );
       centre = uint32_t( nd.a + nd.b ) >> 1;
     }
     const uint32_t first = min( centre > uint32_t( K / 2 ) ? centre - uint32_t( K / 2 ) : 0u, nTree - uint32_t( K ) );
@@ -186,31 +169,22 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
   for ( ;; ) {
     KdNode nd = loadNode( nodes, node );
     while ( nd.dim >= 0 ) {
-      const int  v        = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
-      const int  ocur     = nd.dim == 0 ? o0 : ( nd.dim == 1 ? o1 : o2 );
-      const int  diff1    = v - nd.divlow;
-      const int  diff2    = v - nd.divhigh;
-      const bool leftNear = ( diff1 + diff2 ) < 0;
-      const int  ofar     = leftNear ? abs( diff2 ) : abs( diff1 );
-      const uint32_t nearC = leftNear ? uint32_t( nd.a ) : uint32_t( nd.b );
-      const uint32_t farC  = leftNear ? uint32_t( nd.b ) : uint32_t( nd.a );
-      const uint32_t farMin = uint32_t( o0 * o0 + o1 * o1 + o2 * o2 + ofar * ofar - ocur * ocur );
-      if ( farMin <= min( bd[K - 1], cap ) && sp < ( LDS ? kLdsLevels : kMaxStack ) ) {
-        const uint32_t f0 = uint32_t( nd.dim == 0 ? ofar : o0 ), f1 = uint32_t( nd.dim == 1 ? ofar : o1 ),
-                       f2 = uint32_t( nd.dim == 2 ? ofar : o2 );
+      const KdStep st = kdStep( nd, qx, qy, qz, o );
+      if ( st.farMin <= min( bd[K - 1], cap ) && sp < ( LDS ? kLdsLevels : kMaxStack ) ) {
+        const uint32_t f0 = uint32_t( st.far.o0 ), f1 = uint32_t( st.far.o1 ), f2 = uint32_t( st.far.o2 );
         if ( LDS ) {
-          const unsigned long long e = (unsigned long long)farC | ( (unsigned long long)f0 << sh0 ) |
+          const unsigned long long e = (unsigned long long)st.farC | ( (unsigned long long)f0 << sh0 ) |
                                        ( (unsigned long long)f1 << sh1 ) | ( (unsigned long long)f2 << sh2 );
           if ( sp < kLdsTop )
             ldsStack[sp * 256 + threadIdx.x] = e;
           else
             lowStack[sp - kLdsTop] = e;
         } else {
-          scratchStack[sp] = make_uint4( farC, f0, f1, f2 );
+          scratchStack[sp] = make_uint4( st.farC, f0, f1, f2 );
         }
         ++sp;
       }
-      node = nearC;
+      node = st.nearC;
       nd   = loadNode( nodes, node );
     }
     // The leaf's points: the pair loads of a batch first (loadLeafPairs), then its candidates in ascending tree position (what
@@ -225,12 +199,14 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
         const int   p   = p0 + 2 * i;
         const uint4 two = pr[i];
         if ( p >= nd.a && p < nd.b ) {
-          const int      ex = qx - int( int16_t( two.x & 0xFFFFu ) ), ey = qy - int( int16_t( two.x >> 16 ) ), ez = qz - int( int16_t( two.y & 0xFFFFu ) );
+          const Pt       c  = ptOf( Words2{two.x, two.y} );
+          const int      ex = qx - c.x, ey = qy - c.y, ez = qz - c.z;
           const uint32_t dist = uint32_t( ex * ex + ey * ey + ez * ez );
           if ( dist < bd[K - 1] && dist <= cap ) knnInsert<K>( bd, bi, dist, uint32_t( p ) );
         }
         if ( p + 1 < nd.b ) {
-          const int      ex = qx - int( int16_t( two.z & 0xFFFFu ) ), ey = qy - int( int16_t( two.z >> 16 ) ), ez = qz - int( int16_t( two.w & 0xFFFFu ) );
+          const Pt       c  = ptOf( Words2{two.z, two.w} );
+          const int      ex = qx - c.x, ey = qy - c.y, ez = qz - c.z;
           const uint32_t dist = uint32_t( ex * ex + ey * ey + ez * ez );
           if ( dist < bd[K - 1] && dist <= cap ) knnInsert<K>( bd, bi, dist, uint32_t( p + 1 ) );
         }
@@ -270,9 +246,7 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
       }
       if ( e0 * e0 + e1 * e1 + e2 * e2 <= min( bd[K - 1], cap ) ) {
         node  = en;
-        o0    = int( e0 );
-        o1    = int( e1 );
-        o2    = int( e2 );
+        o     = KdOffsets{int( e0 ), int( e1 ), int( e2 )};
         found = true;
         break;
       }
@@ -293,9 +267,9 @@ __global__ __launch_bounds__( 256 ) void knnKernel( const Pt* __restrict__ ptsTr
 // A tree of fewer points than the instantiated width that would serve the list (nTree < 32): the same search with a list of
 // RUN-TIME length k <= nTree -- no search asks for more results than the tree holds.  One query per lane, the list and the far-child
 // stack in private memory; the traversal is searchLevel's, far children taken when popped (knnKernel's header).  Rows of `stride`
-// words, the first k written.  Such trees are a handful of leaves: nothing here is tuned.
+// words, the first k written.  Such trees are a handful of leaves: nothing here is tuned (kd_walk.h: the one restatement).
 __global__ __launch_bounds__( 256 ) void knnSmallTreeKernel( const Pt* __restrict__ ptsTree, const uint32_t* __restrict__ perm,
-                                                             const KdNode* __restrict__ nodes, RootBox root, const Pt* __restrict__ queries,
+                                                             const KdNode* __restrict__ nodes, KdBox root, const Pt* __restrict__ queries,
                                                              uint32_t nq, int k, int stride, uint32_t* __restrict__ outIdx,
                                                              uint32_t* __restrict__ outDist, const uint32_t* __restrict__ nqLive,
                                                              const uint32_t* __restrict__ rowMap ) {
@@ -368,11 +342,7 @@ int dispatch( hipStream_t s, const TreeDev& t, const Pt* q, uint64_t nq, int k, 
     setError( "k=%d larger than the cloud (%llu points)", kNeed ? kNeed : k, (unsigned long long)t.n );
     return TMC2_E_INVALID;
   }
-  RootBox rb;
-  for ( int d = 0; d < 3; ++d ) {
-    rb.lo[d] = t.lo[d];
-    rb.hi[d] = t.hi[d];
-  }
+  const KdBox rb = kdBoxOf( t.lo, t.hi );
   const dim3 block( 256 );
   if ( uint64_t( k ) > t.n ) {  // (kNeed <= n < k <= 32, queries from the caller)
     if ( SELF || kNeed > 32 ) {
@@ -457,10 +427,7 @@ __global__ __launch_bounds__( 256 ) void easyQueryKernel( const Pt* __restrict__
   const Pt  qp = queries[j];
   const int qx = qp.x, qy = qp.y, qz = qp.z;
   KdNode    nd = loadNode( nodes, 0 );
-  while ( nd.dim >= 0 ) {
-    const int v = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
-    nd          = loadNode( nodes, ( ( v - nd.divlow ) + ( v - nd.divhigh ) ) < 0 ? uint32_t( nd.a ) : uint32_t( nd.b ) );
-  }
+  while ( nd.dim >= 0 ) nd = loadNode( nodes, kdNearChild( nd, qx, qy, qz ) );
   // the leaf in batches of pair loads (loadLeafPairs); the FIRST identical point is the one kept
   const uint32_t qxy = uint32_t( uint16_t( qp.x ) ) | ( uint32_t( uint16_t( qp.y ) ) << 16 ), qzz = uint32_t( uint16_t( qp.z ) );
   uint32_t       found = kHardQuery;

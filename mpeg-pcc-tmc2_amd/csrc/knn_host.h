@@ -1,13 +1,14 @@
-// knn_host.h -- nanoflann's k-NN search restated on the host over tmc2_host_kdtree_build's tree: searchLevel as a recursion, its
-// KNNResultSet::addPoint as a sorted array (insert behind equal distances, drop what equals the worst of a full list).  What the host
-// restatements of the k-NN refinement (refine_knn_host.cpp) and of the colour transfer (color_transfer_host.cpp) search with.
+// knn_host.h -- nanoflann's k-NN search restated on the host over tmc2_host_kdtree_build's tree: searchLevel as a recursion over the
+// kernels' walk step (kd_walk.h), its KNNResultSet::addPoint as a sorted array (insert behind equal distances, drop what equals the
+// worst of a full list).  What the host restatements of the k-NN refinement (refine_knn_host.cpp) and of the colour transfer
+// (color_transfer_host.cpp) search with.
 #pragma once
 #include <algorithm>
-#include <cstdlib>
 #include <thread>
 #include <vector>
 
 #include "internal.h"
+#include "kd_walk.h"
 
 namespace tmc2 {
 
@@ -24,7 +25,7 @@ struct HostSearch {
     if ( i < K ) dist[i] = d, pos[i] = p;
     if ( count < K ) ++count;
   }
-  void level( uint32_t node, int o[3] ) {
+  void level( uint32_t node, const KdOffsets o ) {
     const KdNode& nd = t.nodes[node];
     if ( nd.dim < 0 ) {
       for ( int p = nd.a; p < nd.b; ++p ) {
@@ -35,21 +36,14 @@ struct HostSearch {
       }
       return;
     }
-    const int  v = q[nd.dim], diff1 = v - nd.divlow, diff2 = v - nd.divhigh;
-    const bool leftNear = ( diff1 + diff2 ) < 0;
-    level( leftNear ? uint32_t( nd.a ) : uint32_t( nd.b ), o );
-    const int      kept = o[nd.dim], ofar = leftNear ? std::abs( diff2 ) : std::abs( diff1 );
-    o[nd.dim]           = ofar;
-    const uint32_t farMin = uint32_t( o[0] * o[0] + o[1] * o[1] + o[2] * o[2] );
-    if ( farMin <= worst() ) level( leftNear ? uint32_t( nd.b ) : uint32_t( nd.a ), o );
-    o[nd.dim] = kept;
+    const KdStep st = kdStep( nd, q[0], q[1], q[2], o );
+    level( st.nearC, o );
+    if ( st.farMin <= worst() ) level( st.farC, st.far );
   }
   // the whole search around ( x, y, z ): dist / pos [K] = squared distances and TREE positions in the reference's result order
   static void around( const KdTreeHost& t, int x, int y, int z, uint32_t K, uint32_t* dist, uint32_t* pos ) {
     HostSearch s{t, {x, y, z}, K, 0, dist, pos};
-    int        o[3];  // (nanoflann computeInitialDistances: the offset of the query to the root box)
-    for ( int d = 0; d < 3; ++d ) o[d] = s.q[d] < t.lo[d] ? t.lo[d] - s.q[d] : ( s.q[d] > t.hi[d] ? s.q[d] - t.hi[d] : 0 );
-    s.level( 0, o );
+    s.level( 0, kdInitialOffsets( kdBoxOf( t.lo, t.hi ), x, y, z ) );
   }
 };
 

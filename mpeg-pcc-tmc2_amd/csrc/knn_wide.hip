@@ -17,6 +17,7 @@
 // part of the tree.  Every loop is bounded: the descent by the tree's depth, the walk by its node count, the list steps by K / 64.
 // Squared distances are 32-bit unsigned: every coordinate, of the tree and of the queries, must be >= -4096 (3 x 36863^2 < 2^32).
 #include "internal.h"
+#include "kd_walk.h"
 #include "refine_knn.h"
 #include "wave.h"
 
@@ -31,10 +32,6 @@ constexpr int      kWideMinCoord = -4096;
 // a word of the wave's LDS region: local address space spelled out (a generic volatile pointer is lowered to flat, system-coherent
 // accesses), volatile because the lanes of a wave hand entries to each other through it, in program order
 using LdsWord = volatile __attribute__( ( address_space( 3 ) ) ) uint32_t;
-
-struct WideBox {
-  int lo[3], hi[3];
-};
 
 __device__ __forceinline__ uint32_t wideDist( int qx, int qy, int qz, Pt c ) {
   const int ex = qx - c.x, ey = qy - c.y, ez = qz - c.z;
@@ -71,7 +68,7 @@ __device__ __forceinline__ void wideInsert( LdsWord* ld, LdsWord* li, uint32_t K
 // TRANSPOSED = true : out[e * outStride + j] = TREE POSITION of result e of query j (the voting kernel's layout, refine_knn.hip)
 template <bool TRANSPOSED>
 __global__ __launch_bounds__( 64 * kWideWaves ) void knnWideKernel( const Pt* __restrict__ ptsTree, const uint32_t* __restrict__ perm,
-                                                                    const KdNode* __restrict__ nodes, WideBox root, const Pt* __restrict__ queries,
+                                                                    const KdNode* __restrict__ nodes, KdBox root, const Pt* __restrict__ queries,
                                                                     uint32_t nq, uint32_t nTree, uint32_t K, uint32_t nodeBudget,
                                                                     uint32_t* __restrict__ out, uint32_t outStride ) {
   extern __shared__ uint32_t wideLds[];  // per wave: dist[K] | position[K] | stack[kWideStack][4]
@@ -85,27 +82,16 @@ __global__ __launch_bounds__( 64 * kWideWaves ) void knnWideKernel( const Pt* __
 
   const Pt  qp = queries ? queries[j] : ptsTree[j];
   const int qx = qp.x, qy = qp.y, qz = qp.z;
-  int o0 = 0, o1 = 0, o2 = 0;  // offset of the query to the root box (nanoflann computeInitialDistances)
-  if ( qx < root.lo[0] ) o0 = root.lo[0] - qx;
-  if ( qx > root.hi[0] ) o0 = qx - root.hi[0];
-  if ( qy < root.lo[1] ) o1 = root.lo[1] - qy;
-  if ( qy > root.hi[1] ) o1 = qy - root.hi[1];
-  if ( qz < root.lo[2] ) o2 = root.lo[2] - qz;
-  if ( qz > root.hi[2] ) o2 = qz - root.hi[2];
+  KdOffsets o  = kdInitialOffsets( root, qx, qy, qz );  // (the walk and its offsets: kd_walk.h)
 
-  // the cap (knn.hip): K real points around the query in tree order bound the K-th distance from above; what lies beyond cannot
+  // the cap (knnKernel): K real points around the query in tree order bound the K-th distance from above; what lies beyond cannot
   // stay in the list, and skipping it leaves the order of arrival of everything else as it was
   uint32_t cap = 0;
   {
     uint32_t centre = j;
     if ( queries ) {
-      uint32_t at = 0;
-      KdNode   nd = nodes[0];
-      for ( int level = 0; nd.dim >= 0 && level < kWideStack; ++level ) {
-        const int v = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
-        at          = ( ( v - nd.divlow ) + ( v - nd.divhigh ) ) < 0 ? uint32_t( nd.a ) : uint32_t( nd.b );
-        nd          = nodes[at];
-      }
+      KdNode nd = nodes[0];
+      for ( int level = 0; nd.dim >= 0 && level < kWideStack; ++level ) nd = nodes[kdNearChild( nd, qx, qy, qz )];
       centre = nd.dim < 0 ? uint32_t( nd.a + nd.b ) >> 1 : 0u;
     }
     const uint32_t first = min( centre > K / 2u ? centre - K / 2u : 0u, nTree - K );
@@ -118,25 +104,17 @@ __global__ __launch_bounds__( 64 * kWideWaves ) void knnWideKernel( const Pt* __
   for ( ;; ) {
     KdNode nd = nodes[node];
     for ( int level = 0; nd.dim >= 0 && level <= kWideStack; ++level ) {
-      const int      v        = nd.dim == 0 ? qx : ( nd.dim == 1 ? qy : qz );
-      const int      ocur     = nd.dim == 0 ? o0 : ( nd.dim == 1 ? o1 : o2 );
-      const int      diff1    = v - nd.divlow;
-      const int      diff2    = v - nd.divhigh;
-      const bool     leftNear = ( diff1 + diff2 ) < 0;
-      const int      ofar     = leftNear ? abs( diff2 ) : abs( diff1 );
-      const uint32_t nearC = leftNear ? uint32_t( nd.a ) : uint32_t( nd.b );
-      const uint32_t farC  = leftNear ? uint32_t( nd.b ) : uint32_t( nd.a );
-      const uint32_t farMin = uint32_t( o0 * o0 ) + uint32_t( o1 * o1 ) + uint32_t( o2 * o2 ) + uint32_t( ofar * ofar ) - uint32_t( ocur * ocur );
-      if ( farMin <= min( worst, cap ) && sp < uint32_t( kWideStack ) ) {
+      const KdStep step = kdStep( nd, qx, qy, qz, o );
+      if ( step.farMin <= min( worst, cap ) && sp < uint32_t( kWideStack ) ) {
         if ( lane == 0 ) {
-          st[4u * sp]      = farC;
-          st[4u * sp + 1u] = uint32_t( nd.dim == 0 ? ofar : o0 );
-          st[4u * sp + 2u] = uint32_t( nd.dim == 1 ? ofar : o1 );
-          st[4u * sp + 3u] = uint32_t( nd.dim == 2 ? ofar : o2 );
+          st[4u * sp]      = step.farC;
+          st[4u * sp + 1u] = uint32_t( step.far.o0 );
+          st[4u * sp + 2u] = uint32_t( step.far.o1 );
+          st[4u * sp + 3u] = uint32_t( step.far.o2 );
         }
         ++sp;
       }
-      node = nearC;
+      node = step.nearC;
       nd   = nodes[node];
     }
     if ( nd.dim < 0 ) {
@@ -162,7 +140,7 @@ __global__ __launch_bounds__( 64 * kWideWaves ) void knnWideKernel( const Pt* __
       --sp;
       const uint32_t en = st[4u * sp], e0 = st[4u * sp + 1u], e1 = st[4u * sp + 2u], e2 = st[4u * sp + 3u];
       if ( e0 * e0 + e1 * e1 + e2 * e2 <= min( worst, cap ) ) {
-        node = en, o0 = int( e0 ), o1 = int( e1 ), o2 = int( e2 );
+        node = en, o = KdOffsets{int( e0 ), int( e1 ), int( e2 )};
         found = true;
         break;
       }
@@ -199,9 +177,8 @@ int launchKnnWide( tmc2_ctx* ctx, const TreeDev& t, const Pt* d_queries, uint64_
     setError( "kdtree_search_wide: invalid argument" );
     return TMC2_E_INVALID;
   }
-  WideBox rb;
+  const KdBox rb = kdBoxOf( t.lo, t.hi );
   for ( int d = 0; d < 3; ++d ) {
-    rb.lo[d] = t.lo[d], rb.hi[d] = t.hi[d];
     if ( t.lo[d] < kWideMinCoord ) {
       setError( "kdtree_search_wide: coordinate %d below %d unsupported (squared distances are 32-bit)", t.lo[d], kWideMinCoord );
       return TMC2_E_UNSUPPORTED;

@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "internal.h"
+#include "loads.h"
 #include "wave.h"
 #include "union_find.h"
 
@@ -42,8 +43,6 @@ struct PatchDev {
   int64_t occOff;     // into the frame's occupancy pool
 };
 
-__device__ __forceinline__ int coordOf( const Pt p, int axis ) { return axis == 0 ? p.x : ( axis == 1 ? p.y : p.z ); }
-
 // Wave-aggregated reductions keyed by a small integer (patch / component id).  Neighbouring points almost always
 // share the key, so instead of 64 atomics on one address per wavefront the lanes holding the same key are reduced
 // with cross-lane shuffles and ONE lane issues the atomics.  Loops once per distinct key present in the wave.
@@ -57,46 +56,7 @@ __device__ __forceinline__ void lazyAtomicMax( int32_t* a, int v ) {
   if ( v > loadStaleOk( a ) ) atomicMax( a, v );
 }
 
-// What a point's step needs is fetched TOGETHER, ahead of the branches that consume it, and pinned (kdtree_device.hip: lvPin; knn.hip:
-// loadNode): left alone, the compiler sinks every load into the exec-masked block of its first use, behind that block's own
-// s_waitcnt vmcnt(0), and a wave of a per-point pass lives as long as its slowest lane's chain of round trips.  The empty asm
-// statements consume a batch's registers one after the other with no load between them: the batch's wait sits at the first.
-// A value that was not loaded (its predicate failed) is pinned as the constant it was given.  Every batch keeps the predicate of the
-// serial form on what it turns into an address: an index a batch reads early is one the serial form read too, or one valid by
-// construction (i < n, an entry of a k-NN row).
-typedef uint32_t Words4 __attribute__( ( ext_vector_type( 4 ) ) );
-typedef uint32_t Words2 __attribute__( ( ext_vector_type( 2 ) ) );
-__device__ __forceinline__ void pin( uint32_t& a ) { asm volatile( "" : "+v"( a ) ); }
-__device__ __forceinline__ void pin( int32_t& a ) { asm volatile( "" : "+v"( a ) ); }
-__device__ __forceinline__ void pin( Words2& a ) { asm volatile( "" : "+v"( a ) ); }
-__device__ __forceinline__ void pin( Words4& a ) { asm volatile( "" : "+v"( a ) ); }
-template <typename T, typename... Rest>
-__device__ __forceinline__ void pin( T& a, Rest&... rest ) {
-  pin( a );
-  pin( rest... );
-}
-template <int N>
-__device__ __forceinline__ void pinAll( uint32_t ( &a )[N] ) {
-#pragma unroll
-  for ( int k = 0; k < N; ++k ) pin( a[k] );
-}
-// a whole 16-entry k-NN row in four 16-byte loads (not yet waited for: pin r[0..3] with the rest of the batch)
-__device__ __forceinline__ void loadRow16( const uint32_t* __restrict__ knn, uint32_t u, Words4 ( &r )[4] ) {
-  const Words4* row = reinterpret_cast<const Words4*>( knn + size_t( u ) * 16 );
-#pragma unroll
-  for ( int t = 0; t < 4; ++t ) r[t] = row[t];
-}
-__device__ __forceinline__ void rowEntries( const Words4 ( &r )[4], uint32_t ( &v )[16] ) {
-#pragma unroll
-  for ( int t = 0; t < 4; ++t ) v[4 * t] = r[t].x, v[4 * t + 1] = r[t].y, v[4 * t + 2] = r[t].z, v[4 * t + 3] = r[t].w;
-}
-// the point's own coordinates in one 8-byte load
-__device__ __forceinline__ Pt ptOf( const Words2 w ) {
-  Pt q;
-  q.x = int16_t( w.x & 0xFFFFu ), q.y = int16_t( w.x >> 16 ), q.z = int16_t( w.y & 0xFFFFu ), q.w = int16_t( w.y >> 16 );
-  return q;
-}
-__device__ __forceinline__ Words2 loadPt( const Pt* __restrict__ pts, uint32_t i ) { return reinterpret_cast<const Words2*>( pts )[i]; }
+// (a point's step fetches its k-NN row, its own words, then its 16 neighbours' words in load batches: loads.h)
 
 // ---- S7 ---------------------------------------------------------------------------------------------
 // Connected components of the reference = "smallest eligible seed that reaches v" over the DIRECTED k-NN graph

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "loads.h"
 #include "wave.h"
 
 namespace tmc2 {
@@ -848,8 +849,8 @@ __device__ __forceinline__ uint32_t closureHop( const Closure& c, uint32_t x, ui
   uint32_t        vAll[CHUNKS];
 #pragma unroll
   for ( int k = 0; k < CHUNKS; ++k ) vAll[k] = row[32 * k];
-  // (the empty asm statements consume a batch's registers together: the one wait of the batch sits here, and the optimiser
-  //  can neither take the batch apart nor move a later load's wait in between -- as knn.hip's loadNode)
+  // (loads.h, the form of several operands in one statement: the one wait of a batch sits at its statement, and the optimiser
+  //  cannot move a later load's wait in between)
   if constexpr ( CHUNKS == 1 )
     asm volatile( "" : "+v"( r.x ), "+v"( r.y ), "+v"( r.z ), "+v"( vAll[0] ) );
   else
@@ -894,7 +895,7 @@ __device__ __forceinline__ uint32_t closureHop( const Closure& c, uint32_t x, ui
   //  atomic on an address it knows to be the same in both 32-lane groups is merged into one per wavefront, whose answer it
   //  then has to wait for on the spot to hand it out)
   uint32_t same = 0;
-  asm volatile( "" : "+v"( same ) );
+  pin( same );
   if ( total && lane == 0 ) held.at = atomicAdd( c.count + same, total );
 #pragma unroll
   for ( int ch = 0; ch < CHUNKS; ++ch ) {
@@ -1073,13 +1074,13 @@ __global__ __launch_bounds__( 256 ) void sweepKernel( const uint32_t* __restrict
   };
   uint32_t idx = blockIdx.x * 16 + ( threadIdx.x >> 4 );
   uint32_t raw = idx < count ? listEntry( idx ) : 0u;
-  asm volatile( "" : "+v"( raw ) );  // (waited for here, so that the loop's top waits for nothing: not for the stores and adds of the voxel before)
+  pin( raw );  // (waited for here, so that the loop's top waits for nothing: not for the stores and adds of the voxel before)
   for ( ; idx < count; idx += groups ) {  // (uniform over the 16 lanes)
     const uint32_t v = raw & ~kWorkActive;
     // Everything that is indexed by v alone in ONE batch of loads, whether the decisions below need it or not, and the group's
     // next list entry with it: a voxel costs list entry -> this batch -> pointList -> normals + partition -> radj -> atomics and
     // nothing in between.  (A voxel is on the list exactly once, so what the batch reads is this group's own or frozen for the
-    // launch; pointStart has V + 1 entries.  The empty asm statement consumes the batch's registers together: one wait, here.)
+    // launch; pointStart has V + 1 entries.  One statement over the batch's registers, loads.h: one wait, here.)
     uint32_t st = state[v >> 4], e0w = edge[v], p0 = ppi[v];
     uint4    s  = recCur[v], h = hist[v];
     uint32_t last = lastRescore[v], begin = pointStart[v], end = pointStart[v + 1], rb = roff[v], rl = rlen[v];
